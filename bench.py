@@ -18,8 +18,16 @@ The corpus itself is resident in HBM.  value = batch * steps / wall time of the 
 barrier + synchronize fences, max over ranks; per-step HIP-event deltas give median / p10 / p90.
 
 The JSON line also carries `roofline` (the dense scan kernel, timed with HIP events around every
-launch on the stream it runs on) and, at N=1, `cpu_baseline` (the oracle = port of the
-reference's numpy / rank_bm25-style CPU path, timed on the host cores on a bounded sample).
+launch on the stream it runs on).  A plain run does nothing else: what takes work of its own comes
+with --full -- `host_enqueue_ms_per_step`, `roofline_one_query_set` and `roofline_single_query`
+(extra launches after the timed steps), the invariants check of the last step's answer and, at N=1,
+`cpu_baseline` (the oracle = port of the reference's numpy / rank_bm25-style CPU path, timed on the
+host cores on a bounded sample).
+
+--dump-outputs DIR writes the answer of the last timed step as the caller receives it (float64):
+DIR/rows.npy (batch, pool) candidate rows, DIR/order.npy (batch, k) positions of the top-k in the
+pool, DIR/final.npy (batch, pool) final scores.  Corpus and queries are seeded: the same arguments
+give the same inputs in every run.
 """
 import argparse
 import ctypes as C
@@ -61,7 +69,33 @@ def parse():
                          "use with --batch 64 --k 20")
     ap.add_argument("--force-payload", action="store_true",
                     help="diagnostic: with one rank, still pack / exchange / merge the shard payload")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks: host enqueue cost, one-set and single-query scan "
+                         "rooflines, invariants of the last answer, CPU baseline (one GPU, unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's answer as DIR/{rows,order,final}.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, rows, order, final):
+    """The answer of one step as float64 .npy files; beyond DUMP_LIMIT_BYTES a seeded sample of its queries (rows of
+    every array) is written instead, and `queries.npy` names them."""
+    arrays = {"rows": rows, "order": order, "final": final}
+    per_query = sum(a[0].size * 8 for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    if per_query * len(rows) > DUMP_LIMIT_BYTES:
+        n = (DUMP_LIMIT_BYTES - 4096) // (per_query + 8)          # (4096: the four files' headers)
+        keep = np.sort(np.random.default_rng(0).choice(len(rows), n, replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["queries"] = keep
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def make_queries(torch, args, stats, n_sets=4):
@@ -451,67 +485,71 @@ def main():
     dt = float(t.item())
     total_ms, launches = _scan_stats(index)
     info = _scan_info(index)
-    # the host's cost of ENQUEUEING a step, measured where nothing can block it: six steps on an idle stream (inside the
-    # depth of the pinned staging ring, so no slot is waited for), timed on the host alone.  (host_loop_ms_per_step below is
-    # the timed loop's own host time: it includes the ring's back-pressure once the GPU is the bottleneck, i.e. GPU time.)
-    torch.cuda.synchronize()
-    h0 = time.perf_counter()
-    for i in range(6):
-        step(i)
-    host_enqueue_ms = (time.perf_counter() - h0) / 6 * 1e3
-    fence()
-    _scan_stats(index)
-    # the answer of the last step, as it sits in the pinned buffers: cheap invariants (parity itself is the tests' job:
-    # tests/test_gpu_bench_config.py checks this very configuration against the oracle)
-    r_h, o_h, f_h = last_pins[0][0].numpy(), last_pins[0][1].numpy().astype(np.int64), last_pins[0][2].numpy()
-    top = np.take_along_axis(f_h, o_h, axis=1)
-    ok = (r_h.min() >= 0 and r_h.max() < args.docs and np.all(np.diff(top, axis=1) <= 0)
-          and all(len(set(o.tolist())) == o_h.shape[1] for o in o_h[:8]) and np.isfinite(top).all())
-    if not ok:
-        raise SystemExit("bench.py: the last step's answer violates its invariants (rows in range, top-k sorted, distinct)")
+    # the answer of the last timed step, as it sits in the pinned buffers (copied: later steps reuse them)
+    r_h, o_h, f_h = (p.numpy().copy() for p in last_pins[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r_h, o_h, f_h)
     per_step = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])
     if os.environ.get("RR_BENCH_DEBUG"):
         print("per-step ms:", np.round(per_step, 3).tolist(), file=sys.stderr, flush=True)
+    if args.full:
+        # the host's cost of ENQUEUEING a step, measured where nothing can block it: six steps on an idle stream (inside the
+        # depth of the pinned staging ring, so no slot is waited for), timed on the host alone.  (host_loop_ms_per_step below
+        # is the timed loop's own host time: it includes the ring's back-pressure once the GPU is the bottleneck, i.e. GPU time.)
+        torch.cuda.synchronize()
+        h0 = time.perf_counter()
+        for i in range(6):
+            step(i)
+        host_enqueue_ms = (time.perf_counter() - h0) / 6 * 1e3
+        fence()
+        _scan_stats(index)
+        # the last timed step's answer: cheap invariants (parity itself is the tests' job: tests/test_gpu_bench_config.py
+        # checks this very configuration against the oracle)
+        top = np.take_along_axis(f_h, o_h.astype(np.int64), axis=1)
+        ok = (r_h.min() >= 0 and r_h.max() < args.docs and np.all(np.diff(top, axis=1) <= 0)
+              and all(len(set(o.tolist())) == o_h.shape[1] for o in o_h[:8]) and np.isfinite(top).all())
+        if not ok:
+            raise SystemExit("bench.py: the last step's answer violates its invariants (rows in range, top-k sorted, distinct)")
 
-    # the same filter scan with ONE query set per launch (128 queries per pass over the stream): the HBM-bound form of
-    # the kernel -- the two-set launch above reads the stream once for 256 queries and is paced by the matrix side
-    one_set = None
-    q_dev[0].copy_(qsets[0][0])                  # (the side measurements below search device-resident queries)
-    if args.batch > 128 and info["queries_per_launch"] > 128:
-        q128 = q_dev[0][:128].contiguous()
+        # the same filter scan with ONE query set per launch (128 queries per pass over the stream): the HBM-bound form of
+        # the kernel -- the two-set launch above reads the stream once for 256 queries and is paced by the matrix side
+        one_set = None
+        q_dev[0].copy_(qsets[0][0])                  # (the side measurements below search device-resident queries)
+        if args.batch > 128 and info["queries_per_launch"] > 128:
+            q128 = q_dev[0][:128].contiguous()
+            for _ in range(2):
+                sharded.s.dense_pool(q128, pool)
+            torch.cuda.synchronize()
+            _scan_stats(index)
+            for _ in range(10):
+                sharded.s.dense_pool(q128, pool)
+            torch.cuda.synchronize()
+            ms128, n128 = _scan_stats(index)
+            i128 = _scan_info(index)
+            b128 = n_local * DIM * i128["elem_bytes"]
+            gbs128 = b128 / (ms128 / max(n128, 1) * 1e-3) / 1e9
+            one_set = {"bound": "hbm", "achieved": round(gbs128, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(gbs128 / HBM_PEAK_GBS, 4), "kernel": i128["kernel"], "launches": int(n128),
+                       "avg_launch_ms": round(ms128 / max(n128, 1), 5), "bytes_per_launch": b128,
+                       "queries_per_launch": i128["queries_per_launch"]}
+
+        # the HBM-bound end of the path: one query per matrix read (rr_scan_f32<6,1>), same shard
+        q1 = q_dev[0][:1].contiguous()
         for _ in range(2):
-            sharded.s.dense_pool(q128, pool)
+            sharded.s.dense_pool(q1, pool)
         torch.cuda.synchronize()
         _scan_stats(index)
         for _ in range(10):
-            sharded.s.dense_pool(q128, pool)
+            sharded.s.dense_pool(q1, pool)
         torch.cuda.synchronize()
-        ms128, n128 = _scan_stats(index)
-        i128 = _scan_info(index)
-        b128 = n_local * DIM * i128["elem_bytes"]
-        gbs128 = b128 / (ms128 / max(n128, 1) * 1e-3) / 1e9
-        one_set = {"bound": "hbm", "achieved": round(gbs128, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                   "frac": round(gbs128 / HBM_PEAK_GBS, 4), "kernel": i128["kernel"], "launches": int(n128),
-                   "avg_launch_ms": round(ms128 / max(n128, 1), 5), "bytes_per_launch": b128,
-                   "queries_per_launch": i128["queries_per_launch"]}
-
-    # the HBM-bound end of the path: one query per matrix read (rr_scan_f32<6,1>), same shard
-    q1 = q_dev[0][:1].contiguous()
-    for _ in range(2):
-        sharded.s.dense_pool(q1, pool)
-    torch.cuda.synchronize()
-    _scan_stats(index)
-    for _ in range(10):
-        sharded.s.dense_pool(q1, pool)
-    torch.cuda.synchronize()
-    ms1, n1 = _scan_stats(index)
-    esz = 2 if args.dtype == "bf16" else 4
-    bytes_per_launch = n_local * DIM * esz            # algorithmic: the shard's matrix, read once per launch
-    gbs1 = bytes_per_launch / (ms1 / max(n1, 1) * 1e-3) / 1e9
-    single = {"bound": "hbm", "achieved": round(gbs1, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-              "frac": round(gbs1 / HBM_PEAK_GBS, 4),
-              "kernel": "rr_scan_bf16<1>" if args.dtype == "bf16" else "rr_scan_f32<6,1>", "launches": int(n1),
-              "avg_launch_ms": round(ms1 / max(n1, 1), 5), "bytes_per_launch": bytes_per_launch}
+        ms1, n1 = _scan_stats(index)
+        esz = 2 if args.dtype == "bf16" else 4
+        bytes_per_launch = n_local * DIM * esz            # algorithmic: the shard's matrix, read once per launch
+        gbs1 = bytes_per_launch / (ms1 / max(n1, 1) * 1e-3) / 1e9
+        single = {"bound": "hbm", "achieved": round(gbs1, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                  "frac": round(gbs1 / HBM_PEAK_GBS, 4),
+                  "kernel": "rr_scan_bf16<1>" if args.dtype == "bf16" else "rr_scan_f32<6,1>", "launches": int(n1),
+                  "avg_launch_ms": round(ms1 / max(n1, 1), 5), "bytes_per_launch": bytes_per_launch}
 
     if rank == 0:
         avg_ms = total_ms / max(launches, 1)
@@ -550,7 +588,8 @@ def main():
                       else "queries/sec at top-k=100 (dense only)",
             "value": round(args.batch * args.steps / dt, 3), "unit": "queries/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "host_enqueue_ms_per_step": round(host_enqueue_ms, 4),
+            "ms_per_step": round(dt / args.steps * 1e3, 4),
+            **({"host_enqueue_ms_per_step": round(host_enqueue_ms, 4)} if args.full else {}),
             "host_loop_ms_per_step": round(host_s / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -576,17 +615,18 @@ def main():
                                                        + (" started under the next batch's K1" if pipelined else "")
                                                        + (f"; every batch's tail on {torch.cuda.get_device_properties(dev).multi_processor_count - sharded._ov.scan_cus} CUs beside the next batch's scan on {sharded._ov.scan_cus}" if overlap else ""))},
             "roofline": roof,
-            # the single-query scan on the same shard: the HBM-bound end of the same path
-            "roofline_single_query": single,
-            **({"roofline_one_query_set": one_set} if one_set else {}),
         }
+        if args.full:
+            out["roofline_single_query"] = single     # the single-query scan on the same shard: the HBM-bound end of the path
+            if one_set:
+                out["roofline_one_query_set"] = one_set
         if rerank_fn is not None:
             out["metric"] = f"queries/sec, hybrid + cross-encoder rerank top-{args.rerank_k} -> top-{args.k}"
             out["config"]["workload"] += (f"; rerank of the first {args.rerank_k} pool rows per query by the K5 cross-encoder "
                                           "(MiniLM-L6 shape, seeded weights, synthetic token ids 65..512 per pair)")
             out["rerank"] = {"precision": args.ce_precision, "pairs_per_step": args.batch * args.rerank_k,
                              "mean_tokens_per_pair": round(rerank_fn.tokens / max(rerank_fn.pairs, 1), 1)}
-        if world == 1 and not args.no_cpu_baseline and rerank_fn is None:
+        if args.full and world == 1 and not args.no_cpu_baseline and rerank_fn is None:
             out["cpu_baseline"] = cpu_baseline(torch, args, shard, qsets)
         print(json.dumps(out), flush=True)
     if overlap:

@@ -299,7 +299,12 @@ int rr_ce_destroy(rr_ce* ce);
 #define RR_CE_OUT_CLS    1   /* d_out [n_seqs][hidden]: last_hidden_state[:, 0] (CLS pooling of the query encoder) */
 #define RR_CE_OUT_HIDDEN 2   /* d_out [n_tokens][hidden]: last_hidden_state of every token (diagnostic / parity tests) */
 /* Forward over PACKED sequences (no padding is computed): sequence s owns tokens [cu_seqlens[s], cu_seqlens[s+1]);
- * token / type / position ids are per token (position = index inside its sequence); max_len = longest sequence.
+ * token / type / position ids are per token (position = index inside its sequence); max_len = longest sequence: it must be
+ * at least every sequence's length (attention sizes its LDS from it).  In RR_CE_PRECISION_F32 a longer sequence gets NaN
+ * outputs and rr_ce_range_status fails with RR_E_INVALID naming max_len; the bf16 precision and the wide-range kernels do not
+ * check it (the bf16 attention sizes LDS from it too: an understated max_len is undefined there).
+ * RR_CE_PRECISION_F32 takes at most 2^27 tokens per call (RR_E_INVALID beyond: its GEMMs store with 32-bit offsets inside
+ * a pair of 16-byte chunks of the activation scratch); its scratch is kept at the handle's largest call.
  * Attention is full inside a sequence (what an all-ones attention mask over the unpadded tokens gives).
  * Asynchronous on `stream`; all pointers are device pointers. */
 int rr_ce_forward_dev(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d_type_ids, const int32_t* d_pos_ids,
@@ -311,7 +316,8 @@ int rr_ce_last_forward_ms(rr_ce* ce, float* out_ms);
  * products per fp32 product (csrc/rr_ce_h2.hip; as exact as an fp32 multiply-add chain).  fp16 ends at 65504: a forward pass
  * that meets a larger activation raises a flag on the device, writes NaN logits / CLS rows for the whole call (never a wrong
  * finite number; RR_CE_OUT_HIDDEN rows are left as computed: ask here) and reports it here -- *out_of_range = 1 -- once
- * the pass has finished (this call waits for it).
+ * the pass has finished (this call waits for it).  A pass whose max_len was below a sequence's length (rr_ce_forward_dev)
+ * makes this call return RR_E_INVALID instead: running it again on the wide-range kernels would not help.
  * rr_ce_set_wide_range(ce, 1) switches the handle to three bf16 terms per operand and six products (any fp32 range,
  * ~1.6 x the time): run the pass again after it.  cross_encoder.py does both by itself on the host path. */
 int rr_ce_range_status(rr_ce* ce, int32_t* out_of_range);

@@ -34,6 +34,7 @@ from .wordpiece import WordPieceTokenizer
 OUT_LOGITS, OUT_CLS, OUT_HIDDEN = 0, 1, 2       # RR_CE_OUT_*
 PRECISIONS = {"bf16": 0, "fp32": 1}              # RR_CE_PRECISION_*
 HIDDEN, HEADS, FFN = 384, 12, 1536
+FP32_MAX_TOKENS = 1 << 27                           # tokens per rr_ce_forward_dev call in fp32 precision (include/rr_hip.h)
 
 _LAYER_KEYS = ("attention.self.query.weight", "attention.self.query.bias", "attention.self.key.weight",
                "attention.self.key.bias", "attention.self.value.weight", "attention.self.value.bias",
@@ -132,11 +133,12 @@ class BertEncoderGPU:
             raise ValueError("this encoder was loaded without a classification head")
         out = np.empty((int(lens.sum()) if mode == OUT_HIDDEN else n, width), dtype=np.float32)
         lib = _lib.load()
+        cap = min(self.max_tokens_per_call, FP32_MAX_TOKENS) if self.precision == "fp32" else self.max_tokens_per_call
         start = 0
         tok_done = 0
         while start < n:
             end, tot = start, 0
-            while end < n and (end == start or tot + lens[end] <= self.max_tokens_per_call):
+            while end < n and (end == start or tot + lens[end] <= cap):
                 tot += int(lens[end])
                 end += 1
             part = seqs[start:end]
@@ -179,7 +181,8 @@ class BertEncoderGPU:
     def forward_packed_dev(self, tok, typ, pos, cu, n_seqs: int, max_len: int, mode: int = OUT_LOGITS):
         """Forward over sequences that are already packed ON THE DEVICE (int32 torch tensors: token ids, type ids,
         position ids per token; cu_seqlens per sequence): returns a device tensor, no host hop.  Asynchronous on
-        torch's current stream.  Used where the pairs are assembled on the GPU (bench.py's rerank mode)."""
+        torch's current stream.  Used where the pairs are assembled on the GPU (bench.py's rerank mode).  `max_len` must
+        be at least every sequence's length (`out_of_range` reports a shorter one as a ValueError)."""
         torch = self._torch
         n_tokens = int(tok.numel())
         width = {OUT_LOGITS: self.n_labels, OUT_CLS: HIDDEN, OUT_HIDDEN: HIDDEN}[mode]
@@ -193,7 +196,9 @@ class BertEncoderGPU:
     def out_of_range(self) -> bool:
         """True when the LAST forward pass (waited for here) met a value beyond fp16's range: its logits / CLS rows are NaN
         (include/rr_hip.h: rr_ce_range_status).  `forward_ids` checks and reruns by itself; a caller of
-        `forward_packed_dev` checks after it has synchronised, calls `set_wide_range(True)` and submits the batch again."""
+        `forward_packed_dev` checks after it has synchronised, calls `set_wide_range(True)` and submits the batch again.
+        Raises ValueError (naming max_len) instead when that pass had a sequence longer than the `max_len` it was given:
+        its outputs are NaN, and the wide-range kernels would not help."""
         flag = C.c_int32()
         _lib.check(_lib.load().rr_ce_range_status(self._h, C.byref(flag)), "rr_ce_range_status")
         return bool(flag.value)

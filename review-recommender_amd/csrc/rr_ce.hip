@@ -1941,6 +1941,8 @@ static int ce_set_attributes(int device) {
 
 static int ce_reserve_f32(rr_ce* ce, int64_t tokens) {
     if (tokens <= ce->cap32) return RR_OK;
+    RR_REQUIRE(rr_round_up(tokens, 4096) <= CE_H2_MAX_ROWS, "rr_ce_forward_dev: %lld tokens in one fp32-precision call; at most %lld",
+               (long long)tokens, (long long)CE_H2_MAX_ROWS);
     RR_HIP_TRY(hipDeviceSynchronize());
     hipFree(ce->qkv32); hipFree(ce->y32); hipFree(ce->inter32); hipFree(ce->hx); hipFree(ce->ctxh);
     ce->qkv32 = ce->y32 = ce->inter32 = nullptr;
@@ -2235,7 +2237,10 @@ extern "C" int rr_ce_range_status(rr_ce* ce, int32_t* out_of_range) {
     RR_HIP_TRY(hipEventSynchronize(ce->ev1));
     unsigned f = 0;
     RR_HIP_TRY(hipMemcpy(&f, ce->d_flag, 4, hipMemcpyDeviceToHost));
-    *out_of_range = f ? 1 : 0;
+    // bit 2 (rr_ce_h2.hip, attention): a sequence longer than the call's max_len -- the caller's mistake, not a range problem
+    RR_REQUIRE(!(f & 2u), "rr_ce_range_status: the last forward pass had a sequence longer than its max_len (its outputs are NaN; "
+               "max_len must be at least every sequence's length)");
+    *out_of_range = (f & 1u) ? 1 : 0;
     return RR_OK;
 }
 

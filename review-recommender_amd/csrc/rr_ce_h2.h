@@ -7,6 +7,8 @@
 // "h2" = an fp32 matrix X[R][K] held as TWO fp16 planes, hi = fp16(x) and lo = fp16((x - hi) * 2048) (x = hi + lo / 2048 to
 // 2^-22 |x|), in 16-byte UNITS of eight consecutive k, chunk-major: unit (plane p, chunk kc, row) at index
 // ((p * K / 8 + kc) * row_stride + row).  `row_stride` >= R, a multiple of 256 for the token-side operand of ce_h2_gemm.
+// The largest `os` of ce_h2_gemm's h2 outputs (its stores take 32-bit offsets inside a chunk pair: 32 os < 2^32)
+#define CE_H2_MAX_ROWS (1ll << 27)
 #define CE_H2_SCALE 2048.0f
 #define CE_H2_INV_SCALE 4.8828125e-4f
 
@@ -24,7 +26,8 @@ void ce_h2_gemm(int epi, const void* W2, int N, const void* X2, int64_t xs, int 
                 void* out2, int64_t os, unsigned* flag, hipStream_t st, float qscale = 1.f, int qcols = 0);
 // softmax(Q K^T / sqrt(32)) V per (sequence, head): qkv = ONE h2 image of [T][1152] (Q columns pre-scaled by
 // 1 / sqrt(32) * log2 e, then K, then V; row stride xs), ctx2 = the context as an h2 image (row stride os).
-// cls_only: only query 0 of every sequence, written to row `sequence` of ctx2.
+// cls_only: only query 0 of every sequence, written to row `sequence` of ctx2.  LDS is sized from max_len, which must be at
+// least every sequence's length: a sequence with more key groups of 32 than that gets a NaN context and *flag |= 2.
 void ce_h2_attention(const void* qkv, int64_t xs, const int32_t* cu, int n_seqs, int max_len, void* ctx2, int64_t os, unsigned* flag,
                      int cls_only, hipStream_t st);
 int ce_h2_set_attributes();

@@ -391,14 +391,19 @@ __global__ __launch_bounds__(512, 1) void ce_gemm_h2(const h2_u32x4* __restrict_
     }
     H2_STAMP(te0);
 
-    // ---- epilogue (pairs of values on the packed fp32 pipe; 32-bit byte offsets from the output's base)
+    // ---- epilogue (pairs of values on the packed fp32 pipe).  h2 stores: a 64-bit base per wave and i in scalar registers --
+    // the wave's first chunk (n0 + 64 wf + 16 i) / 8 of each plane; the lo plane starts 2 N os bytes up, past 4 GiB from
+    // os = 1.4 M tokens at N = 1536 -- plus a 32-bit lane offset (chunk kq >> 1, token): < 32 os bytes, os <= CE_H2_MAX_ROWS.
+    // (64-bit lane offsets cost ~4 % of the fp32 forward: the epilogue is vector-bound)
     float amax = 0.f;                                      // max |value split to fp16|: one range test per lane at the end
     {
         // acc[i][j][e]: feature n0 + 64 wf + 16 i + 4 kq + e, token m0 + 64 wt + 16 j + r
-        const uint32_t os32 = (uint32_t)os, lo_plane = (uint32_t)(N >> 3) * os32 * 16u;
+        const int64_t lo_plane = (int64_t)(N >> 3) * os * 16;
+        const uint32_t os16 = (uint32_t)os * 16u;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int f = n0 + 64 * wf + 16 * i + 4 * kq;
+            char* const hib = (char*)out2 + (int64_t)((n0 + 64 * wf + 16 * i) >> 3) * os * 16;
             const h2_f32x4 bv = *reinterpret_cast<const h2_f32x4*>(bias + f);
             const h2_f32x2 b01 = {bv[0], bv[1]}, b23 = {bv[2], bv[3]}, c2 = {CE_H2_INV_SCALE, CE_H2_INV_SCALE};
             const bool scaled = EPI == CE_H2_EPI_H2 && f < qcols;
@@ -425,9 +430,9 @@ __global__ __launch_bounds__(512, 1) void ce_gemm_h2(const h2_u32x4* __restrict_
                     amax = h2_vmax3(amax, __builtin_fabsf(v01[0]), __builtin_fabsf(v01[1]));
                     amax = h2_vmax3(amax, __builtin_fabsf(v23[0]), __builtin_fabsf(v23[1]));
                     // unit (chunk f / 8, token), half kq & 1
-                    const uint32_t off = ((uint32_t)(f >> 3) * os32 + (uint32_t)t) * 16u + 8u * (uint32_t)(kq & 1);
-                    *reinterpret_cast<h2_u32x2*>((char*)out2 + off) = h2_u32x2{__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23)};
-                    *reinterpret_cast<h2_u32x2*>((char*)out2 + lo_plane + off) = h2_u32x2{__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23)};
+                    const uint32_t off = (uint32_t)(kq >> 1) * os16 + (uint32_t)t * 16u + 8u * (uint32_t)(kq & 1);
+                    *reinterpret_cast<h2_u32x2*>(hib + off) = h2_u32x2{__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23)};
+                    *reinterpret_cast<h2_u32x2*>(hib + lo_plane + off) = h2_u32x2{__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23)};
                 }
             }
         }
@@ -649,14 +654,30 @@ __device__ __forceinline__ void h2a_tiles(const h2_u32x4* __restrict__ qkv, int6
     }
 }
 
+// A sequence with more key groups than the launch sized LDS for (max_len below its length: include/rr_hip.h): nothing is staged,
+// the (sequence, head)'s context is NaN in both planes, and the flag gets bit 2 -- a caller error, not a range problem.
+__device__ void h2a_refuse(h2_u32x2* __restrict__ ctx2, int64_t os, int head, int64_t row0, int rows, int i0, int di, unsigned* flag) {
+    h2_u32x4* const ctx = reinterpret_cast<h2_u32x4*>(ctx2);
+    const h2_u32x4 nan = {0x7e007e00u, 0x7e007e00u, 0x7e007e00u, 0x7e007e00u};
+    for (int i = i0; i < 8 * rows; i += di) {               // unit (plane pc >> 2, chunk 4 head + (pc & 3), row)
+        const int pc = i & 7;
+        ctx[(int64_t)((pc >> 2) * (H2_H / 8) + head * 4 + (pc & 3)) * os + row0 + (i >> 3)] = nan;
+    }
+    if (i0 == 0) atomicOr(flag, 2u);
+}
+
 __global__ __launch_bounds__(512, 1) void ce_attention_h2(const h2_u32x4* __restrict__ qkv, int64_t xs, const int32_t* __restrict__ cu,
                                                           h2_u32x2* __restrict__ ctx2, int64_t os, unsigned* __restrict__ flag,
-                                                          int cls_only) {
+                                                          int cls_only, int groups) {
     extern __shared__ __attribute__((aligned(16))) h2_u32x4 h2a_lds[];
     const int seq = blockIdx.x, head = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t0 = cu[seq], S = cu[seq + 1] - t0;
     const int ng = (S + 31) >> 5;
+    if (ng > groups) {                                     // (workgroup-uniform: every wave leaves before the barrier)
+        h2a_refuse(ctx2, os, head, cls_only ? seq : t0, cls_only ? 1 : S, tid, 512, flag);
+        return;
+    }
     // ---- staging: wave w = (K | V: w >> 2, plane (w >> 1) & 1, key half w & 1) of every group; lane = (key, slot)
     {
         const int which = w >> 2, p = (w >> 1) & 1, key = 16 * (w & 1) + (lane >> 2), slot = lane & 3;
@@ -706,7 +727,11 @@ __global__ __launch_bounds__(512) void ce_attention_h2_small(const h2_u32x4* __r
     if (pair >= n_pairs) return;                           // (whole wave; no barrier in this kernel)
     const int seq = pair / 12, head = pair % 12;
     const int t0 = cu[seq], S = cu[seq + 1] - t0;
-    const int ng = (S + 31) >> 5;                          // <= H2A_SMALL_GROUPS (the launcher checked max_len)
+    const int ng = (S + 31) >> 5;
+    if (ng > wave_groups) {                                // (max_len below S: the wave's LDS holds wave_groups groups)
+        h2a_refuse(ctx2, os, head, cls_only ? seq : t0, cls_only ? 1 : S, lane, 64, flag);
+        return;
+    }
     h2_u32x4* const mine = h2a_lds + w * (wave_groups * H2A_GROUP_UNITS);      // (one or two groups per wave: 64 or 128 KB per workgroup)
     // staging: the wave's eight pieces per group, piece j = (K | V: j >> 2, plane (j >> 1) & 1, key half j & 1)
     for (int gi = 0; gi < ng; ++gi)
@@ -735,19 +760,24 @@ __global__ __launch_bounds__(512) void ce_attention_h2_small(const h2_u32x4* __r
     if (bad) atomicOr(flag, 1u);
 }
 
-void ce_h2_attention(const void* qkv, int64_t xs, const int32_t* cu, int n_seqs, int max_len, void* ctx2, int64_t os, unsigned* flag,
-                     int cls_only, hipStream_t st) {
+static void h2_attention(const void* qkv, int64_t xs, const int32_t* cu, int n_seqs, int max_len, void* ctx2, int64_t os, unsigned* flag,
+                         int cls_only, bool small, hipStream_t st) {
     const int groups = (max_len + 31) / 32;
-    static const bool no_small = getenv("RR_CE_H2_ATT_NO_SMALL") != nullptr;      // (A/B)
-    if (groups <= H2A_SMALL_GROUPS && !no_small) {
+    if (groups <= H2A_SMALL_GROUPS && small) {
         const int n_pairs = n_seqs * 12;
         hipLaunchKernelGGL(ce_attention_h2_small, dim3((unsigned)((n_pairs + 7) / 8)), dim3(512), (size_t)8 * groups * H2A_GROUP_UNITS * 16, st,
                            (const h2_u32x4*)qkv, xs, cu, n_pairs, (h2_u32x2*)ctx2, os, flag, cls_only, groups);
         return;
     }
-    const size_t lds = (size_t)(groups < H2A_MAX_GROUPS ? groups : H2A_MAX_GROUPS) * H2A_GROUP_UNITS * 16;
-    hipLaunchKernelGGL(ce_attention_h2, dim3((unsigned)n_seqs, 12), dim3(512), lds, st, (const h2_u32x4*)qkv, xs, cu, (h2_u32x2*)ctx2, os, flag,
-                       cls_only);
+    const int lg = groups < H2A_MAX_GROUPS ? groups : H2A_MAX_GROUPS;
+    hipLaunchKernelGGL(ce_attention_h2, dim3((unsigned)n_seqs, 12), dim3(512), (size_t)lg * H2A_GROUP_UNITS * 16, st, (const h2_u32x4*)qkv, xs, cu,
+                       (h2_u32x2*)ctx2, os, flag, cls_only, lg);
+}
+
+void ce_h2_attention(const void* qkv, int64_t xs, const int32_t* cu, int n_seqs, int max_len, void* ctx2, int64_t os, unsigned* flag,
+                     int cls_only, hipStream_t st) {
+    static const bool no_small = getenv("RR_CE_H2_ATT_NO_SMALL") != nullptr;      // (A/B)
+    h2_attention(qkv, xs, cu, n_seqs, max_len, ctx2, os, flag, cls_only, !no_small, st);
 }
 
 int ce_h2_set_attributes() {
@@ -777,7 +807,8 @@ __global__ __launch_bounds__(256) void ce_h2_unpack_kernel(const h2_u32x4* __res
 // unpacked to fp32 (qscale 0.5 on the first `qcols` features for CE_H2_EPI_H2).  *flag_out = the range flag.
 extern "C" int rr_debug_ce_h2_gemm(int32_t epi, int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_bias,
                                    int32_t qcols, float* d_out, int32_t* flag_out) {
-    RR_REQUIRE(M >= 1 && N % 128 == 0 && K % 32 == 0 && d_x && d_w && d_bias && d_out && flag_out, "rr_debug_ce_h2_gemm: bad arguments");
+    RR_REQUIRE(M >= 1 && rr_round_up(M, 256) <= CE_H2_MAX_ROWS && N % 128 == 0 && K % 32 == 0 && d_x && d_w && d_bias && d_out && flag_out,
+               "rr_debug_ce_h2_gemm: bad arguments");
     if (int rc = ce_h2_set_attributes()) return rc;
     const int64_t xs = rr_round_up(M, 256);
     void *x2 = nullptr, *w2 = nullptr, *o2 = nullptr;
@@ -800,6 +831,63 @@ extern "C" int rr_debug_ce_h2_gemm(int32_t epi, int32_t M, int32_t N, int32_t K,
     RR_HIP_TRY(hipMemcpy(&f, flag, 4, hipMemcpyDeviceToHost));
     *flag_out = (int32_t)f;
     hipFree(x2); hipFree(w2); hipFree(o2); hipFree(flag);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+// tests/test_gpu_k5_h2_kernels.py: the attention by itself.  qkv [T][1152] fp32 (the Q columns already scaled by log2 e /
+// sqrt 32, as the QKV epilogue leaves them) -> ce_h2_pack (row stride round_up(T, 256)) -> attention -> ctx [T][384] fp32, or
+// [n_seqs][384] with cls_only.  kernel = 0: the dispatcher's choice, 1: ce_attention_h2 whatever max_len is.
+extern "C" int rr_debug_ce_h2_attention(const float* d_qkv, int32_t n_tokens, const int32_t* d_cu, int32_t n_seqs, int32_t max_len,
+                                        int32_t cls_only, int32_t kernel, float* d_ctx, int32_t* flag_out) {
+    RR_REQUIRE(n_tokens >= 1 && n_seqs >= 1 && max_len >= 1 && max_len <= 32 * H2A_MAX_GROUPS && (kernel == 0 || kernel == 1) && d_qkv &&
+               d_cu && d_ctx && flag_out, "rr_debug_ce_h2_attention: bad arguments");
+    if (int rc = ce_h2_set_attributes()) return rc;
+    const int64_t xs = rr_round_up(n_tokens, 256);
+    const int rows = cls_only ? n_seqs : n_tokens;
+    const int64_t os = rr_round_up(rows, 256);
+    void *q2 = nullptr, *c2 = nullptr;
+    unsigned* flag = nullptr;
+    RR_HIP_TRY(hipMalloc(&q2, (size_t)xs * 3 * H2_H * 4));
+    RR_HIP_TRY(hipMalloc(&c2, (size_t)os * H2_H * 4));
+    RR_HIP_TRY(hipMalloc((void**)&flag, 4));
+    RR_HIP_TRY(hipMemset(q2, 0, (size_t)xs * 3 * H2_H * 4));
+    RR_HIP_TRY(hipMemset(c2, 0, (size_t)os * H2_H * 4));
+    RR_HIP_TRY(hipMemset(flag, 0, 4));
+    ce_h2_pack(d_qkv, n_tokens, 3 * H2_H, q2, xs, nullptr);
+    h2_attention(q2, xs, d_cu, n_seqs, max_len, c2, os, flag, cls_only ? 1 : 0, kernel == 0, nullptr);
+    const int64_t n = (int64_t)rows * (H2_H / 8);
+    hipLaunchKernelGGL(ce_h2_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const h2_u32x4*)c2, rows, H2_H, os, d_ctx);
+    RR_HIP_TRY(hipDeviceSynchronize());
+    unsigned f = 0;
+    RR_HIP_TRY(hipMemcpy(&f, flag, 4, hipMemcpyDeviceToHost));
+    *flag_out = (int32_t)f;
+    hipFree(q2); hipFree(c2); hipFree(flag);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+// tests/test_gpu_k5_h2_kernels.py: ce_h2_add_ln by itself.  out32 = LayerNorm(y + h) * g + b for T rows of 384 (h copied to
+// out32 first: the kernel updates its residual rows in place), outh2 = the h2 image it wrote, unpacked to fp32.
+extern "C" int rr_debug_ce_h2_add_ln(const float* d_y, const float* d_h, int32_t T, const float* d_g, const float* d_b, float eps, float* d_out32,
+                                     float* d_outh2, int32_t* flag_out) {
+    RR_REQUIRE(T >= 1 && d_y && d_h && d_g && d_b && d_out32 && d_outh2 && flag_out, "rr_debug_ce_h2_add_ln: bad arguments");
+    const int64_t xs = rr_round_up(T, 256);
+    void* hx = nullptr;
+    unsigned* flag = nullptr;
+    RR_HIP_TRY(hipMalloc(&hx, (size_t)xs * H2_H * 4));
+    RR_HIP_TRY(hipMalloc((void**)&flag, 4));
+    RR_HIP_TRY(hipMemset(hx, 0, (size_t)xs * H2_H * 4));
+    RR_HIP_TRY(hipMemset(flag, 0, 4));
+    RR_HIP_TRY(hipMemcpy(d_out32, d_h, (size_t)T * H2_H * 4, hipMemcpyDeviceToDevice));
+    ce_h2_add_ln(d_y, d_out32, T, d_g, d_b, eps, hx, xs, flag, nullptr);
+    const int64_t n = (int64_t)T * (H2_H / 8);
+    hipLaunchKernelGGL(ce_h2_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const h2_u32x4*)hx, T, H2_H, xs, d_outh2);
+    RR_HIP_TRY(hipDeviceSynchronize());
+    unsigned f = 0;
+    RR_HIP_TRY(hipMemcpy(&f, flag, 4, hipMemcpyDeviceToHost));
+    *flag_out = (int32_t)f;
+    hipFree(hx); hipFree(flag);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }

@@ -20,5 +20,11 @@ int rr_debug_ce_h2_stamps(unsigned long long* out16);
 // tests/test_gpu_k5.py: one ce_gemm_h2 product on caller data (pack -> GEMM -> fp32), see the definition
 int rr_debug_ce_h2_gemm(int32_t epi, int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_bias, int32_t qcols,
                         float* d_out, int32_t* flag_out);
+// tests/test_gpu_k5_h2_kernels.py: the fp32 mode's attention (pack -> ce_attention_h2 / _small -> fp32) and add-LayerNorm (fp32
+// rows + the unpacked h2 image) by themselves, see the definitions
+int rr_debug_ce_h2_attention(const float* d_qkv, int32_t n_tokens, const int32_t* d_cu, int32_t n_seqs, int32_t max_len, int32_t cls_only,
+                             int32_t kernel, float* d_ctx, int32_t* flag_out);
+int rr_debug_ce_h2_add_ln(const float* d_y, const float* d_h, int32_t T, const float* d_g, const float* d_b, float eps, float* d_out32,
+                          float* d_outh2, int32_t* flag_out);
 }
 #endif

@@ -166,6 +166,40 @@ int rr_bm25_scores_at_dev(rr_bm25* bm, const int32_t* d_term_ids, const int32_t*
                           int32_t n_queries, const int64_t* d_rows, int32_t pool, int32_t mode,
                           float* d_out, void* stream);
 
+/* BM25Okapi(corpus) built on the GPU (csrc/rr_bm25_build.hip) from a token-id stream instead of
+ * host CSR arrays.  Input contract:
+ *   tok[n_tok] int32 term ids in document order, each in [0, n_terms);
+ *   doc_off[n_src+1] int64, monotone, doc_off[0] = 0, doc_off[n_src] = n_tok (document d is
+ *   tok[doc_off[d] .. doc_off[d+1]), fewer than 2^31 tokens);
+ *   order[n_order] (optional, NULL = the source documents in order): output row j is source
+ *   document order[j], -1 = an empty document, duplicates allowed;
+ *   [row_lo, row_hi): the output rows this handle holds (a shard), local row 0 = row_lo.
+ * inputs_on_device = 1: tok / doc_off / order are device pointers on `device`; 0: host pointers.
+ * stream: the caller's stream (NULL = the device's null stream).  The build runs on the handle's
+ * own stream after everything queued on `stream` so far: inputs written by work queued there
+ * (e.g. torch's current stream) are complete before they are read.  Work on OTHER streams must
+ * be finished, or ordered before `stream`, by the caller.  The call returns when the build is done.
+ * The inputs are checked on the device before any scatter: an id out of range, a decreasing
+ * doc_off or an order entry out of [-1, n_src) returns RR_E_INVALID and creates no handle.
+ * The handle owns its arrays (rr_bm25_destroy frees them).  It scores only after
+ * rr_bm25_set_idf: df and the length sum are those of the whole SOURCE corpus (also for a
+ * shard or a selection), and idf / avgdl are computed from them on the host. */
+int rr_bm25_build(int32_t device, int32_t inputs_on_device, const int32_t* tok, int64_t n_tok,
+                  const int64_t* doc_off, int64_t n_src, int64_t n_terms, const int64_t* order,
+                  int64_t n_order, int64_t row_lo, int64_t row_hi, double k1, double b,
+                  int64_t row_offset, void* stream, rr_bm25** out);
+/* h_df[n_terms]: documents of the source corpus holding each term; h_sizes[5] = n_docs (rows
+ * held), n_terms, nnz, n_src, sum of the source document lengths. */
+int rr_bm25_build_stats(rr_bm25* bm, int64_t* h_df, int64_t* h_sizes);
+/* idf[n_terms] (float64, epsilon floor applied) and avgdl of a built handle (avgdl may be 0 only
+ * when the index holds no entry). */
+int rr_bm25_set_idf(rr_bm25* bm, const double* h_idf, double avgdl);
+/* Copies the CSR arrays out (sizes as for rr_bm25_create); any destination may be NULL (skipped),
+ * a host buffer or a device buffer (blocking copies: a device buffer must have no work pending
+ * on another stream). */
+int rr_bm25_copy_csr(rr_bm25* bm, int64_t* doc_indptr, int32_t* doc_terms, int32_t* doc_tf,
+                     int32_t* doc_len, int64_t* post_indptr, int32_t* post_docs, int32_t* post_tf);
+
 /* ------------------------------------------------------------ K3 fuse + top-k */
 
 typedef struct rr_fuse_params {

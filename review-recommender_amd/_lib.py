@@ -73,6 +73,11 @@ PROTOTYPES = {
     "rr_bm25_get_scores": (C.c_int, [c_vp, c_vp, c_i32, c_vp]),
     "rr_bm25_scores_at": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp]),
     "rr_bm25_scores_at_dev": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "rr_bm25_build": (C.c_int, [c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64,
+                                c_f64, c_f64, c_i64, c_vp, P(c_vp)]),
+    "rr_bm25_build_stats": (C.c_int, [c_vp, c_vp, c_vp]),
+    "rr_bm25_set_idf": (C.c_int, [c_vp, c_vp, c_f64]),
+    "rr_bm25_copy_csr": (C.c_int, [c_vp] + [c_vp] * 7),
     "rr_fuse_topk_dev": (C.c_int, [c_vp, P(FuseParams), c_i32] + [c_vp] * 9 + [c_vp] * 3 + [c_vp]),
     "rr_fuse_topk": (C.c_int, [c_vp, P(FuseParams), c_i32] + [c_vp] * 9 + [c_vp] * 3),
     "rr_index_gather_meta_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),

@@ -8,7 +8,9 @@ package's default parameters k1=1.5, b=0.75, epsilon=0.25.
 Host side (this file): vocabulary in first-appearance order, per-document term
 frequencies, document lengths, avgdl, idf with the epsilon floor -- computed once
 at load, in float64 with ``math.log`` per term and a running sum in vocabulary
-order, like the package.  Device side (csrc/rr_bm25.hip): every per-query operation.
+order, like the package.  ``build_bm25_index`` builds the same CSR arrays on the
+GPU instead (csrc/rr_bm25_build.hip); only the vocabulary ids and idf stay on the
+host.  Device side (csrc/rr_bm25.hip): every per-query operation.
 The corpus is stored twice on the device, 8 bytes per posting each way:
 postings (term -> ascending docs) for ``get_scores`` and a forward list
 (doc -> ascending terms) for scoring a candidate pool.
@@ -102,6 +104,21 @@ class BM25Corpus:
         cat = (lambda xs: np.concatenate(xs) if xs else np.zeros(0, dtype=np.int32))
         return cls(indptr, cat(terms), cat(tfs), doc_len, len(vocab), vocab=vocab, **kw)
 
+    @classmethod
+    def from_ids(cls, tok, doc_off, n_terms: int, **kw) -> "BM25Corpus":
+        """The corpus of an integer-id token stream (``factorize_corpus``): the arrays ``from_corpus`` makes
+        from the token lists the ids came from, computed with numpy (a sort by (doc, term) and run lengths)."""
+        tok = np.asarray(tok, dtype=np.int64)
+        off = np.asarray(doc_off, dtype=np.int64)
+        n_docs = len(off) - 1
+        doc = np.repeat(np.arange(n_docs, dtype=np.int64), np.diff(off))
+        keys, tf = np.unique(doc * max(int(n_terms), 1) + tok, return_counts=True)
+        e_doc = keys // max(int(n_terms), 1)
+        indptr = np.zeros(n_docs + 1, dtype=np.int64)
+        np.cumsum(np.bincount(e_doc, minlength=n_docs), out=indptr[1:])
+        return cls(indptr, (keys - e_doc * max(int(n_terms), 1)).astype(np.int32), tf.astype(np.int32),
+                   np.diff(off).astype(np.int32), int(n_terms), **kw)
+
     def _derive(self, indptr, terms, tf, doc_len) -> "BM25Corpus":
         return BM25Corpus(indptr, terms, tf, doc_len, self.n_terms, idf=self.idf,
                           avgdl=self.avgdl, k1=self.k1, b=self.b, epsilon=self.epsilon,
@@ -162,6 +179,31 @@ class BM25Index:
             C.byref(handle)), "rr_bm25_create")
         self._h = handle
 
+    @classmethod
+    def _adopt(cls, handle, corpus: Optional[BM25Corpus], sizes, df: np.ndarray, device: int,
+               row_offset: int) -> "BM25Index":
+        """An index over the arrays rr_bm25_build left on the device (no second upload)."""
+        self = cls.__new__(cls)
+        self._h = handle
+        self.corpus = corpus
+        self.n_docs, self.n_terms, self.nnz = int(sizes[0]), int(sizes[1]), int(sizes[2])
+        self.n_src, self.length_sum = int(sizes[3]), int(sizes[4])
+        self.df = df
+        self.row_offset, self.device = int(row_offset), int(device)
+        return self
+
+    def copy_csr(self, out: Optional[dict] = None) -> dict:
+        """The device arrays copied to host numpy arrays (``out``: the subset of them to copy, preallocated)."""
+        n, t, z = self.n_docs, self.n_terms, self.nnz
+        o = out or {"doc_indptr": np.empty(n + 1, np.int64), "doc_terms": np.empty(z, np.int32),
+                    "doc_tf": np.empty(z, np.int32), "doc_len": np.empty(n, np.int32),
+                    "post_indptr": np.empty(t + 1, np.int64), "post_docs": np.empty(z, np.int32),
+                    "post_tf": np.empty(z, np.int32)}
+        names = ("doc_indptr", "doc_terms", "doc_tf", "doc_len", "post_indptr", "post_docs", "post_tf")
+        _lib.check(_lib.load().rr_bm25_copy_csr(self._h, *[_lib.ptr(o[k]) if k in o else None for k in names]),
+                   "rr_bm25_copy_csr")
+        return o
+
     def term_ids(self, tokens: Sequence[str]) -> np.ndarray:
         return self.corpus.term_ids(tokens)
 
@@ -208,15 +250,120 @@ class BM25Index:
             pass
 
 
+def doc_offsets(corpus: Sequence[Sequence]) -> np.ndarray:
+    """doc_off[n + 1] (int64) of the flattened token stream: document d is tokens [doc_off[d], doc_off[d + 1])."""
+    off = np.zeros(len(corpus) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, corpus), dtype=np.int64, count=len(corpus)), out=off[1:])
+    return off
+
+
+def factorize_corpus(corpus: Sequence[Sequence[str]]):
+    """-> (tok int32[T], doc_off int64[n + 1], vocab): vocabulary ids in first-appearance order, the ids
+    ``BM25Corpus.from_corpus`` gives.  ``pd.factorize`` does the hashing; a token that is not a ``str``
+    (factorize takes None / NaN for missing values) sends the corpus through the dict loop instead."""
+    import itertools
+    import pandas as pd
+    off = doc_offsets(corpus)
+    T = int(off[-1])
+    flat = np.fromiter(itertools.chain.from_iterable(corpus), dtype=object, count=T)
+    codes, uniques = pd.factorize(flat, sort=False)
+    if not (codes < 0).any() and all(type(u) is str for u in uniques):
+        vocab = {u: i for i, u in enumerate(uniques)}
+        return np.ascontiguousarray(codes, dtype=np.int32), off, vocab
+    vocab: Dict = {}
+    tok = np.empty(T, dtype=np.int32)
+    for i, w in enumerate(flat.tolist()):
+        t = vocab.get(w)
+        if t is None:
+            t = vocab[w] = len(vocab)
+        tok[i] = t
+    return tok, off, vocab
+
+
+def build_bm25_index(corpus: Sequence[Sequence[str]], *, device: int = 0, order=None, rows=None,
+                     row_offset: int = 0, k1: float = 1.5, b: float = 0.75, epsilon: float = 0.25,
+                     host_copy: bool = True) -> BM25Index:
+    """``BM25Corpus.from_corpus(corpus).select(order).slice(lo, hi).to_device(row_offset=...)`` with the
+    index built on the GPU (csrc/rr_bm25_build.hip): vocabulary ids on the host (factorize_corpus),
+    everything else on the device.  ``rows = (lo, hi)`` of the selected rows; idf and avgdl stay those
+    of the whole corpus."""
+    tok, off, vocab = factorize_corpus(corpus)
+    return build_bm25_index_ids(tok, off, len(vocab), device=device, order=order, rows=rows,
+                                row_offset=row_offset, k1=k1, b=b, epsilon=epsilon, vocab=vocab,
+                                host_copy=host_copy)
+
+
+def build_bm25_index_ids(tok, doc_off, n_terms: int, *, device: int = 0, order=None, rows=None,
+                         row_offset: int = 0, k1: float = 1.5, b: float = 0.75, epsilon: float = 0.25,
+                         vocab: Optional[Dict[str, int]] = None, host_copy: bool = True) -> BM25Index:
+    """The same from integer ids: ``tok`` int32[T] in document order, ``doc_off`` int64[n_src + 1], as numpy
+    arrays or tensors on ``device``.  ``host_copy=False`` leaves ``.corpus`` None (no copy of the
+    arrays back to host memory)."""
+    import torch
+    if isinstance(order, np.ndarray) and len(order) == len(doc_off) - 1 and np.array_equal(order, np.arange(len(order))):
+        order = None                                              # (the identity: no second build)
+    on_dev = any(isinstance(a, torch.Tensor) and a.device.type == "cuda" for a in (tok, doc_off, order))
+    keep = []                                                     # (the buffers the call reads)
+
+    def arg(a, np_dtype, t_dtype):
+        if a is None:
+            return None, 0
+        if on_dev:
+            t = torch.as_tensor(a).to(device=f"cuda:{device}", dtype=t_dtype).contiguous()
+            keep.append(t)
+            return C.c_void_p(t.data_ptr() if t.numel() else 0), t.numel()
+        h = np.ascontiguousarray(a, dtype=np_dtype)
+        keep.append(h)
+        return (_lib.ptr(h) if h.size else None), h.size
+
+    p_tok, T = arg(tok, np.int32, torch.int32)
+    p_off, n_off = arg(doc_off, np.int64, torch.int64)
+    p_ord, n_ord = arg(order, np.int64, torch.int64)
+    n_src = n_off - 1
+    n_rows = n_ord if order is not None else n_src
+    lo, hi = (0, n_rows) if rows is None else (int(rows[0]), int(rows[1]))
+    lib = _lib.load()
+    handle = C.c_void_p()
+    # device inputs (and the conversions above) are queued on torch's current stream: the build waits for that stream
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream) if on_dev else None
+    _lib.check(lib.rr_bm25_build(device, int(on_dev), p_tok, T, p_off, n_src, int(n_terms), p_ord, n_ord, lo, hi,
+                                 float(k1), float(b), int(row_offset), stream, C.byref(handle)), "rr_bm25_build")
+    try:
+        sizes = np.zeros(5, dtype=np.int64)
+        df = np.empty(int(n_terms), dtype=np.int64)
+        _lib.check(lib.rr_bm25_build_stats(handle, _lib.ptr(df), _lib.ptr(sizes)), "rr_bm25_build_stats")
+        idf = idf_with_floor(df, int(sizes[3]), epsilon)          # the host's float64 sum order
+        avgdl = int(sizes[4]) / int(sizes[3])                     # BM25Corpus.__init__
+        _lib.check(lib.rr_bm25_set_idf(handle, _lib.ptr(idf), avgdl), "rr_bm25_set_idf")
+    except Exception:
+        lib.rr_bm25_destroy(handle)
+        raise
+    index = BM25Index._adopt(handle, None, sizes, df, device, row_offset)
+    if host_copy:
+        a = index.copy_csr({"doc_indptr": np.empty(index.n_docs + 1, np.int64),
+                            "doc_terms": np.empty(index.nnz, np.int32), "doc_tf": np.empty(index.nnz, np.int32),
+                            "doc_len": np.empty(index.n_docs, np.int32)})
+        index.corpus = BM25Corpus(a["doc_indptr"], a["doc_terms"], a["doc_tf"], a["doc_len"], int(n_terms),
+                                  idf=idf, avgdl=avgdl, k1=k1, b=b, epsilon=epsilon, vocab=vocab)
+    return index
+
+
 class BM25Okapi:
     """Drop-in for ``rank_bm25.BM25Okapi`` on the calls the reference makes:
     ``BM25Okapi(corpus)`` and ``get_scores(tokens) -> float64[N]``."""
 
     def __init__(self, corpus: Sequence[Sequence[str]], tokenizer=None, k1: float = 1.5,
-                 b: float = 0.75, epsilon: float = 0.25, device: int = 0):
+                 b: float = 0.75, epsilon: float = 0.25, device: int = 0, build: str = "device"):
+        """build: "device" = the index built on the GPU (build_bm25_index), "host" = BM25Corpus.from_corpus
+        + upload; the two give bitwise the same index."""
         if tokenizer is not None:
             corpus = [tokenizer(doc) for doc in corpus]
-        self.index = BM25Corpus.from_corpus(corpus, k1=k1, b=b, epsilon=epsilon).to_device(device)
+        if build == "device":
+            self.index = build_bm25_index(corpus, device=device, k1=k1, b=b, epsilon=epsilon)
+        elif build == "host":
+            self.index = BM25Corpus.from_corpus(corpus, k1=k1, b=b, epsilon=epsilon).to_device(device)
+        else:
+            raise ValueError("build must be 'device' or 'host'")
         self.corpus_size = self.index.n_docs
         self.avgdl = self.index.corpus.avgdl
         self.k1, self.b, self.epsilon = k1, b, epsilon

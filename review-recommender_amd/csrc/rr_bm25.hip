@@ -294,7 +294,7 @@ extern "C" int rr_bm25_destroy(rr_bm25* bm) {
     if (bm->owns_arrays) {
         hipFree(bm->d_post_indptr); hipFree(bm->d_post_docs); hipFree(bm->d_post_tf);
         hipFree(bm->d_doc_indptr); hipFree(bm->d_doc_terms); hipFree(bm->d_doc_tf);
-        hipFree(bm->d_doc_len); hipFree(bm->d_idf);
+        hipFree(bm->d_doc_len); hipFree(bm->d_idf); hipFree(bm->d_df);
     }
     hipFree(bm->d_scores);
     hipFree(bm->d_dirty);
@@ -309,6 +309,7 @@ extern "C" int rr_bm25_get_scores(rr_bm25* bm, const int32_t* h_term_ids, int32_
                "rr_bm25_get_scores: NULL argument");
     RR_REQUIRE(n_terms_in_query >= 0 && n_terms_in_query <= 4096,
                "rr_bm25_get_scores: %d query tokens out of [0,4096]", n_terms_in_query);
+    if (!bm->d_idf) { rr_set_error("rr_bm25_get_scores: no idf yet (rr_bm25_set_idf)"); return RR_E_STATE; }
     std::lock_guard<std::mutex> lk(bm->mu);
     RR_HIP_TRY(hipSetDevice(bm->device));
     const unsigned grid = (unsigned)((bm->n_docs + RR_SLICE - 1) / RR_SLICE);
@@ -347,6 +348,7 @@ extern "C" int rr_bm25_scores_at_dev(rr_bm25* bm, const int32_t* d_term_ids,
     RR_REQUIRE(n_queries >= 1 && n_queries <= RR_MAX_BATCH && pool >= 1 && pool <= 8 * RR_MAX_POOL,
                "rr_bm25_scores_at_dev: n_queries %d / pool %d out of range", n_queries, pool);
     RR_REQUIRE(mode == 0 || mode == 1, "rr_bm25_scores_at_dev: mode must be 0 (forward) or 1 (postings)");
+    if (!bm->d_idf) { rr_set_error("rr_bm25_scores_at_dev: no idf yet (rr_bm25_set_idf)"); return RR_E_STATE; }
     RR_HIP_TRY(hipSetDevice(bm->device));
     hipStream_t st = (hipStream_t)stream;  // NULL = the device's default stream
     dim3 grid((unsigned)((pool + RR_AT_CANDS - 1) / RR_AT_CANDS), (unsigned)n_queries);

@@ -134,6 +134,8 @@ struct rr_bm25 {
     int32_t* d_doc_tf = nullptr;
     int32_t* d_doc_len = nullptr;
     double* d_idf = nullptr;
+    int64_t* d_df = nullptr;      // rr_bm25_build: df over the source corpus (n_terms); NULL for rr_bm25_create*
+    int64_t n_src = 0, length_sum = 0;   // rr_bm25_build: documents and tokens of the source corpus
     double avgdl = 1.0, k1 = 1.5, b = 0.75;
     bool owns_arrays = true;
     double* d_scores = nullptr;   // n_docs, scratch of get_scores (all zeros outside the slices d_dirty marks)

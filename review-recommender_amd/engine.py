@@ -25,7 +25,7 @@ import numpy as np
 import pandas as pd
 
 from . import _lib, text
-from .bm25 import BM25Corpus, BM25Index
+from .bm25 import BM25Corpus, BM25Index, build_bm25_index_ids, factorize_corpus
 from .index import MAX_POOL, ProductIndex
 
 APP_POOL_FLOOR = 150    # app/app_product_search.py:253
@@ -440,13 +440,18 @@ class SearchEngine:
     bm25_blob: the ``{"skus", "corpus"}`` dict of product_bm25.pkl, or None.
     encoder: object with ``encode([query], normalize_embeddings=True)`` (SentenceTransformer API).
     cross_encoder: object with ``predict(pairs, batch_size=64, show_progress_bar=False)``.
+    bm25_build: "device" builds the BM25 index on the GPU (bm25.build_bm25_index), "host" with
+    BM25Corpus.from_corpus; the two give bitwise the same index.
     """
 
     def __init__(self, meta: pd.DataFrame, embeddings: np.ndarray, bm25_blob: Optional[dict] = None,
                  *, encoder=None, cross_encoder=None, device: int = 0, normalize: bool = True,
-                 flavour: str = "app", dtype: str = "f32", reviews: Optional[Tuple] = None):
+                 flavour: str = "app", dtype: str = "f32", reviews: Optional[Tuple] = None,
+                 bm25_build: str = "device"):
         if flavour not in ("app", "cli"):
             raise ValueError("flavour must be 'app' or 'cli'")
+        if bm25_build not in ("device", "host"):
+            raise ValueError("bm25_build must be 'device' or 'host'")
         if len(meta) != embeddings.shape[0]:
             # app/app_product_search.py:104-107, app/test.py:141-142: hard error
             raise ValueError(f"metadata has {len(meta)} rows but embeddings have "
@@ -463,18 +468,35 @@ class SearchEngine:
         r = pd.to_numeric(self.meta.get("avg_stars", nan), errors="coerce").values
         self.index.set_meta(n, r)
         self._texts = self.meta["agg_text"].astype(str)
-        self.bm25_corpus: Optional[BM25Corpus] = None
+        self._bm25_corpus: Optional[BM25Corpus] = None
+        self._bm25_source = None
         bm25_index = None
         if bm25_blob:
-            self.bm25_corpus = BM25Corpus.from_corpus(bm25_blob["corpus"])
-            aligned = self.bm25_corpus.select(self._align_bm25([str(s) for s in bm25_blob["skus"]]))
-            bm25_index = aligned.to_device(device)
+            order = self._align_bm25([str(s) for s in bm25_blob["skus"]])
+            if bm25_build == "device":       # the index built on the GPU (csrc/rr_bm25_build.hip): the same arrays
+                # kept for bm25_corpus: the ids (4 B per token, no reference to the blob's token lists)
+                tok, off, vocab = factorize_corpus(bm25_blob["corpus"])
+                self._bm25_source = (tok, off, vocab)
+                bm25_index = build_bm25_index_ids(tok, off, len(vocab), device=device, order=order, vocab=vocab)
+            else:
+                self._bm25_corpus = BM25Corpus.from_corpus(bm25_blob["corpus"])
+                bm25_index = self._bm25_corpus.select(order).to_device(device)
         self.searcher = HybridSearcher(self.index, bm25_index)
         # reviews = (frame with sku/text/stars, (n_reviews, dim) embeddings): reviews_with_embeddings.parquet
         self.reviews = None
         if reviews is not None:
             from .reviews import ReviewIndex
             self.reviews = ReviewIndex(reviews[0], reviews[1], self.meta["sku"].astype(str).tolist(), device=device)
+
+    @property
+    def bm25_corpus(self) -> Optional[BM25Corpus]:
+        """The blob's corpus on the host, in blob order.  When the index was built on the GPU it is made on first use
+        from the token ids kept at load (BM25Corpus.from_ids: the arrays from_corpus makes), which are then dropped."""
+        if self._bm25_corpus is None and self._bm25_source is not None:
+            tok, off, vocab = self._bm25_source
+            self._bm25_corpus = BM25Corpus.from_ids(tok, off, len(vocab), vocab=vocab)
+            self._bm25_source = None
+        return self._bm25_corpus
 
     @classmethod
     def from_artifacts(cls, data_dir, **kw) -> "SearchEngine":

@@ -202,6 +202,11 @@ int rr_bm25_copy_csr(rr_bm25* bm, int64_t* doc_indptr, int32_t* doc_terms, int32
 
 /* ------------------------------------------------------------ K3 fuse + top-k */
 
+/* Candidates K3 takes per query (rr_fuse_params.n_candidates).  A search over `world` row shards merges
+ * world x pool of them, so world x pool <= 4096: 8 shards take a pool of at most 512
+ * (ShardedSearcher refuses a larger one with ValueError before any launch or collective). */
+#define RR_MAX_CANDIDATES 4096
+
 typedef struct rr_fuse_params {
     double w_dense, w_bm25, w_rerank, w_prior, w_best;  /* run_search weights */
     double prior_C;          /* Bayesian prior strength (prior_C) */

@@ -94,6 +94,87 @@ def best_snippets_oracle(reviews: pd.DataFrame, embeddings: np.ndarray, qvec: np
         return {}
 
 
+def fuse_pool_oracle(dense_raw: np.ndarray, bm25_raw: Optional[np.ndarray], n: np.ndarray,
+                     avg_stars: np.ndarray, rerank_k: int, rerank_raw: Optional[np.ndarray],
+                     best_raw: np.ndarray, has_best: bool, gate: np.ndarray, *,
+                     w_dense: float, w_bm25: float, w_rerank: float, w_prior: float,
+                     w_best: float, prior_C: float, min_reviews: int,
+                     trust_sat: int = APP_TRUST_SAT, flavour: str = "app") -> Dict[str, np.ndarray]:
+    """The fused block of run_search (app/app_product_search.py:256-309; CLI app/test.py:250-309)
+    over ONE query's candidate pool, from the ``_dense`` min-max to ``_final``.
+
+    dense_raw: raw cosine scores (float32); bm25_raw: raw BM25 scores (float32), or None for the
+    CLI without a BM25 artefact (``cand["_bm25"] = 0.0``, a float64 column); n / avg_stars: the
+    pool's n_reviews (NaN already filled with 0) and avg_stars (NaN kept); rerank_raw: raw
+    reranker scores of the first min(rerank_k, pool) rows (None: no reranker, zeros); best_raw:
+    best review score per row, min-maxed only when ``has_best`` (snippets were found); gate: the
+    gate factors.  Returns the columns _dense, _bm25, _prior, _rerank, _best, _gate, _trust (app
+    flavour only) and _final, in the order run_search assigns them, with the reference's dtypes."""
+    assert flavour in ("app", "cli")
+    app = flavour == "app"
+    pool = len(dense_raw)
+    cand: Dict[str, np.ndarray] = {}
+    cand["_dense"] = P.minmax_normalize(dense_raw.astype(np.float32),
+                                        empty_passthrough=not app)
+
+    if app:
+        cand["_bm25"] = P.minmax_normalize(bm25_raw)
+    elif bm25_raw is not None:
+        cand["_bm25"] = P.minmax_normalize(bm25_raw, empty_passthrough=True)
+    else:
+        cand["_bm25"] = np.full(pool, 0.0)
+
+    r = avg_stars
+    prior_rating = P.bayesian_prior(r, n, prior_strength=prior_C)
+    prior_volume = np.log1p(n) / (np.log1p(n).max() + 1e-9)
+    cand["_prior"] = P.minmax_normalize(prior_rating, empty_passthrough=not app) * 0.7 \
+        + 0.3 * prior_volume
+
+    if rerank_k > 0:
+        rr_k = min(rerank_k, pool)
+        if rerank_raw is None:
+            rr = np.zeros(rr_k, dtype=np.float32)
+        else:
+            rr = np.array(rerank_raw[:rr_k], dtype=np.float32)
+        z = np.zeros(pool, dtype=np.float32)
+        z[:rr_k] = P.minmax_normalize(rr, empty_passthrough=not app)
+        cand["_rerank"] = z
+    else:
+        cand["_rerank"] = np.full(pool, 0.0)
+
+    best_contrib = np.zeros(pool, dtype=np.float32)
+    if has_best:
+        best_contrib = P.minmax_normalize(best_raw, empty_passthrough=not app)
+    cand["_best"] = best_contrib
+
+    cand["_gate"] = np.asarray(gate, dtype=np.float32)
+    if app:
+        cand["_trust"] = P.trust_score_from_reviews(n, min_reviews=min_reviews,
+                                                    saturation=trust_sat)
+
+    final = (w_dense * cand["_dense"] + w_bm25 * cand["_bm25"]
+             + w_rerank * cand["_rerank"] + w_prior * cand["_prior"]
+             + w_best * cand["_best"]).astype(np.float32)
+    if app:
+        final = final * cand["_trust"] * cand["_gate"]
+    else:
+        final = final * cand["_gate"]
+    cand["_final"] = final
+    return cand
+
+
+def final_order_oracle(final: np.ndarray, k: int) -> np.ndarray:
+    """Pool positions of the top k: final desc (-0.0 == +0.0), ties by pool position, NaN last."""
+    f = np.asarray(final)
+    return np.lexsort((np.arange(len(f)), np.isnan(f), -f.astype(np.float64)))[:k]
+
+
+def merge_order_oracle(rows: np.ndarray, dense: np.ndarray, pool: int) -> np.ndarray:
+    """The shard merge: indices of the best ``pool`` candidates by (dense desc, NaN as -inf; row asc)."""
+    d = np.asarray(dense)
+    return np.lexsort((rows, -np.where(np.isnan(d), -np.inf, d)))[:pool]
+
+
 def run_search_oracle(
     *, query: str, qvec: np.ndarray, meta: pd.DataFrame, V: np.ndarray,
     bm25=None, bm25_skus: Optional[Sequence[str]] = None,
@@ -114,72 +195,49 @@ def run_search_oracle(
 
     cand_idx, dense_scores = cosine_similarity_search(qvec, V, pool)
     cand = meta.iloc[cand_idx].reset_index(drop=True).copy()
-    cand["_dense"] = P.minmax_normalize(dense_scores.astype(np.float32),
-                                        empty_passthrough=not app)
 
     if app:
-        raw = bm25_for_candidates_app(bm25, bm25_skus, query,
-                                      cand["sku"].astype(str).tolist())
-        cand["_bm25"] = P.minmax_normalize(raw)
+        bm25_raw = bm25_for_candidates_app(bm25, bm25_skus, query,
+                                           cand["sku"].astype(str).tolist())
     elif bm25 is not None:
-        raw = bm25_for_candidates_cli(bm25, bm25_skus,
-                                      meta["sku"].astype(str).tolist(), query, cand_idx)
-        cand["_bm25"] = P.minmax_normalize(raw, empty_passthrough=True)
+        bm25_raw = bm25_for_candidates_cli(bm25, bm25_skus,
+                                           meta["sku"].astype(str).tolist(), query, cand_idx)
     else:
-        cand["_bm25"] = 0.0
+        bm25_raw = None                      # `cand["_bm25"] = 0.0`
 
     n = pd.to_numeric(cand.get("n_reviews", pd.Series([np.nan] * len(cand))),
                       errors="coerce").fillna(0).values
     r = pd.to_numeric(cand.get("avg_stars", pd.Series([np.nan] * len(cand))),
                       errors="coerce").fillna(np.nan).values
-    prior_rating = P.bayesian_prior(r, n, prior_strength=prior_C)
-    prior_volume = np.log1p(n) / (np.log1p(n).max() + 1e-9)
-    cand["_prior"] = P.minmax_normalize(prior_rating, empty_passthrough=not app) * 0.7 \
-        + 0.3 * prior_volume
 
-    if rerank_k > 0:
+    rr = None
+    if rerank_k > 0 and rerank_fn is not None:
         rr_k = min(rerank_k, len(cand))
         texts = cand["agg_text"].astype(str).str.slice(0, 2000).tolist()[:rr_k]
-        if rerank_fn is None:
-            rr = np.zeros(rr_k, dtype=np.float32)
-        else:
-            rr = np.array(rerank_fn([(query, t) for t in texts]), dtype=np.float32)
-        z = np.zeros(len(cand), dtype=np.float32)
-        z[:rr_k] = P.minmax_normalize(rr, empty_passthrough=not app)
-        cand["_rerank"] = z
-    else:
-        cand["_rerank"] = 0.0
+        rr = np.array(rerank_fn([(query, t) for t in texts]), dtype=np.float32)
 
     # app/app_product_search.py:285-294 (CLI: app/test.py:273-289)
     snips = {}
     if use_snips and reviews is not None:
         snips = best_snippets_oracle(reviews[0], reviews[1], qvec, cand["sku"].astype(str).tolist(),
                                      max_rows=max_scan, text_cut=600 if app else 400)
-    best_contrib = np.zeros(len(cand), dtype=np.float32)
+    best_raw = np.zeros(len(cand), dtype=np.float32)
     if snips:
         for i, sk in enumerate(cand["sku"].astype(str).tolist()):
             v = snips.get(sk, {}).get("score")
             if v is not None:
-                best_contrib[i] = v
-        best_contrib = P.minmax_normalize(best_contrib, empty_passthrough=not app)
-    cand["_best"] = best_contrib
+                best_raw[i] = v
 
     groups = P.build_gate_groups(query)
     gate = [P.calculate_gate_factor(t, groups, penalty=gate_penalty)[0]
             for t in cand["agg_text"].astype(str).str.slice(0, 6000).tolist()]
-    cand["_gate"] = np.array(gate, dtype=np.float32)
-    if app:
-        cand["_trust"] = P.trust_score_from_reviews(n, min_reviews=min_reviews,
-                                                    saturation=APP_TRUST_SAT)
 
-    final = (w_dense * cand["_dense"].values + w_bm25 * cand["_bm25"].values
-             + w_rerank * cand["_rerank"].values + w_prior * cand["_prior"].values
-             + w_best * cand["_best"].values).astype(np.float32)
-    if app:
-        final = final * cand["_trust"].values * cand["_gate"].values
-    else:
-        final = final * cand["_gate"].values
-    cand["_final"] = final
+    fused = fuse_pool_oracle(dense_scores, bm25_raw, n, r, rerank_k, rr, best_raw, bool(snips),
+                             np.array(gate, dtype=np.float32), w_dense=w_dense, w_bm25=w_bm25,
+                             w_rerank=w_rerank, w_prior=w_prior, w_best=w_best, prior_C=prior_C,
+                             min_reviews=min_reviews, trust_sat=APP_TRUST_SAT, flavour=flavour)
+    for name, col in fused.items():
+        cand[name] = col
     cand["_row"] = cand_idx  # oracle-only helper column: global row of each hit
 
     out = cand.sort_values("_final", ascending=False).head(k).reset_index(drop=True)

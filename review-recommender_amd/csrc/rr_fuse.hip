@@ -21,7 +21,7 @@
 #include "rr_common.h"
 
 #define RR_FUSE_THREADS 256
-#define RR_FUSE_MAXCAND 4096
+#define RR_FUSE_MAXCAND RR_MAX_CANDIDATES
 
 struct rr_fuse_dev_params {
     rr_fuse_params p;
@@ -265,8 +265,12 @@ __global__ __launch_bounds__(RR_FUSE_THREADS) void rr_fuse(
         if (g_n) {
             c_n[i] = at.get(g_n, s); c_avg[i] = at.get(g_avg, s); c_l1p[i] = at.get(g_l1p, s);
         } else {
+            // a row outside this shard reads nothing: (0, NaN, 0), as rr_gather_meta gives it
             const int64_t local = row - fp.row_offset;
-            c_n[i] = ix_n[local]; c_avg[i] = ix_avg[local]; c_l1p[i] = ix_l1p[local];
+            const bool ok = local >= 0 && local < fp.n_rows;
+            c_n[i] = ok ? ix_n[local] : 0.0;
+            c_avg[i] = ok ? ix_avg[local] : (double)NAN;
+            c_l1p[i] = ok ? ix_l1p[local] : 0.0;
         }
         out_rows[(int64_t)q * pool + i] = row;
     }
@@ -365,7 +369,9 @@ __global__ __launch_bounds__(RR_FUSE_THREADS) void rr_fuse(
         for (int i = tid; i < n_sort; i += RR_FUSE_THREADS) {
             uint64_t key = 0;
             if (i < pool) {
-                const float f = c_final[i];
+                // + 0.0f turns -0.0 into +0.0: numpy orders the two as equal (a negative blend times a trust or gate of 0
+                // gives -0.0), so they tie and the slot decides
+                const float f = c_final[i] + 0.0f;
                 // NaN sorts below every number (pandas na_position='last'); slot breaks ties
                 const uint32_t fk = (f == f) ? rr_f2key(f) : 0u;
                 key = ((uint64_t)fk << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)i);

@@ -11,6 +11,7 @@ from . import _lib
 
 MAX_POOL = 2048     # RR_MAX_POOL
 MAX_BATCH = 1024    # RR_MAX_BATCH
+MAX_CANDIDATES = 4096   # RR_MAX_CANDIDATES: K3 merges at most this many candidates per query
 DTYPES = {"f32": 0, "bf16": 1}   # RR_DTYPE_*
 
 

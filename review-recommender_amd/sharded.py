@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _lib
 from .engine import FusionWeights, HybridSearcher
+from .index import MAX_CANDIDATES
 
 
 def shard_bounds(n_rows: int, world: int, rank: int) -> Tuple[int, int]:
@@ -374,6 +375,7 @@ class ShardedSearcher:
         w = weights or FusionWeights()
         B = q_dev.shape[0]
         pool = min(max(k, rerank_k, pool_floor), self.n_total)
+        self._check_merge_size(pool)
         pool_local = min(pool, self.s.index.n_rows)
         rr_k = min(rerank_k, pool)
         if self.world > 1:
@@ -412,6 +414,7 @@ class ShardedSearcher:
         w = weights or FusionWeights()
         B = q_dev.shape[0]
         pool = min(max(k, rerank_k, pool_floor), self.n_total)
+        self._check_merge_size(pool)
         pool_local = min(pool, self.s.index.n_rows)
         rr_k = min(rerank_k, pool)
         if self.world > 1:
@@ -427,6 +430,15 @@ class ShardedSearcher:
         lay, buf = self.local_payload(q_dev, tl, pool_local, bm25_mode)
         pending = exchange_start(buf, self.world, self.group)
         return PendingBatch(B, k, pool, pool_local, rr_k, w, lay, buf, pending, gate_fn, rerank_fn)
+
+    def _check_merge_size(self, pool: int) -> None:
+        """K3 merges world x pool candidates per query and takes at most MAX_CANDIDATES (include/rr_hip.h:
+        RR_MAX_CANDIDATES).  Checked before any launch or collective; every rank computes the same test, so no rank
+        is left waiting in a collective the others never join."""
+        if self.world * pool > MAX_CANDIDATES:
+            raise ValueError(f"{self.world} shards x pool {pool} = {self.world * pool} candidates per query exceed "
+                             f"the merge limit of {MAX_CANDIDATES}: the pool may be at most "
+                             f"{MAX_CANDIDATES // self.world} with {self.world} shards")
 
     # ------------------------------------------------------------------ the overlapped form
     def _flush_overlap(self) -> None:

@@ -114,3 +114,43 @@ def test_get_scores_writes_only_the_slices_it_touches_and_stays_exact_call_after
         want = ora.get_scores([int(t) for t in q if 0 <= t < vocab])     # (unknown ids add +0.0: idf.get -> 0)
         assert got.dtype == np.float64 and np.array_equal(got, want), q[:4]
     assert np.count_nonzero(dev.get_scores_ids(rare)) == int(np.count_nonzero(ora.get_scores(rare.tolist()))) <= 6
+
+
+def test_candidate_scores_at_the_kernels_limits():
+    """rr_bm25_scores_at in both modes, bitwise against the oracle, at the limits of one call: pool 2048, a batch of
+    1024 queries of 0, 1, 64, 65 and 200 tokens (unknown ids and repeats among them), empty documents, a document of
+    400 distinct terms, duplicate candidate rows and rows outside the shard (score 0)."""
+    n, vocab, lo, hi, big = 6000, 3000, 1000, 5000, 1717
+    rng = np.random.default_rng(44)
+    big_toks = np.repeat(rng.permutation(vocab)[:400], rng.integers(1, 4, 400))
+    ip, terms, tf, dl = [0], [], [], []
+    for d in range(n):
+        toks = big_toks if d == big else (np.zeros(0, np.int64) if d % 20 == 3 else rng.integers(0, vocab, rng.poisson(20) + 1))
+        u, c = np.unique(toks, return_counts=True)
+        terms.append(u)
+        tf.append(c)
+        dl.append(len(toks))
+        ip.append(ip[-1] + len(u))
+    corpus = BM25Corpus(np.array(ip), np.concatenate(terms), np.concatenate(tf), np.array(dl), vocab)
+    ora = csr_oracle(corpus)
+    dev = corpus.slice(lo, hi).to_device(row_offset=lo)
+    B, pool = 1024, 2048
+    lens = (0, 1, 64, 65, 200)
+    queries = []
+    for q in range(B):
+        t = rng.integers(-1, vocab, lens[q % len(lens)]).astype(np.int32)
+        if q % 3 == 0 and len(t) > 1:
+            t[: len(t) // 2] = rng.choice(np.unique(big_toks), len(t) // 2)      # terms of the 400-term document
+        queries.append(t)
+    rows = rng.integers(0, n, (B, pool)).astype(np.int64)
+    rows[:, :4] = big                                     # duplicates of the long document
+    rows[:, 4:8] = [3, 1003, 1023, 4983]                  # empty documents (3 lies outside the shard)
+    rows[:, 8:10] = [lo - 1, hi]
+    assert len(corpus.doc_len) == n and corpus.doc_len[1003] == 0 and corpus.doc_len[big] == len(big_toks)
+    inside = (rows >= lo) & (rows < hi)
+    want = np.stack([np.where(inside[q], np.array(ora.get_scores([int(x) for x in queries[q]]), dtype=np.float32)[rows[q]],
+                              np.float32(0)) for q in range(B)])
+    assert np.count_nonzero(want[:, 0]) > B // 4
+    for mode in ("forward", "postings"):
+        got = dev.scores_at_ids(queries, rows, mode)
+        assert got.dtype == np.float32 and np.array_equal(got, want), mode

@@ -32,6 +32,11 @@ CONFIGS = {
                         w_best=0.10, prior_C=20.0, min_reviews=8, gate_penalty=0.5),
     "north_star_alpha": dict(k=100, rerank_k=0, w_dense=0.5, w_bm25=0.5, w_rerank=0.0, w_prior=0.0,
                              w_best=0.0, prior_C=20.0, min_reviews=8, gate_penalty=1.0),
+    # pools no configuration above reaches: k = pool = 1000, and the largest pool (2048) through rerank_k
+    "k_1000": dict(k=1000, rerank_k=0, w_dense=0.5, w_bm25=0.3, w_rerank=0.0, w_prior=0.2, w_best=0.0,
+                   prior_C=20.0, min_reviews=5, gate_penalty=0.5),
+    "rerank_2048": dict(k=10, rerank_k=2048, w_dense=0.4, w_bm25=0.2, w_rerank=0.3, w_prior=0.1, w_best=0.0,
+                        prior_C=20.0, min_reviews=5, gate_penalty=0.5),
 }
 QUERIES = ["wireless headphones for running", "yellow cat socks", "blue insulated coffee mug",
            "the of and", "gaming keyboard rgb design"]
@@ -45,18 +50,21 @@ class FakeCrossEncoder:
                         dtype=np.float32)
 
 
-@pytest.fixture(scope="module")
-def world():
-    n = 10_000                                  # BASELINE config 1 size
-    V = synth.unit_rows(n, 384, 1234)
-    n_rev, stars = synth.metadata(n, 2, nan_fraction=0.0)
-    texts = synth.text_corpus(n, 3, mean_len=25)
+def make_world(n, seeds=(1234, 2, 3)):
+    V = synth.unit_rows(n, 384, seeds[0])
+    n_rev, stars = synth.metadata(n, seeds[1], nan_fraction=0.0)
+    texts = synth.text_corpus(n, seeds[2], mean_len=25)
     meta = pd.DataFrame({"sku": synth.skus(n), "n_reviews": n_rev, "avg_stars": stars,
                          "last_ts": np.arange(n), "agg_text": texts})
     corpus = [t.split() for t in texts]
     blob = {"skus": meta["sku"].tolist(), "corpus": corpus, "tokenizer": "simple_en_v1"}
     ora_bm25 = BM25OkapiOracle(corpus)
     return dict(V=V, meta=meta, blob=blob, ora_bm25=ora_bm25, n=n)
+
+
+@pytest.fixture(scope="module")
+def world():
+    return make_world(10_000)                   # BASELINE config 1 size
 
 
 def run_both(world, engine, query, qvec, cfg, flavour):
@@ -77,13 +85,24 @@ def run_both(world, engine, query, qvec, cfg, flavour):
 @pytest.mark.parametrize("flavour", ["app", "cli"])
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_run_search_matches_oracle(world, name, flavour):
-    cfg = CONFIGS[name]
+    check_against_oracle(world, CONFIGS[name], flavour)
+
+
+@pytest.mark.parametrize("flavour", ["app", "cli"])
+@pytest.mark.parametrize("name", ["hybrid", "ui_defaults"])
+def test_run_search_matches_oracle_on_a_five_product_corpus(name, flavour):
+    """The pool is clamped to the corpus: 5 rows, below numpy's 8-value pairwise block and every bitonic size."""
+    check_against_oracle(make_world(5, seeds=(4321, 5, 6)), CONFIGS[name], flavour)
+
+
+def check_against_oracle(world, cfg, flavour):
     engine = SearchEngine(world["meta"], world["V"], world["blob"], cross_encoder=FakeCrossEncoder(),
                           normalize=False, flavour=flavour)
     Q = synth.unit_rows(len(QUERIES), 384, 99)
+    k = min(cfg["k"], world["n"])
     for query, qvec in zip(QUERIES, Q):
         want, got, cand = run_both(world, engine, query, qvec, cfg, flavour)
-        assert len(got) == len(want) == cfg["k"]
+        assert len(got) == len(want) == k
         np.testing.assert_allclose(got["_final"].values, want["_final"].values, atol=TOL, rtol=0)
         # IDs: exact, except that rows whose oracle finals tie (gate_penalty 0 gives runs of
         # exact zeros) may come in any order -- the reference's own sort is unstable there
@@ -98,7 +117,7 @@ def test_run_search_matches_oracle(world, name, flavour):
                 assert set(got.loc[sel, "sku"]) == set(want.loc[sel, "sku"])
         cols = [c for c in COLUMN_NAMES if c in want.columns]
         common = [s_ for s_ in got["sku"] if s_ in set(want["sku"])]
-        assert len(common) >= cfg["k"] - int((wf == wf[-1]).sum())
+        assert len(common) >= k - int((wf == wf[-1]).sum())
         g_al, w_al = got.set_index("sku").loc[common], want.set_index("sku").loc[common]
         for c in cols:
             np.testing.assert_allclose(g_al[c].values.astype(np.float64),

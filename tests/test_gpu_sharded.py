@@ -74,6 +74,58 @@ def test_sharded_equals_unsharded_bitwise(world, batch):
     assert r0.index(1000) + 1 == r0.index(39_000)      # tie: ascending global row
 
 
+def test_eight_shards_merge_up_to_the_candidate_limit_and_refuse_more():
+    """K3 merges at most RR_MAX_CANDIDATES = 4096 candidates per query, world x pool of them on row shards: 8 shards
+    at pool 512 (the limit exactly) merge bit for bit to the unsharded answer; pool 513 is refused with a ValueError
+    naming the limit before anything runs -- no scan is launched, and no collective is entered."""
+    n, vocab, world, batch, pool = 40_000, 3000, 8, 3, 512
+    V = synth.unit_rows(n, 384, 61)
+    n_rev, stars = synth.metadata(n, 62, nan_fraction=0.01)
+    ip, terms, tf, dl = synth.bm25_forward_csr(n, vocab, 30, 63)
+    corpus = BM25Corpus(ip, terms, tf, dl, vocab)
+    Q = synth.unit_rows(batch, 384, 66)
+    tl = synth.query_terms(batch, vocab, 67, np.bincount(terms, minlength=vocab))
+    w = FusionWeights(w_dense=0.5, w_bm25=0.3, w_rerank=0.0, w_prior=0.2, w_best=0.0, gate_penalty=1.0)
+    q_dev = torch.from_numpy(Q).cuda()
+    whole = ShardedSearcher(build(V, n_rev.astype(np.float64), stars, corpus, 0, n), n, 0, 1)
+    want = [t.cpu().numpy() for t in whole.search_batch_dev(q_dev, tl, pool, w)]
+    shards = [ShardedSearcher(build(V, n_rev.astype(np.float64), stars, corpus, *shard_bounds(n, world, r)), n, r, world)
+              for r in range(world)]
+
+    def launches(sh):
+        ms, cnt = C.c_double(), C.c_int64()
+        _lib.check(sh.s.lib.rr_index_scan_stats(sh.s.index.handle, C.byref(ms), C.byref(cnt)), "rr_index_scan_stats")
+        return cnt.value
+
+    launches(shards[0])
+    with pytest.raises(ValueError, match="4096"):
+        shards[0].search_batch_dev(q_dev, tl, pool + 1, w)
+    with pytest.raises(ValueError, match="4096"):
+        shards[0].submit(q_dev, tl, 10, w, rerank_k=pool + 1)
+    torch.cuda.synchronize()
+    assert launches(shards[0]) == 0
+    lay = PayloadLayout(batch, pool)
+    gathered = torch.empty((world, lay.nbytes), dtype=torch.uint8, device="cuda")
+    for r, sh in enumerate(shards):
+        _, buf = sh.local_payload(q_dev, tl, pool)
+        gathered[r].copy_(buf)
+    s0 = shards[0].s
+    params = HybridSearcher.make_params(w, pool, pool, world * pool, 0, cand_per_rank=pool, stride_bytes=lay.nbytes)
+    out_rows = torch.empty((batch, pool), dtype=torch.int64, device="cuda")
+    cols = torch.empty((batch, 8, pool), dtype=torch.float64, device="cuda")
+    order = torch.empty((batch, pool), dtype=torch.int32, device="cuda")
+    base = gathered.data_ptr()
+    p = lambda off: C.c_void_p(base + off)
+    _lib.check(s0.lib.rr_fuse_topk_dev(
+        s0.index.handle, C.byref(params), batch, p(lay.off_rows), p(lay.off_dense), p(lay.off_bm25),
+        p(lay.off_n), p(lay.off_avg), p(lay.off_l1p), None, None, None, C.c_void_p(out_rows.data_ptr()),
+        C.c_void_p(cols.data_ptr()), C.c_void_p(order.data_ptr()), s0._stream()), "rr_fuse_topk_dev")
+    torch.cuda.synchronize()
+    assert np.array_equal(out_rows.cpu().numpy(), want[0])
+    assert np.array_equal(cols.cpu().numpy(), want[1], equal_nan=True)
+    assert np.array_equal(order.cpu().numpy(), want[2])
+
+
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_config4_shape_bf16_batch_256_sharded_equals_unsharded(dtype):
     """BASELINE config 4's shape on one GPU: batch 256 (two 128-query filter-scan launches per shard), bf16 or

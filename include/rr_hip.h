@@ -70,6 +70,21 @@ int rr_index_upload_rows_f32(rr_index* ix, int64_t first_row, int64_t n_rows, co
  * ABI invalidate them; after writing to an ADOPTED matrix yourself (e.g. an in-place torch update) call
  * rr_index_matrix_changed, or batched searches filter on the old rows. */
 int rr_index_adopt_device(rr_index* ix, const void* d_matrix);
+/* The device-source twin of rr_index_upload_rows_f32 (what nlp/11_build_product_embeddings.py:82-85 leaves in
+ * product_emb.npy, without the file): d_rows [n][dim] fp32, unpadded, on the index's device.  The same kernels as the host
+ * upload, so the same bits: optional x / max(||x||, eps) in fp32, a bf16 index rounds once afterwards, padding columns are
+ * zero, the row-norm bounds and the bf16 filter plane are dropped; refused on an adopted matrix.
+ * d_row_ids == NULL: rows [first_row, first_row + n), everything queued on `stream` behind whatever produces d_rows there.
+ * The call takes the handle's mutex; the FIRST store into an index that has no matrix yet allocates it and waits for its
+ * padding to be zeroed; after that there is no host wait.  A search on ANOTHER stream (rr_dense_topk uses the index's own)
+ * must follow a synchronisation of `stream`.
+ * d_row_ids != NULL (device, n LOCAL row numbers; first_row is ignored): row i goes to row d_row_ids[i] -- a builder's second
+ * pass drops late rows into their places.  This form allocates a staging copy, waits for `stream` and reports ids outside
+ * the index as RR_E_INVALID (those rows are skipped). */
+int rr_index_store_rows_dev(rr_index* ix, const float* d_rows, int64_t n, int64_t first_row, const int64_t* d_row_ids,
+                            float normalize_eps, void* stream);
+/* Rows [first_row, first_row + n) of an fp32 index back to the host, unpadded (waits for the device). */
+int rr_index_download_rows_f32(rr_index* ix, int64_t first_row, int64_t n, float* h_rows);
 int rr_index_matrix_changed(rr_index* ix);
 int rr_index_dim_padded(const rr_index* ix, int32_t* out);
 /* l2_normalize (utils.py:40-44) of every row, in place on the device. */
@@ -305,7 +320,9 @@ int rr_reviews_best_cut_dev(rr_reviews* rv, const float* d_queries, int32_t n_qu
  *   SentenceTransformer.encode([query], normalize_embeddings=True)        app/app_product_search.py:250-251, app/test.py:232
  *     (BAAI/bge-small-en-v1.5: BertModel of the same block shape, 12 layers, CLS pooling; the l2 normalisation is the caller's)
  * The kernels are built for hidden 384 / 12 heads x 32 / FFN 1536; layer count, vocabulary, positions (<= 512) are free.
- * Tokenisation (WordPiece) is host work above this ABI (review-recommender_amd/wordpiece.py). */
+ * Tokenisation (WordPiece): rr_wp_encode_dev below turns ASCII documents into the packed ids this call takes, on the device
+ * (csrc/rr_wordpiece.hip); text with bytes >= 0x80 and text PAIRS (the reranker) are tokenised on the host
+ * (review-recommender_amd/wordpiece.py). */
 typedef struct rr_ce rr_ce;
 typedef struct rr_ce_config {
     int32_t hidden, n_layers, n_heads, ffn;       /* 384, L, 12, 1536 */
@@ -361,6 +378,46 @@ int rr_ce_last_forward_ms(rr_ce* ce, float* out_ms);
  * ~1.6 x the time): run the pass again after it.  cross_encoder.py does both by itself on the host path. */
 int rr_ce_range_status(rr_ce* ce, int32_t* out_of_range);
 int rr_ce_set_wide_range(rr_ce* ce, int32_t on);
+
+/* ------------------------------------------------------------ WordPiece tokenisation on the device */
+
+/* What SentenceTransformer.encode does to its texts before the model runs (nlp/11_build_product_embeddings.py:46-47: the
+ * model's BertTokenizer, lower-casing), for documents whose bytes are all below 0x80 (csrc/rr_wordpiece.hip).
+ * Pieces: piece i (bytes h_piece_off[i] .. h_piece_off[i+1]) has token id i; an empty piece stands for "no such id";
+ * pieces with a byte >= 0x80 or longer than max_chars_per_word (<= 255) can never match ASCII text and are left out of the
+ * device table.  unk / cls / sep are ids in [0, n_pieces). */
+typedef struct rr_wp rr_wp;
+int rr_wp_create(int32_t device, const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces,
+                 int32_t unk_id, int32_t cls_id, int32_t sep_id, int32_t max_chars_per_word, rr_wp** out);
+int rr_wp_destroy(rr_wp* wp);
+/* n_docs UTF-8 documents (document s = bytes d_text_off[s] .. d_text_off[s+1] of d_text; text_bytes = size of d_text,
+ * below 2^31) -> exactly what rr_ce_forward_dev takes: sequence s = [CLS], the first max_length - 2 pieces, [SEP]; type ids
+ * 0; position = index inside the sequence; d_cu_seqlens [n_docs + 1] the running sum; *d_max_len the longest sequence.
+ * For an all-ASCII document the ids equal the host tokenizer's, id for id.  A document with any byte >= 0x80 is not
+ * tokenised: d_needs_host[s] = 1 and its sequence is the placeholder [CLS] [SEP] (the packing stays dense; the caller
+ * tokenises it on the host).  The kernel keeps the first 4 096 bytes of a document on chip: a longer ASCII document is
+ * answered from them when they already hold max_length - 2 pieces in words that end inside them, else needs_host = 1.
+ * token_capacity (elements of the three id arrays; n_docs * max_length always suffices, 2 * n_docs is required) bounds
+ * the writes: ids beyond it are dropped and d_cu_seqlens[n_docs] tells what was needed.
+ * Asynchronous on `stream`, all d_ pointers device pointers; no host wait, except that the first call of a larger
+ * n_docs * max_length grows the handle's scratch (hipFree + hipMalloc).  That scratch (per-document id rows and lengths,
+ * laid out by THIS call's n_docs and max_length) and the bad-offset counter belong to the handle, not to the call: calls
+ * on one handle must be STREAM-ORDERED (the same stream, or ordered by events); two encodes in flight on unordered streams
+ * overwrite each other's scratch.  Use one handle per stream for concurrent tokenisation.  Host-checkable limits are RR_E_INVALID and nothing is
+ * written; offsets live on the device and are checked THERE: a document whose offsets decrease or leave [0, text_bytes]
+ * reads nothing, gets the placeholder with needs_host = 1, and rr_wp_status (which waits for the device) then returns
+ * RR_E_INVALID with the count. */
+int rr_wp_encode_dev(rr_wp* wp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off, int32_t n_docs,
+                     int32_t max_length, int64_t token_capacity, int32_t* d_token_ids, int32_t* d_type_ids, int32_t* d_pos_ids,
+                     int32_t* d_cu_seqlens, int32_t* d_needs_host, int32_t* d_max_len, void* stream);
+int rr_wp_status(rr_wp* wp, int32_t* out_bad_docs);
+/* The piece table rr_wp_create puts on the device, built on the host (no device needed; tests walk it): n_slots =
+ * rr_wp_table_slots(n_pieces) (a power of two, at least twice the pieces); h_slots [n_slots][4] int32 = polynomial hash
+ * (base 0x01000193 mod 2^32) of the piece's bytes without its ##, first byte in h_piece_bytes, length | (## form) << 16,
+ * id (-1 = empty); open addressing, linear probing from murmur3's finaliser of hash ^ (length word * 0x9E3779B1). */
+int rr_wp_table_slots(int32_t n_pieces, int32_t* out_slots);
+int rr_wp_build_table(const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces, int32_t max_chars_per_word,
+                      int32_t n_slots, int32_t* h_slots, int32_t* out_kept);
 
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard

@@ -44,6 +44,8 @@ PROTOTYPES = {
     "rr_index_upload_rows": (C.c_int, [c_vp, c_i64, c_i64, c_vp]),
     "rr_index_upload_rows_f32": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_f32]),
     "rr_index_adopt_device": (C.c_int, [c_vp, c_vp]),
+    "rr_index_store_rows_dev": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_f32, c_vp]),
+    "rr_index_download_rows_f32": (C.c_int, [c_vp, c_i64, c_i64, c_vp]),
     "rr_index_dim_padded": (C.c_int, [c_vp, P(c_i32)]),
     "rr_index_l2_normalize": (C.c_int, [c_vp, c_f32]),
     "rr_index_set_meta": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
@@ -93,6 +95,12 @@ PROTOTYPES = {
     "rr_ce_last_forward_ms": (C.c_int, [c_vp, P(c_f32)]),
     "rr_ce_range_status": (C.c_int, [c_vp, P(C.c_int32)]),
     "rr_ce_set_wide_range": (C.c_int, [c_vp, C.c_int32]),
+    "rr_wp_create": (C.c_int, [c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, P(c_vp)]),
+    "rr_wp_destroy": (C.c_int, [c_vp]),
+    "rr_wp_encode_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rr_wp_status": (C.c_int, [c_vp, P(c_i32)]),
+    "rr_wp_table_slots": (C.c_int, [c_i32, P(c_i32)]),
+    "rr_wp_build_table": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, P(c_i32)]),
     "rr_index_stream": (C.c_int, [c_vp, P(c_vp)]),
     "rr_index_synchronize": (C.c_int, [c_vp]),
 }

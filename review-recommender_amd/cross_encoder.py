@@ -95,6 +95,7 @@ class BertEncoderGPU:
         self.n_layers, self.n_labels, self.vocab, self.max_pos = n_layers, n_labels, word.shape[0], pos.shape[0]
         self.type_vocab, self.device = typ.shape[0], device
         self.max_tokens_per_call = int(max_tokens_per_call)
+        self.wide_range = False                         # set_wide_range: which fp32-mode kernels the NEXT launch runs
         cfg = _lib.CEConfig(HIDDEN, n_layers, HEADS, FFN, self.vocab, self.max_pos, self.type_vocab, n_labels, ln_eps,
                             PRECISIONS[precision])
         ptrs = (C.c_void_p * len(tensors))(*[t.ctypes.data for t in tensors])
@@ -211,6 +212,7 @@ class BertEncoderGPU:
             warnings.warn("encoder activations exceed the fp16 range: this handle switches to the bf16 three-term kernels")
             self._warned_wide = True
         _lib.check(_lib.load().rr_ce_set_wide_range(self._h, 1 if on else 0), "rr_ce_set_wide_range")
+        self.wide_range = bool(on)
 
     def last_forward_ms(self) -> float:
         ms = C.c_float()
@@ -326,6 +328,11 @@ class QueryEncoder:
         if normalize_embeddings:       # torch.nn.functional.normalize(p=2, dim=1, eps=1e-12)
             e = (e / np.maximum(np.linalg.norm(e, axis=1, keepdims=True), 1e-12)).astype(np.float32)
         return e
+
+    def encode_dev(self, tok, typ, pos, cu, n_seqs: int, max_len: int):
+        """CLS rows (n_seqs, 384), a DEVICE tensor, of sequences already packed on the device (embed.DeviceWordPiece makes
+        them from text): `forward_packed_dev` with OUT_CLS, asynchronous on torch's current stream, not normalised."""
+        return self.model.forward_packed_dev(tok, typ, pos, cu, n_seqs, max_len, OUT_CLS)
 
     def encode(self, sentences, normalize_embeddings: bool = False, **_ignored) -> np.ndarray:
         if self.tokenizer is None:

@@ -178,7 +178,8 @@ extern "C" int rr_index_create(const void* h_matrix, int64_t n_rows, int32_t dim
     return RR_OK;
 }
 
-static int rr_alloc_matrix(rr_index* ix) {
+static int rr_alloc_matrix(rr_index* ix, bool* fresh = nullptr) {
+    if (fresh) *fresh = false;
     if (ix->d_matrix) return RR_OK;
     const size_t bytes = (size_t)ix->n_rows * ix->dim_pad * rr_elem_size(ix->dtype);
     hipError_t e = hipMalloc(&ix->d_matrix, bytes);
@@ -187,6 +188,7 @@ static int rr_alloc_matrix(rr_index* ix) {
         return RR_E_NOMEM;
     }
     ix->owns_matrix = true;
+    if (fresh) *fresh = true;
     if (ix->dim_pad != ix->dim) RR_HIP_TRY(hipMemsetAsync(ix->d_matrix, 0, bytes, ix->stream));
     return RR_OK;
 }
@@ -240,6 +242,106 @@ extern "C" int rr_index_upload_rows_f32(rr_index* ix, int64_t first_row, int64_t
     }
     RR_HIP_TRY(hipStreamSynchronize(ix->stream));
     return rc;
+}
+
+// Rows of a contiguous staging buffer to the matrix rows the caller names (rr_index_store_rows_dev with d_row_ids): 16 bytes
+// per thread; a row id outside the index is skipped and counted.
+__global__ __launch_bounds__(256) void rr_scatter_rows(const f32x4* __restrict__ src, int64_t n, int32_t chunks_per_row,
+                                                       const int64_t* __restrict__ row_ids, int64_t n_rows, f32x4* __restrict__ dst,
+                                                       int32_t* __restrict__ bad) {
+    const int64_t total = n * chunks_per_row;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / chunks_per_row, c = i % chunks_per_row;
+        const int64_t to = row_ids[r];
+        if (to < 0 || to >= n_rows) {
+            if (c == 0) atomicAdd(bad, 1);
+            continue;
+        }
+        dst[to * chunks_per_row + c] = src[i];
+    }
+}
+
+extern "C" int rr_index_store_rows_dev(rr_index* ix, const float* d_rows, int64_t n, int64_t first_row, const int64_t* d_row_ids,
+                                       float normalize_eps, void* stream) {
+    RR_REQUIRE(ix && (d_rows || n == 0), "rr_index_store_rows_dev: NULL argument");
+    RR_REQUIRE(n >= 0 && n <= ix->n_rows, "rr_index_store_rows_dev: %lld rows into an index of %lld", (long long)n, (long long)ix->n_rows);
+    RR_REQUIRE(d_row_ids || (first_row >= 0 && first_row + n <= ix->n_rows),
+               "rr_index_store_rows_dev: rows [%lld,%lld) outside [0,%lld)", (long long)first_row, (long long)(first_row + n),
+               (long long)ix->n_rows);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    RR_REQUIRE(ix->owns_matrix || !ix->d_matrix, "rr_index_store_rows_dev: matrix is caller-owned");
+    bool fresh = false;
+    int rc = rr_alloc_matrix(ix, &fresh);
+    if (rc || n == 0) return rc;
+    if (fresh) RR_HIP_TRY(hipStreamSynchronize(ix->stream));     // (the padding memset of a matrix allocated just now)
+    rr_matrix_written(ix);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t es = rr_elem_size(ix->dtype);
+    if (!d_row_ids) {
+        // everything on the caller's stream, behind what produces d_rows: the kernels of the host upload, nothing else
+        if (ix->dtype == RR_DTYPE_F32) {
+            RR_HIP_TRY(hipMemcpy2DAsync((char*)ix->d_matrix + (size_t)first_row * ix->dim_pad * 4, 4 * (size_t)ix->dim_pad, d_rows,
+                                        4 * (size_t)ix->dim, 4 * (size_t)ix->dim, (size_t)n, hipMemcpyDeviceToDevice, st));
+            if (normalize_eps > 0.f) rc = rr_l2norm_rows_f32(ix, first_row, n, normalize_eps, st);
+        } else {
+            rc = rr_store_rows_bf16(ix, first_row, n, const_cast<float*>(d_rows), normalize_eps, st);
+        }
+        return rc;
+    }
+    // scattered: the same kernels into a staging copy of n padded rows, then one copy of every row to its place.  The rows
+    // of a builder's second pass: this form allocates, waits and frees.
+    void* stage = nullptr;
+    int32_t* d_bad = nullptr;
+    RR_HIP_TRY(hipMalloc(&stage, (size_t)n * ix->dim_pad * es + 16));
+    hipError_t e = hipMalloc((void**)&d_bad, 4);
+    if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 4, st);
+    void* const matrix = ix->d_matrix;
+    int32_t bad = 0;
+    if (e == hipSuccess) {
+        if (ix->dtype == RR_DTYPE_F32) {
+            e = hipMemsetAsync(stage, 0, (size_t)n * ix->dim_pad * es, st);
+            if (e == hipSuccess)
+                e = hipMemcpy2DAsync(stage, 4 * (size_t)ix->dim_pad, d_rows, 4 * (size_t)ix->dim, 4 * (size_t)ix->dim, (size_t)n,
+                                     hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess && normalize_eps > 0.f) rc = rr_l2norm_rows_f32_at((float*)stage, ix->dim_pad, n, normalize_eps, st);
+        } else {
+            rc = rr_store_rows_bf16_at(stage, ix->dim, ix->dim_pad, n, d_rows, normalize_eps, st);
+        }
+    }
+    if (e == hipSuccess && !rc) {
+        const int32_t cpr = (int32_t)((size_t)ix->dim_pad * es / 16);       // dim_pad is a multiple of 64 elements
+        int64_t blocks = (n * cpr + 255) / 256;
+        blocks = blocks > 4096 ? 4096 : blocks;
+        hipLaunchKernelGGL(rr_scatter_rows, dim3((unsigned)blocks), dim3(256), 0, st, (const f32x4*)stage, n, cpr, d_row_ids,
+                           ix->n_rows, (f32x4*)matrix, d_bad);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost);
+    } else {
+        hipStreamSynchronize(st);
+    }
+    hipFree(stage);
+    hipFree(d_bad);
+    if (e != hipSuccess) { rr_set_error("rr_index_store_rows_dev: %s", hipGetErrorString(e)); return RR_E_HIP; }
+    if (rc) return rc;
+    RR_REQUIRE(bad == 0, "rr_index_store_rows_dev: %d row id(s) outside [0,%lld) were skipped", bad, (long long)ix->n_rows);
+    return RR_OK;
+}
+
+extern "C" int rr_index_download_rows_f32(rr_index* ix, int64_t first_row, int64_t n, float* h_rows) {
+    RR_REQUIRE(ix && (h_rows || n == 0), "rr_index_download_rows_f32: NULL argument");
+    RR_REQUIRE(ix->dtype == RR_DTYPE_F32, "rr_index_download_rows_f32: the index stores bf16 rows");
+    RR_REQUIRE(first_row >= 0 && n >= 0 && first_row + n <= ix->n_rows, "rr_index_download_rows_f32: rows [%lld,%lld) outside [0,%lld)",
+               (long long)first_row, (long long)(first_row + n), (long long)ix->n_rows);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    RR_REQUIRE(ix->d_matrix, "rr_index_download_rows_f32: the index has no matrix yet");
+    if (n == 0) return RR_OK;
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    RR_HIP_TRY(hipDeviceSynchronize());          // writes may be queued on any stream (rr_index_store_rows_dev)
+    RR_HIP_TRY(hipMemcpy2D(h_rows, 4 * (size_t)ix->dim, (const char*)ix->d_matrix + (size_t)first_row * ix->dim_pad * 4,
+                           4 * (size_t)ix->dim_pad, 4 * (size_t)ix->dim, (size_t)n, hipMemcpyDeviceToHost));
+    return RR_OK;
 }
 
 extern "C" int rr_index_adopt_device(rr_index* ix, const void* d_matrix) {

@@ -91,6 +91,8 @@ int rr_dense_chunk_mfma_bf16(rr_index* ix, const float* d_q, int nq, int pool, i
                              float* d_scores, hipStream_t st);
 // l2_normalize of rows [first, first + n) of an fp32 index, in place
 int rr_l2norm_rows_f32(rr_index* ix, int64_t first_row, int64_t n, float eps, hipStream_t st);
+// ... of n padded rows anywhere on the device (a staging copy): the same kernel
+int rr_l2norm_rows_f32_at(float* d_rows, int32_t dim_pad, int64_t n, float eps, hipStream_t st);
 // split-bf16 matrix-core scan (rr_dense_x3.hip): 5..64 queries, either storage dtype
 int rr_dense_chunk_x3(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                       float* d_scores, hipStream_t st);
@@ -107,6 +109,8 @@ int rr_dense_chunk_flt(rr_index* ix, const float* d_q, int nq, int pool, int64_t
 void rr_flt_drop_pending(rr_index* ix);
 // fp32 rows (device, n x dim) -> the index's bf16 matrix rows [first, first + n), optional l2 normalise
 int rr_store_rows_bf16(rr_index* ix, int64_t first_row, int64_t n, float* d_rows_f32, float eps, hipStream_t st);
+// ... into n padded bf16 rows anywhere on the device (a staging copy): the same kernel
+int rr_store_rows_bf16_at(void* d_dst, int32_t dim, int32_t dim_pad, int64_t n, const float* d_rows_f32, float eps, hipStream_t st);
 
 // rr_api.hip: the address a kernel may use for p (device memory, or pinned host memory through its mapping)
 int rr_device_visible(const void* p, const void** out, const char* what);

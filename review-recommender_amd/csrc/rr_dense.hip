@@ -1771,12 +1771,15 @@ extern "C" int rr_index_scan_stats(rr_index* ix, double* out_total_ms, int64_t* 
     return RR_OK;
 }
 
-int rr_l2norm_rows_f32(rr_index* ix, int64_t first_row, int64_t n, float eps, hipStream_t st) {
+int rr_l2norm_rows_f32_at(float* d_rows, int32_t dim_pad, int64_t n, float eps, hipStream_t st) {
     if (n == 0) return RR_OK;
-    hipLaunchKernelGGL(rr_l2norm_f32, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st,
-                       (float*)ix->d_matrix + first_row * ix->dim_pad, n, ix->dim_pad, eps);
+    hipLaunchKernelGGL(rr_l2norm_f32, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, d_rows, n, dim_pad, eps);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
+}
+
+int rr_l2norm_rows_f32(rr_index* ix, int64_t first_row, int64_t n, float eps, hipStream_t st) {
+    return rr_l2norm_rows_f32_at((float*)ix->d_matrix + first_row * ix->dim_pad, ix->dim_pad, n, eps, st);
 }
 
 extern "C" int rr_index_l2_normalize(rr_index* ix, float eps) {

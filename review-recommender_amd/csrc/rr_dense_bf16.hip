@@ -55,13 +55,17 @@ __global__ void rr_rows_to_bf16(const float* __restrict__ src, int dim, unsigned
     }
 }
 
-int rr_store_rows_bf16(rr_index* ix, int64_t first_row, int64_t n, float* d_rows_f32, float eps, hipStream_t st) {
+int rr_store_rows_bf16_at(void* d_dst, int32_t dim, int32_t dim_pad, int64_t n, const float* d_rows_f32, float eps, hipStream_t st) {
     if (n == 0) return RR_OK;
-    unsigned short* dst = reinterpret_cast<unsigned short*>(ix->d_matrix) + first_row * ix->dim_pad;
-    hipLaunchKernelGGL(rr_rows_to_bf16, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, d_rows_f32, ix->dim, dst,
-                       ix->dim_pad, n, eps);
+    hipLaunchKernelGGL(rr_rows_to_bf16, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, d_rows_f32, dim,
+                       reinterpret_cast<unsigned short*>(d_dst), dim_pad, n, eps);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
+}
+
+int rr_store_rows_bf16(rr_index* ix, int64_t first_row, int64_t n, float* d_rows_f32, float eps, hipStream_t st) {
+    return rr_store_rows_bf16_at(reinterpret_cast<unsigned short*>(ix->d_matrix) + first_row * ix->dim_pad, ix->dim, ix->dim_pad, n,
+                                 d_rows_f32, eps, st);
 }
 
 // ------------------------------------------------------------------ VALU scan, dim 384

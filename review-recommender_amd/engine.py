@@ -447,22 +447,28 @@ class SearchEngine:
     def __init__(self, meta: pd.DataFrame, embeddings: np.ndarray, bm25_blob: Optional[dict] = None,
                  *, encoder=None, cross_encoder=None, device: int = 0, normalize: bool = True,
                  flavour: str = "app", dtype: str = "f32", reviews: Optional[Tuple] = None,
-                 bm25_build: str = "device"):
+                 bm25_build: str = "device", index: Optional[ProductIndex] = None):
+        """``index``: a ready ProductIndex (embed.build_product_embeddings) to use instead of uploading ``embeddings``
+        (then None); it is taken as it is -- ``normalize`` and ``dtype`` describe an upload only."""
         if flavour not in ("app", "cli"):
             raise ValueError("flavour must be 'app' or 'cli'")
         if bm25_build not in ("device", "host"):
             raise ValueError("bm25_build must be 'device' or 'host'")
-        if len(meta) != embeddings.shape[0]:
+        if (index is None) == (embeddings is None):
+            raise ValueError("pass either an embedding matrix or a ready index")
+        n_emb = embeddings.shape[0] if index is None else index.n_rows
+        if len(meta) != n_emb:
             # app/app_product_search.py:104-107, app/test.py:141-142: hard error
             raise ValueError(f"metadata has {len(meta)} rows but embeddings have "
-                             f"{embeddings.shape[0]} rows")
+                             f"{n_emb} rows")
         if "sku" not in meta.columns or "agg_text" not in meta.columns:
             raise ValueError("metadata must have 'sku' and 'agg_text' columns")  # app/test.py:138-139
         self.flavour = flavour
         self.meta = meta.reset_index(drop=True)
         self.encoder, self.cross_encoder = encoder, cross_encoder
         # chunked upload: the matrix may be a memory-mapped product_emb.npy (app/test.py:140)
-        self.index = ProductIndex.from_rows(embeddings, device=device, normalize=normalize, dtype=dtype)
+        self.index = index if index is not None else ProductIndex.from_rows(embeddings, device=device, normalize=normalize,
+                                                                            dtype=dtype)
         nan = pd.Series([np.nan] * len(self.meta))
         n = pd.to_numeric(self.meta.get("n_reviews", nan), errors="coerce").fillna(0).values
         r = pd.to_numeric(self.meta.get("avg_stars", nan), errors="coerce").values
@@ -509,6 +515,33 @@ class SearchEngine:
         if "reviews" not in kw:
             kw["reviews"] = load_reviews(data_dir)     # None when reviews_with_embeddings.parquet is absent
         return cls(meta, emb, blob, **kw)
+
+    @classmethod
+    def from_products(cls, products, encoder, *, text_col: str = "agg_text", dtype: str = "f32", chunk_tokens: int = 131072,
+                      bm25: bool = True, data_dir=None, **kw) -> "SearchEngine":
+        """The engine straight from a product table (sku, agg_text, ...), no files in between: embeddings by
+        embed.build_product_embeddings on the encoder's GPU (nlp/11_build_product_embeddings.py), the BM25 corpus tokenised
+        as nlp/12_product_prep.py:80-89 does and indexed by the GPU builder.  ``encoder`` (a QueryEncoder with a vocabulary)
+        also becomes the engine's query encoder.  With ``data_dir`` the two embedding files are written as well.
+
+        The same engine, bit for bit, as `from_artifacts` on the files this build writes: the loaders l2-normalise the
+        stored unit rows once more (app/test.py:144), so this does too (`index.l2_normalize()` after the build).
+        dtype="bf16": the order is NORMALISE AGAIN, THEN ROUND, the one `from_artifacts(dtype="bf16")` produces (fp32 rows
+        normalised at the build, normalised again at load, rounded once to bf16); the fp32 rows pass through the host once
+        for it."""
+        from .artifacts import build_bm25_blob
+        from .embed import build_product_embeddings
+        index, meta, _ = build_product_embeddings(products, encoder, text_col=text_col, dtype="f32",
+                                                  chunk_tokens=chunk_tokens, data_dir=data_dir)
+        if dtype == "f32":
+            index.l2_normalize()
+        else:
+            rows = index.download_rows()
+            index.close()
+            index = ProductIndex.from_rows(rows, device=encoder.model.device, normalize=True, dtype=dtype)
+        blob = build_bm25_blob(meta) if bm25 else None
+        kw.setdefault("device", encoder.model.device)
+        return cls(meta, None, blob, encoder=encoder, index=index, **kw)
 
     # app: sku -> last position, missing -> 0.0 score (app/app_product_search.py:207-208)
     # cli: same map, but if ANY meta sku is missing the scores are used unpermuted

@@ -81,6 +81,29 @@ class ProductIndex:
         """l2_normalize (utils.py:40-44) of every row, on the device, in place."""
         _lib.check(_lib.load().rr_index_l2_normalize(self._h, eps), "rr_index_l2_normalize")
 
+    def store_rows_dev(self, rows, first_row: int = 0, row_ids=None, normalize: bool = True, eps: float = 1e-12) -> None:
+        """Device rows (a float32 torch tensor (n, dim) on this index's GPU) into rows [first_row, first_row + n), or into
+        the LOCAL rows `row_ids` (int64 device tensor) names: rr_index_store_rows_dev, the device-source twin of
+        `from_rows` (same kernels, same bits), queued on torch's current stream."""
+        import torch
+        if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != self.dim or not rows.is_contiguous():
+            raise ValueError(f"rows must be a contiguous float32 (n, {self.dim}) device tensor")
+        if row_ids is not None and (row_ids.dtype != torch.int64 or row_ids.numel() != rows.shape[0]):
+            raise ValueError("row_ids must be one int64 per row")
+        st = torch.cuda.current_stream(rows.device).cuda_stream
+        _lib.check(_lib.load().rr_index_store_rows_dev(
+            self._h, C.c_void_p(rows.data_ptr()), rows.shape[0], int(first_row),
+            C.c_void_p(row_ids.data_ptr()) if row_ids is not None else None, eps if normalize else 0.0, C.c_void_p(st)),
+            "rr_index_store_rows_dev")
+
+    def download_rows(self, first_row: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Rows of an f32 index back on the host, unpadded (waits for the device)."""
+        n = self.n_rows - first_row if n is None else int(n)
+        out = np.empty((n, self.dim), dtype=np.float32)
+        _lib.check(_lib.load().rr_index_download_rows_f32(self._h, int(first_row), n, _lib.ptr(out)),
+                   "rr_index_download_rows_f32")
+        return out
+
     def set_meta(self, n_reviews: np.ndarray, avg_stars: np.ndarray) -> None:
         """Row-aligned ``n_reviews`` / ``avg_stars`` as run_search derives them
         (app/app_product_search.py:264-265: to_numeric, n NaN -> 0, stars NaN kept)."""

@@ -1,4 +1,4 @@
-// rr_debug.h -- timing-only ablation harness of the scan kernels.  NOT part of the product ABI (include/rr_hip.h):
+// rr_debug.h -- ablation (timing-only) and kernel-test harness of the scan kernels.  NOT part of the product ABI (include/rr_hip.h):
 // compiled only with -DRR_DEBUG_HARNESS into librr_hip_dbg.so (build.py: build_library(debug=True)), which the
 // tools/ scripts load through RR_DEBUG_HARNESS=1.  The ablated kernels leave garbage in the scan scratch and some of
 // them give up the register-liveness contract of the asynchronous ring loads -- never part of a search.
@@ -13,6 +13,14 @@ int rr_debug_scan_x3w(rr_index* ix, int32_t variant, int32_t reps, float* out_ms
 int rr_debug_scan_flt(rr_index* ix, int32_t variant, int32_t reps, float* out_ms);
 // the hand-scheduled loop of rr_scan_fltq against its C++ bodies, tile word by tile word (out: 7 values, see the definition)
 int rr_debug_fltq_compare(rr_index* ix, int64_t* out);
+// tests/test_gpu_flt_words.py: ONE filter scan by itself (product preparation, product launch code) into a scratch filled
+// with sentinels, and its raw output -- geometry, eps, sigma, every tile word and group key -- on the host; then the
+// product's selection on those words; the path trace of every query of the last selection.  See the definitions.
+int rr_debug_flt_words(rr_index* ix, const float* d_queries, int32_t nq_a, int32_t nq_b, int32_t scan, int32_t prefilter, int32_t pool,
+                       int64_t* geom, float* eps, float* sigma, uint32_t* words, int64_t words_cap, uint32_t* keys, int64_t keys_cap);
+int rr_debug_flt_select(rr_index* ix, int32_t pool, uint32_t* mtiles, int64_t cap, int32_t* count, uint32_t* tau, uint32_t* open,
+                        int32_t* fb);
+int rr_debug_select_traces(rr_index* ix, int32_t nq, int32_t* out);
 // tools/k5_stamps.py: in-kernel phase clocks of the last ce_ffn_fused launch (rr_ce.hip)
 int rr_debug_ce_ffn_stamps(unsigned long long* out20);
 // tools/k5_h2_stamps.py: phase clocks of one workgroup of the last FFN1 ce_gemm_h2 launch (rr_ce_h2.hip)

@@ -555,13 +555,18 @@ __device__ uint32_t rr_kth_largest_reg(const uint32_t (&r)[RR_SEL_RK], int n_min
                                        uint32_t (*cnt)[3][16], int& phase, int max_steps) {
     const int tid = threadIdx.x;
     const int ln = tid & 63;
-    uint32_t mx = 0, mn = 0xFFFFFFFFu;
+    // mn: the smallest NON-ZERO key.  Key 0 marks padding (a group without tiles: the short last run of a scan), never a
+    // score; counted into the spread it put the highest differing bit at 31 and left the 14 resolved bits to sign, exponent
+    // and five mantissa bits -- a threshold up to 3 % below the k-th largest.  Zeros still count as keys below every trial
+    // threshold; only when fewer than k keys are non-zero (the k-th largest IS a padding key) does the spread reach down to 0.
+    uint32_t mx = 0, mn = 0xFFFFFFFFu, nz = 0;
 #pragma unroll
-    for (int j = 0; j < RK; ++j)
-        if (j < n_mine) {
-            mx = r[j] > mx ? r[j] : mx;
-            mn = r[j] < mn ? r[j] : mn;
-        }
+    for (int j = 0; j < RK; ++j) {
+        const bool live = j < n_mine && r[j] != 0u;
+        if (j < n_mine) mx = r[j] > mx ? r[j] : mx;
+        if (live) mn = r[j] < mn ? r[j] : mn;
+        nz += (uint32_t)__popcll(__ballot(live));          // (wave-uniform)
+    }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         const uint32_t a = __shfl_xor(mx, m, 64), b = __shfl_xor(mn, m, 64);
@@ -571,12 +576,16 @@ __device__ uint32_t rr_kth_largest_reg(const uint32_t (&r)[RR_SEL_RK], int n_min
     if (ln == 0) {
         cnt[phase][0][tid >> 6] = mx;
         cnt[phase][1][tid >> 6] = mn;
+        cnt[phase][2][tid >> 6] = nz;
     }
     __syncthreads();
+    uint32_t nz_all = 0;
     for (int w = 0; w < 16; ++w) {
         mx = cnt[phase][0][w] > mx ? cnt[phase][0][w] : mx;
         mn = cnt[phase][1][w] < mn ? cnt[phase][1][w] : mn;
+        nz_all += cnt[phase][2][w];
     }
+    if (nz_all < k) mn = 0u;
     phase ^= 1;
     if (mx == mn) return mx;
     int bit = 31 - __clz(mx ^ mn);                        // highest bit in which keys differ
@@ -655,7 +664,8 @@ __device__ uint32_t rr_sel_open_groups(GroupKeyAt group_key_at, int ng, int pool
         n_mine += i < ng ? 1 : 0;
     }
     // 7 two-bit steps below the highest differing bit: tau is within 2^-14 of the spread of
-    // the group maxima below the exact pool-th largest, i.e. it opens a handful more groups
+    // the group maxima (of the groups that hold tiles: rr_kth_largest_reg leaves key 0 out of the
+    // spread) below the exact pool-th largest, i.e. it opens a handful more groups
     uint32_t tau = 1u;
     if (ng > pool) {
         if (ng <= 1 * RR_SEL_THREADS) tau = rr_kth_largest_reg<1>(r, n_mine, (uint32_t)pool, cnt, phase, 7);
@@ -1005,6 +1015,9 @@ __global__ __launch_bounds__(RR_SEL_THREADS) void rr_select_mtiles(
         dbg[q * 16 + 4] = (int32_t)(c1 - c0);         // shader cycles: threshold + group list | M-tile list
         dbg[q * 16 + 5] = (int32_t)(c2 - c1);
         for (int i = 6; i < 16; ++i) dbg[q * 16 + i] = -1;
+#ifdef RR_DEBUG_HARNESS
+        dbg[q * 16 + 6] = (int32_t)open;              // rr_debug_flt_select: the key M-tiles were opened down to
+#endif
     }
 }
 

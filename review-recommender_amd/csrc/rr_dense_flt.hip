@@ -1512,6 +1512,47 @@ static int rr_dense_chunk_flt_t(rr_index* ix, const void* scan_mat, const float*
     return rr_flt_after_scan<ROWS_BF16>(ix, G, d_q, nq, 0, pool, d_rows, d_scores, sigma, st, ph);
 }
 
+// The two-set launches of rr_dense_pair_flt_t (the debug harness launches them through these as well): planes, bounds and
+// [sigma] of both sets are in place.
+static int rr_flt_launch_fltq(rr_index* ix, const rr_scan_geom& G, const void* scan_mat, int nq_a, int nq_b, bool noasm, hipStream_t st) {
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    const int slot = rr_scan_events_begin(ix, st);
+    rr_scan_note(ix, 5, 9, nq_a + nq_b, 1, 2);
+    if (noasm)
+        hipLaunchKernelGGL((rr_scan_fltq<false>), dim3(G.n_waves), dim3(256), 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
+                           reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, X.eps, nq_a, nq_b,
+                           rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr);
+    else
+        hipLaunchKernelGGL((rr_scan_fltq<true>), dim3(G.n_waves), dim3(256), 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
+                           reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, X.eps, nq_a, nq_b,
+                           rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr);
+    rr_scan_events_end(ix, slot, st);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+static int rr_flt_launch_dual(rr_index* ix, const rr_scan_geom& G, const void* scan_mat, int nq_a, int nq_b, const float* sg0, hipStream_t st) {
+    constexpr int THREADS = RR_FLT_THREADS(4);
+    const int nb = (G.n_waves + THREADS / 64 - 1) / (THREADS / 64);        // workgroups per set
+    const dim3 grid(((nb + 7) / 8) * 16), block(THREADS);
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    uint32_t* dummy = sg0 ? reinterpret_cast<uint32_t*>(ix->d_gmax) + (size_t)4 * G.n_tiles * RR_FLT_MAXQ : nullptr;
+    const int slot = rr_scan_events_begin(ix, st);
+    rr_scan_note(ix, 5, 8, nq_a + nq_b, 1, 2);
+    static const bool no_couple = getenv("RR_NO_COUPLE") != nullptr;
+    if (!ix->d_flt_prog) {
+        RR_HIP_TRY(hipMalloc((void**)&ix->d_flt_prog, sizeof(uint32_t) * 2 * RR_MAX_SCAN_WAVES));
+        RR_HIP_TRY(hipMemsetAsync(ix->d_flt_prog, 0, sizeof(uint32_t) * 2 * RR_MAX_SCAN_WAVES, st));
+    }
+    ix->flt_seq = (ix->flt_seq + 1) & 0x7FFFu;
+    hipLaunchKernelGGL((rr_scan_flt16<4, 0, true>), grid, block, 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
+                       reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, X.eps, nq_a, sg0, dummy,
+                       nq_b, rr_flt_mmax_set_stride(G), no_couple ? (uint32_t*)nullptr : ix->d_flt_prog,
+                       (uint32_t)(ix->flt_seq + 1) << 16, rr_flt_tune());
+    rr_scan_events_end(ix, slot, st);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
 // 129 .. 256 queries whose second part still fills a 128-slot launch (> 64 queries): two scan launches, one selection
 template <bool SCAN_BF16, bool ROWS_BF16>
 static int rr_dense_pair_flt_t(rr_index* ix, const void* scan_mat, const float* d_q, int nq_a, int nq_b, int pool,
@@ -1541,40 +1582,12 @@ static int rr_dense_pair_flt_t(rr_index* ix, const void* scan_mat, const float* 
                                        prep_both ? 0 : 1);
     if (rc != RR_OK) return rc;
     if (fltq) {
-        const rr_x3_scratch X = rr_x3_scratch_of(ix);
-        const int slot = rr_scan_events_begin(ix, st);
-        rr_scan_note(ix, 5, 9, nq_a + nq_b, 1, 2);
         static const bool noasm = getenv("RR_FLTQ_NOASM") != nullptr;    // the C++ bodies everywhere (A/B)
-        if (noasm)
-            hipLaunchKernelGGL((rr_scan_fltq<false>), dim3(G.n_waves), dim3(256), 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
-                               reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, X.eps, nq_a, nq_b,
-                               rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr);
-        else
-            hipLaunchKernelGGL((rr_scan_fltq<true>), dim3(G.n_waves), dim3(256), 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
-                               reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, X.eps, nq_a, nq_b,
-                               rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr);
-        rr_scan_events_end(ix, slot, st);
-        RR_HIP_TRY(hipGetLastError());
+        rc = rr_flt_launch_fltq(ix, G, scan_mat, nq_a, nq_b, noasm, st);
+        if (rc != RR_OK) return rc;
     } else if (dual) {
-        constexpr int THREADS = RR_FLT_THREADS(4);
-        const int nb = (G.n_waves + THREADS / 64 - 1) / (THREADS / 64);        // workgroups per set
-        const dim3 grid(((nb + 7) / 8) * 16), block(THREADS);
-        const rr_x3_scratch X = rr_x3_scratch_of(ix);
-        uint32_t* dummy = sg0 ? reinterpret_cast<uint32_t*>(ix->d_gmax) + (size_t)4 * G.n_tiles * RR_FLT_MAXQ : nullptr;
-        const int slot = rr_scan_events_begin(ix, st);
-        rr_scan_note(ix, 5, 8, nq_a + nq_b, 1, 2);
-        static const bool no_couple = getenv("RR_NO_COUPLE") != nullptr;
-        if (!ix->d_flt_prog) {
-            RR_HIP_TRY(hipMalloc((void**)&ix->d_flt_prog, sizeof(uint32_t) * 2 * RR_MAX_SCAN_WAVES));
-            RR_HIP_TRY(hipMemsetAsync(ix->d_flt_prog, 0, sizeof(uint32_t) * 2 * RR_MAX_SCAN_WAVES, st));
-        }
-        ix->flt_seq = (ix->flt_seq + 1) & 0x7FFFu;
-        hipLaunchKernelGGL((rr_scan_flt16<4, 0, true>), grid, block, 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
-                           reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, X.eps, nq_a, sg0, dummy,
-                           nq_b, rr_flt_mmax_set_stride(G), no_couple ? (uint32_t*)nullptr : ix->d_flt_prog,
-                           (uint32_t)(ix->flt_seq + 1) << 16, rr_flt_tune());
-        rr_scan_events_end(ix, slot, st);
-        RR_HIP_TRY(hipGetLastError());
+        rc = rr_flt_launch_dual(ix, G, scan_mat, nq_a, nq_b, sg0, st);
+        if (rc != RR_OK) return rc;
     }
     return rr_flt_after_scan<ROWS_BF16>(ix, G, d_q, nq_a, nq_b, pool, d_rows, d_scores, sg0, st, ph);
 }
@@ -1810,6 +1823,161 @@ extern "C" int rr_debug_fltq_compare(rr_index* ix, int64_t* out) {
                 (long long)by_q32[2], (long long)by_q32[3], (long long)by_nib[0], (long long)by_nib[1], (long long)by_nib[2], (long long)by_nib[3],
                 (long long)by_nib[4], (long long)by_nib[5], (long long)by_nib[6], (long long)by_nib[7]);
     }
+    return RR_OK;
+}
+
+// ---- one filter scan by itself, its raw output on the host (tests/test_gpu_flt_words.py)
+// Sentinels the scratch is filled with before the launch.  Tile word: the low half is the bf16 image of a NaN -- no scan
+// stores one: its maxima are v_max results of finite scores (a NaN operand is dropped), and rounding a finite maximum up
+// ends at +inf (0x7F80) at most.  Group key: rr_f2key of a NaN, above rr_f2key(+inf) = 0xFF800000, the largest key a
+// maximum has.  A word the store prefilter skipped, or one no wave wrote, is still the sentinel afterwards.
+#define RR_DEBUG_WORD_SENTINEL 0x5A5A7FC1u
+#define RR_DEBUG_KEY_SENTINEL 0xFFC00001u
+// (Test-only state: one scan at a time, not thread-safe, and the pointer is not cleared when the index is closed -- call
+//  rr_debug_flt_select only on the index rr_debug_flt_words just ran on.  rr_debug_flt_words turns the index's bf16 plane on
+//  (use_shadow) for scans 1..4 and leaves the sentinels, not the product's "-inf, no gaps" initial words, in the scratch: both
+//  are harmless to later searches -- a sentinel's NaN maximum opens nothing -- but the index is a test index from then on.)
+struct rr_debug_flt_state {          // what rr_debug_flt_words left for rr_debug_flt_select
+    rr_index* ix;
+    rr_scan_geom G;
+    int nq_a, nq_b;
+    const float* sigma;
+};
+static rr_debug_flt_state g_debug_flt = {nullptr, {}, 0, 0, nullptr};
+
+template <int NQ2, bool SCAN_BF16>
+static int rr_debug_flt_single(rr_index* ix, const void* scan_mat, int nq, int pool, bool prefilter, rr_flt_bounds nb, bool launch,
+                               rr_scan_geom* G, const float** sigma, hipStream_t st) {
+    *G = rr_flt_geom<NQ2, SCAN_BF16>(ix);
+    if (!launch) return RR_OK;
+    return rr_flt_scan_set<NQ2, SCAN_BF16>(ix, 0, *G, scan_mat, ix->d_q, nq, pool, nb, st, sigma, true, prefilter, 1);
+}
+
+// scan: 0 rr_scan_flt<NQ2> over the fp32 rows; 1 rr_scan_flt16<NQ2> over the bf16 plane of an fp32 index / over a bf16
+// matrix, `prefilter` != 0: with the store prefilter where the product would run it (>= 2M rows); 2 the two-set
+// rr_scan_flt16<4, 0, true>; 3 rr_scan_fltq<false>; 4 rr_scan_fltq<true>.  NQ2 = 1 | 2 | 4 for nq_a <= 32 | <= 64 | more,
+// as in rr_dense_chunk_flt; the two-set launches want nq_a = RR_FLT_MAXQ and nq_b >= 1.  The queries (device, (nq_a +
+// nq_b) x dim) go through rr_flt_pad_prep, the launch through the product's own launch code.
+// geom[16]: n_rows, n_tiles (64 rows), tiles_per_wave, n_waves, gpw, tiles_per_group, query stride, words per set
+// (= 2 n_tiles x stride), keys per set (= n_waves gpw x stride), sets, store prefilter on, NQ2, word sentinel, key sentinel,
+// the scratch's set strides of the words and of the keys.  words == NULL: geometry only, nothing is launched.
+// eps[256] / sigma[256]: entries of set s at 128 s.  words: [set][32-row tile][stride]; keys: [set][group][stride].
+extern "C" int rr_debug_flt_words(rr_index* ix, const float* d_queries, int32_t nq_a, int32_t nq_b, int32_t scan, int32_t prefilter,
+                                  int32_t pool, int64_t* geom, float* eps, float* sigma, uint32_t* words, int64_t words_cap,
+                                  uint32_t* keys, int64_t keys_cap) {
+    RR_REQUIRE(ix && geom && ix->dim_pad == 384 && ix->d_matrix, "index of dim 384 expected");
+    RR_REQUIRE(scan >= 0 && scan <= 4 && nq_a >= 1 && nq_a <= RR_FLT_MAXQ && nq_b >= 0 && nq_b <= RR_FLT_MAXQ, "scan %d / %d + %d queries", scan, nq_a, nq_b);
+    RR_REQUIRE(scan >= 2 ? (nq_a == RR_FLT_MAXQ && nq_b >= 1) : nq_b == 0, "two-set launches take 128 + nq_b queries, the others one set");
+    RR_REQUIRE(ix->scratch_q >= 64 && ix->maxima_q >= RR_FLT_MAXQ && ix->cur_slot == 0,
+               "run a batched search of 64 queries or more first (allocates the scratch)");
+    const bool b = ix->dtype == RR_DTYPE_BF16;
+    RR_REQUIRE(scan != 0 || !b, "rr_scan_flt scans fp32 rows");
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = nullptr;
+    const bool launch = words != nullptr;
+    RR_REQUIRE(!launch || (d_queries && eps && sigma && keys), "NULL argument");
+    g_debug_flt.ix = nullptr;
+    const void* scan_mat = ix->d_matrix;
+    if (scan != 0 && !b) {
+        ix->use_shadow = 1;
+        const int rc = rr_flt_ensure_shadow(ix, st);
+        if (rc != RR_OK) return rc;
+        RR_REQUIRE(ix->shadow_valid, "no room for the bf16 filter plane");
+        scan_mat = ix->d_shadow;
+    }
+    rr_flt_bounds nb = {0.f, 0.f};
+    const int nq = nq_a + nq_b;
+    if (launch) {
+        int rc = rr_flt_get_bounds(ix, st, &nb);
+        if (rc != RR_OK) return rc;
+        const size_t n_words = (size_t)4 * ((ix->n_rows + 63) / 64) * RR_FLT_MAXQ;       // both sets (rr_ensure_maxima)
+        RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_gmax, (int)RR_DEBUG_WORD_SENTINEL, n_words, st));
+        RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_smax, (int)RR_DEBUG_KEY_SENTINEL, (size_t)2 * rr_flt_smax_set_stride(), st));
+        rc = rr_flt_pad_prep(ix, d_queries, nq, (int)rr_round_up(nq, RR_MFMA_MAXQ), st);
+        RR_REQUIRE(rc == RR_OK, "no finite row-norm bound: the filter scans do not run on this matrix");
+    }
+    rr_flt_fresh_guard fresh_guard{ix};
+    rr_scan_geom G;
+    const float* sg = nullptr;
+    int rc = RR_OK;
+    const int nq2 = nq_a <= 32 ? 1 : nq_a <= 64 ? 2 : 4;
+    const bool pre = prefilter != 0;
+    if (scan == 0) {
+        rc = nq2 == 1 ? rr_debug_flt_single<1, false>(ix, scan_mat, nq_a, pool, false, nb, launch, &G, &sg, st)
+           : nq2 == 2 ? rr_debug_flt_single<2, false>(ix, scan_mat, nq_a, pool, false, nb, launch, &G, &sg, st)
+                      : rr_debug_flt_single<4, false>(ix, scan_mat, nq_a, pool, false, nb, launch, &G, &sg, st);
+    } else if (scan == 1) {
+        rc = nq2 == 1 ? rr_debug_flt_single<1, true>(ix, scan_mat, nq_a, pool, pre, nb, launch, &G, &sg, st)
+           : nq2 == 2 ? rr_debug_flt_single<2, true>(ix, scan_mat, nq_a, pool, pre, nb, launch, &G, &sg, st)
+                      : rr_debug_flt_single<4, true>(ix, scan_mat, nq_a, pool, pre, nb, launch, &G, &sg, st);
+    } else if (scan == 2) {
+        G = rr_flt_geom<4, true>(ix, true);
+        if (launch) rc = rr_flt_launch_dual(ix, G, scan_mat, nq_a, nq_b, nullptr, st);
+    } else {
+        G = rr_fltq_geom(ix);
+        if (launch) rc = rr_flt_launch_fltq(ix, G, scan_mat, nq_a, nq_b, scan == 3, st);
+    }
+    if (rc != RR_OK) return rc;
+    const int sets = nq_b > 0 ? 2 : 1;
+    const int64_t per_set_w = 2 * G.n_tiles * G.qs, per_set_k = (int64_t)G.n_waves * G.gpw * G.qs;
+    const int64_t g[16] = {G.n_rows, G.n_tiles, G.tiles_per_wave, G.n_waves, G.gpw, G.tiles_per_group, G.qs, per_set_w, per_set_k, sets,
+                           sg ? 1 : 0, nq2, (int64_t)RR_DEBUG_WORD_SENTINEL, (int64_t)RR_DEBUG_KEY_SENTINEL,
+                           rr_flt_mmax_set_stride(G), rr_flt_smax_set_stride()};
+    memcpy(geom, g, sizeof(g));
+    if (!launch) return RR_OK;
+    RR_REQUIRE(words_cap >= sets * per_set_w && keys_cap >= sets * per_set_k, "output arrays too small: %lld words, %lld keys wanted",
+               (long long)(sets * per_set_w), (long long)(sets * per_set_k));
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    for (int s = 0; s < sets; ++s) {
+        RR_HIP_TRY(hipMemcpy(words + s * per_set_w, reinterpret_cast<const uint32_t*>(ix->d_gmax) + s * rr_flt_mmax_set_stride(G),
+                             sizeof(uint32_t) * per_set_w, hipMemcpyDeviceToHost));
+        RR_HIP_TRY(hipMemcpy(keys + s * per_set_k, ix->d_smax + s * rr_flt_smax_set_stride(), sizeof(uint32_t) * per_set_k,
+                             hipMemcpyDeviceToHost));
+    }
+    RR_HIP_TRY(hipMemcpy(eps, rr_x3_scratch_of(ix).eps, sizeof(float) * RR_SEL_MAXQ, hipMemcpyDeviceToHost));
+    for (int i = 0; i < RR_SEL_MAXQ; ++i) sigma[i] = -INFINITY;
+    if (sg) RR_HIP_TRY(hipMemcpy(sigma, sg, sizeof(float) * RR_FLT_MAXQ, hipMemcpyDeviceToHost));
+    g_debug_flt = rr_debug_flt_state{ix, G, nq_a, nq_b, sg};
+    return RR_OK;
+}
+
+// The product's selection (rr_select_mtiles, through rr_launch_select_mtiles as rr_flt_finish calls it) on the words and
+// keys the last rr_debug_flt_words of this index left in the scratch.  Per query Q of the launch: mtiles[Q][cap] (the first
+// min(count, cap) listed 8-row M-tiles), count, tau (key of the row cut), open (key the M-tiles were opened down to), fb.
+extern "C" int rr_debug_flt_select(rr_index* ix, int32_t pool, uint32_t* mtiles, int64_t cap, int32_t* count, uint32_t* tau,
+                                   uint32_t* open, int32_t* fb) {
+    RR_REQUIRE(ix && mtiles && count && tau && open && fb && cap >= 1 && cap <= RR_X3_MCAP, "NULL argument / cap out of range");
+    RR_REQUIRE(g_debug_flt.ix == ix, "rr_debug_flt_words has not run on this index");
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = nullptr;
+    const rr_debug_flt_state& S = g_debug_flt;
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    const int nq = S.nq_a + S.nq_b;
+    rr_launch_select_mtiles(ix, S.G, S.nq_a, pool, st, X.eps, S.sigma, S.nq_b, rr_flt_mmax_set_stride(S.G), rr_flt_smax_set_stride());
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    RR_HIP_TRY(hipMemcpy(count, X.count, sizeof(int32_t) * nq, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(tau, X.tau, sizeof(uint32_t) * nq, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(fb, X.fb, sizeof(int32_t) * nq, hipMemcpyDeviceToHost));
+    std::vector<int32_t> trace((size_t)16 * nq);
+    RR_HIP_TRY(hipMemcpy(trace.data(), ix->d_sel_trace, sizeof(int32_t) * 16 * nq, hipMemcpyDeviceToHost));
+    for (int q = 0; q < nq; ++q) {
+        open[q] = (uint32_t)trace[(size_t)16 * q + 6];
+        RR_HIP_TRY(hipMemcpy(mtiles + (int64_t)q * cap, X.mtiles + (int64_t)q * RR_X3_MCAP, sizeof(uint32_t) * cap, hipMemcpyDeviceToHost));
+    }
+    return RR_OK;
+}
+
+// The path trace of every query of the last selection launch (rr_index_select_trace returns query 0's): out[nq][16];
+// [q][0] == 2: the filter path served the query, anything else: one of the fallbacks did.
+extern "C" int rr_debug_select_traces(rr_index* ix, int32_t nq, int32_t* out) {
+    RR_REQUIRE(ix && out && nq >= 1 && nq <= RR_SEL_MAXQ, "NULL argument / nq out of range");
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    RR_HIP_TRY(hipDeviceSynchronize());
+    RR_HIP_TRY(hipMemcpy(out, ix->d_sel_trace, sizeof(int32_t) * 16 * nq, hipMemcpyDeviceToHost));
     return RR_OK;
 }
 

@@ -26,6 +26,18 @@ def test_library_exports_every_declared_symbol(hip):
     assert set(names) == set(_lib.PROTOTYPES), "ctypes prototypes and header disagree"
 
 
+def test_debug_prototypes_match_the_harness_header():
+    """csrc/rr_debug.h (librr_hip_dbg.so only) against _lib.DEBUG_PROTOTYPES: the same names, the same number of arguments;
+    none of them is part of the product ABI."""
+    from review_recommender_amd import _lib
+    header = re.sub(r"//[^\n]*", "", (PKG / "csrc" / "rr_debug.h").read_text())
+    decls = dict(re.findall(r"\bint\s+(rr_debug_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header))
+    assert set(decls) == set(_lib.DEBUG_PROTOTYPES)
+    for name, args in decls.items():
+        assert len([a for a in args.split(",") if a.strip()]) == len(_lib.DEBUG_PROTOTYPES[name][1]), name
+    assert not set(decls) & set(declared_symbols()) and not set(decls) & set(_lib.PROTOTYPES)
+
+
 def test_fuse_params_layout_matches_header():
     from review_recommender_amd import _lib
     header = (ROOT / "include" / "rr_hip.h").read_text()

@@ -335,6 +335,51 @@ def test_one_million_rows_full_size():
     ix.close()
 
 
+_TRACES_10M = r"""
+import os, sys
+os.environ["RR_DEBUG_HARNESS"] = "1"
+sys.path.insert(0, @ROOT@)
+import ctypes as C
+import numpy as np, torch
+from review_recommender_amd import _lib, synth
+from review_recommender_amd.index import ProductIndex
+n, pool = 10_000_000, 150
+mat = torch.empty((n, 384), device="cuda", dtype=torch.float32)
+g = torch.Generator(device="cuda")
+for b, s in enumerate(range(0, n, 1_250_000)):
+    g.manual_seed(9000 + b)
+    blk = torch.randn((1_250_000, 384), generator=g, device="cuda")
+    mat[s:s + 1_250_000] = blk / blk.norm(dim=1, keepdim=True)
+del blk
+ix = ProductIndex(None, n_rows=n, dim=384, device_ptr=mat.data_ptr(), keepalive=mat)
+Q = synth.unit_rows(256, 384, 4242)
+Q[5] = mat[7_654_321].cpu().numpy()
+Q[200] = mat[9_999_999].cpu().numpy()
+ix.dense_topk(Q, pool)
+info = ix.last_scan_info()
+assert info[0] == 5 and info[1] == 9 and info[2] == 256 and info[4] == 2, info      # rr_scan_fltq over the bf16 plane, as in the parent
+tr = np.empty((256, 16), dtype=np.int32)
+_lib.check(_lib.load().rr_debug_select_traces(ix.handle, 256, tr.ctypes.data_as(C.c_void_p)), "rr_debug_select_traces")
+print("TRACES|" + ",".join(str(int(x)) for x in tr[:, 0]))
+"""
+
+
+def _no_query_of_the_10m_batch_fell_back():
+    """rr_index_select_trace returns query 0's trace only: the same matrix, queries and search in a child on the harness
+    library, whose rr_debug_select_traces returns the path of all 256 (2 = served by the filter path, no fallback)."""
+    import pathlib
+    import subprocess
+    import sys
+    from review_recommender_amd.build import DEBUG_LIB_PATH
+    assert DEBUG_LIB_PATH.exists(), "librr_hip_dbg.so not built (python review-recommender_amd/build.py --debug)"
+    root = str(pathlib.Path(__file__).resolve().parent.parent)
+    p = subprocess.run([sys.executable, "-c", _TRACES_10M.replace("@ROOT@", repr(root))], capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    paths = [int(x) for x in next(l for l in p.stdout.splitlines() if l.startswith("TRACES|"))[7:].split(",")]
+    assert len(paths) == 256 and all(x == 2 for x in paths), [i for i, x in enumerate(paths) if x != 2]
+    return True
+
+
 def test_ten_million_rows_batched_at_full_size():
     """BASELINE's headline size (10M x 384 fp32, 15.4 GB), generated on the device in seeded blocks, searched with the
     headline batch: 256 queries = ONE launch of the query-stationary filter scan rr_scan_fltq (what bench.py times),
@@ -363,6 +408,7 @@ def test_ten_million_rows_batched_at_full_size():
     info = ix.last_scan_info()
     assert info[0] == 5 and info[1] == 9 and info[2] == 256 and info[4] == 2, info      # rr_scan_fltq over the bf16 plane
     assert ix.select_trace()[0] == 2
+    assert _no_query_of_the_10m_batch_fell_back()
     assert rows[5][0] == 7_654_321 and abs(scores[5][0] - 1.0) < 1e-6
     assert rows[200][0] == 9_999_999 and abs(scores[200][0] - 1.0) < 1e-6
     for i in range(len(Q)):                                  # properties: sorted, distinct, in range

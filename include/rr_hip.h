@@ -320,8 +320,8 @@ int rr_reviews_best_cut_dev(rr_reviews* rv, const float* d_queries, int32_t n_qu
  *   SentenceTransformer.encode([query], normalize_embeddings=True)        app/app_product_search.py:250-251, app/test.py:232
  *     (BAAI/bge-small-en-v1.5: BertModel of the same block shape, 12 layers, CLS pooling; the l2 normalisation is the caller's)
  * The kernels are built for hidden 384 / 12 heads x 32 / FFN 1536; layer count, vocabulary, positions (<= 512) are free.
- * Tokenisation (WordPiece): rr_wp_encode_dev below turns ASCII documents into the packed ids this call takes, on the device
- * (csrc/rr_wordpiece.hip); text with bytes >= 0x80 and text PAIRS (the reranker) are tokenised on the host
+ * Tokenisation (WordPiece): rr_wp_encode_dev below turns documents (ASCII, or UTF-8 on a handle of rr_wp_create_utf8) into
+ * the packed ids this call takes, on the device (csrc/rr_wordpiece.hip); what it flags and text PAIRS (the reranker) are tokenised on the host
  * (review-recommender_amd/wordpiece.py). */
 typedef struct rr_ce rr_ce;
 typedef struct rr_ce_config {
@@ -390,12 +390,27 @@ typedef struct rr_wp rr_wp;
 int rr_wp_create(int32_t device, const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces,
                  int32_t unk_id, int32_t cls_id, int32_t sep_id, int32_t max_chars_per_word, rr_wp** out);
 int rr_wp_destroy(rr_wp* wp);
+/* The UTF-8 handle: rr_wp_encode_dev on it tokenises Unicode text (csrc/rr_wordpiece.hip: rr_wp_tokenize_utf8) and gives the
+ * host tokenizer's ids for it, all-ASCII documents included.  The three arrays are the per-code-point table of
+ * review-recommender_amd/wp_unicode.py (unicode_tables(): built from the interpreter's unicodedata so that it agrees with
+ * the host tokenizer): h_stage1 [n_stage1 = 8704] maps each block of 128 code points to a block of h_stage2 [n_stage2, whole
+ * blocks]; an entry = class (bits 0-2: 0 deleted, 1 blank, 2 CJK, 3 other, 4 hard) | mapped code points n (bits 3-4, 0..3) |
+ * identity (bit 5) | punctuation flag of mapped code point j (bit 6 + j) | first mapped code point in h_pool [n_pool]
+ * (bits 9-31).  The tables are checked here (RR_E_INVALID): nothing the kernel indexes can leave them.  The piece table
+ * keeps pieces with bytes >= 0x80, and max_chars_per_word counts code points.  needs_host = 1 on this handle only for a
+ * document that, in the bytes the kernel reads (the whole document, or its first 4 096 bytes cut back to a character
+ * boundary): is malformed UTF-8 (overlong forms, surrogates, values above U+10FFFF, truncated sequences); holds a hard code
+ * point; has a mapped text of more than 4 096 bytes; or is longer than the window without max_length - 2 pieces in it. */
+int rr_wp_create_utf8(int32_t device, const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces,
+                      int32_t unk_id, int32_t cls_id, int32_t sep_id, int32_t max_chars_per_word,
+                      const uint16_t* h_stage1, int32_t n_stage1, const uint32_t* h_stage2, int32_t n_stage2,
+                      const uint32_t* h_pool, int32_t n_pool, rr_wp** out);
 /* n_docs UTF-8 documents (document s = bytes d_text_off[s] .. d_text_off[s+1] of d_text; text_bytes = size of d_text,
  * below 2^31) -> exactly what rr_ce_forward_dev takes: sequence s = [CLS], the first max_length - 2 pieces, [SEP]; type ids
  * 0; position = index inside the sequence; d_cu_seqlens [n_docs + 1] the running sum; *d_max_len the longest sequence.
- * For an all-ASCII document the ids equal the host tokenizer's, id for id.  A document with any byte >= 0x80 is not
- * tokenised: d_needs_host[s] = 1 and its sequence is the placeholder [CLS] [SEP] (the packing stays dense; the caller
- * tokenises it on the host).  The kernel keeps the first 4 096 bytes of a document on chip: a longer ASCII document is
+ * For an all-ASCII document the ids equal the host tokenizer's, id for id.  On a handle of rr_wp_create a document with
+ * any byte >= 0x80 is not tokenised (a handle of rr_wp_create_utf8 tokenises it, with the exceptions listed there): d_needs_host[s] = 1 and its sequence is the placeholder [CLS] [SEP] (the packing stays dense; the caller
+ * tokenises it on the host).  The kernel keeps the first 4 096 bytes of a document on chip: a longer document is
  * answered from them when they already hold max_length - 2 pieces in words that end inside them, else needs_host = 1.
  * token_capacity (elements of the three id arrays; n_docs * max_length always suffices, 2 * n_docs is required) bounds
  * the writes: ids beyond it are dropped and d_cu_seqlens[n_docs] tells what was needed.
@@ -418,6 +433,10 @@ int rr_wp_status(rr_wp* wp, int32_t* out_bad_docs);
 int rr_wp_table_slots(int32_t n_pieces, int32_t* out_slots);
 int rr_wp_build_table(const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces, int32_t max_chars_per_word,
                       int32_t n_slots, int32_t* h_slots, int32_t* out_kept);
+/* The same for a UTF-8 handle: pieces with bytes >= 0x80 are kept, and max_chars_per_word counts code points (the bytes that
+ * are not 10xxxxxx); the length word of a slot stays the piece's length in BYTES. */
+int rr_wp_build_table_utf8(const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces, int32_t max_chars_per_word,
+                           int32_t n_slots, int32_t* h_slots, int32_t* out_kept);
 
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard

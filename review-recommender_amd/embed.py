@@ -9,14 +9,17 @@ over `normalize_text(agg_text)`), the builder of product_emb.npy / product_emb_m
     rr_index_store_rows_dev   x / max(||x||, 1e-12) into the index's rows
 
 with no host hop between the three: the host reads back two integers per chunk (tokens, longest sequence: what the forward
-call takes as arguments) and the needs_host flags, and prepares chunk i + 1 while chunk i runs.  Documents with a byte >= 0x80
-are tokenised by wordpiece.py and encoded in one small pass at the end, scattered into their rows.  Review embeddings
+call takes as arguments) and the needs_host flags, and prepares chunk i + 1 while chunk i runs.  The tokenizer is the UTF-8
+kernel (Unicode text through the table of wp_unicode.py); the few documents it flags (a hard code point, a mapped text beyond
+its buffers: wp_unicode.model_tokenize) are tokenised by wordpiece.py and encoded in one small pass at the end, scattered into
+their rows.  RR_WP_ASCII=1 in the environment restores the ASCII kernel, which flags every document with a byte >= 0x80.  Review embeddings
 (nlp/11...:95-169) are not built here.
 """
 from __future__ import annotations
 
 import argparse
 import ctypes as C
+import os
 import re
 import sys
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -82,35 +85,49 @@ def piece_arrays(vocab: Dict[str, int]) -> Tuple[np.ndarray, np.ndarray]:
     return blob, off
 
 
-def build_piece_table(vocab: Dict[str, int], max_chars_per_word: int = 100):
+def build_piece_table(vocab: Dict[str, int], max_chars_per_word: int = 100, unicode: bool = False):
     """The open-addressing table the device matches against, built by the library ON THE HOST (rr_wp_build_table; no GPU
-    needed): (slots [n_slots][4] int32 = hash, first byte, length | ## form << 16, id or -1; piece bytes; pieces kept)."""
+    needed): (slots [n_slots][4] int32 = hash, first byte, length in bytes | ## form << 16, id or -1; piece bytes; pieces
+    kept).  unicode=True: the table of a UTF-8 handle (rr_wp_build_table_utf8), which keeps pieces with bytes >= 0x80 and
+    counts max_chars_per_word in code points."""
     lib = _lib.load()
     blob, off = piece_arrays(vocab)
     n_slots, kept = C.c_int32(), C.c_int32()
     _lib.check(lib.rr_wp_table_slots(len(off) - 1, C.byref(n_slots)), "rr_wp_table_slots")
     slots = np.empty((n_slots.value, 4), dtype=np.int32)
-    _lib.check(lib.rr_wp_build_table(_lib.ptr(blob), _lib.ptr(off), len(off) - 1, max_chars_per_word, n_slots.value,
-                                     _lib.ptr(slots), C.byref(kept)), "rr_wp_build_table")
+    fn, name = (lib.rr_wp_build_table_utf8, "rr_wp_build_table_utf8") if unicode else (lib.rr_wp_build_table, "rr_wp_build_table")
+    _lib.check(fn(_lib.ptr(blob), _lib.ptr(off), len(off) - 1, max_chars_per_word, n_slots.value, _lib.ptr(slots), C.byref(kept)),
+               name)
     return slots, blob, kept.value
 
 
 class DeviceWordPiece:
-    """`WordPieceTokenizer` for all-ASCII single texts on one GPU (csrc/rr_wordpiece.hip)."""
+    """`WordPieceTokenizer` for single texts on one GPU (csrc/rr_wordpiece.hip).  unicode=False: the ASCII kernel, which leaves
+    every document with a byte >= 0x80 to the host.  unicode=True: the UTF-8 kernel over the per-code-point table of
+    wp_unicode.unicode_tables(); it leaves to the host only what wp_unicode.model_tokenize flags."""
 
-    def __init__(self, tokenizer: WordPieceTokenizer, device: int = 0):
+    def __init__(self, tokenizer: WordPieceTokenizer, device: int = 0, unicode: bool = False):
         if not tokenizer.do_lower_case:
             raise ValueError("the device tokenizer lower-cases (uncased vocabularies); this tokenizer does not")
         import torch
         if not torch.cuda.is_available():
             raise _lib.HipLibraryError("no GPU visible: the device tokenizer runs on the device only")
-        self._torch, self.tokenizer, self.device = torch, tokenizer, device
+        self._torch, self.tokenizer, self.device, self.unicode = torch, tokenizer, device, bool(unicode)
         self._dev = torch.device("cuda", device)
         blob, off = piece_arrays(tokenizer.vocab)
         h = C.c_void_p()
-        _lib.check(_lib.load().rr_wp_create(device, _lib.ptr(blob), _lib.ptr(off), len(off) - 1, tokenizer.unk_id,
-                                            tokenizer.cls_id, tokenizer.sep_id, tokenizer.max_chars_per_word, C.byref(h)),
-                   "rr_wp_create")
+        if unicode:
+            from .wp_unicode import unicode_tables
+            t = unicode_tables()
+            st1, st2, pool = t["stage1"], t["stage2"], t["pool"]
+            _lib.check(_lib.load().rr_wp_create_utf8(device, _lib.ptr(blob), _lib.ptr(off), len(off) - 1, tokenizer.unk_id,
+                                                     tokenizer.cls_id, tokenizer.sep_id, tokenizer.max_chars_per_word,
+                                                     _lib.ptr(st1), len(st1), _lib.ptr(st2), len(st2), _lib.ptr(pool), len(pool),
+                                                     C.byref(h)), "rr_wp_create_utf8")
+        else:
+            _lib.check(_lib.load().rr_wp_create(device, _lib.ptr(blob), _lib.ptr(off), len(off) - 1, tokenizer.unk_id,
+                                                tokenizer.cls_id, tokenizer.sep_id, tokenizer.max_chars_per_word, C.byref(h)),
+                       "rr_wp_create")
         self._h = h
 
     @property
@@ -153,8 +170,8 @@ class DeviceWordPiece:
     def encode_dev(self, texts: Sequence[str], max_length: int):
         """The packed device tensors of `texts` (what `forward_packed_dev` takes) and the documents left to the host:
         (tok, typ, pos, cu_seqlens, max_len, needs_host) -- int32 device tensors, the longest sequence, and the indices of
-        the documents that were NOT tokenised (a byte >= 0x80, or longer than the kernel's window and not answerable from
-        it): their sequences are the placeholder [CLS] [SEP].  Waits for the result (the sizes are host integers)."""
+        the documents that were NOT tokenised (ASCII handle: a byte >= 0x80; UTF-8 handle: malformed UTF-8, a hard code point
+        or a mapped text beyond the buffers; both: longer than the kernel's window and not answerable from it): their sequences are the placeholder [CLS] [SEP].  Waits for the result (the sizes are host integers)."""
         torch = self._torch
         packed, info, n, cap, _keep = self.queue([t.encode("utf-8") for t in texts], max_length)
         torch.cuda.current_stream(self._dev).synchronize()
@@ -196,10 +213,11 @@ def _plan_chunks(docs_len: Sequence[int], max_length: int, chunk_tokens: int) ->
 
 
 def embed_texts_into(index: ProductIndex, texts: Sequence[str], encoder, *, first_row: int = 0,
-                     chunk_tokens: int = 131072, keep_rows: bool = False) -> Optional[np.ndarray]:
+                     chunk_tokens: int = 131072, keep_rows: bool = False, stats: Optional[dict] = None) -> Optional[np.ndarray]:
     """Encodes `texts` AS THEY ARE (no normalize_text, no length filter: build_product_embeddings does those) into rows
     [first_row, first_row + len(texts)) of `index` (local rows), l2-normalised with eps 1e-12.  `encoder` is a QueryEncoder
     with a vocabulary.  keep_rows: also return the normalised fp32 rows on the host (what a bf16 index cannot give back).
+    stats: a dict that receives "host_docs", the documents (indices into `texts`) the device tokenizer left to the host pass.
 
     The forward call gets the EXACT longest sequence of its chunk (read back with the token count, which it needs anyway),
     not the bound max_length."""
@@ -213,7 +231,8 @@ def embed_texts_into(index: ProductIndex, texts: Sequence[str], encoder, *, firs
     dev = torch.device("cuda", model.device)
     wp = getattr(encoder, "_device_wp", None)
     if wp is None:
-        wp = encoder._device_wp = DeviceWordPiece(encoder.tokenizer, model.device)
+        wp = encoder._device_wp = DeviceWordPiece(encoder.tokenizer, model.device,
+                                                  unicode=os.environ.get("RR_WP_ASCII") != "1")
     lib = _lib.load()
     kept = np.empty((n, HIDDEN), dtype=np.float32) if keep_rows else None
     fp32 = model.precision == "fp32"
@@ -300,7 +319,8 @@ def embed_texts_into(index: ProductIndex, texts: Sequence[str], encoder, *, firs
             settle(*prev)
         wp.check()
 
-        # the documents the device left to the host (bytes >= 0x80): one small pass, scattered into their rows
+        # the documents the device left to the host (wp_unicode.model_tokenize's reasons; with RR_WP_ASCII=1 every byte
+        # >= 0x80): one small pass, scattered into their rows
         at = 0
         while at < len(host_docs):
             part, tot = [], 0
@@ -330,11 +350,13 @@ def embed_texts_into(index: ProductIndex, texts: Sequence[str], encoder, *, firs
         main.synchronize()
         if scratch[0] is not None:
             scratch[0].close()
+    if stats is not None:
+        stats["host_docs"] = list(host_docs)
     return kept
 
 
 def build_product_embeddings(products, encoder, *, text_col: str = "agg_text", rows: Optional[Tuple[int, int]] = None,
-                             dtype: str = "f32", chunk_tokens: int = 131072, data_dir=None):
+                             dtype: str = "f32", chunk_tokens: int = 131072, data_dir=None, stats: Optional[dict] = None):
     """nlp/11_build_product_embeddings.py:50-92 on the GPU -> (ProductIndex, meta, emb or None).
 
     The product table is filtered as the reference does (`filter_products`), its normalised texts are encoded into a new index
@@ -350,7 +372,7 @@ def build_product_embeddings(products, encoder, *, text_col: str = "agg_text", r
     meta, texts = meta.iloc[lo:hi].reset_index(drop=True), texts[lo:hi]
     index = ProductIndex(None, n_rows=hi - lo, dim=HIDDEN, device=encoder.model.device, row_offset=lo, dtype=dtype)
     emb = embed_texts_into(index, texts, encoder, chunk_tokens=chunk_tokens,
-                           keep_rows=data_dir is not None and dtype != "f32")
+                           keep_rows=data_dir is not None and dtype != "f32", stats=stats)
     if data_dir is not None:
         from .artifacts import save_artifacts
         if emb is None:

@@ -1,0 +1,208 @@
+"""The UTF-8 device tokenizer (csrc/rr_wordpiece.hip: rr_wp_tokenize_utf8, embed.DeviceWordPiece(unicode=True)) against the
+`transformers` fixtures, the host tokenizer and the CPU model of its flags (wp_unicode.model_tokenize): ids exactly, and
+needs_host for the model's reasons only."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT
+from review_recommender_amd import synth, wp_unicode as U
+from review_recommender_amd.wordpiece import WordPieceTokenizer
+
+import wp_utf8_texts as X
+from test_gpu_wordpiece import assert_equals_host, cut, host_ids, run
+
+pytestmark = pytest.mark.gpu
+
+
+def unicode_tokenizer(tok):
+    from review_recommender_amd.embed import DeviceWordPiece
+    return DeviceWordPiece(tok, 0, unicode=True)
+
+
+def run_bytes(wp, docs, L):
+    """encode_dev for documents given as raw bytes: (ids per document, needs_host flags)."""
+    import torch
+    packed, info, n, cap, _keep = wp.queue(docs, L)
+    torch.cuda.current_stream().synchronize()
+    wp.check()                                                   # rr_wp_status stays clean
+    h = info.numpy()
+    tok, _, _, cu = wp.views(packed, n, cap, int(h[0]))
+    tok, cu = tok.cpu().numpy(), cu.cpu().numpy()
+    return [tok[cu[i]:cu[i + 1]].tolist() for i in range(n)], h[1:n + 1].astype(np.int64).tolist()
+
+
+def test_the_existing_fixtures_on_a_utf8_handle():
+    """k5_tokenizer.json (all ten texts: the ASCII handle flags "café" and "中文") and wp_ascii.json: the fixture ids, nothing
+    flagged."""
+    fx = json.loads((GOLDEN / "k5_tokenizer.json").read_text())
+    tok = WordPieceTokenizer({w: i for i, w in enumerate(fx["vocab"])})
+    wp = unicode_tokenizer(tok)
+    assert sum(not t.isascii() for t in fx["texts"]) == 2 and len(fx["texts"]) == 10
+    got = run(wp, fx["texts"], 32)
+    assert got[5] == []
+    assert_equals_host(got, fx["single_max32"], "k5_tokenizer.json on a UTF-8 handle")
+    fx = json.loads((GOLDEN / "wp_ascii.json").read_text())
+    tok = WordPieceTokenizer({w: i for i, w in enumerate(fx["vocab"])})
+    wp = unicode_tokenizer(tok)
+    for L in sorted({c["max_length"] for c in fx["cases"]}):
+        cases = [c for c in fx["cases"] if c["max_length"] == L]
+        got = run(wp, [c["text"] for c in cases], L)
+        assert got[5] == [], (L, got[5])
+        assert_equals_host(got, [c["ids"] for c in cases], f"wp_ascii.json on a UTF-8 handle, max_length {L}")
+
+
+def test_wp_utf8_fixture_exactly():
+    fx = json.loads((GOLDEN / "wp_utf8.json").read_text())
+    print("wp_utf8.json ids written by:", fx["ids_from"])
+    tok = WordPieceTokenizer({w: i for i, w in enumerate(fx["vocab"])})
+    wp = unicode_tokenizer(tok)
+    assert len(fx["texts"]) >= 24 and sum(not t.isascii() for t in fx["texts"]) >= 24
+    for L in (32, 512):
+        got = run(wp, fx["texts"], L)
+        assert got[5] == [], (L, got[5])
+        assert_equals_host(got, fx[f"ids_max{L}"], f"wp_utf8.json max_length {L}")
+
+
+def clean_documents(tok, n, seed):
+    """Documents of up to 4 000 characters at non-ASCII densities 2 % .. 100 %, none with a reason to be flagged: a draw the
+    model flags (its bytes or its mapped text beyond the window) is shortened until it is not."""
+    rng = np.random.default_rng(seed)
+    docs = []
+    for d in range(n):
+        target = int(rng.integers(0, 301)) if rng.random() < 0.5 else int(rng.integers(0, 4001))
+        t = X.random_text(rng, target, float(rng.choice([0.02, 0.1, 0.3, 1.0])))
+        while U.model_tokenize(t, tok, 512, want_ids=False)[1]:
+            t = t[:len(t) * 3 // 4]
+        docs.append(t)
+    return docs
+
+
+def test_random_utf8_documents_equal_the_host_tokenizer():
+    tok = WordPieceTokenizer({w: i for i, w in enumerate(X.vocabulary())})
+    wp = unicode_tokenizer(tok)
+    texts = clean_documents(tok, 20_000, 13)
+    flags = [U.model_tokenize(t, tok, L, want_ids=False)[1] for t in texts for L in (8, 512)]
+    assert sum(flags) == 0                                       # on the CPU: the model flags none of them
+    nonascii = sum(not t.isascii() for t in texts)
+    longest = max(len(t.encode()) for t in texts)
+    print(f"{nonascii} of {len(texts)} documents hold non-ASCII text; longest {longest} bytes, {max(map(len, texts))} characters")
+    assert nonascii > 10_000 and longest > 4000 and max(map(len, texts)) > 3900
+    full = host_ids(tok, texts)
+    for L in (8, 32, 512):
+        got = run(wp, texts, L)
+        print("max_length", L, "documents flagged:", len(got[5]))
+        assert len(got[5]) == 0
+        assert_equals_host(got, cut(tok, full, L), f"random UTF-8 documents, max_length {L}")
+
+
+def test_planted_reasons_are_flagged_as_the_model_says():
+    tok = WordPieceTokenizer({w: i for i, w in enumerate(X.vocabulary())})
+    wp = unicode_tokenizer(tok)
+    rng = np.random.default_rng(3)
+    docs, why = [], []
+
+    def add(raw, reason):
+        docs.append(raw if isinstance(raw, bytes) else raw.encode("utf-8"))
+        why.append(reason)
+
+    for h in X.HARD_SAMPLES:                                      # (a) U+03A3, hard marks: anywhere in the document
+        add("soft " + h + " mug", "hard")
+        add(h, "hard")
+        add(X.random_text(rng, 2000, 0.3) + h, "hard")
+    add("ΚΟΣΜΟΣ κοσμος", "hard")
+    for raw in (b"\xc3", b"soft \xe4\xb8", b"\xf0\x9f\x98", b"\x80 mug", b"mug\xbf", b"\xc0\xaf", b"\xe0\x80\xaf", b"\xf0\x80\x80\xaf",
+                b"\xed\xa0\x80", b"\xf4\x90\x80\x80", b"\xf5\x80\x80\x80", b"\xff", b"a\xc3\xa9\xa9", b"\x80\x80\x80\x80\x80"):
+        add(raw, "malformed")                                     # (b) truncated, stray, overlong, surrogate, too large
+        add(b"caf\xc3\xa9 " + raw, "malformed")
+        add(X.random_text(rng, 900, 0.3).encode() + b" " + raw + b" soft", "malformed")
+    add(("x" * 15 + "é").encode() + b"\xe4\xb8", "malformed")      # a sequence cut by the end of the DOCUMENT: the next document
+    add("soft mug", None)                                         # is not read for it, and is answered as it stands
+    add(b"\xad soft", "malformed")
+    add("中文" * 3334, None)                              # 20 000 bytes of CJK: answered from the window
+    add("中" * 1365 + "文" * 5000, None)                  # the window ends between two characters
+    add("a" + "中" * 6000, None)                               # ... and one and two bytes into a character
+    add("ab" + "中" * 6000, None)
+    add("é" * 3000, "window")                                # one word through the whole window
+    add("soft " * 400 + "é" * 2000, "window")                # 400 pieces, then a word the window cuts
+    add("한" * 1000, "bound")                                # 3 000 bytes raw, 9 000 mapped
+    add("한" * 455 + "a", None)                              # 4 096 mapped bytes: the last that fit
+    add("한" * 455 + "ab", "bound")                          # 4 097
+    add("가" * 682 + "abcd", None)                           # (two jamo each) 4 096
+    add("가" * 682 + "abcde", "bound")
+    add("한국어 " * 2000, "bound")                   # longer than the window AND its mapped window beyond the bound
+    add("", None)
+    for L in (8, 32, 512):
+        model = [U.model_tokenize(d, tok, L) for d in docs]
+        for i, (m, r) in enumerate(zip(model, why)):
+            if not (L < 512 and r == "window"):                  # (the planted window cases are sized for 512)
+                assert m[2] == r, (L, i, docs[i][:40], m[2], r)
+        ids, flags = run_bytes(wp, docs, L)
+        assert flags == [m[1] for m in model], (L, [i for i in range(len(docs)) if flags[i] != model[i][1]])
+        for i, m in enumerate(model):
+            assert ids[i] == m[0], (L, i, docs[i][:40])
+            if not m[1]:
+                assert ids[i] == tok.encode_pair(docs[i].decode("utf-8"), None, L)[0].tolist(), (L, i)
+    assert {"hard", "malformed", "window", "bound", None} == set(why)
+
+
+CHILD = """
+import sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import numpy as np
+import test_gpu_wordpiece_utf8 as T
+rows, stats = T.embed_rows()
+assert len(stats["host_docs"]) == {n_nonascii}, (len(stats["host_docs"]), {n_nonascii})
+np.save({out!r}, rows)
+"""
+
+
+def embed_world():
+    from review_recommender_amd.cross_encoder import QueryEncoder
+    words = X.vocabulary() + [w for w in synth.WORDS if w not in set(X.vocabulary())] + ["caf", "##e", "中", "文"]
+    tok = WordPieceTokenizer({w: i for i, w in enumerate(words)})
+    enc = QueryEncoder(synth.bert_state_dict(78, n_layers=12, n_labels=0, prefix="", vocab=len(words)), tok)
+    return enc, X.mixed_product_texts(1500, 21, 0.3)
+
+
+def embed_rows():
+    from review_recommender_amd.embed import embed_texts_into, normalize_text
+    from review_recommender_amd.index import ProductIndex
+    enc, texts = embed_world()
+    texts = [normalize_text(t) for t in texts]
+    ix = ProductIndex(None, n_rows=len(texts), dim=384)
+    stats = {}
+    embed_texts_into(ix, texts, enc, chunk_tokens=16_384, stats=stats)
+    rows = ix.download_rows()
+    ix.close()
+    return rows, stats
+
+
+def test_embed_path_leaves_only_what_the_model_flags_to_the_host(tmp_path):
+    from review_recommender_amd.embed import normalize_text
+    from review_recommender_amd.index import ProductIndex
+    assert os.environ.get("RR_WP_ASCII") != "1"
+    enc, texts = embed_world()
+    texts = [normalize_text(t) for t in texts]
+    nonascii = [i for i, t in enumerate(texts) if not t.isascii()]
+    assert 0.25 * len(texts) < len(nonascii) < 0.4 * len(texts)
+    model = [i for i, t in enumerate(texts) if U.model_tokenize(t, enc.tokenizer, enc.max_length)[1]]
+    assert 1 <= len(model) <= 8                                  # the planted hard code points, and nothing else
+    rows, stats = embed_rows()
+    print(f"{len(nonascii)} of {len(texts)} texts hold non-ASCII text; left to the host: {stats['host_docs']}")
+    assert sorted(stats["host_docs"]) == model
+    want = ProductIndex.from_rows(enc.encode(texts), normalize=True).download_rows()
+    bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    diff = np.flatnonzero((bits(want) != bits(rows)).any(axis=1))
+    assert len(diff) == 0, diff[:10]
+    # the ASCII handle (RR_WP_ASCII=1, a fresh process): every non-ASCII text through the host pass, the same bits
+    out = tmp_path / "ascii_rows.npy"
+    code = CHILD.format(root=str(ROOT), tests=str(ROOT / "tests"), n_nonascii=len(nonascii), out=str(out))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RR_WP_ASCII="1"), capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert np.array_equal(bits(np.load(out)), bits(rows))

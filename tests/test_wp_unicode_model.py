@@ -1,0 +1,210 @@
+"""The Unicode table and the CPU model of the UTF-8 device tokenizer (review-recommender_amd/wp_unicode.py) against the host
+tokenizer they stand in for (wordpiece.basic_tokenize / WordPieceTokenizer), and the UTF-8 piece table built on the host.
+No GPU: the kernel itself is held to this model in test_gpu_wordpiece_utf8.py."""
+import unicodedata
+
+import numpy as np
+import pytest
+
+from review_recommender_amd import wp_unicode as U
+from review_recommender_amd.wordpiece import WordPieceTokenizer, basic_tokenize
+
+import wp_utf8_texts as X
+
+BASE = 0x01000193
+
+
+def tokenizer():
+    return WordPieceTokenizer({w: i for i, w in enumerate(X.vocabulary())})
+
+
+def test_the_hard_set_is_derived_and_small():
+    t = U.unicode_tables()
+    assert t["unidata_version"] == unicodedata.unidata_version
+    hard = t["hard"]
+    assert hard == [c for c in range(0x110000) if U.char_class(c) == U.HARD]      # derived, not listed
+    assert 0x03A3 in hard
+    assigned = sum(unicodedata.category(chr(c)) not in ("Cn", "Co", "Cs") for c in range(0x110000))
+    print(f"{len(hard)} hard code points of {assigned} assigned (Unicode {unicodedata.unidata_version}); table {U.table_bytes()} bytes")
+    assert 0 < len(hard) < assigned / 1000
+    assert U.table_bytes() < 512 * 1024                                           # beside the 1 MB piece table in L2
+
+
+def test_table_entries_restate_the_per_code_point_rules():
+    """Every entry read back from the two stages equals the rule it was built from; a mapped form never has more code points
+    than the raw character has UTF-8 bytes (a document of b bytes gives at most b pieces: embed._plan_chunks), and never
+    more than three times its bytes."""
+    for cp in range(0x110000):
+        if 0xD800 <= cp <= 0xDFFF:
+            continue
+        k, m, punct = U.lookup(cp)
+        assert k == U.char_class(cp), hex(cp)
+        if k in (U.CJK, U.OTHER):
+            ch = chr(cp)
+            assert m == U.mapped_form(ch), hex(cp)
+            assert punct == tuple(U._is_punctuation(x) for x in m), hex(cp)
+            raw = len(ch.encode("utf-8"))
+            assert len(m) <= min(3, raw) and len(m.encode("utf-8")) <= 3 * raw, hex(cp)
+
+
+CONTEXTS = (("a", "b"), ("", "ab"), ("ab", ""), None, ("\u00e9", "\u0301"), ("", "\u0345"), ("\u1100", "\u1161"))
+
+
+def in_context(ch, ctx):
+    return ch + ch if ctx is None else ctx[0] + ch + ctx[1]
+
+
+def test_every_code_point_in_context_equals_basic_tokenize():
+    """Each non-hard, non-surrogate code point between ASCII letters, first, last, doubled, between a composed letter and a
+    combining accent, before U+0345 and between Hangul jamo: the model's words are basic_tokenize's.  (Blocks of 64 code
+    points are compared in one string, blank-separated; a block that differs is searched code point by code point.)"""
+    hard = set(U.unicode_tables()["hard"])
+    cps = [c for c in range(0x110000) if not (0xD800 <= c <= 0xDFFF) and c not in hard]
+    bad = []
+    for ctx in CONTEXTS:
+        for at in range(0, len(cps), 64):
+            block = cps[at:at + 64]
+            text = " ".join(in_context(chr(c), ctx) for c in block)
+            if U.model_words(text) != basic_tokenize(text):
+                for c in block:
+                    s = in_context(chr(c), ctx)
+                    if U.model_words(s) != basic_tokenize(s):
+                        bad.append((hex(c), ctx, U.model_words(s), basic_tokenize(s)))
+    assert not bad, (len(bad), bad[:10])
+    # one at a time as well, where nothing else is in the string, for a sample that covers every block of the table
+    for c in cps[::61]:
+        for ctx in CONTEXTS:
+            s = in_context(chr(c), ctx)
+            assert U.model_words(s) == basic_tokenize(s), (hex(c), ctx)
+
+
+def test_random_mixed_script_strings_equal_the_host_tokenizer():
+    tok = tokenizer()
+    rng = np.random.default_rng(20240917)
+    seen, n_hard, mismatches = set(), 0, []
+    for i in range(100_000):
+        n = int(rng.integers(1, 48))
+        s = X.random_text(rng, n, density=float(rng.choice([0.3, 0.7, 1.0])), hard=0.02)
+        if i % 7 == 0:                                        # raw draws, any neighbours
+            pools = [X.SCRIPTS[k] for k in X.SCRIPTS]
+            s = "".join(p[rng.integers(len(p))] for p in (pools[j] for j in rng.integers(0, len(pools), size=n)))
+        seen.update(unicodedata.name(c, "?").split(" ")[0] for c in s[:4])
+        L = int(rng.choice([8, 32, 512]))
+        ids, flag, reason = U.model_tokenize(s, tok, L)
+        if flag:
+            n_hard += 1
+            assert reason == "hard" and any(ord(c) in U.unicode_tables()["hard"] for c in s), (s, reason)
+            assert ids == [tok.cls_id, tok.sep_id] and U.model_words(s) is None
+            continue
+        if U.model_words(s) != basic_tokenize(s) or ids != tok.encode_pair(s, None, L)[0].tolist():
+            mismatches.append(s)
+    print(f"{n_hard} strings with a hard code point; scripts seen: {len(seen)}")
+    assert not mismatches, (len(mismatches), [m.encode("unicode_escape") for m in mismatches[:5]])
+    assert 100 < n_hard < 20_000
+    for name in ("LATIN", "COMBINING", "GREEK", "CYRILLIC", "HEBREW", "ARABIC", "DEVANAGARI", "HANGUL", "HIRAGANA", "KATAKANA",
+                 "CJK", "MATHEMATICAL"):
+        assert name in seen, name
+
+
+def test_the_window_rule_and_the_bound_of_the_model():
+    tok = tokenizer()
+    assert U.model_tokenize("café mug", tok, 8) == ([tok.cls_id, tok.vocab["cafe"], tok.vocab["mug"], tok.sep_id], 0, None)
+    # 20 000 bytes of CJK: 1 365 one-character words inside the window answer any max_length up to 512
+    doc = "中文" * 3334
+    ids, flag, reason = U.model_tokenize(doc, tok, 512)
+    assert (flag, reason) == (0, None) and ids == tok.encode_pair(doc, None, 512)[0].tolist()
+    # one word that runs through the window: nothing ends inside it
+    assert U.model_tokenize("é" * 3000, tok, 8)[1:] == (1, "window")
+    # the window ends on a character boundary: 4 095 ASCII bytes, then a 3-byte character across byte 4 096
+    doc = "a " * 2047 + "a" + "中" * 10
+    assert U.window_of(doc.encode())[0] == 4095
+    assert U.model_tokenize(doc, tok, 512)[0] == tok.encode_pair(doc, None, 512)[0].tolist()
+    # Hangul syllables of 3 bytes map to 2 or 3 jamo of 3 bytes each: 1 000 syllables fit the window raw, not mapped
+    assert U.model_tokenize("한" * 1000, tok, 32)[1:] == (1, "bound")
+    assert U.model_tokenize("한 " * 400, tok, 32)[1] == 0
+
+
+def test_malformed_utf8_is_reason_b():
+    tok = tokenizer()
+    bad = [b"\xc3", b"soft \xe4\xb8", b"\xf0\x9f\x98", b"\x80", b"mug\xbf", b"\xc0\xaf", b"\xc1\xbf", b"\xe0\x80\xaf",
+           b"\xe0\x9f\xbf", b"\xf0\x80\x80\xaf", b"\xf0\x8f\xbf\xbf", b"\xed\xa0\x80", b"\xed\xbf\xbf", b"\xf4\x90\x80\x80",
+           b"\xf5\x80\x80\x80", b"\xff", b"\xfe", b"\xc3\x28", b"\xe4\xb8\x28", b"\xe4\x28\xad", b"a\xc3\xa9\xa9",
+           b"\xe4\xb8\xad\xad", b"\xf0\x9f\x98\x80\x80", b"\x80\x80\x80\x80\x80"]
+    for raw in bad:
+        with pytest.raises(UnicodeDecodeError):
+            raw.decode("utf-8")
+        for doc in (raw, b"soft mug " + raw, raw + b" soft mug", b"caf\xc3\xa9 " + raw + b" \xe4\xb8\xad"):
+            assert not U.utf8_well_formed(doc), doc
+            assert U.model_tokenize(doc, tok, 32) == ([tok.cls_id, tok.sep_id], 1, "malformed"), doc
+    for raw in (b"", b"\xc2\x80", b"\xdf\xbf", b"\xe0\xa0\x80", b"\xed\x9f\xbf", b"\xee\x80\x80", b"\xef\xbf\xbf", b"\xf0\x90\x80\x80",
+                b"\xf4\x8f\xbf\xbf", "café 中 \U0001f600".encode()):
+        assert U.utf8_well_formed(raw), raw
+        assert U.model_tokenize(raw, tok, 32)[1] == 0, raw
+    rng = np.random.default_rng(5)                     # the rule is Python's strict decoder, byte string by byte string
+    alphabet = np.array([0x20, 0x61, 0x7F, 0x80, 0x8F, 0x90, 0x9F, 0xA0, 0xBF, 0xC0, 0xC1, 0xC2, 0xDF, 0xE0, 0xE1, 0xEC, 0xED, 0xEE,
+                         0xEF, 0xF0, 0xF1, 0xF3, 0xF4, 0xF5, 0xFF], dtype=np.uint8)
+    for _ in range(50_000):
+        raw = alphabet[rng.integers(0, len(alphabet), size=int(rng.integers(1, 7)))].tobytes()
+        try:
+            raw.decode("utf-8")
+            ok = True
+        except UnicodeDecodeError:
+            ok = False
+        assert U.utf8_well_formed(raw) == ok, raw
+
+
+def test_utf8_piece_table_on_the_host():
+    """rr_wp_build_table_utf8 keeps what can match mapped text (non-ASCII pieces, up to max_chars_per_word CHARACTERS), and
+    a lookup as the kernel does it finds every kept piece and nothing else (the ASCII builder's test, in UTF-8)."""
+    from review_recommender_amd.embed import build_piece_table, piece_arrays
+    long_piece = "##" + "中文字語" * 25                      # 100 characters of 3 bytes
+    too_long = "é" * 101                                               # 101 characters
+    words = X.vocabulary() + ["café", "中", long_piece, too_long, "x" * 100, "y" * 101]
+    vocab = {w: i for i, w in enumerate(words)}
+    slots, blob, kept = build_piece_table(vocab, 100, unicode=True)
+    a_slots, _, a_kept = build_piece_table(vocab, 100)
+    assert a_kept < kept
+    _, off = piece_arrays(vocab)
+    n = slots.shape[0]
+    assert n & (n - 1) == 0 and n >= 2 * kept
+
+    def find(s, form):
+        raw = s.encode("utf-8")
+        h = 0
+        for b in raw:
+            h = (h * BASE + b) & 0xFFFFFFFF
+        lf = len(raw) | form << 16
+        x = (h ^ (lf * 0x9E3779B1)) & 0xFFFFFFFF
+        x ^= x >> 16
+        x = (x * 0x85EBCA6B) & 0xFFFFFFFF
+        x ^= x >> 13
+        x = (x * 0xC2B2AE35) & 0xFFFFFFFF
+        x ^= x >> 16
+        s_ = x & (n - 1)
+        for _ in range(n):
+            hh, o, l, i = (int(v) for v in slots[s_])
+            if i < 0:
+                return -1
+            if (hh & 0xFFFFFFFF) == h and l == lf and blob[o:o + len(raw)].tobytes() == raw:
+                return i
+            s_ = (s_ + 1) & (n - 1)
+        return -1
+
+    want_kept = 0
+    for w, i in vocab.items():
+        form = 1 if w.startswith("##") and len(w) > 2 else 0
+        body = w[2:] if form else w
+        if len(body) <= 100:
+            want_kept += 1
+            assert find(body, form) == i, w
+        else:
+            assert find(body, form) == -1, w
+    assert kept == want_kept
+    assert find("café", 0) == vocab["café"] and find("中", 0) == vocab["中"]
+    assert find(long_piece[2:], 1) == vocab[long_piece] and find(long_piece[2:], 0) == -1
+    assert find(too_long, 0) == -1 and find("y" * 101, 0) == -1 and find("x" * 100, 0) == vocab["x" * 100]
+    for absent in ("caf", "é", "中文字語", "zzzz", "丁"):
+        if absent not in vocab:
+            assert find(absent, 0) == -1, absent
+    # the ASCII builder still drops every non-ASCII piece
+    assert a_kept == sum(1 for w in vocab if w.isascii() and 1 <= len(w[2:] if w.startswith("##") and len(w) > 2 else w) <= 100)

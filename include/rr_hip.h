@@ -85,6 +85,8 @@ int rr_index_store_rows_dev(rr_index* ix, const float* d_rows, int64_t n, int64_
                             float normalize_eps, void* stream);
 /* Rows [first_row, first_row + n) of an fp32 index back to the host, unpadded (waits for the device). */
 int rr_index_download_rows_f32(rr_index* ix, int64_t first_row, int64_t n, float* h_rows);
+/* The same rows into DEVICE memory ([n][dim] fp32, unpadded), queued on `stream`: order it behind the stores yourself. */
+int rr_index_copy_rows_dev(rr_index* ix, int64_t first_row, int64_t n, float* d_rows, void* stream);
 int rr_index_matrix_changed(rr_index* ix);
 int rr_index_dim_padded(const rr_index* ix, int32_t* out);
 /* l2_normalize (utils.py:40-44) of every row, in place on the device. */
@@ -295,6 +297,12 @@ typedef struct rr_reviews rr_reviews;
 int rr_reviews_create(const float* h_emb, int64_t n_reviews, int32_t dim, int64_t n_products,
                       const int64_t* h_indptr, const int32_t* h_ids, int32_t device,
                       float normalize_eps, rr_reviews** out);
+/* The same with the embeddings in DEVICE memory on `device` ([n_reviews][dim] fp32, unpadded; the CSR stays host memory):
+ * rows a builder left on the device become a review index without passing through the host or the file.  Waits for the device
+ * before it copies (the rows may have been written on any stream). */
+int rr_reviews_create_dev(const float* d_emb, int64_t n_reviews, int32_t dim, int64_t n_products,
+                          const int64_t* h_indptr, const int32_t* h_ids, int32_t device,
+                          float normalize_eps, rr_reviews** out);
 int rr_reviews_destroy(rr_reviews* rv);
 /* _best_snippets (app/app_product_search.py:320-370) for the candidates of each query: the review of
  * product rows[q][c] with the largest dot product with query q (first maximum in file order); reviews
@@ -437,6 +445,46 @@ int rr_wp_build_table(const uint8_t* h_piece_bytes, const int64_t* h_piece_off, 
  * are not 10xxxxxx); the length word of a slot stays the piece's length in BYTES. */
 int rr_wp_build_table_utf8(const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces, int32_t max_chars_per_word,
                            int32_t n_slots, int32_t* h_slots, int32_t* out_kept);
+
+/* ------------------------------------------------------------ review text: clean, filter, dedup (csrc/rr_textprep.hip) */
+
+/* nlp/11_build_product_embeddings.py:110-118 in front of rr_wp_encode_dev, which reads what these calls write.  Status word
+ * of a document: 0 = it survives. */
+#define RR_TP_SHORT      1   /* fewer than 10 code points after normalize_text */
+#define RR_TP_SPAM       2   /* looks_spammy(normalised text) */
+#define RR_TP_NEEDS_HOST 4   /* not decided here: the caller cleans this document on the host (no other bit is set, length 0) */
+#define RR_TP_DUP        8   /* an earlier surviving document has the same group and the same bytes */
+typedef struct rr_textprep rr_textprep;
+int rr_textprep_create(int32_t device, rr_textprep** out);
+int rr_textprep_destroy(rr_textprep* tp);
+/* Bytes of a document the clean kernel holds on chip, bytes per step of its walk, consecutive bytes per thread. */
+int rr_textprep_limits(int32_t* out_window, int32_t* out_tile, int32_t* out_per_thread);
+/* normalize_text (:32-36: Unicode whitespace -> one space, strip, the first 4000 code points), the length filter (:112) and,
+ * with spam != 0, looks_spammy (:38-39) for n_docs UTF-8 documents laid out as rr_wp_encode_dev reads them (document s =
+ * bytes d_text_off[s] .. d_text_off[s+1] of d_text).  Document s's normalised text is written at d_out + d_text_off[s]
+ * (never longer than the raw text), its length in bytes to d_out_len[s], its status word to d_status[s].  d_out may be
+ * d_text when the offsets do not decrease (a workgroup reads its whole document before it writes, and then no two
+ * documents overlap).  RR_TP_NEEDS_HOST: a document longer than the window, malformed UTF-8, U+0130 / U+0131 / U+017F
+ * (spam only: the three code points outside ASCII that IGNORECASE folds onto a letter of the patterns), or offsets that
+ * decrease or leave [0, text_bytes]; the last kind reads and writes no text and makes rr_textprep_status (which waits for
+ * the device) return RR_E_INVALID with the count.  Asynchronous on `stream`; n_docs = 0 does nothing. */
+int rr_textprep_clean_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                          int32_t n_docs, int32_t spam, uint8_t* d_out, int32_t* d_out_len, int32_t* d_status, void* stream);
+int rr_textprep_status(rr_textprep* tp, int32_t* out_bad_docs);
+/* drop_duplicates(subset=["sku", "__txt"]) (:117) among the documents whose status word is 0: document s = d_len[s] bytes
+ * at d_text + d_text_off[s], d_group[s] = its sku's number.  Sets RR_TP_DUP on every survivor for which an EARLIER survivor
+ * has the same group and the same bytes; equality is decided by comparing bytes, hash_bits (64; tests pass 3 so that almost
+ * every probe collides) only shortens the hash that picks the first slot.  The result does not depend on scheduling.
+ * Calls on one handle must be stream-ordered (the table is the handle's scratch, grown on the first call of a size). */
+int rr_textprep_dedup_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                          const int32_t* d_len, const int32_t* d_group, int32_t* d_status, int32_t n_docs,
+                          int32_t hash_bits, void* stream);
+/* The survivors (status 0), in order, as rr_wp_encode_dev reads them: texts back to back in d_out_text (capacity out_bytes),
+ * d_out_off [m + 1] (capacity n_docs + 1), d_src_row [m] (capacity n_docs) the document each came from, d_count[0] = m,
+ * d_count[1] = bytes.  A device prefix sum; no host wait. */
+int rr_textprep_compact_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                            const int32_t* d_len, const int32_t* d_status, int32_t n_docs, uint8_t* d_out_text,
+                            int64_t out_bytes, int64_t* d_out_off, int32_t* d_src_row, int64_t* d_count, void* stream);
 
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard

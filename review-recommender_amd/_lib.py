@@ -46,6 +46,7 @@ PROTOTYPES = {
     "rr_index_adopt_device": (C.c_int, [c_vp, c_vp]),
     "rr_index_store_rows_dev": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_f32, c_vp]),
     "rr_index_download_rows_f32": (C.c_int, [c_vp, c_i64, c_i64, c_vp]),
+    "rr_index_copy_rows_dev": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp]),
     "rr_index_dim_padded": (C.c_int, [c_vp, P(c_i32)]),
     "rr_index_l2_normalize": (C.c_int, [c_vp, c_f32]),
     "rr_index_set_meta": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
@@ -86,6 +87,7 @@ PROTOTYPES = {
     "rr_copy_segments_dev": (C.c_int, [c_vp, c_i32, c_i32, c_vp]),
     "rr_index_matrix_changed": (C.c_int, [c_vp]),
     "rr_reviews_create": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i32, c_f32, P(c_vp)]),
+    "rr_reviews_create_dev": (C.c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i32, c_f32, P(c_vp)]),
     "rr_reviews_destroy": (C.c_int, [c_vp]),
     "rr_reviews_best_dev": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "rr_reviews_best_cut_dev": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
@@ -104,6 +106,13 @@ PROTOTYPES = {
     "rr_wp_table_slots": (C.c_int, [c_i32, P(c_i32)]),
     "rr_wp_build_table": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, P(c_i32)]),
     "rr_wp_build_table_utf8": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, P(c_i32)]),
+    "rr_textprep_create": (C.c_int, [c_i32, P(c_vp)]),
+    "rr_textprep_destroy": (C.c_int, [c_vp]),
+    "rr_textprep_limits": (C.c_int, [P(c_i32), P(c_i32), P(c_i32)]),
+    "rr_textprep_clean_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rr_textprep_status": (C.c_int, [c_vp, P(c_i32)]),
+    "rr_textprep_dedup_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    "rr_textprep_compact_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rr_index_stream": (C.c_int, [c_vp, P(c_vp)]),
     "rr_index_synchronize": (C.c_int, [c_vp]),
 }

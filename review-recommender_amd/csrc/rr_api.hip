@@ -344,6 +344,20 @@ extern "C" int rr_index_download_rows_f32(rr_index* ix, int64_t first_row, int64
     return RR_OK;
 }
 
+extern "C" int rr_index_copy_rows_dev(rr_index* ix, int64_t first_row, int64_t n, float* d_rows, void* stream) {
+    RR_REQUIRE(ix && (d_rows || n == 0), "rr_index_copy_rows_dev: NULL argument");
+    RR_REQUIRE(ix->dtype == RR_DTYPE_F32, "rr_index_copy_rows_dev: the index stores bf16 rows");
+    RR_REQUIRE(first_row >= 0 && n >= 0 && first_row + n <= ix->n_rows, "rr_index_copy_rows_dev: rows [%lld,%lld) outside [0,%lld)",
+               (long long)first_row, (long long)(first_row + n), (long long)ix->n_rows);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    RR_REQUIRE(ix->d_matrix, "rr_index_copy_rows_dev: the index has no matrix yet");
+    if (n == 0) return RR_OK;
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    RR_HIP_TRY(hipMemcpy2DAsync(d_rows, 4 * (size_t)ix->dim, (const char*)ix->d_matrix + (size_t)first_row * ix->dim_pad * 4,
+                                4 * (size_t)ix->dim_pad, 4 * (size_t)ix->dim, (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return RR_OK;
+}
+
 extern "C" int rr_index_adopt_device(rr_index* ix, const void* d_matrix) {
     RR_REQUIRE(ix && d_matrix, "rr_index_adopt_device: NULL argument");
     RR_REQUIRE(((uintptr_t)d_matrix & 15) == 0, "rr_index_adopt_device: matrix must be 16-byte aligned");

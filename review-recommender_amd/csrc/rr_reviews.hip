@@ -146,15 +146,17 @@ extern "C" int rr_reviews_destroy(rr_reviews* rv) {
     return RR_OK;
 }
 
-extern "C" int rr_reviews_create(const float* h_emb, int64_t n_reviews, int32_t dim, int64_t n_products,
-                                 const int64_t* h_indptr, const int32_t* h_ids, int32_t device,
-                                 float normalize_eps, rr_reviews** out) {
-    RR_REQUIRE(out, "rr_reviews_create: NULL out");
+// `emb` is host memory (rr_reviews_create) or device memory on `device` (rr_reviews_create_dev): the one difference is the
+// direction of the copy into the padded matrix.
+static int rr_reviews_make(const char* who, const float* emb, hipMemcpyKind kind, int64_t n_reviews, int32_t dim,
+                           int64_t n_products, const int64_t* h_indptr, const int32_t* h_ids, int32_t device,
+                           float normalize_eps, rr_reviews** out) {
+    RR_REQUIRE(out, "%s: NULL out", who);
     *out = nullptr;
-    RR_REQUIRE(h_emb && h_indptr && n_reviews >= 1 && n_reviews < (1ll << 31) && n_products >= 1 && dim >= 1,
-               "rr_reviews_create: bad argument");
+    RR_REQUIRE(emb && h_indptr && n_reviews >= 1 && n_reviews < (1ll << 31) && n_products >= 1 && dim >= 1,
+               "%s: bad argument", who);
     const int64_t nnz = h_indptr[n_products];
-    RR_REQUIRE(nnz >= 0 && nnz <= n_reviews && (nnz == 0 || h_ids), "rr_reviews_create: bad CSR");
+    RR_REQUIRE(nnz >= 0 && nnz <= n_reviews && (nnz == 0 || h_ids), "%s: bad CSR", who);
     RR_HIP_TRY(hipSetDevice(device));
     rr_reviews* rv = new rr_reviews();
     rv->device = device; rv->n_reviews = n_reviews; rv->n_products = n_products;
@@ -165,8 +167,8 @@ extern "C" int rr_reviews_create(const float* h_emb, int64_t n_reviews, int32_t 
     if (e == hipSuccess) e = hipMalloc((void**)&rv->d_cut, sizeof(int32_t) * RR_MAX_BATCH);
     if (e == hipSuccess && rv->dim_pad != dim) e = hipMemset(rv->d_emb, 0, sizeof(float) * (size_t)n_reviews * rv->dim_pad);
     if (e == hipSuccess)
-        e = hipMemcpy2D(rv->d_emb, sizeof(float) * rv->dim_pad, h_emb, sizeof(float) * dim, sizeof(float) * dim,
-                        (size_t)n_reviews, hipMemcpyHostToDevice);
+        e = hipMemcpy2D(rv->d_emb, sizeof(float) * rv->dim_pad, emb, sizeof(float) * dim, sizeof(float) * dim,
+                        (size_t)n_reviews, kind);
     if (e == hipSuccess) e = hipMemcpy(rv->d_indptr, h_indptr, sizeof(int64_t) * (size_t)(n_products + 1), hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz) e = hipMemcpy(rv->d_ids, h_ids, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice);
     if (e == hipSuccess && normalize_eps > 0.f) {
@@ -175,12 +177,28 @@ extern "C" int rr_reviews_create(const float* h_emb, int64_t n_reviews, int32_t 
         e = hipDeviceSynchronize();
     }
     if (e != hipSuccess) {
-        rr_set_error("rr_reviews_create: %s", hipGetErrorString(e));
+        rr_set_error("%s: %s", who, hipGetErrorString(e));
         rr_reviews_destroy(rv);
         return RR_E_HIP;
     }
     *out = rv;
     return RR_OK;
+}
+
+extern "C" int rr_reviews_create(const float* h_emb, int64_t n_reviews, int32_t dim, int64_t n_products,
+                                 const int64_t* h_indptr, const int32_t* h_ids, int32_t device,
+                                 float normalize_eps, rr_reviews** out) {
+    return rr_reviews_make("rr_reviews_create", h_emb, hipMemcpyHostToDevice, n_reviews, dim, n_products, h_indptr, h_ids, device,
+                           normalize_eps, out);
+}
+
+extern "C" int rr_reviews_create_dev(const float* d_emb, int64_t n_reviews, int32_t dim, int64_t n_products,
+                                     const int64_t* h_indptr, const int32_t* h_ids, int32_t device,
+                                     float normalize_eps, rr_reviews** out) {
+    RR_HIP_TRY(hipSetDevice(device));
+    RR_HIP_TRY(hipDeviceSynchronize());          // the rows may still be on their way on any stream
+    return rr_reviews_make("rr_reviews_create_dev", d_emb, hipMemcpyDeviceToDevice, n_reviews, dim, n_products, h_indptr, h_ids,
+                           device, normalize_eps, out);
 }
 
 extern "C" int rr_reviews_best_dev(rr_reviews* rv, const float* d_queries, int32_t n_queries,

@@ -1,0 +1,491 @@
+// rr_textprep.hip -- review text cleaned, filtered and deduplicated on the device, in front of the tokenizer.
+//
+// Stands in for nlp/11_build_product_embeddings.py:110-118 (normalize_text, the length filter, looks_spammy,
+// drop_duplicates(subset=["sku", "__txt"])).  textprep.model_clean states in plain Python what rr_tp_clean computes.
+//
+// rr_tp_clean     one workgroup per document.  The raw document (at most RR_TP_WINDOW bytes) is copied to LDS and walked in
+//                 tiles of RR_TP_TILE bytes, RR_TP_PER consecutive bytes per thread.  Every byte that STARTS a character is
+//                 decoded (reads behind a lead byte are bounded by the document's end) and classed whitespace / other.  A
+//                 character that is not whitespace emits its bytes, with one space in front when the character before it
+//                 is whitespace: that is strip() and the collapse of \s+ at once.  The state at the start of a thread's
+//                 slice (was the previous character whitespace?) is read from the raw bytes in LDS, so it does not matter
+//                 where a tile or a slice ends.  A block scan over (code points, bytes) packed in one int gives every
+//                 character its place in the output and its code-point index; whatever has an index >= 4000 is not
+//                 written (the cut comes after the collapse, so the text may end in a space).  The normalised text is a
+//                 second LDS buffer; the three spam rules then run over THAT buffer with plain bounded look-ahead, so a
+//                 phrase, a URL prefix or a run of ten has no edge to straddle:
+//                   URL_RE     candidates = "http://", "https://", "www." (ASCII, any case) followed by a byte that is not a
+//                              space; after the collapse a match runs to its token's end, so two matches <=> a space lies
+//                              between the first and the last candidate;
+//                   PROMO_RE   three literal phrases, and min(end of "i received this") <= max(start of "free");
+//                   REPEAT_RE  a character of L bytes at p with s[p + k] == s[p + k + L] for k < 9 L.
+// rr_tp_insert    one wave per surviving document: 64-bit hash of (group, bytes), linear probing in a table of >= 2n slots;
+//                 an empty slot is claimed by compare-and-swap on its representative document, an occupied one is compared
+//                 BYTE BY BYTE with its representative (a hash never decides); atomicMin of the document index per slot.
+// rr_tp_mark      a survivor whose slot's minimum is another document is a duplicate.  Slots are never emptied and a
+//                 representative never changes, so equal documents always end in the same slot: the result does not depend
+//                 on which of them claimed it.
+// rr_tp_rank      survivors' ranks and byte offsets (one workgroup, chunks of 1024, as rr_wp_scan).
+// rr_tp_gather    one workgroup per survivor copies its text behind its predecessor's.
+#include "rr_common.h"
+
+#define RR_TP_THREADS 256
+#define RR_TP_PER 16                                   // consecutive bytes per thread
+#define RR_TP_TILE (RR_TP_THREADS * RR_TP_PER)         // 4096 bytes per step of the walk
+#define RR_TP_WINDOW (4 * RR_TP_TILE)                  // 16384: 4000 characters of 3 bytes fit with room to spare
+#define RR_TP_MAX_CHARS 4000                           // nlp/11_build_product_embeddings.py:22-23
+#define RR_TP_MIN_CHARS 10
+
+struct rr_textprep {
+    int device = 0;
+    int32_t* d_bad = nullptr;        // documents whose offsets a kernel refused (rr_textprep_status)
+    int32_t* d_scratch = nullptr;    // dedup: representative [slots], minimum [slots], slot of document [n]; compact: rank [n]
+    int64_t cap_words = 0;
+    std::mutex mu;
+};
+
+__device__ __forceinline__ bool rr_tp_is_space(uint32_t c) {          // str.isspace() == re's \s for str patterns
+    return (c >= 0x09u && c <= 0x0Du) || (c >= 0x1Cu && c <= 0x20u) || c == 0x85u || c == 0xA0u || c == 0x1680u ||
+           (c >= 0x2000u && c <= 0x200Au) || c == 0x2028u || c == 0x2029u || c == 0x202Fu || c == 0x205Fu || c == 0x3000u;
+}
+
+// The character that starts at s[i] (i < len, s[i] not 10xxxxxx): its length in bytes and code point; 0 = malformed
+// (a byte that starts nothing, too few or wrong continuation bytes before the document's end, overlong, surrogate, > 10FFFF).
+__device__ __forceinline__ int rr_tp_decode(const uint8_t* s, int i, int len, uint32_t* cp) {
+    const uint32_t b = s[i];
+    if (b < 0x80u) { *cp = b; return 1; }
+    int n;
+    uint32_t c, lowest;
+    if (b >= 0xC2u && b <= 0xDFu) { n = 2; c = b & 0x1Fu; lowest = 0x80u; }
+    else if ((b & 0xF0u) == 0xE0u) { n = 3; c = b & 0x0Fu; lowest = 0x800u; }
+    else if (b >= 0xF0u && b <= 0xF4u) { n = 4; c = b & 0x07u; lowest = 0x10000u; }
+    else return 0;
+    if (i + n > len) return 0;
+    for (int k = 1; k < n; ++k) {
+        const uint32_t t = s[i + k];
+        if ((t & 0xC0u) != 0x80u) return 0;
+        c = (c << 6) | (t & 0x3Fu);
+    }
+    if (c < lowest || c > 0x10FFFFu || (c >= 0xD800u && c <= 0xDFFFu)) return 0;
+    *cp = c;
+    return n;
+}
+
+// Exclusive sum of one int per thread over the workgroup; *total = the sum, in every thread (rr_wp_block_scan's twin).
+__device__ __forceinline__ int rr_tp_block_scan(int v, int* wave_sums, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    __syncthreads();                       // (wave_sums may still be read from the previous scan)
+    if (lane == 63) wave_sums[wave] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < RR_TP_THREADS / 64; ++w) {
+        const int s = wave_sums[w];
+        before += w < wave ? s : 0;
+        all += s;
+    }
+    *total = all;
+    return before + incl - v;
+}
+
+// s[p .. p + m) equals the lower-case ASCII literal `lit`, letters A-Z of s folded; false when it would leave s[0 .. n).
+__device__ __forceinline__ bool rr_tp_match(const uint8_t* s, int p, int n, const char* lit, int m) {
+    if (p + m > n) return false;
+    for (int k = 0; k < m; ++k) {
+        uint32_t c = s[p + k];
+        if (c >= 'A' && c <= 'Z') c |= 0x20u;
+        if (c != (uint32_t)(uint8_t)lit[k]) return false;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_clean(
+    const uint8_t* text /* no __restrict__: `out` may be the same buffer */, int64_t text_bytes,
+    const int64_t* __restrict__ text_off, int32_t spam, uint8_t* out, int32_t* __restrict__ out_len, int32_t* __restrict__ status, int32_t* __restrict__ bad) {
+    __shared__ uint8_t s_raw[RR_TP_WINDOW];
+    __shared__ uint8_t s_out[RR_TP_WINDOW];
+    __shared__ int s_ws[RR_TP_THREADS / 64];
+    __shared__ int s_end, s_cps, s_claimed, s_umin, s_umax, s_emin, s_fmax;
+    const int tid = threadIdx.x;
+    const int doc = blockIdx.x;
+    const int64_t b0 = text_off[doc], b1 = text_off[doc + 1];
+    if (b0 < 0 || b1 < b0 || b1 > text_bytes) {            // offsets that leave the text: nothing is read, no text is written
+        if (tid == 0) {
+            out_len[doc] = 0; status[doc] = RR_TP_NEEDS_HOST;
+            atomicAdd(bad, 1);
+        }
+        return;
+    }
+    if (b1 - b0 > RR_TP_WINDOW) {                          // longer than the window: the host cleans it
+        if (tid == 0) { out_len[doc] = 0; status[doc] = RR_TP_NEEDS_HOST; }
+        return;
+    }
+    const int len = (int)(b1 - b0);
+    const uint8_t* src = text + b0;
+    for (int i = tid; i < len; i += RR_TP_THREADS) s_raw[i] = src[i];
+    if (tid == 0) { s_end = 0; s_cps = 0; s_claimed = 0; s_umin = RR_TP_WINDOW; s_umax = -1; s_emin = RR_TP_WINDOW; s_fmax = -1; }
+    __syncthreads();
+
+    uint32_t first = 0;
+    const int phantom = (len > 0 && (s_raw[0] & 0xC0u) != 0x80u && rr_tp_decode(s_raw, 0, len, &first) && rr_tp_is_space(first)) ? 1 : 0;
+    int carry_cp = 0, carry_by = 0;                        // emitted before this tile (the same in every thread)
+    int malformed = 0, hard = 0, claimed = 0, my_end = 0, my_cps = 0;
+    for (int base = 0; base < len; base += RR_TP_TILE) {
+        const int i0 = base + tid * RR_TP_PER;
+        // was the character before this slice whitespace?  (the start of the text counts as "no": its space is the phantom)
+        bool prev_ws = false;
+        if (i0 > 0 && i0 < len) {
+            int k = i0 - 1;
+            for (int back = 0; back < 3 && k > 0 && (s_raw[k] & 0xC0u) == 0x80u; ++back) --k;
+            uint32_t c;
+            prev_ws = (s_raw[k] & 0xC0u) != 0x80u && rr_tp_decode(s_raw, k, len, &c) && rr_tp_is_space(c);
+        }
+        uint8_t info[RR_TP_PER];                           // bytes to emit (0 = none) | 8 = a space in front
+        int packed = 0;                                    // code points << 16 | bytes of this slice
+#pragma unroll
+        for (int j = 0; j < RR_TP_PER; ++j) {
+            const int i = i0 + j;
+            info[j] = 0;
+            if (i < len && (s_raw[i] & 0xC0u) != 0x80u) {
+                uint32_t c;
+                const int n = rr_tp_decode(s_raw, i, len, &c);
+                if (n == 0) { malformed = 1; prev_ws = false; }
+                else {
+                    claimed += n;
+                    if (c == 0x130u || c == 0x131u || c == 0x17Fu) hard = 1;
+                    if (rr_tp_is_space(c)) prev_ws = true;
+                    else {
+                        info[j] = (uint8_t)(n | (prev_ws ? 8 : 0));
+                        packed += ((prev_ws ? 2 : 1) << 16) | (n + (prev_ws ? 1 : 0));
+                        prev_ws = false;
+                    }
+                }
+            }
+        }
+        int total;
+        int at = rr_tp_block_scan(packed, s_ws, &total);
+        int g_cp = carry_cp + (at >> 16), g_by = carry_by + (at & 0xFFFF);
+#pragma unroll
+        for (int j = 0; j < RR_TP_PER; ++j) {
+            if (!info[j]) continue;
+            const int n = info[j] & 7;
+            int sp = info[j] >> 3;
+            int cp = g_cp, by = g_by;
+            g_cp += 1 + sp; g_by += n + sp;                // what the scan counted for this character
+            if (cp == 0) sp = 0;                           // the first character of the result: the space in front of it is stripped
+            else { cp -= phantom; by -= phantom; }         // (and was counted: everything behind it moves up)
+            if (sp && cp < RR_TP_MAX_CHARS && by >= 0 && by < RR_TP_WINDOW) {
+                s_out[by] = ' ';
+                my_end = by + 1 > my_end ? by + 1 : my_end;
+                my_cps = cp + 1 > my_cps ? cp + 1 : my_cps;
+            }
+            cp += sp; by += sp;
+            if (cp < RR_TP_MAX_CHARS && by >= 0 && by + n <= RR_TP_WINDOW) {
+                const int i = i0 + j;
+                for (int k = 0; k < n; ++k) s_out[by + k] = s_raw[i + k];
+                my_end = by + n > my_end ? by + n : my_end;
+                my_cps = cp + 1 > my_cps ? cp + 1 : my_cps;
+            }
+        }
+        carry_cp += total >> 16;
+        carry_by += total & 0xFFFF;
+    }
+    atomicMax(&s_end, my_end);
+    atomicMax(&s_cps, my_cps);
+    atomicAdd(&s_claimed, claimed);
+    const int any_bad = __syncthreads_or(malformed);
+    const int any_hard = __syncthreads_or(hard);
+    // every byte belongs to exactly one well-formed character <=> the starts are well formed and their lengths add up
+    if (any_bad || s_claimed != len || (spam && any_hard)) {
+        if (tid == 0) { out_len[doc] = 0; status[doc] = RR_TP_NEEDS_HOST; }
+        return;
+    }
+    const int n = s_end;
+    int st = s_cps < RR_TP_MIN_CHARS ? RR_TP_SHORT : 0;
+
+    if (spam) {
+        int hit = 0;
+        for (int p = tid; p < n; p += RR_TP_THREADS) {
+            uint32_t c = s_out[p];
+            if (c >= 'A' && c <= 'Z') c |= 0x20u;
+            int q = -1;                                    // the byte behind a URL prefix that starts here
+            switch (c) {
+            case 'h':
+                if (rr_tp_match(s_out, p, n, "http://", 7)) q = p + 7;
+                else if (rr_tp_match(s_out, p, n, "https://", 8)) q = p + 8;
+                break;
+            case 'w': if (rr_tp_match(s_out, p, n, "www.", 4)) q = p + 4; break;
+            case 'd': hit |= rr_tp_match(s_out, p, n, "discount code", 13); break;
+            case 'u': hit |= rr_tp_match(s_out, p, n, "use code", 8); break;
+            case 's': hit |= rr_tp_match(s_out, p, n, "sponsored", 9); break;
+            case 'i': if (rr_tp_match(s_out, p, n, "i received this", 15)) atomicMin(&s_emin, p + 15); break;
+            case 'f': if (rr_tp_match(s_out, p, n, "free", 4)) atomicMax(&s_fmax, p); break;
+            default: break;
+            }
+            if (q >= 0 && q < n && s_out[q] != ' ') { atomicMin(&s_umin, p); atomicMax(&s_umax, p); }
+            if ((c & 0xC0u) != 0x80u) {                     // ten equal characters from here on
+                const int L = c < 0x80u ? 1 : c < 0xE0u ? 2 : c < 0xF0u ? 3 : 4;
+                if (p + 10 * L <= n) {
+                    int k = 0;
+                    while (k < 9 * L && s_out[p + k] == s_out[p + k + L]) ++k;
+                    hit |= k == 9 * L;
+                }
+            }
+        }
+        hit = __syncthreads_or(hit);
+        if (s_emin <= s_fmax) hit = 1;                      // "i received this" ... "free"
+        int between = 0;                                    // two URL matches <=> a space between the outermost candidates
+        for (int p = s_umin + tid; p < s_umax; p += RR_TP_THREADS) between |= s_out[p] == ' ';
+        if (__syncthreads_or(between)) hit = 1;
+        if (hit) st |= RR_TP_SPAM;
+    }
+    uint8_t* dst = out + b0;
+    for (int p = tid; p < n; p += RR_TP_THREADS) dst[p] = s_out[p];
+    if (tid == 0) { out_len[doc] = n; status[doc] = st; }
+}
+
+// ------------------------------------------------------------------------------------------------ dedup
+__device__ __forceinline__ uint64_t rr_tp_mix(uint64_t x) {            // murmur3's 64-bit finaliser
+    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
+    return x;
+}
+
+__global__ __launch_bounds__(256) void rr_tp_insert(
+    const uint8_t* __restrict__ text, int64_t text_bytes, const int64_t* __restrict__ text_off, const int32_t* __restrict__ lens,
+    const int32_t* __restrict__ group, const int32_t* __restrict__ status, int32_t n_docs, int32_t hash_bits, uint32_t mask,
+    int32_t* rep, int32_t* minimum, int32_t* __restrict__ slot_of, int32_t* __restrict__ bad) {
+    const int lane = threadIdx.x & 63;
+    const int64_t doc64 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (doc64 >= n_docs) return;
+    const int doc = (int)doc64;
+    if (status[doc] != 0) { if (lane == 0) slot_of[doc] = -1; return; }
+    const int64_t b0 = text_off[doc];
+    const int len = lens[doc];
+    if (b0 < 0 || len < 0 || b0 + len > text_bytes) {       // a survivor whose text leaves the buffer: not read, reported
+        if (lane == 0) { slot_of[doc] = -1; atomicAdd(bad, 1); }
+        return;
+    }
+    const uint8_t* p = text + b0;
+    const int32_t g = group[doc];
+    uint64_t h = 0;                                         // a SUM of mixed 8-byte words: the lanes can add in any order
+    for (int c = lane; 8 * c < len; c += 64) {
+        uint64_t w = 0;
+        for (int k = 0; k < 8 && 8 * c + k < len; ++k) w |= (uint64_t)p[8 * c + k] << (8 * k);
+        h += rr_tp_mix(w + (uint64_t)(c + 1) * 0x9E3779B97F4A7C15ull);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) h += __shfl_xor(h, m, 64);
+    h = rr_tp_mix(h ^ rr_tp_mix(((uint64_t)(uint32_t)g << 32) | (uint32_t)len));
+    if (hash_bits < 64) h &= (1ull << hash_bits) - 1;       // tests: almost every probe collides
+    uint32_t slot = (uint32_t)h & mask;
+    for (;;) {
+        int old = 0;
+        if (lane == 0) old = atomicCAS(&rep[slot], -1, doc);
+        old = __shfl(old, 0, 64);
+        if (old == -1 || old == doc) break;                 // claimed: this document represents the slot
+        bool same = group[old] == g && lens[old] == len;    // (representatives passed the bounds check above)
+        if (same) {
+            const uint8_t* q = text + text_off[old];
+            int diff = 0;
+            for (int i = lane; i < len; i += 64) diff |= p[i] != q[i];
+            same = __ballot(diff) == 0;
+        }
+        if (same) break;
+        slot = (slot + 1) & mask;                           // fewer documents than half the slots: an empty one comes
+    }
+    if (lane == 0) { slot_of[doc] = (int32_t)slot; atomicMin(&minimum[slot], doc); }
+}
+
+__global__ void rr_tp_mark(const int32_t* __restrict__ slot_of, const int32_t* __restrict__ minimum, int32_t n_docs,
+                           int32_t* __restrict__ status) {
+    const int64_t doc = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (doc >= n_docs) return;
+    const int32_t s = slot_of[doc];
+    if (s >= 0 && minimum[s] != (int32_t)doc) status[doc] |= RR_TP_DUP;
+}
+
+// ------------------------------------------------------------------------------------------------ compact
+__global__ __launch_bounds__(1024) void rr_tp_rank(const int32_t* __restrict__ status, const int32_t* __restrict__ lens, int32_t n_docs,
+                                                   int32_t* __restrict__ rank, int64_t* __restrict__ out_off,
+                                                   int32_t* __restrict__ src_row, int64_t* __restrict__ count) {
+    __shared__ int s_c[16];
+    __shared__ long long s_b[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int carry_c = 0;
+    long long carry_b = 0;
+    for (int64_t base = 0; base < n_docs; base += 1024) {
+        const int64_t i = base + tid;
+        const bool keep = i < n_docs && status[i] == 0;
+        const int c = keep ? 1 : 0;
+        const long long b = keep ? (lens[i] > 0 ? lens[i] : 0) : 0;
+        int ic = c;
+        long long ib = b;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int tc = __shfl_up(ic, d, 64);
+            const long long tb = __shfl_up(ib, d, 64);
+            if (lane >= d) { ic += tc; ib += tb; }
+        }
+        __syncthreads();
+        if (lane == 63) { s_c[wave] = ic; s_b[wave] = ib; }
+        __syncthreads();
+        int before_c = 0, all_c = 0;
+        long long before_b = 0, all_b = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            before_c += w < wave ? s_c[w] : 0; all_c += s_c[w];
+            before_b += w < wave ? s_b[w] : 0; all_b += s_b[w];
+        }
+        if (i < n_docs) {
+            const int r = carry_c + before_c + ic - c;
+            rank[i] = keep ? r : -1;
+            if (keep) { out_off[r] = carry_b + before_b + ib - b; src_row[r] = (int32_t)i; }
+        }
+        carry_c += all_c;
+        carry_b += all_b;
+    }
+    if (tid == 0) { out_off[carry_c] = carry_b; count[0] = carry_c; count[1] = carry_b; }
+}
+
+__global__ __launch_bounds__(256) void rr_tp_gather(const uint8_t* __restrict__ text, int64_t text_bytes, const int64_t* __restrict__ text_off,
+                                                    const int32_t* __restrict__ lens, const int32_t* __restrict__ rank,
+                                                    const int64_t* __restrict__ out_off, uint8_t* __restrict__ out_text,
+                                                    int64_t out_bytes, int32_t* __restrict__ bad) {
+    const int doc = blockIdx.x;
+    const int32_t r = rank[doc];
+    if (r < 0) return;
+    const int64_t b0 = text_off[doc], o0 = out_off[r];
+    const int len = lens[doc];
+    if (len <= 0) return;
+    if (b0 < 0 || b0 + len > text_bytes || o0 + len > out_bytes) {     // nothing is read or written outside the two buffers
+        if (threadIdx.x == 0) atomicAdd(bad, 1);
+        return;
+    }
+    for (int i = threadIdx.x; i < len; i += 256) out_text[o0 + i] = text[b0 + i];
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI
+extern "C" int rr_textprep_destroy(rr_textprep* tp) {
+    if (!tp) return RR_OK;
+    hipSetDevice(tp->device);
+    hipFree(tp->d_bad); hipFree(tp->d_scratch);
+    delete tp;
+    return RR_OK;
+}
+
+extern "C" int rr_textprep_create(int32_t device, rr_textprep** out) {
+    RR_REQUIRE(out, "rr_textprep_create: NULL out");
+    *out = nullptr;
+    RR_HIP_TRY(hipSetDevice(device));
+    rr_textprep* tp = new rr_textprep();
+    tp->device = device;
+    hipError_t e = hipMalloc((void**)&tp->d_bad, 4);
+    if (e == hipSuccess) e = hipMemset(tp->d_bad, 0, 4);
+    if (e != hipSuccess) {
+        rr_set_error("rr_textprep_create: %s", hipGetErrorString(e));
+        rr_textprep_destroy(tp);
+        return RR_E_HIP;
+    }
+    *out = tp;
+    return RR_OK;
+}
+
+extern "C" int rr_textprep_limits(int32_t* out_window, int32_t* out_tile, int32_t* out_per_thread) {
+    RR_REQUIRE(out_window && out_tile && out_per_thread, "rr_textprep_limits: NULL argument");
+    *out_window = RR_TP_WINDOW; *out_tile = RR_TP_TILE; *out_per_thread = RR_TP_PER;
+    return RR_OK;
+}
+
+static int rr_tp_scratch(rr_textprep* tp, int64_t words, const char* who) {
+    if (words <= tp->cap_words) return RR_OK;
+    if (tp->d_scratch) RR_HIP_TRY(hipFree(tp->d_scratch));   // (waits for the kernels that use the old one)
+    tp->d_scratch = nullptr;
+    tp->cap_words = 0;
+    if (hipMalloc((void**)&tp->d_scratch, sizeof(int32_t) * (size_t)words) != hipSuccess) {
+        (void)hipGetLastError();
+        rr_set_error("%s: no memory for %lld scratch words", who, (long long)words);
+        return RR_E_NOMEM;
+    }
+    tp->cap_words = words;
+    return RR_OK;
+}
+
+extern "C" int rr_textprep_clean_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                                     int32_t n_docs, int32_t spam, uint8_t* d_out, int32_t* d_out_len, int32_t* d_status,
+                                     void* stream) {
+    RR_REQUIRE(tp && d_text_off && d_out_len && d_status, "rr_textprep_clean_dev: NULL argument");
+    RR_REQUIRE(n_docs >= 0 && text_bytes >= 0, "rr_textprep_clean_dev: %d documents, %lld bytes", n_docs, (long long)text_bytes);
+    RR_REQUIRE((d_text && d_out) || text_bytes == 0, "rr_textprep_clean_dev: NULL text with %lld bytes", (long long)text_bytes);
+    if (n_docs == 0) return RR_OK;
+    std::lock_guard<std::mutex> lk(tp->mu);
+    RR_HIP_TRY(hipSetDevice(tp->device));
+    hipLaunchKernelGGL(rr_tp_clean, dim3((unsigned)n_docs), dim3(RR_TP_THREADS), 0, (hipStream_t)stream, d_text, text_bytes,
+                       d_text_off, spam ? 1 : 0, d_out, d_out_len, d_status, tp->d_bad);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+extern "C" int rr_textprep_status(rr_textprep* tp, int32_t* out_bad_docs) {
+    RR_REQUIRE(tp && out_bad_docs, "rr_textprep_status: NULL argument");
+    std::lock_guard<std::mutex> lk(tp->mu);
+    RR_HIP_TRY(hipSetDevice(tp->device));
+    RR_HIP_TRY(hipDeviceSynchronize());
+    int32_t bad = 0;
+    RR_HIP_TRY(hipMemcpy(&bad, tp->d_bad, 4, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemset(tp->d_bad, 0, 4));
+    *out_bad_docs = bad;
+    RR_REQUIRE(bad == 0, "rr_textprep_status: %d document(s) had text offsets that decrease or leave the text (no text was "
+               "read or written for them)", bad);
+    return RR_OK;
+}
+
+extern "C" int rr_textprep_dedup_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                                     const int32_t* d_len, const int32_t* d_group, int32_t* d_status, int32_t n_docs,
+                                     int32_t hash_bits, void* stream) {
+    RR_REQUIRE(tp && d_text_off && d_len && d_group && d_status, "rr_textprep_dedup_dev: NULL argument");
+    RR_REQUIRE(n_docs >= 0 && n_docs <= (1 << 29), "rr_textprep_dedup_dev: %d documents outside [0, 2^29]", n_docs);
+    RR_REQUIRE(d_text || text_bytes == 0, "rr_textprep_dedup_dev: NULL text with %lld bytes", (long long)text_bytes);
+    RR_REQUIRE(text_bytes >= 0 && hash_bits >= 1 && hash_bits <= 64, "rr_textprep_dedup_dev: hash_bits %d outside [1, 64]", hash_bits);
+    if (n_docs == 0) return RR_OK;
+    int64_t slots = 64;
+    while (slots < 2 * (int64_t)n_docs) slots <<= 1;
+    std::lock_guard<std::mutex> lk(tp->mu);
+    RR_HIP_TRY(hipSetDevice(tp->device));
+    int rc = rr_tp_scratch(tp, 2 * slots + n_docs, "rr_textprep_dedup_dev");
+    if (rc != RR_OK) return rc;
+    int32_t *rep = tp->d_scratch, *minimum = rep + slots, *slot_of = minimum + slots;
+    hipStream_t st = (hipStream_t)stream;
+    RR_HIP_TRY(hipMemsetAsync(rep, 0xFF, sizeof(int32_t) * (size_t)slots, st));          // -1 = empty
+    RR_HIP_TRY(hipMemsetAsync(minimum, 0x7F, sizeof(int32_t) * (size_t)slots, st));      // above every document index
+    hipLaunchKernelGGL(rr_tp_insert, dim3((unsigned)((n_docs + 3) / 4)), dim3(256), 0, st, d_text, text_bytes, d_text_off, d_len,
+                       d_group, d_status, n_docs, hash_bits, (uint32_t)(slots - 1), rep, minimum, slot_of, tp->d_bad);
+    hipLaunchKernelGGL(rr_tp_mark, dim3((unsigned)((n_docs + 255) / 256)), dim3(256), 0, st, slot_of, minimum, n_docs, d_status);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+extern "C" int rr_textprep_compact_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                                       const int32_t* d_len, const int32_t* d_status, int32_t n_docs, uint8_t* d_out_text,
+                                       int64_t out_bytes, int64_t* d_out_off, int32_t* d_src_row, int64_t* d_count, void* stream) {
+    RR_REQUIRE(tp && d_text_off && d_len && d_status && d_out_off && d_src_row && d_count, "rr_textprep_compact_dev: NULL argument");
+    RR_REQUIRE(n_docs >= 0 && text_bytes >= 0 && out_bytes >= 0, "rr_textprep_compact_dev: %d documents, %lld / %lld bytes", n_docs,
+               (long long)text_bytes, (long long)out_bytes);
+    RR_REQUIRE((d_text && d_out_text) || text_bytes == 0 || out_bytes == 0, "rr_textprep_compact_dev: NULL text");
+    std::lock_guard<std::mutex> lk(tp->mu);
+    RR_HIP_TRY(hipSetDevice(tp->device));
+    int rc = rr_tp_scratch(tp, n_docs > 0 ? n_docs : 1, "rr_textprep_compact_dev");
+    if (rc != RR_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(rr_tp_rank, dim3(1), dim3(1024), 0, st, d_status, d_len, n_docs, tp->d_scratch, d_out_off, d_src_row, d_count);
+    if (n_docs > 0 && d_text && d_out_text)
+        hipLaunchKernelGGL(rr_tp_gather, dim3((unsigned)n_docs), dim3(256), 0, st, d_text, text_bytes, d_text_off, d_len,
+                           tp->d_scratch, d_out_off, d_out_text, out_bytes, tp->d_bad);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}

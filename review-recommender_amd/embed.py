@@ -1,4 +1,4 @@
-"""Product embeddings built on the GPU: text in, searchable index (and the reference's files) out.
+"""Product and review embeddings built on the GPU: text in, searchable index (and the reference's files) out.
 
 Stands in for nlp/11_build_product_embeddings.py:46-92 (`SentenceTransformer.encode(texts, normalize_embeddings=True)`
 over `normalize_text(agg_text)`), the builder of product_emb.npy / product_emb_meta.parquet.  Per chunk of documents:
@@ -12,8 +12,18 @@ with no host hop between the three: the host reads back two integers per chunk (
 call takes as arguments) and the needs_host flags, and prepares chunk i + 1 while chunk i runs.  The tokenizer is the UTF-8
 kernel (Unicode text through the table of wp_unicode.py); the few documents it flags (a hard code point, a mapped text beyond
 its buffers: wp_unicode.model_tokenize) are tokenised by wordpiece.py and encoded in one small pass at the end, scattered into
-their rows.  RR_WP_ASCII=1 in the environment restores the ASCII kernel, which flags every document with a byte >= 0x80.  Review embeddings
-(nlp/11...:95-169) are not built here.
+their rows.  RR_WP_ASCII=1 in the environment restores the ASCII kernel, which flags every document with a byte >= 0x80.
+
+Review embeddings (nlp/11...:95-169, the builder of reviews_with_embeddings.parquet) take the same chain behind three more
+device stages (csrc/rr_textprep.hip, textprep.py), because the reference cleans review text before the model sees it:
+
+    raw UTF-8 bytes, in row blocks through pinned staging -> the device
+    rr_textprep_clean_dev     normalize_text, the length filter, looks_spammy: text in place, length and status per row
+    (the few rows the kernel flags are cleaned by normalize_text / looks_spammy below and written into their slots)
+    rr_textprep_dedup_dev     drop_duplicates(subset=["sku", "__txt"]): byte-compared, first row in file order survives
+    rr_textprep_compact_dev   the survivors' texts back to back + offsets: what rr_wp_encode_dev reads, still on the device
+
+and from there chunk by chunk through the tokenizer, the encoder and the row store (`build_review_embeddings`).
 """
 from __future__ import annotations
 
@@ -36,6 +46,16 @@ MAX_TEXT_LEN = 4000
 NORMALIZE_EPS = 1e-12   # torch.nn.functional.normalize's eps (normalize_embeddings=True)
 META_COLUMNS = ("sku", "n_reviews", "avg_stars", "last_ts", "agg_text")     # nlp/11...:86-89
 _WS = re.compile(r"\s+")
+REVIEW_COLUMNS = ("id", "sku", "ts", "stars", "text")                       # nlp/11...:103
+REVIEW_INPUT = "data/processed/reviews_merged.parquet"                      # nlp/11...:14
+PRODUCT_INPUT = "data/processed/products.parquet"
+URL_RE = re.compile(r"https?://\S+|www\.\S+", re.IGNORECASE)               # nlp/11...:25-27
+PROMO_RE = re.compile(r"(discount code|use code|sponsored|i received this.*free)", re.IGNORECASE)
+REPEAT_RE = re.compile(r"(.)\1{9,}")
+MAX_TEXT_BYTES = 8 << 30        # review text kept on the device until it is encoded (dedup must see all of it)
+STAGE_BYTES = 64 << 20          # one of the two pinned staging buffers the raw text passes through
+RESUME_REFUSED = ("--resume is not supported: the reference reopens reviews_with_embeddings.parquet with a fresh writer, "
+                  "which truncates the rows it claims to keep; run the build again without --resume")
 
 
 def normalize_text(s) -> str:
@@ -45,6 +65,11 @@ def normalize_text(s) -> str:
     s = s.replace("\r", " ").replace("\n", " ").strip()
     s = _WS.sub(" ", s)
     return s[:MAX_TEXT_LEN]
+
+
+def looks_spammy(s: str) -> bool:
+    """nlp/11_build_product_embeddings.py:38-39."""
+    return (len(URL_RE.findall(s)) >= 2) or bool(PROMO_RE.search(s)) or bool(REPEAT_RE.search(s))
 
 
 def filter_products(products, text_col: str = "agg_text"):
@@ -162,6 +187,25 @@ class DeviceWordPiece:
             info.copy_(packed[3 * cap + n:], non_blocking=True)
         return packed, info, n, cap, (stage, d_in)
 
+    def queue_dev(self, d_text: int, text_bytes: int, d_off, max_length: int, capacity: Optional[int] = None):
+        """`queue` for text that is ALREADY on the device: d_text = address of the first byte, d_off = int64 device tensor of
+        n + 1 offsets relative to it (text_bytes = the last one, a host integer below 2^31).  Same return value; the
+        keepalive holds d_off, the text stays the caller's."""
+        torch = self._torch
+        n = int(d_off.numel()) - 1
+        cap = int(capacity) if capacity else n * int(max_length)
+        with torch.cuda.device(self._dev):
+            packed = torch.empty(3 * cap + 2 * n + 2, dtype=torch.int32, device=self._dev)
+            base, st = packed.data_ptr(), torch.cuda.current_stream(self._dev).cuda_stream
+            _lib.check(_lib.load().rr_wp_encode_dev(
+                self._h, C.c_void_p(d_text), int(text_bytes), C.c_void_p(d_off.data_ptr()), n, int(max_length), cap,
+                C.c_void_p(base), C.c_void_p(base + 4 * cap), C.c_void_p(base + 8 * cap), C.c_void_p(base + 12 * cap),
+                C.c_void_p(base + 4 * (3 * cap + n + 1)), C.c_void_p(base + 4 * (3 * cap + 2 * n + 1)), C.c_void_p(st)),
+                "rr_wp_encode_dev")
+            info = torch.empty(n + 2, dtype=torch.int32, pin_memory=True)
+            info.copy_(packed[3 * cap + n:], non_blocking=True)
+        return packed, info, n, cap, (None, d_off)
+
     @staticmethod
     def views(packed, n: int, cap: int, total: int):
         """(tok, typ, pos, cu) views of `packed` once the host knows `total` = cu[n]."""
@@ -221,10 +265,24 @@ def embed_texts_into(index: ProductIndex, texts: Sequence[str], encoder, *, firs
 
     The forward call gets the EXACT longest sequence of its chunk (read back with the token count, which it needs anyway),
     not the bound max_length."""
+    lens = [len(t.encode("utf-8")) for t in texts]
+
+    def queue_docs(wp, a, b, L, cap):
+        return wp.queue([t.encode("utf-8") for t in texts[a:b]], L, cap)
+
+    return _embed_into(index, lens, queue_docs, lambda i: texts[i], encoder, first_row=first_row, chunk_tokens=chunk_tokens,
+                       keep_rows=keep_rows, stats=stats)
+
+
+def _embed_into(index: ProductIndex, lens: Sequence[int], queue_docs, host_text, encoder, *, first_row: int, chunk_tokens: int,
+                keep_rows: bool, stats: Optional[dict]) -> Optional[np.ndarray]:
+    """`embed_texts_into` for any source of documents: lens = their lengths in bytes; queue_docs(wp, a, b, max_length,
+    capacity) queues documents [a, b) on the current stream as DeviceWordPiece.queue does (host text) or queue_dev (text on
+    the device); host_text(i) = document i as a str, asked only for what the tokenizer leaves to the host."""
     import torch
     if encoder.tokenizer is None:
         raise ValueError("no vocabulary was loaded: the builder tokenises text")
-    n = len(texts)
+    n = len(lens)
     if first_row < 0 or first_row + n > index.n_rows or index.dim != HIDDEN:
         raise ValueError(f"{n} rows of dim {HIDDEN} from row {first_row} do not fit an index of {index.n_rows} x {index.dim}")
     model, L = encoder.model, encoder.max_length
@@ -260,9 +318,8 @@ def embed_texts_into(index: ProductIndex, texts: Sequence[str], encoder, *, firs
             # allocator hands out blocks of the side stream's own pool (record_stream below covers their use on `main`),
             # and the tokenizer's scratch is only ever touched on `side`.  The copy and the kernels of chunk i + 1 so run
             # while chunk i's layers do.
-            docs = [t.encode("utf-8") for t in texts[a:b]]
             with torch.cuda.stream(side):
-                q = wp.queue(docs, L, max(chunk_tokens, L, 2 * (b - a)))
+                q = queue_docs(wp, a, b, L, max(chunk_tokens, L, 2 * (b - a)))
                 ev = torch.cuda.Event()
                 ev.record(side)
             for t in (q[0], q[4][1]):
@@ -298,7 +355,6 @@ def embed_texts_into(index: ProductIndex, texts: Sequence[str], encoder, *, firs
             if keep_rows:
                 keep(out, slice(job[2], job[3]))
 
-        lens = [len(t.encode("utf-8")) for t in texts] if n else []
         chunks = _plan_chunks(lens, L, int(chunk_tokens))
         nxt = None
         if chunks:
@@ -328,7 +384,7 @@ def embed_texts_into(index: ProductIndex, texts: Sequence[str], encoder, *, firs
                 part.append(host_docs[at])
                 tot += L
                 at += 1
-            seqs = [encoder.tokenizer.encode_pair(texts[i], None, L) for i in part]
+            seqs = [encoder.tokenizer.encode_pair(host_text(i), None, L) for i in part]
             sl = np.array([len(s[0]) for s in seqs], dtype=np.int64)
             cu = np.zeros(len(part) + 1, dtype=np.int32)
             np.cumsum(sl, out=cu[1:])
@@ -381,12 +437,216 @@ def build_product_embeddings(products, encoder, *, text_col: str = "agg_text", r
     return index, meta, emb
 
 
+def prepare_reviews(reviews):
+    """nlp/11_build_product_embeddings.py:99-108: the five columns, id / sku / text as str, stars numeric, ts a UTC time."""
+    import pandas as pd
+    miss = {"id", "sku", "text"} - set(reviews.columns)
+    if miss:
+        raise ValueError(f"review table missing {sorted(miss)}")
+    miss = {"ts", "stars"} - set(reviews.columns)
+    if miss:                                      # (the reference dies on these with a KeyError)
+        raise ValueError(f"review table missing {sorted(miss)}")
+    df = reviews[list(REVIEW_COLUMNS)].copy()
+    df["id"] = df["id"].astype(str)
+    df["sku"] = df["sku"].astype(str)
+    df["text"] = df["text"].fillna("").astype(str)
+    df["stars"] = pd.to_numeric(df["stars"], errors="coerce")
+    df["ts"] = pd.to_datetime(df["ts"], utc=True, errors="coerce")
+    return df
+
+
+def _utf8_column(texts) -> Tuple[np.ndarray, np.ndarray]:
+    """(bytes, int64 offsets [n + 1]) of a column of str, without a Python loop where every row has a UTF-8 form."""
+    import pyarrow as pa
+    try:
+        arr = pa.array(texts, type=pa.large_string())
+        _, off, data = arr.buffers()
+        off = np.frombuffer(off, dtype=np.int64)[arr.offset:arr.offset + len(arr) + 1]
+        raw = np.frombuffer(data, dtype=np.uint8) if data is not None else np.zeros(0, dtype=np.uint8)
+        return raw, off
+    except (pa.ArrowInvalid, UnicodeEncodeError):  # a lone surrogate: three bytes the kernel calls malformed, so the host cleans the row
+        docs = [t.encode("utf-8", "surrogatepass") for t in texts]
+        off = np.zeros(len(docs) + 1, dtype=np.int64)
+        np.cumsum([len(d) for d in docs], out=off[1:])
+        return np.frombuffer(b"".join(docs), dtype=np.uint8), off
+
+
+def build_review_embeddings(reviews, encoder, *, no_spam: bool = False, no_dedup: bool = False, chunk_tokens: int = 131072,
+                            data_dir=None, product_skus=None, stats: Optional[dict] = None, max_text_bytes: int = MAX_TEXT_BYTES,
+                            stage_bytes: int = STAGE_BYTES, log=None):
+    """nlp/11_build_product_embeddings.py:99-165 on the GPU -> (table, emb, ReviewIndex or None).
+
+    table = the surviving rows of id, sku, ts, stars, text (the RAW text) in file order, emb = their float32 (m, 384) rows,
+    l2-normalised with eps 1e-12.  The raw text goes to the device in row blocks through two pinned buffers of `stage_bytes`;
+    rr_textprep_clean_dev normalises it in place and answers a length and a status word per row; the rows it flags
+    (textprep.model_clean says which) are cleaned by `normalize_text` / `looks_spammy` here and written into their slots
+    (a normalised text is never longer than its raw text); rr_textprep_dedup_dev marks duplicates per sku; the survivors are
+    compacted on the device and tokenised, encoded and stored from there, chunk by chunk (`_embed_into`).
+    The cleaned text of the WHOLE table stays on the device until it is encoded, because dedup must see all of it:
+    more than `max_text_bytes` (default 8 GiB) of raw text is refused.  With `product_skus` the rows become a ReviewIndex
+    without leaving the device (rr_reviews_create_dev); with `data_dir`, reviews_with_embeddings.parquet is written there.
+    stats receives "short", "spam", "duplicate" (rows dropped, counted as the reference logs them), "host_clean_docs" and
+    "host_docs" (table rows the clean stage / survivors the tokenizer left to the host) and "seconds", the wall clock of the
+    phases (each ends at a point where the host waits for the device anyway).  log: a callable that receives the
+    reference's `[review] ...` lines where the reference prints them (the counts before the encoding starts)."""
+    import time
+    import pandas as pd
+    import torch
+    from . import textprep as T
+    seconds: Dict[str, float] = {}
+    clock = [time.perf_counter()]
+
+    def lap(name):
+        now = time.perf_counter()
+        seconds[name] = seconds.get(name, 0.0) + now - clock[0]
+        clock[0] = now
+
+    if stats is not None:
+        stats["seconds"] = seconds
+    df = prepare_reviews(reviews)
+    n = len(df)
+    if n == 0:
+        raise RuntimeError("No reviews left after filtering.")
+    texts = df["text"].tolist()
+    lap("prepare_columns")
+    raw, off = _utf8_column(texts)
+    total = int(off[-1])
+    lap("utf8_bytes")
+    if total > int(max_text_bytes):
+        raise ValueError(f"{total:,} bytes of review text exceed max_text_bytes = {int(max_text_bytes):,}: the cleaned text of the "
+                         "whole table stays on the device until it is encoded.  Split the table by sku and build the parts one "
+                         "after the other: duplicates are dropped per sku, so the result is the same.")
+    if encoder.tokenizer is None:
+        raise ValueError("no vocabulary was loaded: the builder tokenises text")
+    model, L = encoder.model, encoder.max_length
+    dev = torch.device("cuda", model.device)
+    tp = T.TextPrep(model.device)
+    try:
+        with torch.cuda.device(dev):
+            main = torch.cuda.current_stream(dev)
+            st_ptr = main.cuda_stream
+            d_text = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+            d_off = torch.from_numpy(np.ascontiguousarray(off)).to(dev)
+            d_len = torch.empty(n, dtype=torch.int32, device=dev)
+            d_st = torch.empty(n, dtype=torch.int32, device=dev)
+            blk = max(1, min(int(stage_bytes), max(total, 1)))
+            stage = [torch.empty(blk, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            busy: List[Optional[object]] = [None, None]
+            turn = 0
+            a = 0
+            while a < n:                              # row blocks of about `blk` bytes; a longer row goes through in pieces
+                b = int(np.searchsorted(off, off[a] + blk, side="right")) - 1
+                b = min(n, max(b, a + 1))
+                for lo in range(int(off[a]), int(off[b]), blk):
+                    hi = min(int(off[b]), lo + blk)
+                    if busy[turn] is not None:
+                        busy[turn].synchronize()
+                    stage[turn].numpy()[:hi - lo] = raw[lo:hi]
+                    d_text[lo:hi].copy_(stage[turn][:hi - lo], non_blocking=True)
+                    busy[turn] = torch.cuda.Event()
+                    busy[turn].record(main)
+                    turn ^= 1
+                tp.clean(d_text.data_ptr(), total, d_off.data_ptr() + 8 * a, b - a, not no_spam, d_text.data_ptr(),
+                         d_len.data_ptr() + 4 * a, d_st.data_ptr() + 4 * a, st_ptr)
+                a = b
+            main.synchronize()
+            tp.check()
+            status, lens = d_st.cpu().numpy(), d_len.cpu().numpy()
+            lap("copy_and_clean")
+
+            # the rows the kernel left to the host: the reference's own functions, into the rows' slots
+            host_clean = np.flatnonzero(status & T.NEEDS_HOST)
+            parts, where = [], []
+            for i in host_clean.tolist():
+                t = normalize_text(texts[i])
+                tb = np.frombuffer(t.encode("utf-8", "surrogatepass"), dtype=np.uint8)
+                assert len(tb) <= off[i + 1] - off[i]
+                parts.append(tb)
+                where.append(np.arange(int(off[i]), int(off[i]) + len(tb), dtype=np.int64))
+                lens[i] = len(tb)
+                status[i] = (T.SHORT if len(t) < MIN_TEXT_LEN else 0) | (T.SPAM if not no_spam and looks_spammy(t) else 0)
+            if parts and sum(len(x) for x in parts):          # all of them in two copies and one scatter, not a copy per row
+                d_text.index_copy_(0, torch.from_numpy(np.concatenate(where)).to(dev), torch.from_numpy(np.concatenate(parts)).to(dev))
+            if len(host_clean):
+                d_len.copy_(torch.from_numpy(lens))
+                d_st.copy_(torch.from_numpy(status))
+            n_short = int(np.count_nonzero(status & T.SHORT))
+            n_spam = int(np.count_nonzero((status & (T.SHORT | T.SPAM)) == T.SPAM))
+            lap("host_clean")
+
+            if not no_dedup:
+                group = torch.from_numpy(pd.factorize(df["sku"])[0].astype(np.int32)).to(dev)
+                tp.dedup(d_text.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), group.data_ptr(), d_st.data_ptr(), n, 64, st_ptr)
+                status = d_st.cpu().numpy()
+                lap("dedup")
+            keep = np.flatnonzero(status == 0)
+            m = len(keep)
+            n_dup = int(np.count_nonzero(status & T.DUP))
+            if log is not None:                       # nlp/11...:115,118,124
+                if not no_spam:
+                    log(f"[review] spam filtered {n_spam:,} rows")
+                if not no_dedup:
+                    log(f"[review] dedup removed {n_dup:,}")
+            if stats is not None:
+                stats.update(short=n_short, spam=n_spam, duplicate=n_dup, host_clean_docs=host_clean.tolist(), host_docs=[])
+            if m == 0:
+                raise RuntimeError("No reviews left after filtering.")
+
+            if log is not None:
+                log(f"[review] rows={m:,}  chunk_tokens={int(chunk_tokens):,}")
+            lens_k = lens[keep].astype(np.int64)
+            coff = np.zeros(m + 1, dtype=np.int64)
+            np.cumsum(lens_k, out=coff[1:])
+            cbytes = int(coff[-1])
+            d_ctext = torch.empty(cbytes + 16, dtype=torch.uint8, device=dev)
+            d_coff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            d_src = torch.empty(n, dtype=torch.int32, device=dev)
+            d_count = torch.empty(2, dtype=torch.int64, device=dev)
+            tp.compact(d_text.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), d_st.data_ptr(), n, d_ctext.data_ptr(), cbytes,
+                       d_coff.data_ptr(), d_src.data_ptr(), d_count.data_ptr(), st_ptr)
+            count = d_count.cpu().numpy()             # (waits: the tokenizer's stream reads what this one wrote)
+            tp.check()
+            if int(count[0]) != m or int(count[1]) != cbytes:
+                raise _lib.HipLibraryError(f"compaction kept {count.tolist()}, the host counts {[m, cbytes]}")
+            del d_text
+            lap("compact")
+
+            def queue_docs(wp, a, b, L, cap):
+                return wp.queue_dev(d_ctext.data_ptr() + int(coff[a]), int(coff[b] - coff[a]), d_coff[a:b + 1] - int(coff[a]), L, cap)
+
+            index = ProductIndex(None, n_rows=m, dim=HIDDEN, device=model.device)
+            tok_stats: dict = {}
+            _embed_into(index, lens_k.tolist(), queue_docs, lambda i: normalize_text(texts[int(keep[i])]), encoder, first_row=0,
+                        chunk_tokens=chunk_tokens, keep_rows=False, stats=tok_stats)
+            if stats is not None:
+                stats["host_docs"] = tok_stats["host_docs"]
+            lap("tokenize_encode_store")
+            table = df.iloc[keep].reset_index(drop=True)
+            emb = index.download_rows(0, m)
+            review_index = None
+            if product_skus is not None:
+                from .reviews import ReviewIndex
+                d_rows = torch.empty((m, HIDDEN), dtype=torch.float32, device=dev)
+                _lib.check(_lib.load().rr_index_copy_rows_dev(index.handle, 0, m, C.c_void_p(d_rows.data_ptr()), C.c_void_p(st_ptr)),
+                           "rr_index_copy_rows_dev")
+                review_index = ReviewIndex.from_device_rows(table, d_rows, product_skus, device=model.device)
+            index.close()
+    finally:
+        tp.close()
+    lap("table_and_rows")
+    if data_dir is not None:
+        from .artifacts import save_reviews
+        save_reviews(data_dir, table, emb)
+        lap("write_file")
+    return table, emb, review_index
+
+
 # ---------------------------------------------------------------------------------- command line
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m review_recommender_amd.embed",
-                                 description="Build product embeddings on the GPU (nlp/11_build_product_embeddings.py's flags).")
+                                 description="Build product or review embeddings on the GPU (nlp/11_build_product_embeddings.py's flags).")
     ap.add_argument("--target", choices=["product", "review"], required=True)
-    ap.add_argument("--input", type=str, default="data/processed/products.parquet")
+    ap.add_argument("--input", type=str, default="", help=f"default: {PRODUCT_INPUT} (product), {REVIEW_INPUT} (review)")
     ap.add_argument("--text-col", type=str, default="")
     ap.add_argument("--model", type=str, required=True, help="LOCAL model directory (weights + vocab.txt); nothing is fetched")
     ap.add_argument("--device", type=str, default="0", help="GPU ordinal (0, cuda:0)")
@@ -396,17 +656,22 @@ def parse_args(argv=None):
                          "tokens (--batch), not by rows")
     ap.add_argument("--out-dir", type=str, default="data/processed")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32", help="encoder arithmetic")
+    # review-only options
+    ap.add_argument("--no-spam", action="store_true", help="disable spam filter")
+    ap.add_argument("--no-dedup", action="store_true", help="disable (sku,text) dedup")
+    ap.add_argument("--resume", action="store_true",
+                    help="refused (exit status 2): the reference's resume reopens the output with a fresh writer and so "
+                         "truncates the rows it claims to keep; reproducing that would lose data")
     return ap.parse_args(argv)
 
 
 def main(argv=None) -> int:
     args = parse_args(argv)
     if args.target == "review":
-        print("review embeddings are not built here (product embeddings only)", file=sys.stderr)
-        return 2
+        return _main_review(args)
     import pandas as pd
     from .cross_encoder import QueryEncoder
-    df = pd.read_parquet(args.input)
+    df = pd.read_parquet(args.input or PRODUCT_INPUT)
     text_col = args.text_col or ("agg_text" if "agg_text" in df.columns else None)
     if not text_col:
         raise ValueError("Provide --text-col for product text (e.g., agg_text).")
@@ -417,6 +682,30 @@ def main(argv=None) -> int:
     print(f"[product] rows={len(meta):,}  batch={args.batch}", flush=True)
     print(f"[ok] wrote {args.out_dir}/product_emb.npy shape={emb.shape}", flush=True)
     print(f"[ok] wrote {args.out_dir}/product_emb_meta.parquet rows={len(meta):,}", flush=True)
+    return 0
+
+
+def _main_review(args) -> int:
+    import pandas as pd
+    from .artifacts import REVIEWS_FILE
+    from .cross_encoder import QueryEncoder
+    if args.resume:
+        print(RESUME_REFUSED, file=sys.stderr)
+        return 2
+    src = args.input or REVIEW_INPUT
+    df = pd.read_parquet(src)
+    try:
+        prepare_reviews(df.iloc[:0])
+    except ValueError as e:                     # e.g. a product table: say so instead of a traceback
+        print(f"{src} {str(e).split('review table ', 1)[-1]}: review embeddings are not built here from a table without "
+              "id, sku, ts, stars and text", file=sys.stderr)
+        return 2
+    device = int(str(args.device).split(":")[-1])
+    encoder = QueryEncoder.from_pretrained_dir(args.model, device=device, precision=args.precision)
+    table, emb, _ = build_review_embeddings(df, encoder, no_spam=args.no_spam, no_dedup=args.no_dedup,
+                                            chunk_tokens=max(1, args.batch) * 512, data_dir=args.out_dir,
+                                            log=lambda line: print(line, flush=True))
+    print(f"[ok] wrote {args.out_dir}/{REVIEWS_FILE} total rows={len(table):,}", flush=True)
     return 0
 
 

@@ -29,6 +29,36 @@ class ReviewIndex:
         emb = np.ascontiguousarray(embeddings, dtype=np.float32)
         if emb.ndim != 2 or emb.shape[0] != len(reviews):
             raise ValueError("embeddings must be (n_reviews, dim), row-aligned with the review table")
+        self._group(reviews, product_skus, emb.shape)
+        h = C.c_void_p()
+        _lib.check(_lib.load().rr_reviews_create(_lib.ptr(emb), self.n_reviews, self.dim, self.n_products,
+                                                 _lib.ptr(self.indptr), _lib.ptr(self.ids), device, eps,
+                                                 C.byref(h)), "rr_reviews_create")
+        self._h = h
+
+    @classmethod
+    def from_device_rows(cls, reviews: pd.DataFrame, rows, product_skus: Sequence[str], device: int = 0,
+                         eps: float = 1e-12) -> "ReviewIndex":
+        """The same index from embeddings that are already on the GPU: `rows` = a contiguous float32 (n_reviews, dim) torch
+        tensor on `device` (rr_reviews_create_dev copies it; what a builder left there needs no trip through the host)."""
+        import torch
+        if "sku" not in reviews.columns:
+            raise ValueError("review table lacks a 'sku' column")
+        if (rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[0] != len(reviews) or not rows.is_contiguous()
+                or not rows.is_cuda or rows.device.index != device):
+            raise ValueError("rows must be a contiguous float32 (n_reviews, dim) tensor on the index's GPU, row-aligned with "
+                             "the review table")
+        self = cls.__new__(cls)
+        self._group(reviews, product_skus, tuple(rows.shape))
+        h = C.c_void_p()
+        _lib.check(_lib.load().rr_reviews_create_dev(C.c_void_p(rows.data_ptr()), self.n_reviews, self.dim, self.n_products,
+                                                     _lib.ptr(self.indptr), _lib.ptr(self.ids), device, eps,
+                                                     C.byref(h)), "rr_reviews_create_dev")
+        self._h = h
+        return self
+
+    def _group(self, reviews: pd.DataFrame, product_skus: Sequence[str], shape) -> None:
+        """Texts, stars and the CSR product row -> review ids (file order inside a product)."""
         self.texts = reviews["text"].astype(str).tolist() if "text" in reviews.columns else [""] * len(reviews)
         self.stars = (pd.to_numeric(reviews["stars"], errors="coerce").to_numpy(dtype=np.float64)
                       if "stars" in reviews.columns else np.full(len(reviews), np.nan))
@@ -40,12 +70,7 @@ class ReviewIndex:
         self.indptr = np.zeros(n_products + 1, dtype=np.int64)
         np.cumsum(np.bincount(prod[known], minlength=n_products), out=self.indptr[1:])
         self.ids = np.ascontiguousarray(order, dtype=np.int32)
-        self.n_reviews, self.dim, self.n_products = emb.shape[0], emb.shape[1], n_products
-        h = C.c_void_p()
-        _lib.check(_lib.load().rr_reviews_create(_lib.ptr(emb), self.n_reviews, self.dim, n_products,
-                                                 _lib.ptr(self.indptr), _lib.ptr(self.ids), device, eps,
-                                                 C.byref(h)), "rr_reviews_create")
-        self._h = h
+        self.n_reviews, self.dim, self.n_products = int(shape[0]), int(shape[1]), n_products
 
     @property
     def handle(self):

@@ -486,6 +486,65 @@ int rr_textprep_compact_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text
                             const int32_t* d_len, const int32_t* d_status, int32_t n_docs, uint8_t* d_out_text,
                             int64_t out_bytes, int64_t* d_out_off, int32_t* d_src_row, int64_t* d_count, void* stream);
 
+/* ------------------------------------------------------------ BM25 corpus: tokens and vocabulary ids (csrc/rr_doctok.hip) */
+
+/* nlp/12_product_prep.py:42-49,75-83 and pd.factorize(sort=False) on the device: from the raw text column to
+ * (tok int32[T], doc_off int64[n + 1], vocabulary) -- the arrays bm25.factorize_corpus(build_bm25_blob(meta)["corpus"]) makes
+ * and rr_bm25_build reads.  The rules (doctok.model_tokenize states them in Python):
+ *   - a byte is an alnum (0-9 a-z, A-Z lower-cased), an apostrophe or a separator; E2 84 AA (U+212A KELVIN SIGN) is the alnum
+ *     'k' and C4 B0 (U+0130) the alnum 'i' followed by a separator: the only two code points outside ASCII that str.lower()
+ *     maps onto ASCII.  Every other byte >= 0x80, and NUL, is a separator, so no document is left to the host;
+ *   - a token is a run of alnums, and one more run behind a single apostrophe: [a-z0-9]+(?:'[a-z0-9]+)?, greedy, left to
+ *     right (a'b'c -> a'b, c; ab''cd -> ab, cd); its bytes are the MAPPED bytes;
+ *   - tokens of one byte and the stop words given at create are dropped, then the document keeps its first 5000 tokens.
+ * The calls of one handle must be stream-ordered, in this order:
+ *   rr_doctok_count_dev   pass 1: kept tokens per document and their int64 prefix sum into d_doc_off [n_docs + 1];
+ *   rr_doctok_sizes       waits for the device; out_sizes[0] = T, [1] = bytes of the token arena (= text_bytes: a token's
+ *                         bytes sit at the offset of its first byte in the text), [2] = n_terms, [3] = bytes of the vocabulary
+ *                         (the last two once rr_doctok_vocab_dev has run, else 0).  When a document's offsets decrease or
+ *                         leave [0, text_bytes] (no text is read for it), or a token has 2^31 bytes or more: RR_E_INVALID,
+ *                         out_sizes[0] = the number of such documents, the count is dropped and the handle keeps what the
+ *                         calls before it established.  More than 2^31 - 1 terms: RR_E_INVALID;
+ *   rr_doctok_emit_dev    pass 2 over the same text and offsets: per token its arena offset, length and 64-bit hash, at the
+ *                         global position d_doc_off[d] + index (buffers of the handle, sized from T);
+ *   rr_doctok_vocab_dev   ids in first-appearance order into d_tok [T]: an open-addressing table of max(64, 2 T) slots of
+ *                         8 bytes (it cannot fill; the probe loop is bounded by the table's size all the same and a token
+ *                         without a slot makes rr_doctok_sizes fail), claimed by compare-and-swap, every hit decided by a
+ *                         BYTE compare, a 64-bit atomicMin of the token's position per slot; first[p] = (minimum == p), an
+ *                         exclusive int64 scan of first = the id.  hash_bits (64; tests pass 3 so that nearly every probe
+ *                         collides) only shortens the hash that picks the first slot.  The result does not depend on
+ *                         scheduling.  May be called again on the same token stream;
+ *   rr_doctok_copy_vocab  (after rr_doctok_sizes) the vocabulary in id order to the host: h_bytes [sizes[3]], h_off
+ *                         [n_terms + 1].  Waits.  d_tok = what rr_doctok_vocab_dev wrote;
+ *   rr_doctok_copy_tokens the token stream before the vocabulary, for tests: h_pos [T] arena offsets, h_len [T], h_arena
+ *                         [text_bytes] (may be NULL).  Waits.
+ * count / emit / vocab are asynchronous on `stream` and ordered after it.  The calls that wait (rr_doctok_sizes,
+ * rr_doctok_copy_vocab, rr_doctok_copy_tokens) synchronise the whole DEVICE, not only that stream, and rr_doctok_copy_vocab
+ * runs its gather on the NULL stream (as rr_textprep_status waits).
+ * Time: one workgroup per document, and a token is walked by the ONE thread that holds its first byte (from global memory
+ * once it leaves the tile's window).  Ordinary text costs nothing for that; a document that is a single alphanumeric run
+ * of many MB is walked by one lane, a byte per step, in both passes: its time grows with the run's length and nothing
+ * bounds it (DESIGN.md K2-text quotes a 1 MiB run).
+ * n_docs = 0 gives d_doc_off = [0]; T = 0 an empty vocabulary.
+ * Every position, count and offset is int64; only ids and a token's length are int32.
+ * Device memory of the handle, at its peak (rr_doctok_vocab_dev): text_bytes (arena) + 28 T (offset 8, length 4, hash 8,
+ * slot 8 per token) + 16 T (table: 2 T slots of 8 bytes) + 8 T / 4096 (scan), beside the caller's text, d_doc_off and 4 T
+ * of ids: 44 T + text_bytes.  rr_doctok_copy_vocab adds 16 n_terms + the vocabulary's bytes while it runs. */
+typedef struct rr_doctok rr_doctok;
+/* Stop words: n_stop <= 64 words of 1..8 bytes, h_stop_off [n_stop + 1] into h_stop_bytes (text.INDEX_STOP_WORDS). */
+int rr_doctok_create(int32_t device, const uint8_t* h_stop_bytes, const int64_t* h_stop_off, int32_t n_stop, rr_doctok** out);
+int rr_doctok_destroy(rr_doctok* dt);
+/* Bytes per step of the walk, consecutive bytes per thread, tokens kept per document. */
+int rr_doctok_limits(int32_t* out_tile, int32_t* out_per_thread, int32_t* out_token_cap);
+int rr_doctok_count_dev(rr_doctok* dt, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off, int32_t n_docs,
+                        int64_t* d_doc_off, void* stream);
+int rr_doctok_sizes(rr_doctok* dt, int64_t* out_sizes);
+int rr_doctok_emit_dev(rr_doctok* dt, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off, int32_t n_docs,
+                       const int64_t* d_doc_off, void* stream);
+int rr_doctok_vocab_dev(rr_doctok* dt, int32_t hash_bits, int32_t* d_tok, void* stream);
+int rr_doctok_copy_vocab(rr_doctok* dt, const int32_t* d_tok, uint8_t* h_bytes, int64_t* h_off);
+int rr_doctok_copy_tokens(rr_doctok* dt, int64_t* h_pos, int32_t* h_len, uint8_t* h_arena);
+
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard
  * that selects on its own rescoring ~8x the candidates the merged answer needs.  Instead:

@@ -113,6 +113,15 @@ PROTOTYPES = {
     "rr_textprep_status": (C.c_int, [c_vp, P(c_i32)]),
     "rr_textprep_dedup_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "rr_textprep_compact_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rr_doctok_create": (C.c_int, [c_i32, c_vp, c_vp, c_i32, P(c_vp)]),
+    "rr_doctok_destroy": (C.c_int, [c_vp]),
+    "rr_doctok_limits": (C.c_int, [P(c_i32), P(c_i32), P(c_i32)]),
+    "rr_doctok_count_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    "rr_doctok_sizes": (C.c_int, [c_vp, c_vp]),
+    "rr_doctok_emit_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    "rr_doctok_vocab_dev": (C.c_int, [c_vp, c_i32, c_vp, c_vp]),
+    "rr_doctok_copy_vocab": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "rr_doctok_copy_tokens": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "rr_index_stream": (C.c_int, [c_vp, P(c_vp)]),
     "rr_index_synchronize": (C.c_int, [c_vp]),
 }

@@ -348,6 +348,20 @@ def build_bm25_index_ids(tok, doc_off, n_terms: int, *, device: int = 0, order=N
     return index
 
 
+def build_bm25_index_texts(texts, *, device: int = 0, order=None, rows=None, row_offset: int = 0, k1: float = 1.5,
+                           b: float = 0.75, epsilon: float = 0.25, host_copy: bool = True) -> BM25Index:
+    """``build_bm25_index([text.tokenize_document(t) for t in texts], ...)`` with the tokens and the vocabulary ids made on
+    the GPU as well (csrc/rr_doctok.hip): raw text in, the same index out, bit for bit."""
+    from .doctok import DeviceDocTokenizer
+    dt = DeviceDocTokenizer(device)
+    try:
+        tok, off, vocab = dt.tokenize(texts)
+        return build_bm25_index_ids(tok, off, len(vocab), device=device, order=order, rows=rows, row_offset=row_offset,
+                                    k1=k1, b=b, epsilon=epsilon, vocab=vocab, host_copy=host_copy)
+    finally:
+        dt.close()
+
+
 class BM25Okapi:
     """Drop-in for ``rank_bm25.BM25Okapi`` on the calls the reference makes:
     ``BM25Okapi(corpus)`` and ``get_scores(tokens) -> float64[N]``."""
@@ -364,9 +378,21 @@ class BM25Okapi:
             self.index = BM25Corpus.from_corpus(corpus, k1=k1, b=b, epsilon=epsilon).to_device(device)
         else:
             raise ValueError("build must be 'device' or 'host'")
+        self._adopt(k1, b, epsilon)
+
+    def _adopt(self, k1: float, b: float, epsilon: float) -> None:
+        """The attributes rank_bm25 exposes, from ``self.index``."""
         self.corpus_size = self.index.n_docs
         self.avgdl = self.index.corpus.avgdl
         self.k1, self.b, self.epsilon = k1, b, epsilon
+
+    @classmethod
+    def from_texts(cls, texts, k1: float = 1.5, b: float = 0.75, epsilon: float = 0.25, device: int = 0) -> "BM25Okapi":
+        """``BM25Okapi([text.tokenize_document(t) for t in texts])`` from the raw texts, tokenised on the GPU."""
+        self = cls.__new__(cls)
+        self.index = build_bm25_index_texts(texts, device=device, k1=k1, b=b, epsilon=epsilon)
+        self._adopt(k1, b, epsilon)
+        return self
 
     @property
     def idf(self) -> Dict[str, float]:

@@ -447,9 +447,11 @@ class SearchEngine:
     def __init__(self, meta: pd.DataFrame, embeddings: np.ndarray, bm25_blob: Optional[dict] = None,
                  *, encoder=None, cross_encoder=None, device: int = 0, normalize: bool = True,
                  flavour: str = "app", dtype: str = "f32", reviews: Optional[Tuple] = None,
-                 bm25_build: str = "device", index: Optional[ProductIndex] = None):
+                 bm25_build: str = "device", index: Optional[ProductIndex] = None, bm25_ids: Optional[Tuple] = None):
         """``index``: a ready ProductIndex (embed.build_product_embeddings) to use instead of uploading ``embeddings``
-        (then None); it is taken as it is -- ``normalize`` and ``dtype`` describe an upload only."""
+        (then None); it is taken as it is -- ``normalize`` and ``dtype`` describe an upload only.
+        ``bm25_ids``: ``(skus, tok, doc_off, vocab)`` instead of ``bm25_blob`` -- the corpus as token ids (numpy arrays or
+        tensors on ``device``, doctok.DeviceDocTokenizer): what ``factorize_corpus(bm25_blob["corpus"])`` gives."""
         if flavour not in ("app", "cli"):
             raise ValueError("flavour must be 'app' or 'cli'")
         if bm25_build not in ("device", "host"):
@@ -477,7 +479,18 @@ class SearchEngine:
         self._bm25_corpus: Optional[BM25Corpus] = None
         self._bm25_source = None
         bm25_index = None
-        if bm25_blob:
+        if bm25_ids is not None:
+            if bm25_blob:
+                raise ValueError("pass either bm25_blob or bm25_ids")
+            if bm25_build != "device":
+                raise ValueError("bm25_ids are indexed by the GPU builder: bm25_build must be 'device'")
+            skus, tok, off, vocab = bm25_ids
+            order = self._align_bm25([str(s) for s in skus])
+            bm25_index = build_bm25_index_ids(tok, off, len(vocab), device=device, order=order, vocab=vocab)
+            if not isinstance(tok, np.ndarray):            # kept for bm25_corpus on the HOST, as the blob path keeps them:
+                tok, off = tok.cpu().numpy(), off.cpu().numpy()    # 4 B per token of device memory is given back
+            self._bm25_source = (tok, off, vocab)
+        elif bm25_blob:
             order = self._align_bm25([str(s) for s in bm25_blob["skus"]])
             if bm25_build == "device":       # the index built on the GPU (csrc/rr_bm25_build.hip): the same arrays
                 # kept for bm25_corpus: the ids (4 B per token, no reference to the blob's token lists)
@@ -518,11 +531,15 @@ class SearchEngine:
 
     @classmethod
     def from_products(cls, products, encoder, *, text_col: str = "agg_text", dtype: str = "f32", chunk_tokens: int = 131072,
-                      bm25: bool = True, data_dir=None, **kw) -> "SearchEngine":
+                      bm25: bool = True, data_dir=None, bm25_tokenize: str = "device", **kw) -> "SearchEngine":
         """The engine straight from a product table (sku, agg_text, ...), no files in between: embeddings by
         embed.build_product_embeddings on the encoder's GPU (nlp/11_build_product_embeddings.py), the BM25 corpus tokenised
         as nlp/12_product_prep.py:80-89 does and indexed by the GPU builder.  ``encoder`` (a QueryEncoder with a vocabulary)
         also becomes the engine's query encoder.  With ``data_dir`` the two embedding files are written as well.
+        bm25_tokenize: "device" tokenises ``agg_text`` and numbers the vocabulary on the GPU (doctok.DeviceDocTokenizer),
+        "host" with ``build_bm25_blob`` + ``factorize_corpus``; the two give bitwise the same index.  The device tokenizer
+        feeds the GPU index builder only: with ``bm25_build="host"`` (the index built by BM25Corpus.from_corpus, which reads
+        token lists) the corpus is tokenised on the host whatever ``bm25_tokenize`` says.
 
         The same engine, bit for bit, as `from_artifacts` on the files this build writes: the loaders l2-normalise the
         stored unit rows once more (app/test.py:144), so this does too (`index.l2_normalize()` after the build).
@@ -531,6 +548,8 @@ class SearchEngine:
         for it."""
         from .artifacts import build_bm25_blob
         from .embed import build_product_embeddings
+        if bm25_tokenize not in ("device", "host"):
+            raise ValueError("bm25_tokenize must be 'device' or 'host'")
         index, meta, _ = build_product_embeddings(products, encoder, text_col=text_col, dtype="f32",
                                                   chunk_tokens=chunk_tokens, data_dir=data_dir)
         if dtype == "f32":
@@ -539,8 +558,17 @@ class SearchEngine:
             rows = index.download_rows()
             index.close()
             index = ProductIndex.from_rows(rows, device=encoder.model.device, normalize=True, dtype=dtype)
-        blob = build_bm25_blob(meta) if bm25 else None
         kw.setdefault("device", encoder.model.device)
+        if bm25 and bm25_tokenize == "device" and kw.get("bm25_build", "device") == "device":   # (the host builder reads token lists)
+            from .doctok import DeviceDocTokenizer
+            dt = DeviceDocTokenizer(kw["device"])
+            try:                                           # build_bm25_blob's column: fillna("").astype(str)
+                tok, off, vocab = dt.tokenize(meta["agg_text"].fillna("").astype(str).tolist())
+            finally:
+                dt.close()
+            return cls(meta, None, None, encoder=encoder, index=index,
+                       bm25_ids=(meta["sku"].astype(str).tolist(), tok, off, vocab), **kw)
+        blob = build_bm25_blob(meta) if bm25 else None
         return cls(meta, None, blob, encoder=encoder, index=index, **kw)
 
     # app: sku -> last position, missing -> 0.0 score (app/app_product_search.py:207-208)

@@ -1,0 +1,255 @@
+"""The device tokenizer of the BM25 corpus (csrc/rr_doctok.hip) against doctok.model_tokenize and bm25.factorize_corpus:
+token for token and id for id, no tolerance.  Then the index, the engine and the prep command line built from raw text
+against the host path, bit for bit."""
+import ctypes as C
+import json
+import pathlib
+import pickle
+import random
+
+import numpy as np
+import pandas as pd
+import pytest
+
+from review_recommender_amd import _lib, doctok, synth, text
+from review_recommender_amd.bm25 import BM25Okapi, build_bm25_index, build_bm25_index_texts, factorize_corpus
+
+pytestmark = pytest.mark.gpu
+GOLDEN = pathlib.Path(__file__).resolve().parent / "golden"
+ALPHABET = list("ab1AZ' .-\n") + ["\u0130", "\u212a", "\u0307", "\u00e9", "\u6f22", "\U0001F600"]
+KELVIN, DOTTED_I = "\u212a".encode(), "\u0130".encode()
+
+
+@pytest.fixture(scope="module")
+def dt():
+    d = doctok.DeviceDocTokenizer(0)
+    yield d
+    d.close()
+
+
+@pytest.fixture(scope="module")
+def tile(dt):
+    t, per, cap = C.c_int32(), C.c_int32(), C.c_int32()
+    _lib.check(_lib.load().rr_doctok_limits(C.byref(t), C.byref(per), C.byref(cap)), "rr_doctok_limits")
+    assert cap.value == text.INDEX_TOKEN_CAP and t.value % per.value == 0
+    return t.value
+
+
+def raw(docs):
+    return [doctok.encode_text(d) for d in docs]
+
+
+def want_of(docs):
+    """(token lists of the model, and factorize_corpus of them)."""
+    lists = [[b.decode("ascii") for b in doctok.model_tokenize(d)] for d in raw(docs)]
+    return lists, factorize_corpus(lists)
+
+
+def check(dt, docs, hash_bits=64):
+    """Tokenises `docs` on the device; the token stream (bytes per document) and the ids must be the model's."""
+    docs = raw(docs)
+    lists, (w_tok, w_off, w_vocab) = want_of(docs)
+    tok, off, vocab = dt.tokenize(docs, hash_bits=hash_bits)
+    assert tok.dtype.is_floating_point is False and tok.is_cuda and off.is_cuda
+    off_h, tok_h = off.cpu().numpy(), tok.cpu().numpy()
+    assert off_h.dtype == np.int64 and tok_h.dtype == np.int32
+    assert np.array_equal(off_h, w_off), "tokens per document"
+    pos, ln, arena = dt.token_stream()                                 # the stream before the vocabulary
+    blob = arena.tobytes()
+    got = [[blob[pos[p]:pos[p] + ln[p]].decode("ascii") for p in range(off_h[d], off_h[d + 1])] for d in range(len(docs))]
+    bad = [d for d in range(len(docs)) if got[d] != lists[d]]
+    assert not bad, (bad[:5], docs[bad[0]][:80], got[bad[0]][:8], lists[bad[0]][:8])
+    assert np.array_equal(tok_h, w_tok), "ids"
+    assert vocab == w_vocab and list(vocab) == list(w_vocab)
+    return tok_h, off_h, vocab
+
+
+def test_fixtures_and_random_documents(dt, tile):
+    cases = [c["text"] for c in json.loads((GOLDEN / "index_tokenizer.json").read_text())["cases"]]
+    rng = random.Random(11)
+    nrng = np.random.default_rng(11)
+    lens = [rng.randint(0, 60) for _ in range(18_000)] + nrng.integers(0, 3 * tile + 1, 2_000).tolist()   # 0 .. 3 * tile
+    lens[:8] = [3 * tile, 3 * tile - 1, 2 * tile + 5, tile, tile + 1, tile - 1, 0, 1]
+    letters = np.array(ALPHABET, dtype=object)
+    docs = cases + ["".join(letters[nrng.integers(0, len(letters), n)]) for n in lens]
+    assert len(docs) == 20_027 and sum(n > tile for n in lens) > 1_000
+    check(dt, docs)
+
+
+def test_tile_edges(dt, tile):
+    docs = []
+    for n in (tile - 1, tile, tile + 1, 2 * tile + 1):
+        docs.append(("ab cd " * n)[:n])
+        docs.append("q" * n)
+        docs.append((" " * (n - 2)) + "zz")
+    for piece in (b"token", b"aa'bb'cc'dd", b"a'b'c'd", b"x" + DOTTED_I + b"y", b"x" + KELVIN + b"y", b"'" + KELVIN + b"'" + KELVIN,
+                  DOTTED_I + b"'" + DOTTED_I):
+        for edge in (tile, 2 * tile):
+            for shift in range(len(piece) + 2):                       # the piece across every offset of the edge
+                at = edge - shift
+                docs.append(b"." * at + piece + b" tail")
+                docs.append(b"g" * (at - 1) + b" " + piece)            # (behind a long token)
+    docs.append("w" * (3 * tile))                                     # one token longer than any tile
+    docs.append("w" * (3 * tile) + "'" + "v" * (tile + 3) + "'uu")
+    docs.append(" .-\n\u00e9\u6f22" * 700)                             # separators only
+    docs = [""] + docs[:40] + [""] + docs[40:] + [""]                  # empty documents first, in the middle, last
+    check(dt, docs)
+    check(dt, ["", "", ""])
+    tok, off, vocab = dt.tokenize([])                                 # n_docs = 0
+    assert tok.numel() == 0 and off.cpu().tolist() == [0] and vocab == {}
+    tok, off, vocab = dt.tokenize([" . ", "a I the"])                 # T = 0
+    assert tok.numel() == 0 and off.cpu().tolist() == [0, 0, 0] and vocab == {}
+
+
+def test_the_cap_counts_kept_tokens(dt):
+    def doc(kept, plant):
+        words = []
+        for i in range(kept):
+            words += ["the", "x", "kw%d" % (i % 700)] if i % 3 == 0 else ["kw%d" % (i % 700)]
+        if plant:
+            words[-1] = plant                                         # the last kept token of the document
+        return " ".join(words) + " the a I"
+    docs = [doc(4999, "last4999"), doc(5000, "last5000"), doc(5001, "past5001"), doc(12_000, "past12000"), "kw1 end"]
+    lists, _ = want_of(docs)
+    assert [len(x) for x in lists] == [4999, 5000, 5000, 5000, 2]
+    tok, off, vocab = check(dt, docs)
+    assert "last4999" in vocab and "last5000" in vocab and "past5001" not in vocab and "past12000" not in vocab
+
+
+def test_vocabulary_ids_do_not_depend_on_the_hash(dt):
+    rng = random.Random(5)
+    words = ["t%d" % i for i in range(1500)] + ["abcdefgh", "abcdefgi", "abcdefg", "abcdefghijklmnop", "abcdefghijklmnoq", "ab", "abc"]
+    docs = [" ".join(rng.choices(words, k=rng.randint(0, 60))) for _ in range(600)]
+    docs.append("seen before: " + docs[0] + " onlyinthelastdocument")
+    a = check(dt, docs, hash_bits=3)
+    b = check(dt, docs, hash_bits=64)
+    assert np.array_equal(a[0], b[0]) and a[2] == b[2] and list(a[2]) == list(b[2])
+    assert a[2]["onlyinthelastdocument"] == len(a[2]) - 1
+    # the same vocabulary call twice on one handle
+    T = int(a[1][-1])
+    t1, n1, v1 = dt.vocab_dev(T, 64)
+    t2, n2, v2 = dt.vocab_dev(T, 5)
+    assert (n1, v1) == (n2, v2) and np.array_equal(t1.cpu().numpy(), a[0]) and np.array_equal(t2.cpu().numpy(), a[0])
+    assert dt.vocab_terms(t2, n2, v2) == list(a[2])
+
+
+def test_many_terms_race_for_slots(dt):
+    rng = np.random.default_rng(3)
+    ids = rng.integers(0, 50_000, size=(2000, 60))
+    docs = [" ".join("v%x" % i for i in row) for row in ids]
+    tok, off, vocab = check(dt, docs)
+    assert len(vocab) > 45_000
+
+
+def test_bad_offsets_are_refused_and_change_nothing(dt):
+    docs = raw(["alpha beta", "gamma delta epsilon", "zeta"])
+    check(dt, docs)
+    before = dt.token_stream()
+    sizes = dt.sizes()
+    n_bytes = sum(map(len, docs))
+    for off, count in (([0, 10, 5, n_bytes], 1), ([0, 10, 29, n_bytes + 1], 1), ([-1, 10, 29, n_bytes], 1),
+                       ([0, 40, 5, n_bytes + 9], 3)):
+        with pytest.raises(ValueError, match=r"rr_doctok_sizes: %d document\(s\)" % count):
+            dt.tokenize(docs, offsets=np.array(off, dtype=np.int64))
+        assert dt.sizes() == sizes
+        after = dt.token_stream()
+        assert all(np.array_equal(x, y) for x, y in zip(before, after))
+    check(dt, docs)                                                   # and the handle still works
+
+
+# ------------------------------------------------------------------------------------------------ end to end
+def product_texts(n=3000, seed=21):
+    rng = np.random.default_rng(seed)
+    texts = synth.text_corpus(n, seed, mean_len=25)
+    for i in rng.choice(n, 300, replace=False):
+        texts[i] = texts[i].title().replace(" ", ", ", 2) + " It's the KID'S 5 o'clock caf\u00e9 \u212aelvin \u0130stanbul won't"
+    texts[7] = ""
+    texts[n - 1] = "firstseenhere " + texts[n - 1]
+    return texts
+
+
+def test_index_from_texts_equals_the_host_path_bit_for_bit():
+    from review_recommender_amd.artifacts import build_bm25_blob
+    texts = product_texts()
+    n = len(texts)
+    meta = pd.DataFrame({"sku": synth.skus(n), "agg_text": texts})
+    corpus = build_bm25_blob(meta)["corpus"]
+    rng = np.random.default_rng(2)
+    order = rng.permutation(n).astype(np.int64)
+    order[5] = -1
+    for kw in ({}, {"order": order, "rows": (100, 2500), "row_offset": 100}):
+        a = build_bm25_index(corpus, **kw)
+        b = build_bm25_index_texts(texts, **kw)
+        ca, cb = a.copy_csr(), b.copy_csr()
+        assert set(ca) == set(cb) and all(np.array_equal(ca[k], cb[k]) and ca[k].dtype == cb[k].dtype for k in ca)
+        assert np.array_equal(a.df, b.df)
+        assert np.array_equal(a.corpus.idf.view(np.uint64), b.corpus.idf.view(np.uint64))
+        assert a.corpus.avgdl == b.corpus.avgdl and a.corpus.vocab == b.corpus.vocab
+    x, y = BM25Okapi(corpus), BM25Okapi.from_texts(texts)
+    assert x.corpus_size == y.corpus_size and x.avgdl == y.avgdl and x.idf == y.idf
+    for q in ("wireless cat socks", "kid's kelvin istanbul mug", "firstseenhere usb cable nosuchword"):
+        sa, sb = x.get_scores(text.tokenize_query(q)), y.get_scores(text.tokenize_query(q))
+        assert np.array_equal(sa.view(np.uint64), sb.view(np.uint64)) and sa.max() > 0
+
+
+def small_engine_world(n=600):
+    from review_recommender_amd.cross_encoder import QueryEncoder
+    from review_recommender_amd.wordpiece import WordPieceTokenizer
+    words = ["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"] + list(synth.WORDS) + ["##s", "##ing"]
+    tok = WordPieceTokenizer({w: i for i, w in enumerate(words)})
+    enc = QueryEncoder(synth.bert_state_dict(31, n_layers=2, n_labels=0, prefix="", vocab=len(words)), tok)
+    texts = product_texts(n, seed=4)
+    texts[7] = "empty of keywords: the a I"
+    n_rev, stars = synth.metadata(n, 5)
+    return enc, pd.DataFrame({"sku": synth.skus(n), "n_reviews": n_rev, "avg_stars": stars, "agg_text": texts})
+
+
+def test_engine_from_products_device_tokenizer_equals_host():
+    from review_recommender_amd.engine import SearchEngine
+    enc, products = small_engine_world()
+    a = SearchEngine.from_products(products, enc, bm25_tokenize="host")
+    b = SearchEngine.from_products(products, enc, bm25_tokenize="device")
+    with pytest.raises(ValueError):
+        SearchEngine.from_products(products, enc, bm25_tokenize="nowhere")
+    with pytest.raises(ValueError, match="bm25_build"):
+        SearchEngine(a.meta, None, None, index=a.index, bm25_build="host", bm25_ids=(["x"], np.zeros(0, np.int32), np.zeros(2, np.int64), {}))
+    assert isinstance(b._bm25_source[0], np.ndarray)                  # the ids wait on the host, not in device memory
+    for query in ("wireless cat socks", "blue insulated coffee mug", "kid's usb cable"):
+        fa, sa, da = a.run_search(query, 10, 0, 0.5, 0.3, 0.0, 0.2, 0.0, 20.0)
+        fb, sb, db = b.run_search(query, 10, 0, 0.5, 0.3, 0.0, 0.2, 0.0, 20.0)
+        pd.testing.assert_frame_equal(fa, fb, check_exact=True)
+        assert sa == sb and da == db and len(fa) == 10
+    ca, cb = a.bm25_corpus, b.bm25_corpus                             # lazily, from the ids
+    for k in ("doc_indptr", "doc_terms", "doc_tf", "doc_len", "idf"):
+        assert np.array_equal(getattr(ca, k), getattr(cb, k)), k
+    assert ca.vocab == cb.vocab and ca.avgdl == cb.avgdl
+
+
+def test_prep_command_line_writes_the_reference_pickle(tmp_path):
+    from review_recommender_amd import prep
+    from review_recommender_amd.artifacts import build_bm25_blob
+    texts = product_texts(500, seed=8)
+    meta = pd.DataFrame({"sku": np.arange(500) * 3, "merged_text": texts, "n_reviews": 1})
+    meta.loc[[3, 77], "merged_text"] = None                           # fillna("")
+    meta.to_parquet(tmp_path / "product_emb_meta.parquet", index=False)
+    assert prep.main(["--data-dir", str(tmp_path)]) == 0
+    with open(tmp_path / "product_bm25.pkl", "rb") as f:
+        head = f.read(2)
+        f.seek(0)
+        blob = pickle.load(f)
+    assert head == b"\x80\x04"                                        # protocol 4
+    want = build_bm25_blob(meta.rename(columns={"merged_text": "agg_text"}))
+    assert blob == want and list(blob) == ["skus", "corpus", "tokenizer"] and blob["corpus"][3] == []
+    empty = tmp_path / "empty"                                        # no products: no documents, not one empty document
+    empty.mkdir()
+    meta.iloc[:0].to_parquet(empty / "product_emb_meta.parquet", index=False)
+    assert prep.main(["--data-dir", str(empty)]) == 0
+    with open(empty / "product_bm25.pkl", "rb") as f:
+        assert pickle.load(f) == {"skus": [], "corpus": [], "tokenizer": "simple_en_v1"}
+    assert all(type(t) is str for d in blob["corpus"][:50] for t in d)
+    # products.parquet wins over product_emb_meta.parquet, agg_text over the other names
+    pd.DataFrame({"sku": ["a", "b"], "text": ["no", "no"], "agg_text": ["Yes it's here", "\u212a2 summit"]}).to_parquet(
+        tmp_path / "products.parquet", index=False)
+    assert prep.main(["--data-dir", str(tmp_path)]) == 0
+    with open(tmp_path / "product_bm25.pkl", "rb") as f:
+        assert pickle.load(f) == {"skus": ["a", "b"], "corpus": [["yes", "it's", "here"], ["k2", "summit"]], "tokenizer": "simple_en_v1"}

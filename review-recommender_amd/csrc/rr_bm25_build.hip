@@ -15,8 +15,8 @@
 //
 // The radix sort: 8-bit digits, ceil(bits(max key) / 8) passes (at least one), each
 //   rb_hist     per-tile digit counts (a tile = RB_TILE elements, one workgroup);
-//   rb_scan_*   exclusive scan of the digit-major count matrix (int64) -> where every
-//               (digit, tile) run starts in the output;
+//   rr_scan     (rr_prims.h) exclusive scan of the digit-major count matrix (int64) -> where
+//               every (digit, tile) run starts in the output;
 //   rb_scatter  the tile in rounds of 256 elements, in input order: a wave's lanes with the
 //               same digit find each other with eight __ballot masks, rank themselves with a
 //               popcount below their lane, and add the counts of the waves before them.  The
@@ -26,11 +26,11 @@
 #include <vector>
 #include <algorithm>
 
-#include "rr_common.h"
+#include "rr_prims.h"
 
 #define RB_THREADS 256
 #define RB_ROUNDS 16
-#define RB_TILE (RB_THREADS * RB_ROUNDS)   // elements per workgroup of the sort, the scan and the run-length pass
+#define RB_TILE (RB_THREADS * RB_ROUNDS)   // elements per workgroup of the sort and the run-length pass
 #define RB_GRID_CAP 8192                     // grid of the grid-stride kernels
 
 #define RB_ERR_TERM 1u      // a term id outside [0, n_terms)
@@ -130,73 +130,6 @@ __global__ __launch_bounds__(RB_THREADS) void rb_gather_rows(const int64_t* __re
         const int64_t src = off[s], cnt = off[s + 1] - src, dst = new_off[r];
         for (int64_t i = lane; i < cnt; i += 64) new_tok[dst + i] = tok[src + i];
     }
-}
-
-// ------------------------------------------------------------------ exclusive scan (int64)
-// out[0..m] = exclusive prefix sums of in[0..m), out[m] = the total.  in == out is allowed.
-__device__ __forceinline__ int64_t rb_block_excl_scan(int64_t v, int64_t* sh, int64_t* total) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int s = 1; s < RB_THREADS; s <<= 1) {
-        const int64_t a = tid >= s ? sh[tid - s] : 0;
-        __syncthreads();
-        sh[tid] += a;
-        __syncthreads();
-    }
-    const int64_t incl = sh[tid];
-    *total = sh[RB_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-__global__ __launch_bounds__(RB_THREADS) void rb_scan_reduce(const int64_t* __restrict__ in, int64_t m,
-                                                             int64_t* __restrict__ part) {
-    __shared__ int64_t sh[RB_THREADS];
-    const int64_t base = (int64_t)blockIdx.x * RB_TILE + (int64_t)threadIdx.x * RB_ROUNDS;
-    int64_t s = 0;
-    for (int j = 0; j < RB_ROUNDS; ++j)
-        if (base + j < m) s += in[base + j];
-    int64_t total;
-    rb_block_excl_scan(s, sh, &total);
-    if (threadIdx.x == 0) part[blockIdx.x] = total;
-}
-
-// one workgroup: exclusive scan of part[0..nb) in place, part[nb] = total
-__global__ __launch_bounds__(RB_THREADS) void rb_scan_parts(int64_t* __restrict__ part, int64_t nb) {
-    __shared__ int64_t sh[RB_THREADS];
-    int64_t carry = 0;
-    for (int64_t c = 0; c < nb; c += RB_THREADS) {
-        const int64_t i = c + threadIdx.x;
-        const int64_t v = i < nb ? part[i] : 0;
-        int64_t total;
-        const int64_t ex = rb_block_excl_scan(v, sh, &total);
-        if (i < nb) part[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) part[nb] = carry;
-}
-
-__global__ __launch_bounds__(RB_THREADS) void rb_scan_apply(const int64_t* in, int64_t m,
-                                                            const int64_t* __restrict__ part, int64_t nb,
-                                                            int64_t* out) {
-    __shared__ int64_t sh[RB_THREADS];
-    const int64_t base = (int64_t)blockIdx.x * RB_TILE + (int64_t)threadIdx.x * RB_ROUNDS;
-    int64_t v[RB_ROUNDS];
-    int64_t s = 0;
-#pragma unroll
-    for (int j = 0; j < RB_ROUNDS; ++j) {
-        v[j] = base + j < m ? in[base + j] : 0;
-        s += v[j];
-    }
-    int64_t total;
-    int64_t run = part[blockIdx.x] + rb_block_excl_scan(s, sh, &total);   // (every read of `in` is done: in == out is safe)
-#pragma unroll
-    for (int j = 0; j < RB_ROUNDS; ++j) {
-        if (base + j < m) out[base + j] = run;
-        run += v[j];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[m] = part[nb];
 }
 
 // ------------------------------------------------------------------ radix sort
@@ -333,6 +266,7 @@ namespace {
 struct RbPool {
     hipStream_t st;
     std::vector<void*> live;
+    int64_t* scan_sums = nullptr;   // chunk sums of the build's scans (rb_build sizes it for the largest of them)
     explicit RbPool(hipStream_t s) : st(s) {}
     template <typename T>
     int alloc(T** p, int64_t n) {
@@ -369,20 +303,14 @@ struct RbPool {
         if (_rc != RR_OK) return _rc; \
     } while (0)
 
-int rb_scan(hipStream_t st, RbPool& pool, const int64_t* in, int64_t m, int64_t* out) {
-    const int64_t nb = rb_tiles(m) > 0 ? rb_tiles(m) : 1;
-    int64_t* part = nullptr;
-    RB_TRY(pool.alloc(&part, nb + 1));
-    if (m > 0) {
-        hipLaunchKernelGGL(rb_scan_reduce, dim3((unsigned)nb), dim3(RB_THREADS), 0, st, in, m, part);
-    } else {
-        RR_HIP_TRY(hipMemsetAsync(part, 0, sizeof(int64_t), st));
-    }
-    hipLaunchKernelGGL(rb_scan_parts, dim3(1), dim3(RB_THREADS), 0, st, part, m > 0 ? nb : 1);
-    hipLaunchKernelGGL(rb_scan_apply, dim3((unsigned)nb), dim3(RB_THREADS), 0, st, in, m, part, m > 0 ? nb : 1, out);
-    RR_HIP_TRY(hipGetLastError());
-    pool.release(part);   // (hipFree waits for the device)
-    return RR_OK;
+struct rb_f_i64 {   // what the build's scans sum: an int64 array
+    const int64_t* in;
+    __device__ __forceinline__ long long operator()(int64_t i) const { return in[i]; }
+};
+
+// the chunk sums of the scans of one rb_build_core over T tokens and of n_rows row lengths: the count matrix is the largest
+int rb_alloc_scan_sums(RbPool& pool, int64_t T, int64_t n_rows) {
+    return pool.alloc(&pool.scan_sums, rr_scan_sums_len(std::max(256 * rb_tiles(T), n_rows)));
 }
 
 int rb_passes(uint32_t max_key) {
@@ -409,7 +337,7 @@ int rb_sort(hipStream_t st, RbPool& pool, int64_t n, uint32_t max_key, const uin
         const uint32_t* b_in = p == 0 ? p1src : (NP >= 2 ? P1[(p - 1) & 1] : nullptr);
         hipLaunchKernelGGL(rb_hist, dim3((unsigned)nt), dim3(RB_THREADS), 0, st, kin, n, 8 * p, nt, hist);
         RR_HIP_TRY(hipGetLastError());
-        RB_TRY(rb_scan(st, pool, hist, m, offs));
+        rr_scan(rb_f_i64{hist}, m, pool.scan_sums, offs, (int32_t*)nullptr, (int64_t*)nullptr, st);
         hipLaunchKernelGGL((rb_scatter<NP>), dim3((unsigned)nt), dim3(RB_THREADS), 0, st, kin, a_in, b_in, n, 8 * p, nt,
                            offs, K[p & 1], NP >= 1 ? P0[p & 1] : nullptr, NP >= 2 ? P1[p & 1] : nullptr);
         RR_HIP_TRY(hipGetLastError());
@@ -463,7 +391,8 @@ int rb_build_core(hipStream_t st, RbPool& pool, const int32_t* tok, int64_t T, c
         hipLaunchKernelGGL(rb_rle_count, dim3((unsigned)nt), dim3(RB_THREADS), 0, st, SK, SP, T, tile_off);
         RR_HIP_TRY(hipGetLastError());
     }
-    RB_TRY(rb_scan(st, pool, tile_off, nt, tile_off));
+    rr_scan(rb_f_i64{tile_off}, nt, pool.scan_sums, tile_off, (int32_t*)nullptr, (int64_t*)nullptr, st);   // (in place)
+    RR_HIP_TRY(hipGetLastError());
     int64_t nnz = 0;
     RB_TRY(rb_read_i64(st, tile_off + nt, &nnz));
     o->nnz = nnz;
@@ -572,6 +501,7 @@ int rb_build(rr_bm25* bm, int32_t on_device, const int32_t* tok, int64_t T, cons
 
     const int64_t n_rows = hi - lo;
     const bool relay = order != nullptr || lo != 0 || hi != n_src;
+    RB_TRY(rb_alloc_scan_sums(pool, T, n_rows));
     RbCsr src, out;
     RB_TRY(rb_build_core(st, pool, d_tok, T, d_off, n_src, n_terms, !relay, &src));
     if (!relay) {
@@ -586,11 +516,16 @@ int rb_build(rr_bm25* bm, int32_t on_device, const int32_t* tok, int64_t T, cons
         hipLaunchKernelGGL(rb_row_len, dim3(rb_grid(n_rows, RB_THREADS)), dim3(RB_THREADS), 0, st, d_order, lo, n_rows,
                            d_off, len);
         RR_HIP_TRY(hipGetLastError());
-        RB_TRY(rb_scan(st, pool, len, n_rows, new_off));
+        rr_scan(rb_f_i64{len}, n_rows, pool.scan_sums, new_off, (int32_t*)nullptr, (int64_t*)nullptr, st);
+        RR_HIP_TRY(hipGetLastError());
         pool.release(len);
         int64_t T2 = 0;
         RB_TRY(rb_read_i64(st, new_off + n_rows, &T2));
         RB_TRY(pool.alloc(&new_tok, T2));
+        if (T2 > T) {   // an order that repeats rows: the second build's scans are the larger ones
+            pool.release(pool.scan_sums);
+            RB_TRY(rb_alloc_scan_sums(pool, T2, 0));
+        }
         hipLaunchKernelGGL(rb_gather_rows, dim3(rb_grid(n_rows, RB_THREADS / 64)), dim3(RB_THREADS), 0, st, d_order, lo,
                            n_rows, d_off, d_tok, new_off, new_tok);
         RR_HIP_TRY(hipGetLastError());

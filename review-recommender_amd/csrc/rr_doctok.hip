@@ -39,8 +39,8 @@
 // first / id         first[p] = (table[slot[p]] == p); the exclusive int64 scan of first is the term id in
 //                    first-appearance order; a second sweep copies it to every token of the term.
 // rr_dt_term_pos, rr_dt_gather    the vocabulary's bytes and offsets in id order, for the host.
-// rr_dt_sum / rr_dt_scan_sums / rr_dt_apply   the device-wide exclusive int64 scan (chunks of 4096 per workgroup).
-#include "rr_common.h"
+// The prefix sums over documents, tokens and terms are rr_scan (rr_prims.h), the device-wide exclusive int64 scan.
+#include "rr_prims.h"
 
 #define RR_DT_THREADS 256
 #define RR_DT_PER 16                                   // consecutive bytes per thread
@@ -48,7 +48,6 @@
 #define RR_DT_HALO 16                                  // bytes of the neighbouring tiles held in LDS on either side
 #define RR_DT_CAP 5000                                 // nlp/12_product_prep.py:78 (text.INDEX_TOKEN_CAP)
 #define RR_DT_MAX_STOP 64
-#define RR_DT_CHUNK 4096                               // elements per workgroup of the device-wide scan
 #define RR_DT_EMPTY 0xFFFFFFFFFFFFFFFFull
 
 // control words on the device
@@ -104,10 +103,6 @@ __device__ __forceinline__ uint32_t rr_dt_compose(uint32_t first, uint32_t then)
 __device__ __forceinline__ bool rr_dt_ascii_alnum(uint32_t b) {
     return (b >= '0' && b <= '9') || (b >= 'a' && b <= 'z') || (b >= 'A' && b <= 'Z');
 }
-__device__ __forceinline__ uint64_t rr_dt_mix(uint64_t x) {           // murmur3's 64-bit finaliser
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
-    return x;
-}
 
 // The document's bytes around one tile: LDS for [base - HALO, base + TILE + HALO), global memory beyond; 0 outside the
 // document (a separator, like NUL inside it).
@@ -126,30 +121,6 @@ struct rr_dt_view {
     }
 };
 
-// Exclusive sum of one int64 per thread over a workgroup of NT threads; *total = the sum, in every thread.
-template <int NT>
-__device__ __forceinline__ long long rr_dt_block_scan(long long v, long long* wave_sums, long long* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    __syncthreads();                       // (wave_sums may still be read from the previous scan)
-    if (lane == 63) wave_sums[wave] = incl;
-    __syncthreads();
-    long long before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-        const long long s = wave_sums[w];
-        before += w < wave ? s : 0;
-        all += s;
-    }
-    *total = all;
-    return before + incl - v;
-}
-
 template <bool EMIT>
 __global__ __launch_bounds__(RR_DT_THREADS) void rr_dt_walk(
     const uint8_t* __restrict__ text, int64_t text_bytes, const int64_t* __restrict__ text_off,
@@ -166,12 +137,11 @@ __global__ __launch_bounds__(RR_DT_THREADS) void rr_dt_walk(
     __shared__ uint8_t s_at[EMIT ? RR_DT_PER / 2 : 1][RR_DT_THREADS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int doc = blockIdx.x;
-    const int64_t b0 = text_off[doc], b1 = text_off[doc + 1];
-    if (b0 < 0 || b1 < b0 || b1 > text_bytes) {            // offsets that leave the text: nothing is read
+    int64_t b0, len;
+    if (!rr_doc_span(text_off, doc, text_bytes, &b0, &len)) {   // offsets that leave the text: nothing is read
         if (!EMIT && tid == 0) { cnt[doc] = 0; atomicAdd((unsigned long long*)&ctl[RR_DT_C_BAD], 1ull); }
         return;
     }
-    const int64_t len = b1 - b0;
     const uint8_t* src = text + b0;
     if (tid < RR_DT_MAX_STOP) s_stop[tid] = tid < n_stop ? stop[tid] : 0ull;
     const int64_t out0 = EMIT ? doc_off[doc] : 0;
@@ -275,14 +245,14 @@ __global__ __launch_bounds__(RR_DT_THREADS) void rr_dt_walk(
             if (keep) {
                 if (EMIT) {
                     s_len[mine][tid] = (int)n;
-                    s_hash[mine][tid] = rr_dt_mix(h ^ (uint64_t)n);
+                    s_hash[mine][tid] = rr_mix64(h ^ (uint64_t)n);
                     s_at[mine][tid] = (uint8_t)j;
                 }
                 ++mine;
             }
         }
         long long total;
-        const long long at = rr_dt_block_scan<RR_DT_THREADS>(mine, s_ws, &total);
+        const long long at = rr_block_scan<long long, RR_DT_THREADS>(mine, s_ws, &total);
         if (EMIT) {
             for (int m = 0; m < mine; ++m) {               // (a thread reads back only what it wrote itself)
                 const int64_t idx = kept + at + m, o = out0 + idx;
@@ -301,7 +271,7 @@ __global__ __launch_bounds__(RR_DT_THREADS) void rr_dt_walk(
     }
 }
 
-// ------------------------------------------------------------------------------------------------ the device-wide scan
+// ------------------------------------------------------------------------------------------------ what the scans sum
 struct rr_dt_f_cnt {                                       // kept tokens of a document
     const int32_t* cnt;
     __device__ __forceinline__ long long operator()(int64_t i) const { return cnt[i]; }
@@ -328,69 +298,6 @@ struct rr_dt_f_term_len {                                  // bytes of term id
     const int32_t* len;
     __device__ __forceinline__ long long operator()(int64_t id) const { return len[term_pos[id]]; }
 };
-
-template <class F>
-__global__ __launch_bounds__(256) void rr_dt_sum(F f, int64_t n, int64_t* __restrict__ sums) {
-    __shared__ long long s_ws[4];
-    const int64_t c0 = (int64_t)blockIdx.x * RR_DT_CHUNK;
-    long long v = 0;
-    for (int r = 0; r < RR_DT_CHUNK / 256; ++r) {
-        const int64_t i = c0 + r * 256 + threadIdx.x;
-        if (i < n) v += f(i);
-    }
-    long long total;
-    rr_dt_block_scan<256>(v, s_ws, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void rr_dt_scan_sums(int64_t* __restrict__ sums, int64_t nb, int64_t* __restrict__ total_out) {
-    __shared__ long long s_ws[16];
-    long long carry = 0;
-    for (int64_t base = 0; base < nb; base += 1024) {
-        const int64_t i = base + threadIdx.x;
-        const long long v = i < nb ? sums[i] : 0;
-        long long total;
-        const long long at = rr_dt_block_scan<1024>(v, s_ws, &total);
-        if (i < nb) sums[i] = carry + at;
-        carry += total;
-    }
-    if (threadIdx.x == 0 && total_out) *total_out = carry;
-}
-
-// out64[i] / out32[i] = the exclusive sum in front of element i; out64[n] = the total.
-template <class F>
-__global__ __launch_bounds__(256) void rr_dt_apply(F f, int64_t n, const int64_t* __restrict__ sums, int64_t nb,
-                                                   int64_t* __restrict__ out64, int32_t* __restrict__ out32) {
-    __shared__ long long s_ws[4];
-    const int64_t c0 = (int64_t)blockIdx.x * RR_DT_CHUNK;
-    long long carry = sums[blockIdx.x];
-    for (int r = 0; r < RR_DT_CHUNK / 256; ++r) {
-        const int64_t i = c0 + r * 256 + threadIdx.x;
-        const long long v = i < n ? f(i) : 0;
-        long long total;
-        const long long at = rr_dt_block_scan<256>(v, s_ws, &total);
-        if (i < n) {
-            if (out64) out64[i] = carry + at;
-            if (out32) out32[i] = (int32_t)(carry + at);
-        }
-        carry += total;
-    }
-    if (out64 && blockIdx.x == nb - 1 && threadIdx.x == 0) out64[n] = carry;
-}
-
-// Exclusive scan of f over [0, n) on `st`: out64 [n + 1] and / or out32 [n] (either may be NULL), *total (may be NULL).
-template <class F>
-static void rr_dt_scan(F f, int64_t n, int64_t* sums, int64_t* out64, int32_t* out32, int64_t* total, hipStream_t st) {
-    const int64_t nb = (n + RR_DT_CHUNK - 1) / RR_DT_CHUNK;
-    if (nb == 0) {
-        if (out64) hipMemsetAsync(out64, 0, sizeof(int64_t), st);
-        if (total) hipMemsetAsync(total, 0, sizeof(int64_t), st);
-        return;
-    }
-    hipLaunchKernelGGL(rr_dt_sum<F>, dim3((unsigned)nb), dim3(256), 0, st, f, n, sums);
-    hipLaunchKernelGGL(rr_dt_scan_sums, dim3(1), dim3(1024), 0, st, sums, nb, total);
-    if (out64 || out32) hipLaunchKernelGGL(rr_dt_apply<F>, dim3((unsigned)nb), dim3(256), 0, st, f, n, sums, nb, out64, out32);
-}
 
 // ------------------------------------------------------------------------------------------------ the vocabulary
 __global__ __launch_bounds__(256) void rr_dt_insert(const uint8_t* __restrict__ arena, const int64_t* __restrict__ tok_pos,
@@ -511,22 +418,6 @@ extern "C" int rr_doctok_limits(int32_t* out_tile, int32_t* out_per_thread, int3
     return RR_OK;
 }
 
-// Grows *p to `want` elements of `size` bytes (the old contents are dropped; hipFree waits for the kernels that use them).
-static int rr_dt_grow(void** p, int64_t* cap, int64_t want, size_t size, const char* who) {
-    if (want <= *cap) return RR_OK;
-    if (*p) RR_HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, size * (size_t)want) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        rr_set_error("%s: no memory for %lld x %zu bytes", who, (long long)want, size);
-        return RR_E_NOMEM;
-    }
-    *cap = want;
-    return RR_OK;
-}
-
 static int rr_dt_check_text(const char* who, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off, int32_t n_docs) {
     RR_REQUIRE(n_docs >= 0 && text_bytes >= 0, "%s: %d documents, %lld bytes", who, n_docs, (long long)text_bytes);
     RR_REQUIRE(d_text_off || n_docs == 0, "%s: NULL offsets", who);
@@ -542,14 +433,14 @@ extern "C" int rr_doctok_count_dev(rr_doctok* dt, const uint8_t* d_text, int64_t
     std::lock_guard<std::mutex> lk(dt->mu);
     RR_HIP_TRY(hipSetDevice(dt->device));
     hipStream_t st = (hipStream_t)stream;
-    rc = rr_dt_grow((void**)&dt->d_cnt, &dt->cap_docs, n_docs > 0 ? n_docs : 1, sizeof(int32_t), "rr_doctok_count_dev");
-    if (rc == RR_OK) rc = rr_dt_grow((void**)&dt->d_sums, &dt->cap_sums, (int64_t)n_docs / RR_DT_CHUNK + 1, sizeof(int64_t), "rr_doctok_count_dev");
+    rc = rr_grow((void**)&dt->d_cnt, &dt->cap_docs, n_docs > 0 ? n_docs : 1, sizeof(int32_t), "rr_doctok_count_dev");
+    if (rc == RR_OK) rc = rr_grow((void**)&dt->d_sums, &dt->cap_sums, rr_scan_sums_len(n_docs), sizeof(int64_t), "rr_doctok_count_dev");
     if (rc != RR_OK) return rc;
     if (n_docs > 0)
         hipLaunchKernelGGL(rr_dt_walk<false>, dim3((unsigned)n_docs), dim3(RR_DT_THREADS), 0, st, d_text, text_bytes, d_text_off,
                            dt->d_stop, dt->n_stop, dt->d_cnt, dt->d_ctl, (const int64_t*)nullptr, (int64_t)0, (uint8_t*)nullptr,
                            (int64_t*)nullptr, (int32_t*)nullptr, (uint64_t*)nullptr);
-    rr_dt_scan(rr_dt_f_cnt{dt->d_cnt}, (int64_t)n_docs, dt->d_sums, d_doc_off, (int32_t*)nullptr, dt->d_ctl + RR_DT_C_T, st);
+    rr_scan(rr_dt_f_cnt{dt->d_cnt}, (int64_t)n_docs, dt->d_sums, d_doc_off, (int32_t*)nullptr, dt->d_ctl + RR_DT_C_T, st);
     RR_HIP_TRY(hipGetLastError());
     dt->counted_docs = n_docs;
     dt->counted_bytes = text_bytes;
@@ -610,13 +501,13 @@ extern "C" int rr_doctok_emit_dev(rr_doctok* dt, const uint8_t* d_text, int64_t 
     RR_HIP_TRY(hipSetDevice(dt->device));
     const int64_t T = dt->T;
     const int64_t t1 = T > 0 ? T : 1;
-    rc = rr_dt_grow((void**)&dt->d_arena, &dt->cap_arena, text_bytes > 0 ? text_bytes : 1, 1, "rr_doctok_emit_dev");
+    rc = rr_grow((void**)&dt->d_arena, &dt->cap_arena, text_bytes > 0 ? text_bytes : 1, 1, "rr_doctok_emit_dev");
     if (rc == RR_OK && t1 > dt->cap_tok) {                    // the four token arrays grow together
         int64_t c0 = dt->cap_tok, c1 = dt->cap_tok, c2 = dt->cap_tok, c3 = dt->cap_tok;
-        rc = rr_dt_grow((void**)&dt->d_pos, &c0, t1, sizeof(int64_t), "rr_doctok_emit_dev");
-        if (rc == RR_OK) rc = rr_dt_grow((void**)&dt->d_len, &c1, t1, sizeof(int32_t), "rr_doctok_emit_dev");
-        if (rc == RR_OK) rc = rr_dt_grow((void**)&dt->d_hash, &c2, t1, sizeof(uint64_t), "rr_doctok_emit_dev");
-        if (rc == RR_OK) rc = rr_dt_grow((void**)&dt->d_slot, &c3, t1, sizeof(int64_t), "rr_doctok_emit_dev");
+        rc = rr_grow((void**)&dt->d_pos, &c0, t1, sizeof(int64_t), "rr_doctok_emit_dev");
+        if (rc == RR_OK) rc = rr_grow((void**)&dt->d_len, &c1, t1, sizeof(int32_t), "rr_doctok_emit_dev");
+        if (rc == RR_OK) rc = rr_grow((void**)&dt->d_hash, &c2, t1, sizeof(uint64_t), "rr_doctok_emit_dev");
+        if (rc == RR_OK) rc = rr_grow((void**)&dt->d_slot, &c3, t1, sizeof(int64_t), "rr_doctok_emit_dev");
         dt->cap_tok = rc == RR_OK ? t1 : 0;
         if (rc != RR_OK) {                                    // all or nothing
             hipFree(dt->d_pos); hipFree(dt->d_len); hipFree(dt->d_hash); hipFree(dt->d_slot);
@@ -645,8 +536,8 @@ extern "C" int rr_doctok_vocab_dev(rr_doctok* dt, int32_t hash_bits, int32_t* d_
     RR_HIP_TRY(hipSetDevice(dt->device));
     hipStream_t st = (hipStream_t)stream;
     const int64_t slots = 2 * T > 64 ? 2 * T : 64;            // twice the tokens: it cannot fill
-    int rc = rr_dt_grow((void**)&dt->d_table, &dt->cap_slots, slots, sizeof(unsigned long long), "rr_doctok_vocab_dev");
-    if (rc == RR_OK) rc = rr_dt_grow((void**)&dt->d_sums, &dt->cap_sums, T / RR_DT_CHUNK + 1, sizeof(int64_t), "rr_doctok_vocab_dev");
+    int rc = rr_grow((void**)&dt->d_table, &dt->cap_slots, slots, sizeof(unsigned long long), "rr_doctok_vocab_dev");
+    if (rc == RR_OK) rc = rr_grow((void**)&dt->d_sums, &dt->cap_sums, rr_scan_sums_len(T), sizeof(int64_t), "rr_doctok_vocab_dev");
     if (rc != RR_OK) return rc;
     dt->slots = slots;
     dt->vocab_done = false;
@@ -657,9 +548,9 @@ extern "C" int rr_doctok_vocab_dev(rr_doctok* dt, int32_t hash_bits, int32_t* d_
         RR_HIP_TRY(hipMemsetAsync(dt->d_table, 0xFF, sizeof(unsigned long long) * (size_t)slots, st));
         hipLaunchKernelGGL(rr_dt_insert, dim3(grid), dim3(256), 0, st, dt->d_arena, dt->d_pos, dt->d_len, dt->d_hash, T, hash_bits,
                            slots, dt->d_table, dt->d_slot, dt->d_ctl);
-        rr_dt_scan(rr_dt_f_first_len{dt->d_slot, dt->d_table, dt->d_len}, T, dt->d_sums, (int64_t*)nullptr, (int32_t*)nullptr,
+        rr_scan(rr_dt_f_first_len{dt->d_slot, dt->d_table, dt->d_len}, T, dt->d_sums, (int64_t*)nullptr, (int32_t*)nullptr,
                    dt->d_ctl + RR_DT_C_VBYTES, st);
-        rr_dt_scan(rr_dt_f_first{dt->d_slot, dt->d_table}, T, dt->d_sums, (int64_t*)nullptr, d_tok, dt->d_ctl + RR_DT_C_TERMS, st);
+        rr_scan(rr_dt_f_first{dt->d_slot, dt->d_table}, T, dt->d_sums, (int64_t*)nullptr, d_tok, dt->d_ctl + RR_DT_C_TERMS, st);
         hipLaunchKernelGGL(rr_dt_assign, dim3(grid), dim3(256), 0, st, dt->d_slot, dt->d_table, T, d_tok);
     }
     RR_HIP_TRY(hipGetLastError());
@@ -681,12 +572,12 @@ extern "C" int rr_doctok_copy_vocab(rr_doctok* dt, const int32_t* d_tok, uint8_t
     if (e == hipSuccess) e = hipMalloc((void**)&d_voc_off, sizeof(int64_t) * (size_t)(n + 1));
     if (e == hipSuccess) e = hipMalloc((void**)&d_bytes, (size_t)(vb > 0 ? vb : 1));
     int rc = RR_OK;
-    if (e == hipSuccess) rc = rr_dt_grow((void**)&dt->d_sums, &dt->cap_sums, n / RR_DT_CHUNK + 1, sizeof(int64_t), "rr_doctok_copy_vocab");
+    if (e == hipSuccess) rc = rr_grow((void**)&dt->d_sums, &dt->cap_sums, rr_scan_sums_len(n), sizeof(int64_t), "rr_doctok_copy_vocab");
     if (e == hipSuccess && rc == RR_OK) {
         hipStream_t st = nullptr;
         hipLaunchKernelGGL(rr_dt_term_pos, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, dt->d_slot, dt->d_table, d_tok, T, n,
                            d_term_pos);
-        rr_dt_scan(rr_dt_f_term_len{d_term_pos, dt->d_len}, n, dt->d_sums, d_voc_off, (int32_t*)nullptr, (int64_t*)nullptr, st);
+        rr_scan(rr_dt_f_term_len{d_term_pos, dt->d_len}, n, dt->d_sums, d_voc_off, (int32_t*)nullptr, (int64_t*)nullptr, st);
         hipLaunchKernelGGL(rr_dt_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dt->d_arena, dt->d_pos, dt->d_len,
                            d_term_pos, d_voc_off, n, vb, d_bytes);
         e = hipGetLastError();

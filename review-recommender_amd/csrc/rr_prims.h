@@ -1,0 +1,172 @@
+// rr_prims.h -- what the index builders share (rr_wordpiece.hip, rr_textprep.hip, rr_doctok.hip, rr_bm25_build.hip):
+// the workgroup scan, the device-wide scan, and the small helpers every builder needs once.
+#pragma once
+
+#include "rr_common.h"
+
+// ---------------------------------------------------------------- host helpers
+// Grows *p to `want` elements of `elem` bytes (the old contents are dropped; hipFree waits for the kernels that use them).
+static inline int rr_grow(void** p, int64_t* cap, int64_t want, size_t elem, const char* who) {
+    if (want <= *cap) return RR_OK;
+    if (*p) RR_HIP_TRY(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    if (hipMalloc(p, elem * (size_t)want) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        rr_set_error("%s: no memory for %lld x %zu bytes", who, (long long)want, elem);
+        return RR_E_NOMEM;
+    }
+    *cap = want;
+    return RR_OK;
+}
+
+// The documents whose offsets the kernels refused since the last call: waits for the device, reads the counter, clears it.
+static inline int rr_take_bad_docs(int32_t* d_bad, int32_t* out) {
+    RR_HIP_TRY(hipDeviceSynchronize());
+    RR_HIP_TRY(hipMemcpy(out, d_bad, 4, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemset(d_bad, 0, 4));
+    return RR_OK;
+}
+
+#ifdef __HIPCC__
+// ---------------------------------------------------------------- device helpers
+__device__ __forceinline__ uint64_t rr_mix64(uint64_t x) {             // murmur3's 64-bit finaliser
+    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
+    return x;
+}
+
+// Document `doc` of a packed text: its first byte and its length.  false = the offsets decrease or leave the text, and
+// nothing of it may be read.
+__device__ __forceinline__ bool rr_doc_span(const int64_t* __restrict__ text_off, int doc, int64_t text_bytes, int64_t* b0,
+                                            int64_t* len) {
+    const int64_t a = text_off[doc], b = text_off[doc + 1];
+    *b0 = a;
+    *len = b - a;
+    return a >= 0 && b >= a && b <= text_bytes;
+}
+
+// The character that starts at s[i] (i < len, s[i] not 10xxxxxx): its length in bytes and code point; 0 = malformed
+// (a byte that starts nothing, too few or wrong continuation bytes before s[len], overlong, surrogate, > 10FFFF).
+__device__ __forceinline__ int rr_utf8_decode(const uint8_t* s, int i, int len, uint32_t* cp) {
+    const uint32_t b = s[i];
+    if (b < 0x80u) { *cp = b; return 1; }
+    int n;
+    uint32_t c, lowest;
+    if (b >= 0xC2u && b <= 0xDFu) { n = 2; c = b & 0x1Fu; lowest = 0x80u; }
+    else if ((b & 0xF0u) == 0xE0u) { n = 3; c = b & 0x0Fu; lowest = 0x800u; }
+    else if (b >= 0xF0u && b <= 0xF4u) { n = 4; c = b & 0x07u; lowest = 0x10000u; }
+    else return 0;
+    if (i + n > len) return 0;
+    for (int k = 1; k < n; ++k) {
+        const uint32_t t = s[i + k];
+        if ((t & 0xC0u) != 0x80u) return 0;
+        c = (c << 6) | (t & 0x3Fu);
+    }
+    if (c < lowest || c > 0x10FFFFu || (c >= 0xD800u && c <= 0xDFFFu)) return 0;
+    *cp = c;
+    return n;
+}
+
+// ---------------------------------------------------------------- the workgroup scan
+// Exclusive sum of one T (int or long long) per thread over a workgroup of NT threads; *total = the sum, in every thread.
+// Every thread of the workgroup calls it.  wave_sums: LDS [NT / 64]; the leading barrier lets back-to-back calls share it.
+template <typename T, int NT>
+__device__ __forceinline__ T rr_block_scan(T v, T* wave_sums, T* total) {
+    static_assert(NT % 64 == 0 && NT >= 64 && NT <= 1024, "a workgroup of whole waves");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    __syncthreads();                       // (wave_sums may still be read from the previous scan)
+    if (lane == 63) wave_sums[wave] = incl;
+    __syncthreads();
+    T before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) {
+        const T s = wave_sums[w];
+        before += w < wave ? s : 0;
+        all += s;
+    }
+    *total = all;
+    return before + incl - v;
+}
+
+// ---------------------------------------------------------------- the device-wide scan
+// Exclusive int64 scan of f(0) .. f(n - 1): rr_scan_sum (a sum per chunk of RR_SCAN_CHUNK elements, one workgroup each),
+// rr_scan_sums (one workgroup scans the chunk sums in place), rr_scan_apply (every chunk again, from its sum onwards).
+#define RR_SCAN_CHUNK 4096
+
+static inline int64_t rr_scan_sums_len(int64_t n) { return n / RR_SCAN_CHUNK + 1; }   // the `sums` rr_scan needs for n elements
+
+template <class F>
+__global__ __launch_bounds__(256) void rr_scan_sum(F f, int64_t n, int64_t* __restrict__ sums) {
+    __shared__ long long s_ws[4];
+    const int64_t c0 = (int64_t)blockIdx.x * RR_SCAN_CHUNK;
+    long long v = 0;
+    for (int r = 0; r < RR_SCAN_CHUNK / 256; ++r) {
+        const int64_t i = c0 + r * 256 + threadIdx.x;
+        if (i < n) v += f(i);
+    }
+    long long total;
+    rr_block_scan<long long, 256>(v, s_ws, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+template <int NT>   // (a template, so that only the sources that scan carry the kernel)
+__global__ __launch_bounds__(NT) void rr_scan_sums(int64_t* __restrict__ sums, int64_t nb, int64_t* __restrict__ total_out) {
+    __shared__ long long s_ws[NT / 64];
+    long long carry = 0;
+    for (int64_t base = 0; base < nb; base += NT) {
+        const int64_t i = base + threadIdx.x;
+        const long long v = i < nb ? sums[i] : 0;
+        long long total;
+        const long long at = rr_block_scan<long long, NT>(v, s_ws, &total);
+        if (i < nb) sums[i] = carry + at;
+        carry += total;
+    }
+    if (threadIdx.x == 0 && total_out) *total_out = carry;
+}
+
+// out64[i] / out32[i] = the exclusive sum in front of element i; out64[n] = the total.  (No __restrict__ on the outputs:
+// see rr_scan.)
+template <class F>
+__global__ __launch_bounds__(256) void rr_scan_apply(F f, int64_t n, const int64_t* __restrict__ sums, int64_t nb, int64_t* out64,
+                                                     int32_t* out32) {
+    __shared__ long long s_ws[4];
+    const int64_t c0 = (int64_t)blockIdx.x * RR_SCAN_CHUNK;
+    long long carry = sums[blockIdx.x];
+    for (int r = 0; r < RR_SCAN_CHUNK / 256; ++r) {
+        const int64_t i = c0 + r * 256 + threadIdx.x;
+        const long long v = i < n ? f(i) : 0;
+        long long total;
+        const long long at = rr_block_scan<long long, 256>(v, s_ws, &total);
+        if (i < n) {
+            if (out64) out64[i] = carry + at;
+            if (out32) out32[i] = (int32_t)(carry + at);
+        }
+        carry += total;
+    }
+    if (out64 && blockIdx.x == nb - 1 && threadIdx.x == 0) out64[n] = carry;
+}
+
+// Exclusive scan of f over [0, n) on `st`: out64 [n + 1] and / or out32 [n] (either may be NULL), *total (may be NULL);
+// `sums`: rr_scan_sums_len(n) words of the caller's.  An output may be the array f reads: a thread writes only the element
+// it has just read, every read of rr_scan_sum is over before rr_scan_apply starts, and out64[n] lies behind the input.
+template <class F>
+static void rr_scan(F f, int64_t n, int64_t* sums, int64_t* out64, int32_t* out32, int64_t* total, hipStream_t st) {
+    const int64_t nb = (n + RR_SCAN_CHUNK - 1) / RR_SCAN_CHUNK;
+    if (nb == 0) {
+        if (out64) hipMemsetAsync(out64, 0, sizeof(int64_t), st);
+        if (total) hipMemsetAsync(total, 0, sizeof(int64_t), st);
+        return;
+    }
+    hipLaunchKernelGGL(rr_scan_sum<F>, dim3((unsigned)nb), dim3(256), 0, st, f, n, sums);
+    hipLaunchKernelGGL(rr_scan_sums<1024>, dim3(1), dim3(1024), 0, st, sums, nb, total);
+    if (out64 || out32) hipLaunchKernelGGL(rr_scan_apply<F>, dim3((unsigned)nb), dim3(256), 0, st, f, n, sums, nb, out64, out32);
+}
+
+#endif  // __HIPCC__

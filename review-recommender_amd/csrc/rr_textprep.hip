@@ -27,7 +27,7 @@
 //                 on which of them claimed it.
 // rr_tp_rank      survivors' ranks and byte offsets (one workgroup, chunks of 1024, as rr_wp_scan).
 // rr_tp_gather    one workgroup per survivor copies its text behind its predecessor's.
-#include "rr_common.h"
+#include "rr_prims.h"
 
 #define RR_TP_THREADS 256
 #define RR_TP_PER 16                                   // consecutive bytes per thread
@@ -47,51 +47,6 @@ struct rr_textprep {
 __device__ __forceinline__ bool rr_tp_is_space(uint32_t c) {          // str.isspace() == re's \s for str patterns
     return (c >= 0x09u && c <= 0x0Du) || (c >= 0x1Cu && c <= 0x20u) || c == 0x85u || c == 0xA0u || c == 0x1680u ||
            (c >= 0x2000u && c <= 0x200Au) || c == 0x2028u || c == 0x2029u || c == 0x202Fu || c == 0x205Fu || c == 0x3000u;
-}
-
-// The character that starts at s[i] (i < len, s[i] not 10xxxxxx): its length in bytes and code point; 0 = malformed
-// (a byte that starts nothing, too few or wrong continuation bytes before the document's end, overlong, surrogate, > 10FFFF).
-__device__ __forceinline__ int rr_tp_decode(const uint8_t* s, int i, int len, uint32_t* cp) {
-    const uint32_t b = s[i];
-    if (b < 0x80u) { *cp = b; return 1; }
-    int n;
-    uint32_t c, lowest;
-    if (b >= 0xC2u && b <= 0xDFu) { n = 2; c = b & 0x1Fu; lowest = 0x80u; }
-    else if ((b & 0xF0u) == 0xE0u) { n = 3; c = b & 0x0Fu; lowest = 0x800u; }
-    else if (b >= 0xF0u && b <= 0xF4u) { n = 4; c = b & 0x07u; lowest = 0x10000u; }
-    else return 0;
-    if (i + n > len) return 0;
-    for (int k = 1; k < n; ++k) {
-        const uint32_t t = s[i + k];
-        if ((t & 0xC0u) != 0x80u) return 0;
-        c = (c << 6) | (t & 0x3Fu);
-    }
-    if (c < lowest || c > 0x10FFFFu || (c >= 0xD800u && c <= 0xDFFFu)) return 0;
-    *cp = c;
-    return n;
-}
-
-// Exclusive sum of one int per thread over the workgroup; *total = the sum, in every thread (rr_wp_block_scan's twin).
-__device__ __forceinline__ int rr_tp_block_scan(int v, int* wave_sums, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    __syncthreads();                       // (wave_sums may still be read from the previous scan)
-    if (lane == 63) wave_sums[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < RR_TP_THREADS / 64; ++w) {
-        const int s = wave_sums[w];
-        before += w < wave ? s : 0;
-        all += s;
-    }
-    *total = all;
-    return before + incl - v;
 }
 
 // s[p .. p + m) equals the lower-case ASCII literal `lit`, letters A-Z of s folded; false when it would leave s[0 .. n).
@@ -114,26 +69,26 @@ __global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_clean(
     __shared__ int s_end, s_cps, s_claimed, s_umin, s_umax, s_emin, s_fmax;
     const int tid = threadIdx.x;
     const int doc = blockIdx.x;
-    const int64_t b0 = text_off[doc], b1 = text_off[doc + 1];
-    if (b0 < 0 || b1 < b0 || b1 > text_bytes) {            // offsets that leave the text: nothing is read, no text is written
+    int64_t b0, len64;
+    if (!rr_doc_span(text_off, doc, text_bytes, &b0, &len64)) {   // offsets that leave the text: nothing is read, no text is written
         if (tid == 0) {
             out_len[doc] = 0; status[doc] = RR_TP_NEEDS_HOST;
             atomicAdd(bad, 1);
         }
         return;
     }
-    if (b1 - b0 > RR_TP_WINDOW) {                          // longer than the window: the host cleans it
+    if (len64 > RR_TP_WINDOW) {                          // longer than the window: the host cleans it
         if (tid == 0) { out_len[doc] = 0; status[doc] = RR_TP_NEEDS_HOST; }
         return;
     }
-    const int len = (int)(b1 - b0);
+    const int len = (int)len64;
     const uint8_t* src = text + b0;
     for (int i = tid; i < len; i += RR_TP_THREADS) s_raw[i] = src[i];
     if (tid == 0) { s_end = 0; s_cps = 0; s_claimed = 0; s_umin = RR_TP_WINDOW; s_umax = -1; s_emin = RR_TP_WINDOW; s_fmax = -1; }
     __syncthreads();
 
     uint32_t first = 0;
-    const int phantom = (len > 0 && (s_raw[0] & 0xC0u) != 0x80u && rr_tp_decode(s_raw, 0, len, &first) && rr_tp_is_space(first)) ? 1 : 0;
+    const int phantom = (len > 0 && (s_raw[0] & 0xC0u) != 0x80u && rr_utf8_decode(s_raw, 0, len, &first) && rr_tp_is_space(first)) ? 1 : 0;
     int carry_cp = 0, carry_by = 0;                        // emitted before this tile (the same in every thread)
     int malformed = 0, hard = 0, claimed = 0, my_end = 0, my_cps = 0;
     for (int base = 0; base < len; base += RR_TP_TILE) {
@@ -144,7 +99,7 @@ __global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_clean(
             int k = i0 - 1;
             for (int back = 0; back < 3 && k > 0 && (s_raw[k] & 0xC0u) == 0x80u; ++back) --k;
             uint32_t c;
-            prev_ws = (s_raw[k] & 0xC0u) != 0x80u && rr_tp_decode(s_raw, k, len, &c) && rr_tp_is_space(c);
+            prev_ws = (s_raw[k] & 0xC0u) != 0x80u && rr_utf8_decode(s_raw, k, len, &c) && rr_tp_is_space(c);
         }
         uint8_t info[RR_TP_PER];                           // bytes to emit (0 = none) | 8 = a space in front
         int packed = 0;                                    // code points << 16 | bytes of this slice
@@ -154,7 +109,7 @@ __global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_clean(
             info[j] = 0;
             if (i < len && (s_raw[i] & 0xC0u) != 0x80u) {
                 uint32_t c;
-                const int n = rr_tp_decode(s_raw, i, len, &c);
+                const int n = rr_utf8_decode(s_raw, i, len, &c);
                 if (n == 0) { malformed = 1; prev_ws = false; }
                 else {
                     claimed += n;
@@ -169,7 +124,7 @@ __global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_clean(
             }
         }
         int total;
-        int at = rr_tp_block_scan(packed, s_ws, &total);
+        int at = rr_block_scan<int, RR_TP_THREADS>(packed, s_ws, &total);
         int g_cp = carry_cp + (at >> 16), g_by = carry_by + (at & 0xFFFF);
 #pragma unroll
         for (int j = 0; j < RR_TP_PER; ++j) {
@@ -251,11 +206,6 @@ __global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_clean(
 }
 
 // ------------------------------------------------------------------------------------------------ dedup
-__device__ __forceinline__ uint64_t rr_tp_mix(uint64_t x) {            // murmur3's 64-bit finaliser
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
-    return x;
-}
-
 __global__ __launch_bounds__(256) void rr_tp_insert(
     const uint8_t* __restrict__ text, int64_t text_bytes, const int64_t* __restrict__ text_off, const int32_t* __restrict__ lens,
     const int32_t* __restrict__ group, const int32_t* __restrict__ status, int32_t n_docs, int32_t hash_bits, uint32_t mask,
@@ -277,11 +227,11 @@ __global__ __launch_bounds__(256) void rr_tp_insert(
     for (int c = lane; 8 * c < len; c += 64) {
         uint64_t w = 0;
         for (int k = 0; k < 8 && 8 * c + k < len; ++k) w |= (uint64_t)p[8 * c + k] << (8 * k);
-        h += rr_tp_mix(w + (uint64_t)(c + 1) * 0x9E3779B97F4A7C15ull);
+        h += rr_mix64(w + (uint64_t)(c + 1) * 0x9E3779B97F4A7C15ull);
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) h += __shfl_xor(h, m, 64);
-    h = rr_tp_mix(h ^ rr_tp_mix(((uint64_t)(uint32_t)g << 32) | (uint32_t)len));
+    h = rr_mix64(h ^ rr_mix64(((uint64_t)(uint32_t)g << 32) | (uint32_t)len));
     if (hash_bits < 64) h &= (1ull << hash_bits) - 1;       // tests: almost every probe collides
     uint32_t slot = (uint32_t)h & mask;
     for (;;) {
@@ -314,41 +264,24 @@ __global__ void rr_tp_mark(const int32_t* __restrict__ slot_of, const int32_t* _
 __global__ __launch_bounds__(1024) void rr_tp_rank(const int32_t* __restrict__ status, const int32_t* __restrict__ lens, int32_t n_docs,
                                                    int32_t* __restrict__ rank, int64_t* __restrict__ out_off,
                                                    int32_t* __restrict__ src_row, int64_t* __restrict__ count) {
-    __shared__ int s_c[16];
-    __shared__ long long s_b[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ long long s_ws[16];
+    const int tid = threadIdx.x;
+    const long long bytes_mask = (1ll << 48) - 1;          // one scan of survivors << 48 | bytes: a chunk's bytes stay below 2^41
     int carry_c = 0;
     long long carry_b = 0;
     for (int64_t base = 0; base < n_docs; base += 1024) {
         const int64_t i = base + tid;
         const bool keep = i < n_docs && status[i] == 0;
-        const int c = keep ? 1 : 0;
         const long long b = keep ? (lens[i] > 0 ? lens[i] : 0) : 0;
-        int ic = c;
-        long long ib = b;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int tc = __shfl_up(ic, d, 64);
-            const long long tb = __shfl_up(ib, d, 64);
-            if (lane >= d) { ic += tc; ib += tb; }
-        }
-        __syncthreads();
-        if (lane == 63) { s_c[wave] = ic; s_b[wave] = ib; }
-        __syncthreads();
-        int before_c = 0, all_c = 0;
-        long long before_b = 0, all_b = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            before_c += w < wave ? s_c[w] : 0; all_c += s_c[w];
-            before_b += w < wave ? s_b[w] : 0; all_b += s_b[w];
-        }
+        long long all;
+        const long long at = rr_block_scan<long long, 1024>(((long long)keep << 48) | b, s_ws, &all);
         if (i < n_docs) {
-            const int r = carry_c + before_c + ic - c;
+            const int r = carry_c + (int)(at >> 48);
             rank[i] = keep ? r : -1;
-            if (keep) { out_off[r] = carry_b + before_b + ib - b; src_row[r] = (int32_t)i; }
+            if (keep) { out_off[r] = carry_b + (at & bytes_mask); src_row[r] = (int32_t)i; }
         }
-        carry_c += all_c;
-        carry_b += all_b;
+        carry_c += (int)(all >> 48);
+        carry_b += all & bytes_mask;
     }
     if (tid == 0) { out_off[carry_c] = carry_b; count[0] = carry_c; count[1] = carry_b; }
 }
@@ -402,20 +335,6 @@ extern "C" int rr_textprep_limits(int32_t* out_window, int32_t* out_tile, int32_
     return RR_OK;
 }
 
-static int rr_tp_scratch(rr_textprep* tp, int64_t words, const char* who) {
-    if (words <= tp->cap_words) return RR_OK;
-    if (tp->d_scratch) RR_HIP_TRY(hipFree(tp->d_scratch));   // (waits for the kernels that use the old one)
-    tp->d_scratch = nullptr;
-    tp->cap_words = 0;
-    if (hipMalloc((void**)&tp->d_scratch, sizeof(int32_t) * (size_t)words) != hipSuccess) {
-        (void)hipGetLastError();
-        rr_set_error("%s: no memory for %lld scratch words", who, (long long)words);
-        return RR_E_NOMEM;
-    }
-    tp->cap_words = words;
-    return RR_OK;
-}
-
 extern "C" int rr_textprep_clean_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
                                      int32_t n_docs, int32_t spam, uint8_t* d_out, int32_t* d_out_len, int32_t* d_status,
                                      void* stream) {
@@ -435,11 +354,9 @@ extern "C" int rr_textprep_status(rr_textprep* tp, int32_t* out_bad_docs) {
     RR_REQUIRE(tp && out_bad_docs, "rr_textprep_status: NULL argument");
     std::lock_guard<std::mutex> lk(tp->mu);
     RR_HIP_TRY(hipSetDevice(tp->device));
-    RR_HIP_TRY(hipDeviceSynchronize());
-    int32_t bad = 0;
-    RR_HIP_TRY(hipMemcpy(&bad, tp->d_bad, 4, hipMemcpyDeviceToHost));
-    RR_HIP_TRY(hipMemset(tp->d_bad, 0, 4));
-    *out_bad_docs = bad;
+    const int rc = rr_take_bad_docs(tp->d_bad, out_bad_docs);
+    if (rc != RR_OK) return rc;
+    const int32_t bad = *out_bad_docs;
     RR_REQUIRE(bad == 0, "rr_textprep_status: %d document(s) had text offsets that decrease or leave the text (no text was "
                "read or written for them)", bad);
     return RR_OK;
@@ -457,7 +374,7 @@ extern "C" int rr_textprep_dedup_dev(rr_textprep* tp, const uint8_t* d_text, int
     while (slots < 2 * (int64_t)n_docs) slots <<= 1;
     std::lock_guard<std::mutex> lk(tp->mu);
     RR_HIP_TRY(hipSetDevice(tp->device));
-    int rc = rr_tp_scratch(tp, 2 * slots + n_docs, "rr_textprep_dedup_dev");
+    int rc = rr_grow((void**)&tp->d_scratch, &tp->cap_words, 2 * slots + n_docs, sizeof(int32_t), "rr_textprep_dedup_dev");
     if (rc != RR_OK) return rc;
     int32_t *rep = tp->d_scratch, *minimum = rep + slots, *slot_of = minimum + slots;
     hipStream_t st = (hipStream_t)stream;
@@ -479,7 +396,7 @@ extern "C" int rr_textprep_compact_dev(rr_textprep* tp, const uint8_t* d_text, i
     RR_REQUIRE((d_text && d_out_text) || text_bytes == 0 || out_bytes == 0, "rr_textprep_compact_dev: NULL text");
     std::lock_guard<std::mutex> lk(tp->mu);
     RR_HIP_TRY(hipSetDevice(tp->device));
-    int rc = rr_tp_scratch(tp, n_docs > 0 ? n_docs : 1, "rr_textprep_compact_dev");
+    int rc = rr_grow((void**)&tp->d_scratch, &tp->cap_words, n_docs > 0 ? n_docs : 1, sizeof(int32_t), "rr_textprep_compact_dev");
     if (rc != RR_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(rr_tp_rank, dim3(1), dim3(1024), 0, st, d_status, d_len, n_docs, tp->d_scratch, d_out_off, d_src_row, d_count);

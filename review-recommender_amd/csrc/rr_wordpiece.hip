@@ -25,7 +25,7 @@
 // rr_wp_pack       scratch rows -> packed token / type / position ids.
 #include <vector>
 
-#include "rr_common.h"
+#include "rr_prims.h"
 
 #define RR_WP_THREADS 256
 #define RR_WP_PER 16                                   // bytes per thread of the window
@@ -282,29 +282,6 @@ __device__ __forceinline__ int rr_wp_class(unsigned c) {
     return 3;
 }
 
-// Exclusive sum of one int per thread over the workgroup (RR_WP_THREADS = 4 waves); *total = the sum, in every thread.
-__device__ __forceinline__ int rr_wp_block_scan(int v, int* wave_sums, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    __syncthreads();                       // (wave_sums may still be read from the previous scan)
-    if (lane == 63) wave_sums[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < RR_WP_THREADS / 64; ++w) {
-        const int s = wave_sums[w];
-        before += w < wave ? s : 0;
-        all += s;
-    }
-    *total = all;
-    return before + incl - v;
-}
-
 __device__ __forceinline__ int rr_wp_lookup(const rr_wp_entry* __restrict__ table, uint32_t mask, const uint8_t* __restrict__ bytes,
                                             uint32_t hash, int len, int form, const uint8_t* word /* LDS */) {
     const int32_t lf = len | (form << 16);
@@ -338,15 +315,14 @@ __global__ __launch_bounds__(RR_WP_THREADS) void rr_wp_tokenize(
     const int tid = threadIdx.x;
     const int doc = blockIdx.x;
     int32_t* row = rows + (int64_t)doc * max_length;
-    const int64_t b0 = text_off[doc], b1 = text_off[doc + 1];
-    if (b0 < 0 || b1 < b0 || b1 > text_bytes) {            // offsets that leave the text: nothing is read (rr_wp_status reports it)
+    int64_t b0, len;
+    if (!rr_doc_span(text_off, doc, text_bytes, &b0, &len)) {   // offsets that leave the text: nothing is read (rr_wp_status reports it)
         if (tid == 0) {
             row[0] = cls; row[1] = sep; lens[doc] = 2; needs_host[doc] = 1;
             atomicAdd(bad, 1);
         }
         return;
     }
-    const int64_t len = b1 - b0;
     const uint8_t* src = text + b0;
     if (tid <= max_chars) {
         uint32_t p = 1;
@@ -373,7 +349,7 @@ __global__ __launch_bounds__(RR_WP_THREADS) void rr_wp_tokenize(
         keep += (i < wlen && rr_wp_class(c) != 0) ? 1 : 0;
     }
     int n = 0;
-    int at = rr_wp_block_scan(keep, s_ws, &n);
+    int at = rr_block_scan<int, RR_WP_THREADS>(keep, s_ws, &n);
 #pragma unroll
     for (int j = 0; j < RR_WP_PER; ++j) {
         const int i = tid * RR_WP_PER + j;
@@ -440,7 +416,7 @@ __global__ __launch_bounds__(RR_WP_THREADS) void rr_wp_tokenize(
         mine += (i < n && s_pf[i]) ? 1 : 0;
     }
     int total = 0;
-    int rank = rr_wp_block_scan(mine, s_ws, &total);
+    int rank = rr_block_scan<int, RR_WP_THREADS>(mine, s_ws, &total);
     const int room = max_length - 2;
     if (cut && total < room) {                           // the window was not enough to fill the sequence
         if (tid == 0) { row[0] = cls; row[1] = sep; lens[doc] = 2; needs_host[doc] = 1; }
@@ -503,18 +479,8 @@ __device__ __forceinline__ int rr_wpu_char_at(const uint8_t* raw, int i, int wle
         if (need <= k) *flags |= 1;
         return 0;
     }
-    const int len = b >= 0xF0u ? 4 : b >= 0xE0u ? 3 : 2;
-    if (b < 0xC2u || b > 0xF4u || i + len > wlen) { *flags |= 1; return 0; }
-    uint32_t cp = b & (0xFFu >> (len + 1));
-    for (int j = 1; j < len; ++j) {
-        const unsigned c = raw[i + j];
-        if ((c & 0xC0u) != 0x80u) { *flags |= 1; return 0; }
-        cp = (cp << 6) | (c & 0x3Fu);
-    }
-    if ((len == 3 && cp < 0x800u) || (len == 4 && cp < 0x10000u) || cp > 0x10FFFFu || (cp >= 0xD800u && cp <= 0xDFFFu)) {
-        *flags |= 1;                                    // overlong, beyond Unicode, a surrogate
-        return 0;
-    }
+    uint32_t cp;
+    if (!rr_utf8_decode(raw, i, wlen, &cp)) { *flags |= 1; return 0; }
     const uint32_t e = st2[(uint32_t)st1[cp >> 7] * RR_WPU_BLOCK + (cp & (RR_WPU_BLOCK - 1))];
     const unsigned cls = e & 7u;
     if (cls == RR_WPU_HARD) { *flags |= 2; return 0; }
@@ -557,15 +523,14 @@ __global__ __launch_bounds__(RR_WP_THREADS) void rr_wp_tokenize_utf8(
     const int tid = threadIdx.x;
     const int doc = blockIdx.x;
     int32_t* row = rows + (int64_t)doc * max_length;
-    const int64_t b0 = text_off[doc], b1 = text_off[doc + 1];
-    if (b0 < 0 || b1 < b0 || b1 > text_bytes) {            // offsets that leave the text: nothing is read (rr_wp_status reports it)
+    int64_t b0, len;
+    if (!rr_doc_span(text_off, doc, text_bytes, &b0, &len)) {   // offsets that leave the text: nothing is read (rr_wp_status reports it)
         if (tid == 0) {
             row[0] = cls; row[1] = sep; lens[doc] = 2; needs_host[doc] = 1;
             atomicAdd(bad, 1);
         }
         return;
     }
-    const int64_t len = b1 - b0;
     const uint8_t* src = text + b0;
     for (int k = tid; k <= 4 * max_chars; k += RR_WP_THREADS) {     // base^k by squaring
         uint32_t p = 1, q = RR_WP_BASE;
@@ -600,7 +565,7 @@ __global__ __launch_bounds__(RR_WP_THREADS) void rr_wp_tokenize_utf8(
         return;
     }
     int n = 0;
-    int at = rr_wp_block_scan(mine, s_ws, &n);
+    int at = rr_block_scan<int, RR_WP_THREADS>(mine, s_ws, &n);
     if (n > RR_WP_WINDOW) {                                // the mapped text does not fit the LDS buffers
         if (tid == 0) { row[0] = cls; row[1] = sep; lens[doc] = 2; needs_host[doc] = 1; }
         return;
@@ -702,7 +667,7 @@ __global__ __launch_bounds__(RR_WP_THREADS) void rr_wp_tokenize_utf8(
         mine += (i < n && s_pf[i]) ? 1 : 0;
     }
     int total = 0;
-    int rank = rr_wp_block_scan(mine, s_ws, &total);
+    int rank = rr_block_scan<int, RR_WP_THREADS>(mine, s_ws, &total);
     const int room = max_length - 2;
     if (cut && total < room) {                           // the window was not enough to fill the sequence
         if (tid == 0) { row[0] = cls; row[1] = sep; lens[doc] = 2; needs_host[doc] = 1; }
@@ -736,22 +701,9 @@ __global__ __launch_bounds__(1024) void rr_wp_scan(const int32_t* __restrict__ l
         const int i = base + tid;
         const int v = i < n_docs ? lens[i] : 0;
         longest = v > longest ? v : longest;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += t;
-        }
-        __syncthreads();
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            before += w < wave ? s_w[w] : 0;
-            all += s_w[w];
-        }
-        if (i < n_docs) cu[i + 1] = carry + before + incl;
+        int all;
+        const int at = rr_block_scan<int, 1024>(v, s_w, &all);
+        if (i < n_docs) cu[i + 1] = carry + at + v;
         carry += all;
     }
 #pragma unroll
@@ -804,17 +756,9 @@ extern "C" int rr_wp_encode_dev(rr_wp* wp, const uint8_t* d_text, int64_t text_b
     std::lock_guard<std::mutex> lk(wp->mu);
     RR_HIP_TRY(hipSetDevice(wp->device));
     const int64_t words = (int64_t)n_docs * max_length + n_docs;
-    if (words > wp->cap_words) {          // grown on the first call of a size (hipFree waits for the kernels that use the old one)
-        if (wp->d_rows) RR_HIP_TRY(hipFree(wp->d_rows));
-        wp->d_rows = nullptr;
-        wp->cap_words = 0;
-        if (hipMalloc((void**)&wp->d_rows, sizeof(int32_t) * (size_t)words) != hipSuccess) {
-            (void)hipGetLastError();
-            rr_set_error("rr_wp_encode_dev: no memory for %lld scratch words", (long long)words);
-            return RR_E_NOMEM;
-        }
-        wp->cap_words = words;
-    }
+    // grown on the first call of a size
+    const int rc = rr_grow((void**)&wp->d_rows, &wp->cap_words, words, sizeof(int32_t), "rr_wp_encode_dev");
+    if (rc != RR_OK) return rc;
     int32_t* d_lens = wp->d_rows + (int64_t)n_docs * max_length;
     hipStream_t st = (hipStream_t)stream;
     if (wp->d_st1)                        // a UTF-8 handle (rr_wp_create_utf8)
@@ -836,11 +780,9 @@ extern "C" int rr_wp_status(rr_wp* wp, int32_t* out_bad_docs) {
     RR_REQUIRE(wp && out_bad_docs, "rr_wp_status: NULL argument");
     std::lock_guard<std::mutex> lk(wp->mu);
     RR_HIP_TRY(hipSetDevice(wp->device));
-    RR_HIP_TRY(hipDeviceSynchronize());
-    int32_t bad = 0;
-    RR_HIP_TRY(hipMemcpy(&bad, wp->d_bad, 4, hipMemcpyDeviceToHost));
-    RR_HIP_TRY(hipMemset(wp->d_bad, 0, 4));
-    *out_bad_docs = bad;
+    const int rc = rr_take_bad_docs(wp->d_bad, out_bad_docs);
+    if (rc != RR_OK) return rc;
+    const int32_t bad = *out_bad_docs;
     RR_REQUIRE(bad == 0, "rr_wp_status: %d document(s) had text offsets that decrease or leave the text (they were answered "
                "[CLS] [SEP] with needs_host = 1)", bad);
     return RR_OK;

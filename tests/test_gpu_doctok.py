@@ -141,6 +141,26 @@ def test_many_terms_race_for_slots(dt):
     assert len(vocab) > 45_000
 
 
+@pytest.mark.parametrize("n_docs, planted", [
+    (4095, {0: 0, 4094: 2}),                                          # T = 4095
+    (4096, {0: 0, 4095: 2}),                                          # T = 4096: the token scans end on a chunk's last element
+    (4097, {0: 0, 4095: 2}),                                          # T = 4097: ... and one element into the next chunk
+    (4097, {0: 2, 4095: 0, 4096: 2}),
+    (8193, {0: 2, 4095: 0, 4096: 2, 8191: 0, 8192: 2}),
+])
+def test_documents_and_tokens_at_the_edges_of_the_scan_chunks(dt, n_docs, planted):
+    """The device-wide scan (rr_scan: tokens per document -> doc_off, first appearances -> ids) works in chunks of 4096
+    elements: documents of one kept token, with empty and two-token documents on either side of a chunk's edge."""
+    docs = ["w%d" % (i % 300) for i in range(n_docs)]
+    for i, k in planted.items():
+        docs[i] = " ".join("p%dx%d" % (i, j) for j in range(k))
+    counts = np.ones(n_docs, dtype=np.int64)
+    counts[list(planted)] = list(planted.values())
+    tok, off, vocab = check(dt, docs)                                 # ids and vocabulary = factorize_corpus
+    assert np.array_equal(off, np.concatenate([[0], np.cumsum(counts)]))
+    assert len(tok) == counts.sum() and len(vocab) == min(300, n_docs - len(planted)) + sum(planted.values())
+
+
 def test_bad_offsets_are_refused_and_change_nothing(dt):
     docs = raw(["alpha beta", "gamma delta epsilon", "zeta"])
     check(dt, docs)

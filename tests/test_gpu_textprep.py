@@ -192,24 +192,17 @@ def test_dedup_equals_drop_duplicates(tp):
         tp.dedup(d_text.data_ptr(), len(blob) - 1, d_off.data_ptr(), d_len.data_ptr(), d_grp.data_ptr(), d_st.data_ptr(), n, 0, st)
 
 
-@pytest.mark.parametrize("case", ["mixed", "all dropped", "none dropped", "only the last kept"])
-def test_compact_equals_the_host(tp, case):
+def check_compact(tp, texts, status):
+    """rr_textprep_compact_dev against numpy: counts, offsets (a cumsum of the kept lengths), src_row and the gathered text
+    (every survivor at its rank)."""
     import torch
-    texts, _, status = dedup_world(seed=6, n=1500)
-    if case == "all dropped":
-        status[:] = T.SHORT
-    elif case == "none dropped":
-        status[:] = 0
-    elif case == "only the last kept":
-        status[:] = T.DUP
-        status[-1] = 0
     n = len(texts)
     blob, off = slots_of(texts, 2)
     lens = np.array([len(t) for t in texts], dtype=np.int32)
     keep = np.flatnonzero(status == 0)
     want_text = b"".join(texts[i] for i in keep)
     want_off = np.concatenate([[0], np.cumsum(lens[keep], dtype=np.int64)])
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a if len(a) else np.zeros(1, a.dtype))).cuda()   # (no NULL for n = 0)
     d_text, d_off, d_len, d_st = dev(blob), dev(off), dev(lens), dev(status.astype(np.int32))
     o_text = torch.full((len(want_text) + 8,), 0xEE, dtype=torch.uint8, device="cuda")
     o_off = torch.full((n + 1,), -1, dtype=torch.int64, device="cuda")
@@ -225,6 +218,30 @@ def test_compact_equals_the_host(tp, case):
     assert np.array_equal(o_src.cpu().numpy()[:m], keep) and (o_src.cpu().numpy()[m:] == -1).all()
     got = o_text.cpu().numpy()
     assert got[:len(want_text)].tobytes() == want_text and (got[len(want_text):] == 0xEE).all()
+
+
+@pytest.mark.parametrize("case", ["mixed", "all dropped", "none dropped", "only the last kept"])
+def test_compact_equals_the_host(tp, case):
+    texts, _, status = dedup_world(seed=6, n=1500)
+    if case == "all dropped":
+        status[:] = T.SHORT
+    elif case == "none dropped":
+        status[:] = 0
+    elif case == "only the last kept":
+        status[:] = T.DUP
+        status[-1] = 0
+    check_compact(tp, texts, status)
+
+
+@pytest.mark.parametrize("n", [0, 1, 1023, 1024, 1025, 2049])
+def test_compact_at_the_edges_of_the_scan_chunks(tp, n):
+    """The ranking kernel scans the documents in chunks of 1024 and carries (count, bytes) from chunk to chunk: no document,
+    one, a chunk less one, a full chunk, one more, and two chunks and one.  Every third document is dropped."""
+    rng = np.random.default_rng(100 + n)
+    texts = [rng.integers(97, 123, int(rng.integers(0, 12)), dtype=np.uint8).tobytes() for _ in range(n)]
+    status = np.zeros(n, dtype=np.int32)
+    status[2::3] = [T.SHORT, T.SPAM, T.DUP, T.NEEDS_HOST][n % 4]
+    check_compact(tp, texts, status)
 
 
 def test_review_index_from_device_rows_equals_the_host_one(hip):

@@ -133,6 +133,25 @@ def test_random_ascii_documents_equal_the_host_tokenizer():
         assert_equals_host(got, cut(tok, full, L), f"random documents, max_length {L}")
 
 
+@pytest.mark.parametrize("n_docs", [1, 1023, 1024, 1025, 2049])
+def test_cu_seqlens_at_the_edges_of_the_scan_chunks(n_docs):
+    """rr_wp_scan sums the lengths in chunks of 1024 documents and keeps the longest: documents of one to three short
+    words on either side of a chunk's edge, the longest one last."""
+    fx = json.loads((GOLDEN / "wp_ascii.json").read_text())
+    tok = WordPieceTokenizer({w: i for i, w in enumerate(fx["vocab"])})
+    plain = [w for w in fx["vocab"] if w.isascii() and w.isalnum() and len(w) <= 6 and len(tok.text_ids(w)) == 1]   # one piece each
+    rng = np.random.default_rng(n_docs)
+    texts = [" ".join(plain[i] for i in rng.integers(0, len(plain), int(rng.integers(1, 4)))) for _ in range(n_docs)]
+    texts[-1] = " ".join(plain[i] for i in rng.integers(0, len(plain), 5))
+    want = cut(tok, host_ids(tok, texts), 32)
+    lens = np.array([len(w) for w in want])
+    assert lens[-1] == 7 and (lens[:-1] <= 5).all()                   # the maximum is the last document's alone
+    got = run(device_tokenizer(tok), texts, 32)
+    assert got[5] == []
+    assert np.array_equal(got[3], np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)) and got[4] == 7
+    assert_equals_host(got, want, f"{n_docs} short documents")
+
+
 def test_documents_beyond_the_window_are_right_or_flagged():
     """20 000-byte ASCII documents: only the first max_length - 2 pieces matter, so the first 4 096 bytes answer them unless
     they hold too few pieces (then, and only then, the document may be left to the host)."""

@@ -258,7 +258,7 @@ __device__ unsigned long long h2_dbg[2][8];
 // slower.
 // A step: `s_waitcnt vmcnt(6)` + the barrier make stage s visible (the pieces of stage s + 1 may still fly); every wave issues
 // its sixteen fragment reads; the SIMD's first wave (w < 4) issues its six pieces of stage s + 2 under their latency, the
-// second one behind its MFMAs (RR_CE_H2_NO_STAGGER=1: both up front); 16 MFMAs hi x hi (acc1), 16 hi x lo + 16 lo x hi (acc2).
+// second one behind its MFMAs; 16 MFMAs hi x hi (acc1), 16 hi x lo + 16 lo x hi (acc2).
 // In-kernel clocks (FFN1 shape, 1.5 GHz shader clock): the SIMD's two waves share one matrix pipe, 2 x 48 MFMAs = 1 536 cycles,
 // and a step takes ~2 330 -- 300 - 500 until the first MFMA (eight waves read 128 KB of LDS at once), the pieces' issue
 // 190 - 300, ~150 at the barrier.  The epilogue (GELU + split + stores: ~11 000 cycles of vector work for the SIMD's two
@@ -274,7 +274,7 @@ template <int EPI>
 __global__ __launch_bounds__(512, 1) void ce_gemm_h2(const h2_u32x4* __restrict__ W2, int N, const h2_u32x4* __restrict__ X2, int64_t xs, int M,
                                                      int K, const float* __restrict__ bias, float* __restrict__ out32,
                                                      h2_u32x2* __restrict__ out2, int64_t os, unsigned* __restrict__ flag, float qscale,
-                                                     int qcols, int stagger) {
+                                                     int qcols) {
     extern __shared__ __attribute__((aligned(16))) h2_u32x4 h2g_lds[];
     constexpr int TB = H2G_BT;
     constexpr int PW = 6;                                  // 1 KB pieces per wave and stage: 48 / 8
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(512, 1) void ce_gemm_h2(const h2_u32x4* __restrict_
     H2_DBG(unsigned long long dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long wall0 = __builtin_amdgcn_s_memrealtime();)
     H2_STAMP(tp0);
     // the SIMD's second wave (w >= 4) issues its pieces behind its MFMAs, the first one under the latency of its reads
-    const bool late = stagger && w >= 4;
+    const bool late = w >= 4;
     issue(0, 0);
     if (KS > 1) issue(1, 1);
     int buf = 0;
@@ -450,12 +450,11 @@ __global__ __launch_bounds__(512, 1) void ce_gemm_h2(const h2_u32x4* __restrict_
 
 void ce_h2_gemm(int epi, const void* W2, int N, const void* X2, int64_t xs, int M, int K, const float* bias, float* out32,
                 void* out2, int64_t os, unsigned* flag, hipStream_t st, float qscale, int qcols) {
-    static const int stagger = getenv("RR_CE_H2_NO_STAGGER") == nullptr;      // (A/B)
     const int tbs = (M + H2G_BT - 1) / H2G_BT;
     const dim3 grid((unsigned)(((tbs + 7) / 8) * 8 * (N / H2G_BF)));
 #define H2_LAUNCH(E) \
     hipLaunchKernelGGL((ce_gemm_h2<E>), grid, dim3(512), H2G_LDS, st, (const h2_u32x4*)W2, N, (const h2_u32x4*)X2, xs, M, K, bias, out32, \
-                       (h2_u32x2*)out2, os, flag, qscale, qcols, stagger)
+                       (h2_u32x2*)out2, os, flag, qscale, qcols)
     if (epi == CE_H2_EPI_F32) H2_LAUNCH(CE_H2_EPI_F32);
     else if (epi == CE_H2_EPI_H2) H2_LAUNCH(CE_H2_EPI_H2);
     else H2_LAUNCH(CE_H2_EPI_GELU_H2);
@@ -776,8 +775,7 @@ static void h2_attention(const void* qkv, int64_t xs, const int32_t* cu, int n_s
 
 void ce_h2_attention(const void* qkv, int64_t xs, const int32_t* cu, int n_seqs, int max_len, void* ctx2, int64_t os, unsigned* flag,
                      int cls_only, hipStream_t st) {
-    static const bool no_small = getenv("RR_CE_H2_ATT_NO_SMALL") != nullptr;      // (A/B)
-    h2_attention(qkv, xs, cu, n_seqs, max_len, ctx2, os, flag, cls_only, !no_small, st);
+    h2_attention(qkv, xs, cu, n_seqs, max_len, ctx2, os, flag, cls_only, true, st);
 }
 
 int ce_h2_set_attributes() {

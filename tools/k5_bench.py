@@ -20,8 +20,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--precision", choices=["bf16", "fp32"], default="bf16",
                     help="bf16 = the fast path (roofline: bf16 MFMA); fp32 = reference precision: every fp32 product as three fp16 MFMA "
-                         "products (roofline: 3 x the executed FLOPs against the fp16 MFMA peak; RR_CE_F32_SPLIT=bf16x3: six bf16 "
-                         "products, RR_CE_F32_MFMA=1: the fp32-input instruction)")
+                         "products (roofline: 3 x the executed FLOPs against the fp16 MFMA peak)")
     a = ap.parse_args()
     from review_recommender_amd import synth
     from review_recommender_amd.cross_encoder import CrossEncoder

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where a ce_gemm_h2 workgroup (fp32-mode FFN1: K = 384, N = 1536, GELU + h2 epilogue) spends its cycles: in-kernel phase
 clocks (librr_hip_dbg.so) of waves 0 and 4 of workgroup 2048 in a 256 x 512-token forward.
-    python tools/k5_h2_stamps.py            (RR_CE_H2_STAGE=regs | RR_CE_H2_NO_STAGGER=1 for the variants)"""
+    python tools/k5_h2_stamps.py"""
 import ctypes as C
 import os
 import sys

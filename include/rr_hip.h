@@ -470,6 +470,11 @@ int rr_textprep_limits(int32_t* out_window, int32_t* out_tile, int32_t* out_per_
  * the device) return RR_E_INVALID with the count.  Asynchronous on `stream`; n_docs = 0 does nothing. */
 int rr_textprep_clean_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
                           int32_t n_docs, int32_t spam, uint8_t* d_out, int32_t* d_out_len, int32_t* d_status, void* stream);
+/* The same with the cut at max_chars code points instead of 4000; 0 = no cut (nlp/10_product_prep.py:21-24 has none).
+ * rr_textprep_clean_dev is this call with 4000. */
+int rr_textprep_clean_chars_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                                int32_t n_docs, int32_t spam, int32_t max_chars, uint8_t* d_out, int32_t* d_out_len,
+                                int32_t* d_status, void* stream);
 int rr_textprep_status(rr_textprep* tp, int32_t* out_bad_docs);
 /* drop_duplicates(subset=["sku", "__txt"]) (:117) among the documents whose status word is 0: document s = d_len[s] bytes
  * at d_text + d_text_off[s], d_group[s] = its sku's number.  Sets RR_TP_DUP on every survivor for which an EARLIER survivor
@@ -544,6 +549,45 @@ int rr_doctok_emit_dev(rr_doctok* dt, const uint8_t* d_text, int64_t text_bytes,
 int rr_doctok_vocab_dev(rr_doctok* dt, int32_t hash_bits, int32_t* d_tok, void* stream);
 int rr_doctok_copy_vocab(rr_doctok* dt, const int32_t* d_tok, uint8_t* h_bytes, int64_t* h_off);
 int rr_doctok_copy_tokens(rr_doctok* dt, int64_t* h_pos, int32_t* h_len, uint8_t* h_arena);
+
+/* ------------------------------------------------------------ products.parquet: order, KPIs, agg_text (csrc/rr_products.hip) */
+
+/* nlp/10_product_prep.py:54-78 on the device, behind rr_textprep_clean_chars_dev (max_chars 0, spam 0) and
+ * rr_textprep_dedup_dev (products.model_build_products states the whole step in numpy).  The calls of one handle must be
+ * stream-ordered; they use the handle's scratch. */
+typedef struct rr_products rr_products;
+int rr_products_create(int32_t device, rr_products** out);
+int rr_products_destroy(rr_products* pb);
+/* Rows s of [0, n) with d_status[s] == 0 survive; d_group[s] in [0, n_skus) = the rank of the row's sku among the sorted
+ * distinct skus, d_stars[s] a double (NaN = none), d_ts[s] int64 ns (INT64_MIN = NaT).  Writes
+ *   d_perm      int32 [n]: its first m = d_seg_off[n_skus] entries are the survivors, sku-major, within a sku by stars
+ *               descending (NaN last, -0.0 == 0.0, the infinities as numbers), then ts descending (NaT last), then row
+ *               ascending -- pandas' stable sort_values(["sku", "stars", "ts"], ascending=[True, False, False]).  The rest
+ *               holds the rows that did not survive;
+ *   d_seg_off   int64 [n_skus + 1]: sku k owns d_perm[d_seg_off[k] .. d_seg_off[k + 1]);
+ *   per sku k:  d_n_reviews[k] (int64) = its survivors, d_star_sum[k] (double) = the sum of their non-NaN stars added one
+ *               by one in d_perm order, d_star_cnt[k] (int64) = how many those are, d_last_ts[k] = the largest ts
+ *               (INT64_MIN when every one is NaT).
+ * A stable LSD radix sort (csrc/rr_prims.h) over order-preserving key words, least significant first: linear in n whatever
+ * the segment lengths, and no atomic decides an order.  The groups of the survivors are checked on the device before
+ * anything is sorted (this call waits for that): one outside [0, n_skus) returns RR_E_INVALID and writes no output. */
+int rr_products_order_dev(rr_products* pb, const int32_t* d_status, const int32_t* d_group, const double* d_stars,
+                          const int64_t* d_ts, int32_t n, int32_t n_skus, int32_t* d_perm, int64_t* d_seg_off,
+                          int64_t* d_n_reviews, double* d_star_sum, int64_t* d_star_cnt, int64_t* d_last_ts, void* stream);
+/* agg_text: for sku k the texts of its first min(length, max_per_sku) rows of d_perm (row s = d_len[s] bytes at d_text +
+ * d_text_off[s]) joined by the two bytes " \n", back to back in d_out_text (capacity out_bytes; the cleaned bytes of the
+ * survivors + 2 m always suffice), d_out_off int64 [n_skus + 1], d_count[0] = the bytes written: the layout
+ * rr_doctok_count_dev reads.  One device scan over the skus; no host wait.  A segment offset that decreases or leaves
+ * [0, n], a row outside [0, n), a text that leaves [0, text_bytes] or a capacity that is too small write NO text (d_out_off
+ * and d_count are still written) and make rr_products_status return RR_E_INVALID. */
+int rr_products_concat_dev(rr_products* pb, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                           const int32_t* d_len, int32_t n, const int32_t* d_perm, const int64_t* d_seg_off, int32_t n_skus,
+                           int32_t max_per_sku, uint8_t* d_out_text, int64_t out_bytes, int64_t* d_out_off, int64_t* d_count,
+                           void* stream);
+/* Waits for the device; RR_E_INVALID when a rr_products_concat_dev since the last call refused its arguments
+ * (*out_bad = how many skus or buffers it refused).  Until it is called, later rr_products_concat_dev calls on the handle
+ * write no text either: ask after every concatenation whose text is used. */
+int rr_products_status(rr_products* pb, int32_t* out_bad);
 
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard

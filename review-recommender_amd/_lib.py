@@ -110,9 +110,16 @@ PROTOTYPES = {
     "rr_textprep_destroy": (C.c_int, [c_vp]),
     "rr_textprep_limits": (C.c_int, [P(c_i32), P(c_i32), P(c_i32)]),
     "rr_textprep_clean_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rr_textprep_clean_chars_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rr_textprep_status": (C.c_int, [c_vp, P(c_i32)]),
     "rr_textprep_dedup_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "rr_textprep_compact_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rr_products_create": (C.c_int, [c_i32, P(c_vp)]),
+    "rr_products_destroy": (C.c_int, [c_vp]),
+    "rr_products_order_dev": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rr_products_concat_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp,
+                                         c_vp]),
+    "rr_products_status": (C.c_int, [c_vp, P(c_i32)]),
     "rr_doctok_create": (C.c_int, [c_i32, c_vp, c_vp, c_i32, P(c_vp)]),
     "rr_doctok_destroy": (C.c_int, [c_vp]),
     "rr_doctok_limits": (C.c_int, [P(c_i32), P(c_i32), P(c_i32)]),

@@ -13,14 +13,7 @@
 //   2. forward lists: the entries stably radix-sorted by doc, carrying (term, tf): terms come
 //      out ascending within each document; doc_indptr is a lower bound over the sorted docs.
 //
-// The radix sort: 8-bit digits, ceil(bits(max key) / 8) passes (at least one), each
-//   rb_hist     per-tile digit counts (a tile = RB_TILE elements, one workgroup);
-//   rr_scan     (rr_prims.h) exclusive scan of the digit-major count matrix (int64) -> where
-//               every (digit, tile) run starts in the output;
-//   rb_scatter  the tile in rounds of 256 elements, in input order: a wave's lanes with the
-//               same digit find each other with eight __ballot masks, rank themselves with a
-//               popcount below their lane, and add the counts of the waves before them.  The
-//               order of the writes does not depend on atomics (stable).
+// The radix sort is rr_prims.h's (rr_radix_sort): 8-bit digits, ceil(bits(max key) / 8) passes (at least one), stable.
 // Every element count and offset is int64 (T, nnz and byte offsets pass 2^31 and 4 GiB).
 // The inputs are checked on the device (rb_check) before anything is scattered.
 #include <vector>
@@ -28,9 +21,9 @@
 
 #include "rr_prims.h"
 
-#define RB_THREADS 256
-#define RB_ROUNDS 16
-#define RB_TILE (RB_THREADS * RB_ROUNDS)   // elements per workgroup of the sort and the run-length pass
+#define RB_THREADS RR_SORT_THREADS
+#define RB_ROUNDS RR_SORT_ROUNDS
+#define RB_TILE RR_SORT_TILE                 // elements per workgroup of the sort and the run-length pass
 #define RB_GRID_CAP 8192                     // grid of the grid-stride kernels
 
 #define RB_ERR_TERM 1u      // a term id outside [0, n_terms)
@@ -129,73 +122,6 @@ __global__ __launch_bounds__(RB_THREADS) void rb_gather_rows(const int64_t* __re
         if (s < 0) continue;
         const int64_t src = off[s], cnt = off[s + 1] - src, dst = new_off[r];
         for (int64_t i = lane; i < cnt; i += 64) new_tok[dst + i] = tok[src + i];
-    }
-}
-
-// ------------------------------------------------------------------ radix sort
-__global__ __launch_bounds__(RB_THREADS) void rb_hist(const uint32_t* __restrict__ key, int64_t n, int shift,
-                                                      int64_t n_tiles, int64_t* __restrict__ hist) {
-    __shared__ unsigned cnt[256];
-    const int tid = threadIdx.x;
-    cnt[tid] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * RB_TILE;
-    for (int r = 0; r < RB_ROUNDS; ++r) {
-        const int64_t i = base + r * RB_THREADS + tid;
-        if (i < n) atomicAdd(&cnt[(key[i] >> shift) & 255u], 1u);     // (a count: the same whatever the order)
-    }
-    __syncthreads();
-    hist[(int64_t)tid * n_tiles + blockIdx.x] = cnt[tid];               // digit-major: the scan gives stable offsets
-}
-
-// rank of this lane among the active lanes of its wave with the same 8-bit digit, and the mask of those lanes
-__device__ __forceinline__ uint64_t rb_match8(unsigned d, bool valid) {
-    uint64_t m = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const uint64_t bb = __ballot((d >> b) & 1u);
-        m &= ((d >> b) & 1u) ? bb : ~bb;
-    }
-    return m;
-}
-
-template <int NP>
-__global__ __launch_bounds__(RB_THREADS) void rb_scatter(const uint32_t* __restrict__ kin,
-                                                         const uint32_t* __restrict__ p0in,
-                                                         const uint32_t* __restrict__ p1in, int64_t n, int shift,
-                                                         int64_t n_tiles, const int64_t* __restrict__ offs,
-                                                         uint32_t* __restrict__ kout, uint32_t* __restrict__ p0out,
-                                                         uint32_t* __restrict__ p1out) {
-    __shared__ int64_t run[256];                 // next output position of every digit
-    __shared__ unsigned wc[RB_THREADS / 64][256];  // this round: elements of every digit per wave
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    run[tid] = offs[(int64_t)tid * n_tiles + blockIdx.x];
-    const int64_t base = (int64_t)blockIdx.x * RB_TILE;
-    const uint64_t below = (1ull << lane) - 1ull;
-    for (int r = 0; r < RB_ROUNDS; ++r) {
-#pragma unroll
-        for (int w = 0; w < RB_THREADS / 64; ++w) wc[w][tid] = 0;
-        __syncthreads();
-        const int64_t i = base + r * RB_THREADS + tid;
-        const bool valid = i < n;
-        const uint32_t k = valid ? kin[i] : 0u;
-        const unsigned d = (k >> shift) & 255u;
-        const uint64_t m = rb_match8(d, valid);
-        const int rank = __popcll(m & below);
-        if (valid && rank == 0) wc[wave][d] = (unsigned)__popcll(m);
-        __syncthreads();
-        if (valid) {
-            int64_t pos = run[d] + rank;
-            for (int w = 0; w < wave; ++w) pos += wc[w][d];
-            kout[pos] = k;
-            if (NP >= 1) p0out[pos] = p0in[i];
-            if (NP >= 2) p1out[pos] = p1in[i];
-        }
-        __syncthreads();
-        unsigned add = 0;
-#pragma unroll
-        for (int w = 0; w < RB_THREADS / 64; ++w) add += wc[w][tid];
-        run[tid] += add;
     }
 }
 
@@ -303,45 +229,25 @@ struct RbPool {
         if (_rc != RR_OK) return _rc; \
     } while (0)
 
-struct rb_f_i64 {   // what the build's scans sum: an int64 array
-    const int64_t* in;
-    __device__ __forceinline__ long long operator()(int64_t i) const { return in[i]; }
-};
+using rb_f_i64 = rr_f_i64;   // what the build's scans sum: an int64 array
 
 // the chunk sums of the scans of one rb_build_core over T tokens and of n_rows row lengths: the count matrix is the largest
 int rb_alloc_scan_sums(RbPool& pool, int64_t T, int64_t n_rows) {
-    return pool.alloc(&pool.scan_sums, rr_scan_sums_len(std::max(256 * rb_tiles(T), n_rows)));
+    return pool.alloc(&pool.scan_sums, rr_scan_sums_len(std::max(rr_sort_counts(T), n_rows)));
 }
 
-int rb_passes(uint32_t max_key) {
-    int bits = 0;
-    while (bits < 32 && (max_key >> bits)) ++bits;
-    return bits ? (bits + 7) / 8 : 1;
-}
-
-// stable sort of n keys (< 2^32) with NP payload arrays: pass p reads the source (p == 0) or buffer (p - 1) & 1 and
-// writes buffer p & 1; the sources are never written.  Returns the buffer index that holds the result.
+// rr_radix_sort of n keys (< 2^32, at most max_key) with its counts in the pool.  Returns the buffer index that holds the
+// result.
 template <int NP>
 int rb_sort(hipStream_t st, RbPool& pool, int64_t n, uint32_t max_key, const uint32_t* ksrc, const uint32_t* p0src,
             const uint32_t* p1src, uint32_t* K[2], uint32_t* P0[2], uint32_t* P1[2], int* result) {
-    const int passes = rb_passes(max_key);
+    const int passes = rr_sort_passes(max_key);
     *result = (passes - 1) & 1;
     if (n == 0) return RR_OK;
-    const int64_t nt = rb_tiles(n), m = 256 * nt;
     int64_t *hist = nullptr, *offs = nullptr;
-    RB_TRY(pool.alloc(&hist, m));
-    RB_TRY(pool.alloc(&offs, m + 1));
-    for (int p = 0; p < passes; ++p) {
-        const uint32_t* kin = p == 0 ? ksrc : K[(p - 1) & 1];
-        const uint32_t* a_in = p == 0 ? p0src : (NP >= 1 ? P0[(p - 1) & 1] : nullptr);
-        const uint32_t* b_in = p == 0 ? p1src : (NP >= 2 ? P1[(p - 1) & 1] : nullptr);
-        hipLaunchKernelGGL(rb_hist, dim3((unsigned)nt), dim3(RB_THREADS), 0, st, kin, n, 8 * p, nt, hist);
-        RR_HIP_TRY(hipGetLastError());
-        rr_scan(rb_f_i64{hist}, m, pool.scan_sums, offs, (int32_t*)nullptr, (int64_t*)nullptr, st);
-        hipLaunchKernelGGL((rb_scatter<NP>), dim3((unsigned)nt), dim3(RB_THREADS), 0, st, kin, a_in, b_in, n, 8 * p, nt,
-                           offs, K[p & 1], NP >= 1 ? P0[p & 1] : nullptr, NP >= 2 ? P1[p & 1] : nullptr);
-        RR_HIP_TRY(hipGetLastError());
-    }
+    RB_TRY(pool.alloc(&hist, rr_sort_counts(n)));
+    RB_TRY(pool.alloc(&offs, rr_sort_counts(n) + 1));
+    RB_TRY(rr_radix_sort<NP>(st, n, passes, ksrc, p0src, p1src, K, P0, P1, hist, offs, pool.scan_sums));
     pool.release(hist);
     pool.release(offs);
     return RR_OK;

@@ -1,5 +1,6 @@
-// rr_prims.h -- what the index builders share (rr_wordpiece.hip, rr_textprep.hip, rr_doctok.hip, rr_bm25_build.hip):
-// the workgroup scan, the device-wide scan, and the small helpers every builder needs once.
+// rr_prims.h -- what the index builders share (rr_wordpiece.hip, rr_textprep.hip, rr_doctok.hip, rr_bm25_build.hip,
+// rr_products.hip): the workgroup scan, the device-wide scan, the stable radix sort, and the small helpers every builder
+// needs once.
 #pragma once
 
 #include "rr_common.h"
@@ -167,6 +168,126 @@ static void rr_scan(F f, int64_t n, int64_t* sums, int64_t* out64, int32_t* out3
     hipLaunchKernelGGL(rr_scan_sum<F>, dim3((unsigned)nb), dim3(256), 0, st, f, n, sums);
     hipLaunchKernelGGL(rr_scan_sums<1024>, dim3(1), dim3(1024), 0, st, sums, nb, total);
     if (out64 || out32) hipLaunchKernelGGL(rr_scan_apply<F>, dim3((unsigned)nb), dim3(256), 0, st, f, n, sums, nb, out64, out32);
+}
+
+// ---------------------------------------------------------------- the stable radix sort
+// LSD, 8-bit digits, 32-bit keys with up to two 32-bit payload arrays.  A pass is
+//   rr_sort_hist     per-tile digit counts (a tile = RR_SORT_TILE elements, one workgroup);
+//   rr_scan          exclusive scan of the digit-major count matrix (int64) -> where every (digit, tile) run starts;
+//   rr_sort_scatter  the tile in rounds of 256 elements, in input order: a wave's lanes with the same digit find each other
+//                    with eight __ballot masks, rank themselves with a popcount below their lane, and add the counts of the
+//                    waves before them.  The order of the writes does not depend on atomics (stable).
+// Every element count and offset is int64.
+#define RR_SORT_THREADS 256
+#define RR_SORT_ROUNDS 16
+#define RR_SORT_TILE (RR_SORT_THREADS * RR_SORT_ROUNDS)
+
+static inline int64_t rr_sort_tiles(int64_t n) { return (n + RR_SORT_TILE - 1) / RR_SORT_TILE; }
+// the words a sort of n elements needs besides its buffers: `hist` and `offs` (one more) of rr_sort_counts(n) int64 each,
+// and rr_scan_sums_len(rr_sort_counts(n)) chunk sums
+static inline int64_t rr_sort_counts(int64_t n) { return 256 * rr_sort_tiles(n); }
+
+static inline int rr_sort_passes(uint32_t max_key) {   // at least one
+    int bits = 0;
+    while (bits < 32 && (max_key >> bits)) ++bits;
+    return bits ? (bits + 7) / 8 : 1;
+}
+
+template <int ROUNDS>   // (templates, so that only the sources that sort carry the kernels)
+__global__ __launch_bounds__(RR_SORT_THREADS) void rr_sort_hist(const uint32_t* __restrict__ key, int64_t n, int shift,
+                                                                int64_t n_tiles, int64_t* __restrict__ hist) {
+    __shared__ unsigned cnt[256];
+    const int tid = threadIdx.x;
+    cnt[tid] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * (RR_SORT_THREADS * ROUNDS);
+    for (int r = 0; r < ROUNDS; ++r) {
+        const int64_t i = base + r * RR_SORT_THREADS + tid;
+        if (i < n) atomicAdd(&cnt[(key[i] >> shift) & 255u], 1u);     // (a count: the same whatever the order)
+    }
+    __syncthreads();
+    hist[(int64_t)tid * n_tiles + blockIdx.x] = cnt[tid];               // digit-major: the scan gives stable offsets
+}
+
+// the mask of the active lanes of this wave that hold the same 8-bit digit
+__device__ __forceinline__ uint64_t rr_match8(unsigned d, bool valid) {
+    uint64_t m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const uint64_t bb = __ballot((d >> b) & 1u);
+        m &= ((d >> b) & 1u) ? bb : ~bb;
+    }
+    return m;
+}
+
+template <int NP>
+__global__ __launch_bounds__(RR_SORT_THREADS) void rr_sort_scatter(const uint32_t* __restrict__ kin,
+                                                                   const uint32_t* __restrict__ p0in,
+                                                                   const uint32_t* __restrict__ p1in, int64_t n, int shift,
+                                                                   int64_t n_tiles, const int64_t* __restrict__ offs,
+                                                                   uint32_t* __restrict__ kout, uint32_t* __restrict__ p0out,
+                                                                   uint32_t* __restrict__ p1out) {
+    __shared__ int64_t run[256];                        // next output position of every digit
+    __shared__ unsigned wc[RR_SORT_THREADS / 64][256];  // this round: elements of every digit per wave
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    run[tid] = offs[(int64_t)tid * n_tiles + blockIdx.x];
+    const int64_t base = (int64_t)blockIdx.x * RR_SORT_TILE;
+    const uint64_t below = (1ull << lane) - 1ull;
+    for (int r = 0; r < RR_SORT_ROUNDS; ++r) {
+#pragma unroll
+        for (int w = 0; w < RR_SORT_THREADS / 64; ++w) wc[w][tid] = 0;
+        __syncthreads();
+        const int64_t i = base + r * RR_SORT_THREADS + tid;
+        const bool valid = i < n;
+        const uint32_t k = valid ? kin[i] : 0u;
+        const unsigned d = (k >> shift) & 255u;
+        const uint64_t m = rr_match8(d, valid);
+        const int rank = __popcll(m & below);
+        if (valid && rank == 0) wc[wave][d] = (unsigned)__popcll(m);
+        __syncthreads();
+        if (valid) {
+            int64_t pos = run[d] + rank;
+            for (int w = 0; w < wave; ++w) pos += wc[w][d];
+            kout[pos] = k;
+            if (NP >= 1) p0out[pos] = p0in[i];
+            if (NP >= 2) p1out[pos] = p1in[i];
+        }
+        __syncthreads();
+        unsigned add = 0;
+#pragma unroll
+        for (int w = 0; w < RR_SORT_THREADS / 64; ++w) add += wc[w][tid];
+        run[tid] += add;
+    }
+}
+
+struct rr_f_i64 {   // what a scan over an int64 array sums
+    const int64_t* in;
+    __device__ __forceinline__ long long operator()(int64_t i) const { return in[i]; }
+};
+
+// Stable sort of n keys by their low 8 * passes bits with NP payload arrays: pass p reads the source (p == 0) or buffer
+// (p - 1) & 1 and writes buffer p & 1; the sources are never written, and a source may be buffer 1 (pass 0 writes buffer 0
+// and nothing reads the source after it).  The result is in buffer (passes - 1) & 1.  hist, offs, scan_sums: see
+// rr_sort_counts.
+template <int NP>
+static int rr_radix_sort(hipStream_t st, int64_t n, int passes, const uint32_t* ksrc, const uint32_t* p0src,
+                         const uint32_t* p1src, uint32_t* const K[2], uint32_t* const P0[2], uint32_t* const P1[2],
+                         int64_t* hist, int64_t* offs, int64_t* scan_sums) {
+    if (n == 0) return RR_OK;
+    const int64_t nt = rr_sort_tiles(n), m = 256 * nt;
+    for (int p = 0; p < passes; ++p) {
+        const uint32_t* kin = p == 0 ? ksrc : K[(p - 1) & 1];
+        const uint32_t* a_in = p == 0 ? p0src : (NP >= 1 ? P0[(p - 1) & 1] : nullptr);
+        const uint32_t* b_in = p == 0 ? p1src : (NP >= 2 ? P1[(p - 1) & 1] : nullptr);
+        hipLaunchKernelGGL(rr_sort_hist<RR_SORT_ROUNDS>, dim3((unsigned)nt), dim3(RR_SORT_THREADS), 0, st, kin, n, 8 * p, nt,
+                           hist);
+        RR_HIP_TRY(hipGetLastError());
+        rr_scan(rr_f_i64{hist}, m, scan_sums, offs, (int32_t*)nullptr, (int64_t*)nullptr, st);
+        hipLaunchKernelGGL((rr_sort_scatter<NP>), dim3((unsigned)nt), dim3(RR_SORT_THREADS), 0, st, kin, a_in, b_in, n, 8 * p,
+                           nt, offs, K[p & 1], NP >= 1 ? P0[p & 1] : nullptr, NP >= 2 ? P1[p & 1] : nullptr);
+        RR_HIP_TRY(hipGetLastError());
+    }
+    return RR_OK;
 }
 
 #endif  // __HIPCC__

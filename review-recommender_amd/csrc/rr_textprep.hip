@@ -10,8 +10,8 @@
 //                 is whitespace: that is strip() and the collapse of \s+ at once.  The state at the start of a thread's
 //                 slice (was the previous character whitespace?) is read from the raw bytes in LDS, so it does not matter
 //                 where a tile or a slice ends.  A block scan over (code points, bytes) packed in one int gives every
-//                 character its place in the output and its code-point index; whatever has an index >= 4000 is not
-//                 written (the cut comes after the collapse, so the text may end in a space).  The normalised text is a
+//                 character its place in the output and its code-point index; whatever has an index >= max_chars (4000 for
+//                 nlp/11, none for nlp/10) is not written (the cut comes after the collapse, so the text may end in a space).  The normalised text is a
 //                 second LDS buffer; the three spam rules then run over THAT buffer with plain bounded look-ahead, so a
 //                 phrase, a URL prefix or a run of ten has no edge to straddle:
 //                   URL_RE     candidates = "http://", "https://", "www." (ASCII, any case) followed by a byte that is not a
@@ -62,7 +62,7 @@ __device__ __forceinline__ bool rr_tp_match(const uint8_t* s, int p, int n, cons
 
 __global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_clean(
     const uint8_t* text /* no __restrict__: `out` may be the same buffer */, int64_t text_bytes,
-    const int64_t* __restrict__ text_off, int32_t spam, uint8_t* out, int32_t* __restrict__ out_len, int32_t* __restrict__ status, int32_t* __restrict__ bad) {
+    const int64_t* __restrict__ text_off, int32_t spam, int32_t max_chars, uint8_t* out, int32_t* __restrict__ out_len, int32_t* __restrict__ status, int32_t* __restrict__ bad) {
     __shared__ uint8_t s_raw[RR_TP_WINDOW];
     __shared__ uint8_t s_out[RR_TP_WINDOW];
     __shared__ int s_ws[RR_TP_THREADS / 64];
@@ -135,13 +135,13 @@ __global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_clean(
             g_cp += 1 + sp; g_by += n + sp;                // what the scan counted for this character
             if (cp == 0) sp = 0;                           // the first character of the result: the space in front of it is stripped
             else { cp -= phantom; by -= phantom; }         // (and was counted: everything behind it moves up)
-            if (sp && cp < RR_TP_MAX_CHARS && by >= 0 && by < RR_TP_WINDOW) {
+            if (sp && cp < max_chars && by >= 0 && by < RR_TP_WINDOW) {
                 s_out[by] = ' ';
                 my_end = by + 1 > my_end ? by + 1 : my_end;
                 my_cps = cp + 1 > my_cps ? cp + 1 : my_cps;
             }
             cp += sp; by += sp;
-            if (cp < RR_TP_MAX_CHARS && by >= 0 && by + n <= RR_TP_WINDOW) {
+            if (cp < max_chars && by >= 0 && by + n <= RR_TP_WINDOW) {
                 const int i = i0 + j;
                 for (int k = 0; k < n; ++k) s_out[by + k] = s_raw[i + k];
                 my_end = by + n > my_end ? by + n : my_end;
@@ -335,19 +335,27 @@ extern "C" int rr_textprep_limits(int32_t* out_window, int32_t* out_tile, int32_
     return RR_OK;
 }
 
-extern "C" int rr_textprep_clean_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
-                                     int32_t n_docs, int32_t spam, uint8_t* d_out, int32_t* d_out_len, int32_t* d_status,
-                                     void* stream) {
+extern "C" int rr_textprep_clean_chars_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                                           int32_t n_docs, int32_t spam, int32_t max_chars, uint8_t* d_out, int32_t* d_out_len,
+                                           int32_t* d_status, void* stream) {
     RR_REQUIRE(tp && d_text_off && d_out_len && d_status, "rr_textprep_clean_dev: NULL argument");
     RR_REQUIRE(n_docs >= 0 && text_bytes >= 0, "rr_textprep_clean_dev: %d documents, %lld bytes", n_docs, (long long)text_bytes);
     RR_REQUIRE((d_text && d_out) || text_bytes == 0, "rr_textprep_clean_dev: NULL text with %lld bytes", (long long)text_bytes);
+    RR_REQUIRE(max_chars >= 0, "rr_textprep_clean_dev: max_chars %d is negative", max_chars);
     if (n_docs == 0) return RR_OK;
     std::lock_guard<std::mutex> lk(tp->mu);
     RR_HIP_TRY(hipSetDevice(tp->device));
     hipLaunchKernelGGL(rr_tp_clean, dim3((unsigned)n_docs), dim3(RR_TP_THREADS), 0, (hipStream_t)stream, d_text, text_bytes,
-                       d_text_off, spam ? 1 : 0, d_out, d_out_len, d_status, tp->d_bad);
+                       d_text_off, spam ? 1 : 0, max_chars > 0 ? max_chars : INT32_MAX, d_out, d_out_len, d_status, tp->d_bad);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
+}
+
+extern "C" int rr_textprep_clean_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                                     int32_t n_docs, int32_t spam, uint8_t* d_out, int32_t* d_out_len, int32_t* d_status,
+                                     void* stream) {
+    return rr_textprep_clean_chars_dev(tp, d_text, text_bytes, d_text_off, n_docs, spam, RR_TP_MAX_CHARS, d_out, d_out_len, d_status,
+                                       stream);
 }
 
 extern "C" int rr_textprep_status(rr_textprep* tp, int32_t* out_bad_docs) {

@@ -471,6 +471,46 @@ def _utf8_column(texts) -> Tuple[np.ndarray, np.ndarray]:
         return np.frombuffer(b"".join(docs), dtype=np.uint8), off
 
 
+def _stage_rows(raw: np.ndarray, off: np.ndarray, d_text, main, stage_bytes: int, on_rows) -> None:
+    """The text column `raw` (rows at `off`, int64 [n + 1]) copied to `d_text` on stream `main` in row blocks of about
+    `stage_bytes` through two pinned buffers (a longer row goes through in pieces); on_rows(a, b) is called once rows
+    [a, b) are queued, to queue what reads them.  Does not wait for the last block."""
+    import torch
+    n, total = len(off) - 1, int(off[-1])
+    blk = max(1, min(int(stage_bytes), max(total, 1)))
+    stage = [torch.empty(blk, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+    busy: List[Optional[object]] = [None, None]
+    turn = 0
+    a = 0
+    while a < n:
+        b = int(np.searchsorted(off, off[a] + blk, side="right")) - 1
+        b = min(n, max(b, a + 1))
+        for lo in range(int(off[a]), int(off[b]), blk):
+            hi = min(int(off[b]), lo + blk)
+            if busy[turn] is not None:
+                busy[turn].synchronize()
+            stage[turn].numpy()[:hi - lo] = raw[lo:hi]
+            d_text[lo:hi].copy_(stage[turn][:hi - lo], non_blocking=True)
+            busy[turn] = torch.cuda.Event()
+            busy[turn].record(main)
+            turn ^= 1
+        on_rows(a, b)
+        a = b
+
+
+def _write_host_rows(d_text, off: np.ndarray, rows, cleaned) -> None:
+    """The texts `cleaned` (bytes, each no longer than its raw text) written into the slots of `rows` of `d_text`: two
+    copies and one scatter, not a copy per row."""
+    import torch
+    parts = [np.frombuffer(t, dtype=np.uint8) for t in cleaned]
+    for i, tb in zip(rows, parts):
+        assert len(tb) <= off[i + 1] - off[i]
+    if parts and sum(len(x) for x in parts):
+        where = [np.arange(int(off[i]), int(off[i]) + len(tb), dtype=np.int64) for i, tb in zip(rows, parts)]
+        d_text.index_copy_(0, torch.from_numpy(np.concatenate(where)).to(d_text.device),
+                           torch.from_numpy(np.concatenate(parts)).to(d_text.device))
+
+
 def build_review_embeddings(reviews, encoder, *, no_spam: bool = False, no_dedup: bool = False, chunk_tokens: int = 131072,
                             data_dir=None, product_skus=None, stats: Optional[dict] = None, max_text_bytes: int = MAX_TEXT_BYTES,
                             stage_bytes: int = STAGE_BYTES, log=None):
@@ -529,26 +569,9 @@ def build_review_embeddings(reviews, encoder, *, no_spam: bool = False, no_dedup
             d_off = torch.from_numpy(np.ascontiguousarray(off)).to(dev)
             d_len = torch.empty(n, dtype=torch.int32, device=dev)
             d_st = torch.empty(n, dtype=torch.int32, device=dev)
-            blk = max(1, min(int(stage_bytes), max(total, 1)))
-            stage = [torch.empty(blk, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-            busy: List[Optional[object]] = [None, None]
-            turn = 0
-            a = 0
-            while a < n:                              # row blocks of about `blk` bytes; a longer row goes through in pieces
-                b = int(np.searchsorted(off, off[a] + blk, side="right")) - 1
-                b = min(n, max(b, a + 1))
-                for lo in range(int(off[a]), int(off[b]), blk):
-                    hi = min(int(off[b]), lo + blk)
-                    if busy[turn] is not None:
-                        busy[turn].synchronize()
-                    stage[turn].numpy()[:hi - lo] = raw[lo:hi]
-                    d_text[lo:hi].copy_(stage[turn][:hi - lo], non_blocking=True)
-                    busy[turn] = torch.cuda.Event()
-                    busy[turn].record(main)
-                    turn ^= 1
-                tp.clean(d_text.data_ptr(), total, d_off.data_ptr() + 8 * a, b - a, not no_spam, d_text.data_ptr(),
-                         d_len.data_ptr() + 4 * a, d_st.data_ptr() + 4 * a, st_ptr)
-                a = b
+            _stage_rows(raw, off, d_text, main, stage_bytes,
+                        lambda a, b: tp.clean(d_text.data_ptr(), total, d_off.data_ptr() + 8 * a, b - a, not no_spam, d_text.data_ptr(),
+                                              d_len.data_ptr() + 4 * a, d_st.data_ptr() + 4 * a, st_ptr))
             main.synchronize()
             tp.check()
             status, lens = d_st.cpu().numpy(), d_len.cpu().numpy()
@@ -556,17 +579,14 @@ def build_review_embeddings(reviews, encoder, *, no_spam: bool = False, no_dedup
 
             # the rows the kernel left to the host: the reference's own functions, into the rows' slots
             host_clean = np.flatnonzero(status & T.NEEDS_HOST)
-            parts, where = [], []
+            cleaned = []
             for i in host_clean.tolist():
                 t = normalize_text(texts[i])
-                tb = np.frombuffer(t.encode("utf-8", "surrogatepass"), dtype=np.uint8)
-                assert len(tb) <= off[i + 1] - off[i]
-                parts.append(tb)
-                where.append(np.arange(int(off[i]), int(off[i]) + len(tb), dtype=np.int64))
+                tb = t.encode("utf-8", "surrogatepass")
+                cleaned.append(tb)
                 lens[i] = len(tb)
                 status[i] = (T.SHORT if len(t) < MIN_TEXT_LEN else 0) | (T.SPAM if not no_spam and looks_spammy(t) else 0)
-            if parts and sum(len(x) for x in parts):          # all of them in two copies and one scatter, not a copy per row
-                d_text.index_copy_(0, torch.from_numpy(np.concatenate(where)).to(dev), torch.from_numpy(np.concatenate(parts)).to(dev))
+            _write_host_rows(d_text, off, host_clean.tolist(), cleaned)
             if len(host_clean):
                 d_len.copy_(torch.from_numpy(lens))
                 d_st.copy_(torch.from_numpy(status))

@@ -30,9 +30,10 @@ PROMO_PHRASES = ("discount code", "use code", "sponsored")
 _LOWER = {c: c + 32 for c in range(ord("A"), ord("Z") + 1)}
 
 
-def model_clean_bytes(raw: bytes, spam: bool = True) -> Tuple[bytes, int]:
+def model_clean_bytes(raw: bytes, spam: bool = True, max_chars: int = MAX_CHARS) -> Tuple[bytes, int]:
     """What rr_textprep_clean_dev answers for one document: (normalised UTF-8 text, status word).  A document left to the
-    host has the status NEEDS_HOST alone and no text."""
+    host has the status NEEDS_HOST alone and no text.  max_chars: the cut of rr_textprep_clean_chars_dev, 0 = none
+    (nlp/10_product_prep.py)."""
     if len(raw) > WINDOW_BYTES:
         return b"", NEEDS_HOST
     try:
@@ -51,7 +52,8 @@ def model_clean_bytes(raw: bytes, spam: bool = True) -> Tuple[bytes, int]:
             out.append(" ")
         out.append(c)
         after_space = False
-    del out[MAX_CHARS:]                            # after the collapse: the text may now end in a space
+    if max_chars:
+        del out[max_chars:]                        # after the collapse: the text may now end in a space
     status = SHORT if len(out) < MIN_CHARS else 0
     txt = "".join(out)
     if spam and _spammy(txt, out):
@@ -77,11 +79,11 @@ def _spammy(txt: str, chars: List[str]) -> bool:
     return False
 
 
-def model_clean(text, spam: bool = True) -> Tuple[str, int]:
+def model_clean(text, spam: bool = True, max_chars: int = MAX_CHARS) -> Tuple[str, int]:
     """`model_clean_bytes` for a str (or bytes): (normalised text, status word).  A str with a lone surrogate has no UTF-8
     form: it is encoded as the three bytes the kernel calls malformed."""
     raw = text if isinstance(text, (bytes, bytearray)) else str(text).encode("utf-8", "surrogatepass")
-    out, status = model_clean_bytes(bytes(raw), spam)
+    out, status = model_clean_bytes(bytes(raw), spam, max_chars)
     return out.decode("utf-8"), status
 
 
@@ -104,10 +106,12 @@ class TextPrep:
         self._h = h
 
     def clean(self, text: int, text_bytes: int, offsets: int, n_docs: int, spam: bool, out: int, out_len: int, status: int,
-              stream: Optional[int] = None) -> None:
-        _lib.check(_lib.load().rr_textprep_clean_dev(self._h, C.c_void_p(text), int(text_bytes), C.c_void_p(offsets), int(n_docs),
-                                                     1 if spam else 0, C.c_void_p(out), C.c_void_p(out_len), C.c_void_p(status),
-                                                     C.c_void_p(stream)), "rr_textprep_clean_dev")
+              stream: Optional[int] = None, max_chars: int = MAX_CHARS) -> None:
+        """max_chars: the cut in code points (nlp/11's 4000), 0 = none (nlp/10)."""
+        _lib.check(_lib.load().rr_textprep_clean_chars_dev(self._h, C.c_void_p(text), int(text_bytes), C.c_void_p(offsets),
+                                                           int(n_docs), 1 if spam else 0, int(max_chars), C.c_void_p(out),
+                                                           C.c_void_p(out_len), C.c_void_p(status), C.c_void_p(stream)),
+                   "rr_textprep_clean_dev")
 
     def dedup(self, text: int, text_bytes: int, offsets: int, lens: int, group: int, status: int, n_docs: int,
               hash_bits: int = 64, stream: Optional[int] = None) -> None:
@@ -128,7 +132,8 @@ class TextPrep:
         _lib.check(_lib.load().rr_textprep_status(self._h, C.byref(bad)), "rr_textprep_status")
 
     # -- whole batches from host data: what the tests and small callers use
-    def clean_docs(self, docs: Sequence[bytes], spam: bool = True, offsets: Optional[np.ndarray] = None):
+    def clean_docs(self, docs: Sequence[bytes], spam: bool = True, offsets: Optional[np.ndarray] = None,
+                   max_chars: int = MAX_CHARS):
         """(texts, lengths, status words) of rr_textprep_clean_dev for `docs`, out of place; `offsets` replaces the running
         sum of their lengths (tests: broken offsets).  Does not call check()."""
         import torch
@@ -146,7 +151,7 @@ class TextPrep:
             d_len = torch.full((max(n, 1),), -7, dtype=torch.int32, device=dev)
             d_st = torch.full((max(n, 1),), -7, dtype=torch.int32, device=dev)
             self.clean(d_text.data_ptr(), len(blob), d_off.data_ptr(), n, spam, d_out.data_ptr(), d_len.data_ptr(), d_st.data_ptr(),
-                       torch.cuda.current_stream(dev).cuda_stream)
+                       torch.cuda.current_stream(dev).cuda_stream, max_chars)
             torch.cuda.current_stream(dev).synchronize()
             out, lens, st = d_out.cpu().numpy(), d_len.cpu().numpy()[:n], d_st.cpu().numpy()[:n]
         return out, lens, st

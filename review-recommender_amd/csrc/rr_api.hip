@@ -401,7 +401,7 @@ extern "C" int rr_index_destroy(rr_index* ix) {
     rr_slot_park(ix);          // both slots' buffers now sit in ix->parked[]
     for (rr_scan_slot& s : ix->parked) {
         hipFree(s.d_q); hipFree(s.d_qplanes); hipFree(s.d_eps); hipFree(s.d_gmax); hipFree(s.d_smax);
-        hipFree(s.d_flt_samp); hipFree(s.d_flt_sigma); hipFree(s.d_flt_prog); free(s.flt_pending);
+        hipFree(s.d_flt_samp); hipFree(s.d_flt_sigma); free(s.flt_pending);
     }
     hipFree(ix->d_sims); hipFree(ix->d_sel_trace); hipFree(ix->d_flag_list); hipFree(ix->d_x3);
     hipFree(ix->d_rows_out); hipFree(ix->d_scores_out); hipFree(ix->d_shadow);

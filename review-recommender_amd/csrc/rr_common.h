@@ -48,8 +48,6 @@ struct rr_scan_slot {
     int32_t maxima_q = 0;
     float* d_flt_samp = nullptr;
     float* d_flt_sigma = nullptr;
-    uint32_t* d_flt_prog = nullptr;
-    uint32_t flt_seq = 0;
     bool flt_prep_fresh = false;
     void* flt_pending = nullptr;
 };
@@ -85,8 +83,6 @@ struct rr_index {
     // rounds to bf16 anyway); candidates are rescored on the fp32 rows.  Built lazily, dropped by any write to the matrix.
     float* d_flt_samp = nullptr;     // [<= RR_FLT_SAMP_CAP][RR_FLT_MAXQ] sampled tile maxima (store prefilter of rr_scan_flt)
     float* d_flt_sigma = nullptr;    // [RR_FLT_MAXQ] per-query store threshold
-    uint32_t* d_flt_prog = nullptr;  // [2][n_waves] progress words of the two-set scan launch (pairs of waves keep in step)
-    uint32_t flt_seq = 0;            // launch counter of the two-set scan (epoch of the progress words)
     bool scratch_small = false;      // no room for one score slice per 64 queries of a call: the fallback goes block by block
     bool flt_prep_fresh = false;     // rr_flt_pad_prep has written the planes / bounds of the queries in d_q (slots 0 ..): the next filter call skips its own preparation launch
     void* flt_pending = nullptr;     // rr_flt_pending: what a scan-only call (row shards, phase 1) left for its selection

@@ -1253,13 +1253,13 @@ static int rr_ensure_scratch(rr_index* ix, int nq) {
 // ---- scan slots (rr_common.h: rr_scan_slot)
 static void rr_slot_store(const rr_index* ix, rr_scan_slot& s) {
     s.d_q = ix->d_q; s.d_qplanes = ix->d_qplanes; s.d_eps = ix->d_eps; s.d_gmax = ix->d_gmax; s.d_smax = ix->d_smax;
-    s.maxima_q = ix->maxima_q; s.d_flt_samp = ix->d_flt_samp; s.d_flt_sigma = ix->d_flt_sigma; s.d_flt_prog = ix->d_flt_prog;
-    s.flt_seq = ix->flt_seq; s.flt_prep_fresh = ix->flt_prep_fresh; s.flt_pending = ix->flt_pending;
+    s.maxima_q = ix->maxima_q; s.d_flt_samp = ix->d_flt_samp; s.d_flt_sigma = ix->d_flt_sigma;
+    s.flt_prep_fresh = ix->flt_prep_fresh; s.flt_pending = ix->flt_pending;
 }
 static void rr_slot_fetch(rr_index* ix, const rr_scan_slot& s) {
     ix->d_q = s.d_q; ix->d_qplanes = s.d_qplanes; ix->d_eps = s.d_eps; ix->d_gmax = s.d_gmax; ix->d_smax = s.d_smax;
-    ix->maxima_q = s.maxima_q; ix->d_flt_samp = s.d_flt_samp; ix->d_flt_sigma = s.d_flt_sigma; ix->d_flt_prog = s.d_flt_prog;
-    ix->flt_seq = s.flt_seq; ix->flt_prep_fresh = s.flt_prep_fresh; ix->flt_pending = s.flt_pending;
+    ix->maxima_q = s.maxima_q; ix->d_flt_samp = s.d_flt_samp; ix->d_flt_sigma = s.d_flt_sigma;
+    ix->flt_prep_fresh = s.flt_prep_fresh; ix->flt_pending = s.flt_pending;
 }
 // (rr_index_destroy) every slot's buffers into ix->parked[], none left in the index fields
 void rr_slot_park(rr_index* ix) {

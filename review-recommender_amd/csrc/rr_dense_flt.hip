@@ -426,9 +426,10 @@ __global__ __launch_bounds__(RR_FLT_THREADS(NQ2), (RR_FLT_THREADS(NQ2) == 256 ? 
 }
 
 // ------------------------------------------------------------------ the filter scan over a bf16 stream: 16x16x32 tiles
-// The scan of a bf16 matrix / of the bf16 filter plane (rr_scan_flt above stays the scan of fp32 rows).  Same stream,
-// same tile words, same bound; what differs is the matrix-core tiling.  In-kernel stamps on the 32x32x16 tiling of this stream (round 2's first) showed
-// the K-loop, not HBM, pacing the two-set launch: a wave alone on its SIMD needed 45 cycles per 32-cycle MFMA, two
+// The scan of a bf16 matrix / of the bf16 filter plane for ONE set of up to 128 queries per launch (rr_scan_flt above
+// stays the scan of fp32 rows; 193 .. 256 queries over a bf16 stream go to rr_scan_fltq below).  Same stream, same tile
+// words, same bound; what differs is the matrix-core tiling.  In-kernel stamps on the 32x32x16 tiling of this stream
+// (round 2's first) showed the K-loop, not HBM, pacing the scan: a wave alone on its SIMD needed 45 cycles per 32-cycle MFMA, two
 // waves together no less -- the four v_permlane16_swap per 64 bytes of a row (the 32x32x16 A operand wants lane (row c,
 // k half h), the coalesced loads deliver (row l & 15, 16-byte piece l >> 4)) sit on the vector issue between the MFMAs.
 // v_mfma_f32_16x16x32_bf16 takes its A operand exactly as the loads deliver it (16 rows x 32 dims: lane l = row l & 15,
@@ -443,12 +444,12 @@ __global__ __launch_bounds__(RR_FLT_THREADS(NQ2), (RR_FLT_THREADS(NQ2) == 256 ? 
 // later with a counted wait (the other five groups' 20 loads, and the NQ2 tile-word stores unless they fall inside
 // the group's own K-steps, are younger): a group has most of an M-tile of time to arrive, and no burst of twelve
 // loads holds the wave's issue while the matrix pipe idles.
-template <int NQ2, int DBG = 0, bool DUAL = false>
+template <int NQ2, int DBG = 0>
 __global__ __launch_bounds__(512, 2) void rr_scan_flt16(
     const u32x4* __restrict__ mat, rr_scan_geom G, const u32x4* __restrict__ plane,   // [32*NQ2][48] units, NATURAL k order
     float* __restrict__ gmax, uint32_t* __restrict__ smax, const float* __restrict__ eps, int nq,
-    const float* __restrict__ sigma, uint32_t* __restrict__ dummy, int nq_b, int64_t gmax_set_stride,
-    uint32_t* __restrict__ prog, uint32_t seq, int tune) {
+    const float* __restrict__ sigma, uint32_t* __restrict__ dummy,
+    uint32_t* __restrict__ stamps) {                  // stamps: [n_waves][6] cycle counts of the DBG & 128 harness kernels only
     constexpr int THREADS = 512;
     constexpr int QN = 32 * NQ2;
     constexpr int NF = 2 * NQ2;                       // 16-query B fragments per K-step
@@ -456,18 +457,7 @@ __global__ __launch_bounds__(512, 2) void rr_scan_flt16(
     constexpr int STORE_KS = 4;                       // the K-step whose first NQ2 slots carry the previous M-tile's words
     __shared__ u32x4 qs[QN * RR_X3_UNITS];            // [K-step][fragment][k quarter][query of the fragment]: a fragment = 1 KiB, lane l reads unit l
     __shared__ float sg[QN];
-    int wg = blockIdx.x;
-    int set = 0;
-    if (DUAL) {                                       // workgroups b and b + 8 (same XCD): sets 0 and 1 of the same rows
-        set = (wg >> 3) & 1;
-        wg = ((wg >> 4) << 3) | (wg & 7);
-        plane += (size_t)set * (RR_FLT_MAXQ * RR_X3_UNITS);
-        eps += set * RR_FLT_MAXQ;
-        if (sigma) sigma += set * RR_FLT_MAXQ;
-        gmax += set * gmax_set_stride;
-        smax += (size_t)set * RR_FLT_MAXQ * RR_MAX_SCAN_WAVES;
-        nq = set ? nq_b : nq;
-    }
+    const int wg = blockIdx.x;
     const int tid = threadIdx.x;
     const uint64_t dbg_entry = (DBG & 128) ? __builtin_amdgcn_s_memrealtime() : 0;      // (100 MHz)
     for (int i = tid; i < QN * RR_X3_UNITS; i += THREADS) {
@@ -484,7 +474,6 @@ __global__ __launch_bounds__(512, 2) void rr_scan_flt16(
     const int64_t t0 = wave * G.tiles_per_wave;
     const int64_t t1 = t0 + G.tiles_per_wave < G.n_tiles ? t0 + G.tiles_per_wave : G.n_tiles;
     const int64_t m0 = t0 * 2, m1 = t1 * 2;           // 32-row M-tiles of this wave
-    if ((DBG & 128) && (tune & 32) && (tid >> 6) >= 4) return;     // timing only (stamped harness kernels): one wave per SIMD
 
     const int lrow = lane & 15, lpc = lane >> 4;      // load = operand order: row of the 16-row half, 16-B piece (k quarter)
     const u32x4* px;
@@ -509,16 +498,7 @@ __global__ __launch_bounds__(512, 2) void rr_scan_flt16(
     uint32_t pend[NQ2];                               // packed maxima of the 32-row tile just finished, stored one tile late
     uint32_t pend_keep = 0xFFFFFFFFu;                 // bit j: the pending word of group j is wanted (wave-uniform), see rr_scan_flt
     uint32_t junk = 0u;                               // destination of the loads that stand in for skipped stores
-    uint32_t* const my_dummy = dummy ? dummy + ((size_t)set * G.n_waves + wave) * QN : nullptr;
-    uint32_t* const my_prog = DUAL && prog ? prog + (size_t)set * G.n_waves + wave : nullptr;
-    const uint32_t* partner_prog = nullptr;
-    bool coupled = false;
-    if (DUAL && prog) {
-        const uint64_t pa = reinterpret_cast<uint64_t>(prog + (size_t)(set ^ 1) * G.n_waves + wave);
-        const uint32_t lo32 = __builtin_amdgcn_readfirstlane((uint32_t)pa), hi32 = __builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32));
-        partner_prog = reinterpret_cast<const uint32_t*>(((uint64_t)hi32 << 32) | lo32);
-        coupled = true;
-    }
+    uint32_t* const my_dummy = dummy ? dummy + (size_t)wave * QN : nullptr;
     const uint32_t code_shift = 16u + 4u * (uint32_t)h;
     const float step = rr_flt_gap_step(eps, nq);
     const float inv_step = step > 0.f ? 0.9999f / step : 0.f;
@@ -581,16 +561,7 @@ __global__ __launch_bounds__(512, 2) void rr_scan_flt16(
                     // the previous M-tile's words: NQ2 vector-memory operations, always (the ring waits count them);
                     // first M-tile of the wave: nothing pending, the stores go to its own slot
                     const int64_t mprev = mt > m0 ? mt - 1 : mt;
-                    if (DUAL && f == 0 && my_prog) {
-                        // ONE store instruction: group 0's tile words from the h == 0 lanes (if wanted) and this
-                        // wave's progress word from lane 32
-                        const bool want = !my_dummy || (pend_keep & 1u);
-                        if ((h == 0 && want) || lane == 32) {
-                            uint32_t* dst = lane == 32 ? my_prog : reinterpret_cast<uint32_t*>(gmax) + mprev * QN + c;
-                            const int64_t in_run = mt - m0 + 1;
-                            *dst = lane == 32 ? seq + (uint32_t)(in_run < 65535 ? in_run : 65535) : pend[0];
-                        }
-                    } else if (my_dummy && !((pend_keep >> f) & 1u)) {
+                    if (my_dummy && !((pend_keep >> f) & 1u)) {
                         // skipped line: a load of this wave's own line stands in (see rr_scan_flt)
                         asm volatile("global_load_dword %0, %1, off" : "+v"(junk) : "v"(my_dummy + lane) : "memory");
                     } else if (h == 0) {
@@ -672,26 +643,11 @@ __global__ __launch_bounds__(512, 2) void rr_scan_flt16(
             ts_end = __builtin_amdgcn_s_memtime();
             dbg_epi += ts_end - ts1;
         }
-        if (DUAL && coupled) {                        // the wave of the other set with the same rows: stay within L2's reach (see rr_scan_flt)
-            const int64_t in_run = mt - m0 + 1;
-            const uint32_t mine = seq + (uint32_t)(in_run < 65535 ? in_run : 65535);
-            uint32_t theirs;
-            int spins = 0;
-            for (;;) {
-                asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(theirs) : "s"(partner_prog) : "memory");
-                if ((int32_t)(theirs - mine) >= 0) break;
-                if (++spins >= 64) {
-                    coupled = false;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(8);
-            }
-        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last (redundant) loads
     asm volatile("" :: "v"(junk));
-    if ((DBG & 128) && prog && lane == 0) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(prog) + wave * 6;
+    if ((DBG & 128) && stamps && lane == 0) {
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(stamps) + wave * 6;
         o[0] = dbg_kloop; o[1] = dbg_epi; o[2] = dbg_turn; o[3] = __builtin_amdgcn_s_memtime() - dbg_t0;
         o[4] = __builtin_amdgcn_s_memrealtime() - dbg_r0; o[5] = dbg_r0 - dbg_entry;
     }
@@ -719,7 +675,7 @@ __global__ __launch_bounds__(512, 2) void rr_scan_flt16(
 //     six per wave, three M-tiles ahead in a ring of four 24 KB images; all four waves read their A operands from that one
 //     image (ds_read_b128 = 16 rows x 32 dims, one per four MFMAs, conflict-free: a piece is stored 16-byte-swizzled
 //     through its SOURCE addresses);
-//   * so the stream leaves HBM once for 256 queries without any pairing of workgroups.
+//   * so the stream leaves HBM once for 256 queries, with nothing to keep in step between workgroups.
 // MFMA shape (round 3): v_mfma_f32_16x16x32_bf16.  The kernel is not paced by its cycles but by the clock the chip holds
 // under this load (1.2 - 1.5 GHz in-kernel, profiles/r03_fltq_asm_ablations_10M.txt): the same MACs as 16x16x32 MFMAs run
 // at a ~12 % higher clock than as 32x32x16 (same cycles per FLOP; MI355X_MICROARCH.md "DVFS give-back" (7)).
@@ -1089,14 +1045,13 @@ __global__ __launch_bounds__(512, 1) void rr_flt_sample(const u32x4* __restrict_
 // slot: every thread takes the maximum of its strided share of the samples (256 values, each a sampled tile maximum),
 // and the m-th largest of those 256 -- found by counting, no bisection -- is at most the m-th largest sample (m
 // distinct samples reach it) and sits close to it (m << 256: the top samples rarely share a thread).
-// `force` (timing experiments only, RR_FLT_SIGMA_FORCE): +1 = +inf for every query (no line is kept), -1 = -inf.
 __global__ __launch_bounds__(256) void rr_flt_sigma(const float* __restrict__ samp, int n_samp, int qn, int nq, int m,
-                                                    const float* __restrict__ eps, float* __restrict__ sigma, int force) {
+                                                    const float* __restrict__ eps, float* __restrict__ sigma) {
     __shared__ uint32_t tmax[256];
     const int tid = threadIdx.x, q = blockIdx.x;
-    if (q >= nq || force > 0) { if (tid == 0) sigma[q] = INFINITY; return; }
+    if (q >= nq) { if (tid == 0) sigma[q] = INFINITY; return; }
     const float e = eps[q];
-    if (n_samp < 256 || m > 128 || force < 0 || !(e >= 0.f && e < 3.0e38f)) { if (tid == 0) sigma[q] = -INFINITY; return; }
+    if (n_samp < 256 || m > 128 || !(e >= 0.f && e < 3.0e38f)) { if (tid == 0) sigma[q] = -INFINITY; return; }
     float best = -INFINITY;
     for (int i = tid; i < n_samp; i += 256) best = fmaxf(best, samp[(int64_t)i * qn + q]);    // (fmaxf drops NaN)
     const uint32_t mine = rr_f2key(best);
@@ -1292,20 +1247,18 @@ static int rr_flt_get_bounds(rr_index* ix, hipStream_t st, rr_flt_bounds* out) {
     return RR_OK;
 }
 
-// dual: the geometry of a two-set launch (rr_scan_flt16<.., DUAL>): half the resident waves per set, runs twice as long,
-// eighth runs as selection groups (the same number and size of groups as a single-set launch)
+// geometry of rr_scan_flt / rr_scan_flt16: one run per resident wave, quarter runs as selection groups
 template <int NQ2, bool A_BF16>
-static rr_scan_geom rr_flt_geom(rr_index* ix, bool dual = false) {
+static rr_scan_geom rr_flt_geom(rr_index* ix) {
     constexpr int THREADS = RR_FLT_THREADS(NQ2);
     static int waves = 0;
     if (!waves) waves = A_BF16 ? rr_resident_waves((const void*)rr_scan_flt16<NQ2>, 512, ix->device)
                                : rr_resident_waves((const void*)rr_scan_flt<NQ2>, THREADS, ix->device);
-    rr_scan_geom G = rr_make_geom(ix, dual ? waves / 8 : waves / 4);
+    rr_scan_geom G = rr_make_geom(ix, waves / 4);
     G.qs = 32 * NQ2;
     G.mm_pairs = 3;
     // selection groups = quarter runs: ~4x fewer tile maxima to open per group (at most 8192 groups)
-    const int gcap = dual ? 8 : 4;
-    G.gpw = RR_MAX_SCAN_WAVES / G.n_waves < gcap ? (RR_MAX_SCAN_WAVES / G.n_waves < 1 ? 1 : RR_MAX_SCAN_WAVES / G.n_waves) : gcap;
+    G.gpw = RR_MAX_SCAN_WAVES / G.n_waves < 4 ? (RR_MAX_SCAN_WAVES / G.n_waves < 1 ? 1 : RR_MAX_SCAN_WAVES / G.n_waves) : 4;
     if (G.gpw > G.tiles_per_wave) G.gpw = (int32_t)G.tiles_per_wave;
     G.tiles_per_group = (G.tiles_per_wave + G.gpw - 1) / G.gpw;
     G.gpw = (int32_t)((G.tiles_per_wave + G.tiles_per_group - 1) / G.tiles_per_group);     // no empty trailing groups
@@ -1358,12 +1311,6 @@ static int rr_flt_ensure_shadow(rr_index* ix, hipStream_t st) {
     return RR_OK;
 }
 
-// RR_FLT_TUNE: debug-harness switches of the stamped rr_scan_flt16 variants only (32: one wave per SIMD)
-static int rr_flt_tune() {
-    static const int t = getenv("RR_FLT_TUNE") ? atoi(getenv("RR_FLT_TUNE")) : 0;
-    return t;
-}
-
 // SCAN_BF16: element type of the matrix the filter scan streams (the index's own bf16 rows, or the bf16 plane of an
 // fp32 index); ROWS_BF16: storage of the index, i.e. of the rows the candidates are rescored on.
 //
@@ -1376,8 +1323,7 @@ static int64_t rr_flt_smax_set_stride() { return (int64_t)RR_FLT_MAXQ * RR_MAX_S
 
 template <int NQ2, bool SCAN_BF16>
 static int rr_flt_scan_set(rr_index* ix, int set, const rr_scan_geom& G, const void* scan_mat, const float* d_q, int nq,
-                           int pool, rr_flt_bounds bounds, hipStream_t st, const float** sigma_out,
-                           bool launch_scan = true, bool allow_prefilter = true, int prep_sets = 1) {   // prep_sets: planes + bounds of 0 | this | this and the next set (one launch)
+                           int pool, rr_flt_bounds bounds, hipStream_t st, const float** sigma_out, bool allow_prefilter = true) {
     constexpr int THREADS = RR_FLT_THREADS(NQ2);
     constexpr int QN = 32 * NQ2;
     unsigned short* plane = reinterpret_cast<unsigned short*>(ix->d_qplanes) + (size_t)set * RR_FLT_MAXQ * 384;
@@ -1385,8 +1331,8 @@ static int rr_flt_scan_set(rr_index* ix, int set, const rr_scan_geom& G, const v
     float* eps = X.eps + set * RR_FLT_MAXQ;
     float* gmax = ix->d_gmax + set * rr_flt_mmax_set_stride(G);
     uint32_t* smax = ix->d_smax + set * rr_flt_smax_set_stride();
-    if (prep_sets && !ix->flt_prep_fresh)         // (rr_flt_pad_prep has done it with the padding, for every slot of the call)
-        hipLaunchKernelGGL(rr_flt_prep_queries, dim3(QN * prep_sets), dim3(64), 0, st, d_q, plane, eps, bounds);   // (planes in memory order)
+    if (!ix->flt_prep_fresh)                      // (rr_flt_pad_prep has done it with the padding, for every slot of the call)
+        hipLaunchKernelGGL(rr_flt_prep_queries, dim3(QN), dim3(64), 0, st, d_q, plane, eps, bounds);   // (planes in memory order)
     const dim3 grid((G.n_waves + THREADS / 64 - 1) / (THREADS / 64)), block(THREADS);
     // Store prefilter (bf16 stream, >= 2M rows): a 1/64 tile sample gives every query sigma = its m-th largest sampled
     // tile maximum - 2.05 eps.  The m-th largest of a 1/stride sample sits near rank m * stride of all rows; m leaves the
@@ -1408,23 +1354,18 @@ static int rr_flt_scan_set(rr_index* ix, int set, const rr_scan_geom& G, const v
         float* sg = ix->d_flt_sigma + set * RR_FLT_MAXQ;
         hipLaunchKernelGGL((rr_flt_sample<NQ2>), dim3(256), dim3(512), 0, st, reinterpret_cast<const u32x4*>(scan_mat),
                            reinterpret_cast<const u32x4*>(plane), stride, (int)n_samp, ix->d_flt_samp);
-        static const int force = getenv("RR_FLT_SIGMA_FORCE") ? atoi(getenv("RR_FLT_SIGMA_FORCE")) : 0;
-        hipLaunchKernelGGL(rr_flt_sigma, dim3(QN), dim3(256), 0, st, ix->d_flt_samp, (int)n_samp, QN, nq, m, eps, sg, force);
+        hipLaunchKernelGGL(rr_flt_sigma, dim3(QN), dim3(256), 0, st, ix->d_flt_samp, (int)n_samp, QN, nq, m, eps, sg);
         sigma = sg;
         // one line per scan wave behind the two sets of tile words (rr_ensure_scratch)
         dummy = reinterpret_cast<uint32_t*>(ix->d_gmax) + (size_t)4 * G.n_tiles * RR_FLT_MAXQ;
     }
     *sigma_out = sigma ? ix->d_flt_sigma : nullptr;        // (set 0's base: the selection adds set * RR_FLT_MAXQ itself)
-    if (!launch_scan) {                                    // the caller scans both sets in one launch
-        RR_HIP_TRY(hipGetLastError());
-        return RR_OK;
-    }
     const int slot = rr_scan_events_begin(ix, st);
     rr_scan_note(ix, 5, NQ2, nq, 1, SCAN_BF16 ? 2 : 4);
     if (SCAN_BF16)
         hipLaunchKernelGGL((rr_scan_flt16<NQ2>), grid, block, 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
-                           reinterpret_cast<const u32x4*>(plane), gmax, smax, eps, nq, sigma, dummy, 0, (int64_t)0,
-                           (uint32_t*)nullptr, 0u, rr_flt_tune());
+                           reinterpret_cast<const u32x4*>(plane), gmax, smax, eps, nq, sigma, dummy,
+                           (uint32_t*)nullptr);
     else
         hipLaunchKernelGGL((rr_scan_flt<NQ2>), grid, block, 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
                            reinterpret_cast<const u32x4*>(plane), gmax, smax, eps, nq, sigma, dummy);
@@ -1512,8 +1453,8 @@ static int rr_dense_chunk_flt_t(rr_index* ix, const void* scan_mat, const float*
     return rr_flt_after_scan<ROWS_BF16>(ix, G, d_q, nq, 0, pool, d_rows, d_scores, sigma, st, ph);
 }
 
-// The two-set launches of rr_dense_pair_flt_t (the debug harness launches them through these as well): planes, bounds and
-// [sigma] of both sets are in place.
+// The two-set launch of rr_dense_pair_flt_t (the debug harness launches it through this as well): planes and bounds of
+// both sets are in place.
 static int rr_flt_launch_fltq(rr_index* ix, const rr_scan_geom& G, const void* scan_mat, int nq_a, int nq_b, bool noasm, hipStream_t st) {
     const rr_x3_scratch X = rr_x3_scratch_of(ix);
     const int slot = rr_scan_events_begin(ix, st);
@@ -1530,65 +1471,35 @@ static int rr_flt_launch_fltq(rr_index* ix, const rr_scan_geom& G, const void* s
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }
-static int rr_flt_launch_dual(rr_index* ix, const rr_scan_geom& G, const void* scan_mat, int nq_a, int nq_b, const float* sg0, hipStream_t st) {
-    constexpr int THREADS = RR_FLT_THREADS(4);
-    const int nb = (G.n_waves + THREADS / 64 - 1) / (THREADS / 64);        // workgroups per set
-    const dim3 grid(((nb + 7) / 8) * 16), block(THREADS);
-    const rr_x3_scratch X = rr_x3_scratch_of(ix);
-    uint32_t* dummy = sg0 ? reinterpret_cast<uint32_t*>(ix->d_gmax) + (size_t)4 * G.n_tiles * RR_FLT_MAXQ : nullptr;
-    const int slot = rr_scan_events_begin(ix, st);
-    rr_scan_note(ix, 5, 8, nq_a + nq_b, 1, 2);
-    static const bool no_couple = getenv("RR_NO_COUPLE") != nullptr;
-    if (!ix->d_flt_prog) {
-        RR_HIP_TRY(hipMalloc((void**)&ix->d_flt_prog, sizeof(uint32_t) * 2 * RR_MAX_SCAN_WAVES));
-        RR_HIP_TRY(hipMemsetAsync(ix->d_flt_prog, 0, sizeof(uint32_t) * 2 * RR_MAX_SCAN_WAVES, st));
-    }
-    ix->flt_seq = (ix->flt_seq + 1) & 0x7FFFu;
-    hipLaunchKernelGGL((rr_scan_flt16<4, 0, true>), grid, block, 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
-                       reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, X.eps, nq_a, sg0, dummy,
-                       nq_b, rr_flt_mmax_set_stride(G), no_couple ? (uint32_t*)nullptr : ix->d_flt_prog,
-                       (uint32_t)(ix->flt_seq + 1) << 16, rr_flt_tune());
-    rr_scan_events_end(ix, slot, st);
-    RR_HIP_TRY(hipGetLastError());
-    return RR_OK;
-}
 
 // 129 .. 256 queries whose second part still fills a 128-slot launch (> 64 queries): two scan launches, one selection
 template <bool SCAN_BF16, bool ROWS_BF16>
 static int rr_dense_pair_flt_t(rr_index* ix, const void* scan_mat, const float* d_q, int nq_a, int nq_b, int pool,
                                int64_t* d_rows, float* d_scores, rr_flt_bounds bounds, hipStream_t st,
                                const rr_flt_phase& ph = rr_flt_phase()) {
-    // bf16 stream: both sets in ONE launch, the matrix leaves HBM once for the 256 queries (rr_scan_flt16<.., DUAL>).
-    // RR_NO_DUAL=1: two launches back to back (A/B).  An fp32 stream (no plane) keeps the two launches: its ring is
-    // two segments per M-tile and the pair's lock-step window would be twice as wide.
+    // bf16 stream: both sets in ONE launch of the query-stationary rr_scan_fltq, the matrix leaves HBM once for the 256
+    // queries.  It runs without the store prefilter: the launch is paced by the matrix side, where the skipped stores
+    // saved 0.08 ms and the two samples cost 0.125 (r02).  RR_NO_DUAL=1: two launches back to back (A/B).  An fp32
+    // stream (no plane) has no two-set kernel and takes the two launches as well.
+    // (nq_a = RR_FLT_MAXQ at every caller: the two sets' query slots, planes and bounds are contiguous)
+    RR_REQUIRE(nq_a == RR_FLT_MAXQ && nq_b >= 1 && nq_b <= RR_FLT_MAXQ, "a pair is %d + nq_b queries", RR_FLT_MAXQ);
     static const bool no_dual = getenv("RR_NO_DUAL") != nullptr;
-    const bool dual = SCAN_BF16 && !no_dual;
-    // the two-set launch runs the query-stationary kernel (rows through LDS once per CU); RR_NO_FLTQ=1: rr_scan_flt16<.., DUAL>
-    static const bool use_q = getenv("RR_NO_FLTQ") == nullptr;
-    const bool fltq = dual && use_q;
-    const rr_scan_geom G = fltq ? rr_fltq_geom(ix) : rr_flt_geom<4, SCAN_BF16>(ix, dual);
-    const float *sg0 = nullptr, *sg1 = nullptr;
-    // The store prefilter pays where the scan is HBM-bound (one set per launch: 1.41 -> 1.31 ms for 0.06 ms of sample
-    // and sigma).  The two-set launch is paced by the matrix side: there the skipped stores save 0.08 ms per launch and
-    // the two samples cost 0.125 (r02, same box: 2.74 -> 2.67 ms per step without them), so it runs without.
-    static const bool dual_prefilter = getenv("RR_DUAL_PREFILTER") != nullptr;
-    const bool pre = !dual || dual_prefilter;
-    // (nq_a = RR_FLT_MAXQ: the two sets' query slots, planes and bounds are contiguous -- one preparation launch for both
-    //  when nothing sits between them)
-    const bool prep_both = dual && !pre && nq_a == RR_FLT_MAXQ;
-    int rc = rr_flt_scan_set<4, SCAN_BF16>(ix, 0, G, scan_mat, d_q, nq_a, pool, bounds, st, &sg0, !dual, pre, prep_both ? 2 : 1);
-    if (rc != RR_OK) return rc;
-    rc = rr_flt_scan_set<4, SCAN_BF16>(ix, 1, G, scan_mat, d_q + (int64_t)nq_a * ix->dim_pad, nq_b, pool, bounds, st, &sg1, !dual, pre,
-                                       prep_both ? 0 : 1);
-    if (rc != RR_OK) return rc;
-    if (fltq) {
+    if (SCAN_BF16 && !no_dual) {
+        const rr_scan_geom G = rr_fltq_geom(ix);
+        if (!ix->flt_prep_fresh)                      // one preparation launch for both sets
+            hipLaunchKernelGGL(rr_flt_prep_queries, dim3(2 * RR_FLT_MAXQ), dim3(64), 0, st, d_q,
+                               reinterpret_cast<unsigned short*>(ix->d_qplanes), rr_x3_scratch_of(ix).eps, bounds);
         static const bool noasm = getenv("RR_FLTQ_NOASM") != nullptr;    // the C++ bodies everywhere (A/B)
-        rc = rr_flt_launch_fltq(ix, G, scan_mat, nq_a, nq_b, noasm, st);
+        const int rc = rr_flt_launch_fltq(ix, G, scan_mat, nq_a, nq_b, noasm, st);
         if (rc != RR_OK) return rc;
-    } else if (dual) {
-        rc = rr_flt_launch_dual(ix, G, scan_mat, nq_a, nq_b, sg0, st);
-        if (rc != RR_OK) return rc;
+        return rr_flt_after_scan<ROWS_BF16>(ix, G, d_q, nq_a, nq_b, pool, d_rows, d_scores, nullptr, st, ph);
     }
+    const rr_scan_geom G = rr_flt_geom<4, SCAN_BF16>(ix);
+    const float *sg0 = nullptr, *sg1 = nullptr;
+    int rc = rr_flt_scan_set<4, SCAN_BF16>(ix, 0, G, scan_mat, d_q, nq_a, pool, bounds, st, &sg0);
+    if (rc != RR_OK) return rc;
+    rc = rr_flt_scan_set<4, SCAN_BF16>(ix, 1, G, scan_mat, d_q + (int64_t)nq_a * ix->dim_pad, nq_b, pool, bounds, st, &sg1);
+    if (rc != RR_OK) return rc;
     return rr_flt_after_scan<ROWS_BF16>(ix, G, d_q, nq_a, nq_b, pool, d_rows, d_scores, sg0, st, ph);
 }
 
@@ -1697,8 +1608,7 @@ static float rr_debug_time_flt(rr_index* ix, hipStream_t st, int reps) {
         if constexpr (PLANE)
             hipLaunchKernelGGL((rr_scan_flt16<4, DBG>), grid, block, 0, st, reinterpret_cast<const u32x4*>(ix->d_shadow), G,
                                reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, rr_x3_scratch_of(ix).eps, 128,
-                               (const float*)nullptr, (uint32_t*)nullptr, 0, (int64_t)0, reinterpret_cast<uint32_t*>(d_stamps), 0u,
-                               rr_flt_tune());
+                               (const float*)nullptr, (uint32_t*)nullptr, reinterpret_cast<uint32_t*>(d_stamps));
         else
             hipLaunchKernelGGL((rr_scan_flt<4, DBG>), grid, block, 0, st, reinterpret_cast<const u32x4*>(ix->d_matrix), G,
                                reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, rr_x3_scratch_of(ix).eps, 128,
@@ -1721,7 +1631,6 @@ static float rr_debug_time_flt(rr_index* ix, hipStream_t st, int reps) {
             if (h[(size_t)6 * w + 3]) ++live;
             for (int k = 0; k < 6; ++k) sum[k] += (double)h[(size_t)6 * w + k];
         }
-        // (with RR_FLT_TUNE=32 only every other wave runs: the per-M-tile figures are then per TWO M-tiles of a running wave)
         const double tiles = (double)((G.n_rows + 31) / 32);
         fprintf(stderr, "[flt stamps] per M-tile and wave, shader cycles: K-loop %.0f, between epilogue and K-loop (or ring waits) %.0f, "
                         "epilogue %.0f; tile loop per wave %.0f cycles = %.1f us (100 MHz clock), kernel entry to the loop %.1f us, "
@@ -1850,12 +1759,13 @@ static int rr_debug_flt_single(rr_index* ix, const void* scan_mat, int nq, int p
                                rr_scan_geom* G, const float** sigma, hipStream_t st) {
     *G = rr_flt_geom<NQ2, SCAN_BF16>(ix);
     if (!launch) return RR_OK;
-    return rr_flt_scan_set<NQ2, SCAN_BF16>(ix, 0, *G, scan_mat, ix->d_q, nq, pool, nb, st, sigma, true, prefilter, 1);
+    return rr_flt_scan_set<NQ2, SCAN_BF16>(ix, 0, *G, scan_mat, ix->d_q, nq, pool, nb, st, sigma, prefilter);
 }
 
 // scan: 0 rr_scan_flt<NQ2> over the fp32 rows; 1 rr_scan_flt16<NQ2> over the bf16 plane of an fp32 index / over a bf16
-// matrix, `prefilter` != 0: with the store prefilter where the product would run it (>= 2M rows); 2 the two-set
-// rr_scan_flt16<4, 0, true>; 3 rr_scan_fltq<false>; 4 rr_scan_fltq<true>.  NQ2 = 1 | 2 | 4 for nq_a <= 32 | <= 64 | more,
+// matrix, `prefilter` != 0: with the store prefilter where the product would run it (>= 2M rows); 2 was the two-set
+// workgroup-pair form of rr_scan_flt16, which is gone (refused; the code keeps its number so that recorded logs stay
+// readable); 3 rr_scan_fltq<false>; 4 rr_scan_fltq<true>.  NQ2 = 1 | 2 | 4 for nq_a <= 32 | <= 64 | more,
 // as in rr_dense_chunk_flt; the two-set launches want nq_a = RR_FLT_MAXQ and nq_b >= 1.  The queries (device, (nq_a +
 // nq_b) x dim) go through rr_flt_pad_prep, the launch through the product's own launch code.
 // geom[16]: n_rows, n_tiles (64 rows), tiles_per_wave, n_waves, gpw, tiles_per_group, query stride, words per set
@@ -1867,6 +1777,7 @@ extern "C" int rr_debug_flt_words(rr_index* ix, const float* d_queries, int32_t 
                                   uint32_t* keys, int64_t keys_cap) {
     RR_REQUIRE(ix && geom && ix->dim_pad == 384 && ix->d_matrix, "index of dim 384 expected");
     RR_REQUIRE(scan >= 0 && scan <= 4 && nq_a >= 1 && nq_a <= RR_FLT_MAXQ && nq_b >= 0 && nq_b <= RR_FLT_MAXQ, "scan %d / %d + %d queries", scan, nq_a, nq_b);
+    RR_REQUIRE(scan != 2, "scan 2 was the two-set rr_scan_flt16, which is gone: 3 / 4 are the two-set rr_scan_fltq");
     RR_REQUIRE(scan >= 2 ? (nq_a == RR_FLT_MAXQ && nq_b >= 1) : nq_b == 0, "two-set launches take 128 + nq_b queries, the others one set");
     RR_REQUIRE(ix->scratch_q >= 64 && ix->maxima_q >= RR_FLT_MAXQ && ix->cur_slot == 0,
                "run a batched search of 64 queries or more first (allocates the scratch)");
@@ -1911,9 +1822,6 @@ extern "C" int rr_debug_flt_words(rr_index* ix, const float* d_queries, int32_t 
         rc = nq2 == 1 ? rr_debug_flt_single<1, true>(ix, scan_mat, nq_a, pool, pre, nb, launch, &G, &sg, st)
            : nq2 == 2 ? rr_debug_flt_single<2, true>(ix, scan_mat, nq_a, pool, pre, nb, launch, &G, &sg, st)
                       : rr_debug_flt_single<4, true>(ix, scan_mat, nq_a, pool, pre, nb, launch, &G, &sg, st);
-    } else if (scan == 2) {
-        G = rr_flt_geom<4, true>(ix, true);
-        if (launch) rc = rr_flt_launch_dual(ix, G, scan_mat, nq_a, nq_b, nullptr, st);
     } else {
         G = rr_fltq_geom(ix);
         if (launch) rc = rr_flt_launch_fltq(ix, G, scan_mat, nq_a, nq_b, scan == 3, st);

@@ -1,4 +1,4 @@
-"""The filter scans (csrc/rr_dense_flt.hip: rr_scan_flt, rr_scan_flt16, its two-set launch, rr_scan_fltq with the C++ bodies
+"""The filter scans (csrc/rr_dense_flt.hip: rr_scan_flt, rr_scan_flt16, the two-set rr_scan_fltq with the C++ bodies
 and with the generated loop) one launch at a time against float64: EVERY tile word and EVERY group key a launch leaves is
 decoded and held against properties P1..P6 of flt_words_model.check_words (safe and tight maximum, safe and tight gaps,
 group maxima, ragged end / NaN / sentinel), then the product's selection (rr_select_mtiles) is run on those words and its
@@ -18,13 +18,11 @@ Worst margins on hardware (a record, not a bar: the bars are the derived ones), 
 checked, tight side (bound - M8) / step, safe side (M8 - bound) / delta (P2 allows 1):
     rr_scan_flt               5.6M words   2.580   0.002
     rr_scan_flt16            55.1M words   5.230   0.003
-    rr_scan_flt16, two sets  66.5M words   5.493   0.003
     rr_scan_fltq<false>      53.9M words   5.493   0.003
     rr_scan_fltq<true>       78.1M words   5.493   0.003
 (the tight side is largest on bf16 storage with rows of norm 0.01 .. 30: one bf16 ulp of a large mx is several steps of the
 launch's smallest eps.)  On the first run rr_scan_flt and rr_scan_flt16 left bit-identical words and keys (pinned below), as did
-rr_scan_fltq's generated loop and its C++ bodies; the two-set rr_scan_flt16 and rr_scan_fltq differed in no word either
-(printed, not pinned).
+rr_scan_fltq's generated loop and its C++ bodies.
 
 Kernel-side mutations, each applied to the debug library alone, run against one test and reverted:
     rr_flt_gap_code rounding up (8.0f -> 8.999f)      every-scan[f32-unit] fails: "10708 x P2 (low)" .. "68530 x P2 (low)"
@@ -52,7 +50,7 @@ from review_recommender_amd import _lib
 from review_recommender_amd.index import ProductIndex
 lib = _lib.load()
 dev = torch.device("cuda", 0)
-KERNEL = {0: "rr_scan_flt", 1: "rr_scan_flt16", 2: "rr_scan_flt16<dual>", 3: "rr_scan_fltq<false>", 4: "rr_scan_fltq<true>"}
+KERNEL = {0: "rr_scan_flt", 1: "rr_scan_flt16", 3: "rr_scan_fltq<false>", 4: "rr_scan_fltq<true>"}      # (2 was the two-set rr_scan_flt16)
 GN = ["n_rows", "n_tiles", "tiles_per_wave", "n_waves", "gpw", "tiles_per_group", "stride", "words_per_set", "keys_per_set", "sets",
       "prefilter", "nq2", "word_sentinel", "key_sentinel", "word_set_stride", "key_set_stride"]
 P = lambda a: a.ctypes.data_as(C.c_void_p)
@@ -263,9 +261,9 @@ def _lines(out: str, tag: str):
     return [l.split("|")[1:] for l in out.splitlines() if l.startswith(tag + "|")]
 
 
-def _assert_clean(out: str, min_launches: int):
-    launches = _lines(out, "LAUNCH")
-    assert len(launches) >= min_launches, out[-2000:]
+def _assert_clean(out: str, n_launches: int):
+    launches = _lines(out, "LAUNCH")          # one line per set and per launch: exactly what the child's loops make
+    assert len(launches) == n_launches, (len(launches), out[-2000:])
     bad = [l for l in launches if l[9] != "violations=0"]
     assert not bad, "\n".join("|".join(l) for l in bad) + "\n" + "\n".join("|".join(l) for l in _lines(out, "VIOLATIONS"))
     assert all(int(l[6].split("=")[1]) > 0 for l in launches)
@@ -299,11 +297,10 @@ for nq in (5, 32, 33, 64, 65, 128):
 for nq_b in (65, 128):
     q = queries(128 + nq_b, 300 + nq_b, a_b, rows=[(1, n - 1), (130, 1003), (128 + nq_b - 1, n - 1)])
     ref, got = None, {}
-    for scan in (2, 3, 4):
+    for scan in (3, 4):
         G, eps, sigma, words, keys, ref, bad = check_launch("paired", ix, a_b, q, 128, nq_b, scan, ref=ref)
         got[scan] = words
         total += bad
-    print(f"PAIR|rr_scan_flt16<dual> vs rr_scan_fltq|nq=128+{nq_b}|words differ={int((got[2] != got[4]).sum())}", flush=True)
     print(f"PAIR|rr_scan_fltq<false> vs <true>|nq=128+{nq_b}|words differ={int((got[3] != got[4]).sum())}", flush=True)
 print("DONE", total)
 """
@@ -316,16 +313,15 @@ def test_every_scan_at_the_smallest_filter_size(bf16, norms):
     5, 32, 33, 64, 65, 128 alone and 193, 256 paired; a query that is the matrix's last row, equal rows over a tile edge and
     over the ragged end."""
     out = _child(SINGLE.replace("@N@", str(8 * 150 * 64 + 37)).replace("@BF16@", str(bf16)).replace("@NORMS@", norms), 900)
-    _assert_clean(out, 12 if bf16 else 18)
+    _assert_clean(out, 14 if bf16 else 20)
     assert "DONE 0" in out
     pairs = _lines(out, "PAIR")
     # pinned from the first hardware run: on the same plane and queries rr_scan_flt and rr_scan_flt16 leave bit-identical
-    # words and keys, and so do the generated loop and the C++ bodies of rr_scan_fltq (the two-set rr_scan_flt16 against
-    # rr_scan_fltq is printed only: both pass the properties above)
+    # words and keys, and so do the generated loop and the C++ bodies of rr_scan_fltq
     for l in pairs:
         if l[0] in ("rr_scan_flt vs rr_scan_flt16", "rr_scan_fltq<false> vs <true>"):
             assert l[2] == "words differ=0" and (len(l) < 4 or l[3] == "keys differ=0"), "|".join(l)
-    assert len(pairs) == (4 if bf16 else 10)
+    assert len(pairs) == (2 if bf16 else 8)
     assert not any("differ=-1" in f for l in pairs for f in l)
 
 
@@ -347,7 +343,7 @@ for extra, norms in ((1, ()), (31, ()), (32, ()), (33, ()), (33, (0.01, 30.0))):
         for nq_b in ((65, 128) if norms else (128,)):
             q = queries(128 + nq_b, 8 + nq_b, a_b, rows=[(0, n - 1), (127 + nq_b, n - 1)])
             ref = None
-            for scan in ((2, 3, 4) if norms else (2, 4)):
+            for scan in ((3, 4) if norms else (4,)):
                 *_, ref, bad = check_launch(tag, ix, a_b, q, 128, nq_b, scan, ref=ref)
                 total += bad
         ix.close()
@@ -359,7 +355,7 @@ def test_ragged_ends_at_300k_rows():
     """A multiple of 64 plus 1, 31, 32 and 33 rows, fp32 and bf16 storage; queries that are the last row (what a counted pad
     row would repeat).  At plus 33 also rows of norm 0.01 .. 30 with every query count and every selectable scan."""
     out = _child(RAGGED, 1500)
-    _assert_clean(out, 86)
+    _assert_clean(out, 62)
     assert "DONE 0" in out
 
 
@@ -478,7 +474,7 @@ for bf16 in (False, True):
     nq_b = 65 if bf16 else 128
     q = queries(128 + nq_b, 22, a_b, rows=[(1, n - 1), (127 + nq_b, n - 1)])
     ref = None
-    for scan in (2, 3, 4):
+    for scan in (3, 4):
         *_, ref, bad = check_launch("2.2M", ix, a_b, q, 128, nq_b, scan, ref=ref)
         total += bad
     ix.close()
@@ -487,10 +483,10 @@ print("DONE", total)
 
 
 def test_the_other_scans_at_two_million_rows():
-    """2.2M + 33 rows: rr_scan_flt on the fp32 rows, the two-set rr_scan_flt16 and rr_scan_fltq<false|true> with 256 queries
+    """2.2M + 33 rows: rr_scan_flt on the fp32 rows and rr_scan_fltq<false|true> with 256 queries
     (fp32 storage) and 193 (bf16 storage); rr_scan_flt16 alone at this size is the prefilter test's."""
     out = _child(BIG, 1500)
-    _assert_clean(out, 13)
+    _assert_clean(out, 9)
     assert "DONE 0" in out
 
 
@@ -501,7 +497,7 @@ total = 0
 for bf16 in (False, True):
     ix, a_b = make_index(mat, bf16)
     warm(ix)
-    for nq_a, nq_b, scan in ((64, 0, 1), (128, 128, 4), (128, 65, 2)):
+    for nq_a, nq_b, scan in ((64, 0, 1), (128, 128, 4), (128, 65, 4)):
         q = queries(nq_a + nq_b, 50 + nq_b, a_b, rows=[(1, n - 1)])
         G, eps, sigma, words, keys, ref, bad = check_launch("selection", ix, a_b, q, nq_a, nq_b, scan, pool=pool)
         total += bad
@@ -530,7 +526,7 @@ def test_selection_on_the_words_lists_what_it_must_and_no_more():
     model's may-open count stays below RR_X3_MCAP / 2 and its group count below RR_SEL_LCAP / 2.  With 20 000 copies of
     one row, the flag of the query that is that row is up and its neighbours' are down."""
     out = _child(SELECTION, 1500)
-    _assert_clean(out, 9)
+    _assert_clean(out, 11)
     assert len(_lines(out, "SELECT")) == 7
     ties = _lines(out, "TIES")[0][0]
     assert ties[0] == "1" and set(ties[1:]) == {"0"}, ties

@@ -589,6 +589,64 @@ int rr_products_concat_dev(rr_products* pb, const uint8_t* d_text, int64_t text_
  * write no text either: ask after every concatenation whose text is used. */
 int rr_products_status(rr_products* pb, int32_t* out_bad);
 
+/* ------------------------------------------------------------ the attribute gate: plane and match (csrc/rr_gate.hip) */
+
+/* calculate_gate_factor (utils.py:88-101; app/app_product_search.py:297-302, app/test.py:292-297) on the device: a group of
+ * terms hits when any of its terms occurs as a substring of agg_text[:6000].lower(); factor = penalty ** (groups missed).
+ * gate.model_gate_plane / gate.model_gate_hits state both halves in Python.  The calls of one handle must be stream-ordered.
+ *
+ * THE PLANE, once per index: for every document the byte image of its first max_chars code points (code points = the bytes
+ * that are not 10xxxxxx), back to back with int64 offsets, such that for every string s of ASCII characters
+ * s in text[:max_chars].lower() <=> s's bytes occur in the image:  A-Z -> a-z;  C4 B0 (U+0130) -> 69 B0 (lower() gives 'i' +
+ * U+0307);  E2 84 AA (U+212A) -> 6B ('k', its two continuation bytes dropped);  every other byte -> itself.  Those two are
+ * the only code points outside ASCII whose lower() holds an ASCII character.  The image need not be valid UTF-8, and the
+ * text is not validated: it comes from a Python str (`surrogatepass` where needed), so no document is left to the host.
+ *   rr_gate_measure_dev  pass 1 over the text in the layout rr_wp_encode_dev reads: the images' lengths and their exclusive
+ *                        int64 sum into d_plane_off [n_docs + 1], the total also into d_total[0] (device) -- the only number
+ *                        the host reads back, to size the plane: total + the slack of rr_gate_limits, 16-byte aligned;
+ *   rr_gate_write_dev    pass 2 over the same text and offsets: the images into d_plane (capacity plane_bytes; too small =
+ *                        nothing is written and rr_gate_status fails).
+ * A workgroup per document walks it in steps and stops at the step that holds code point max_chars + 1 (a 100 KB agg_text
+ * is read to its 6000th code point).  A document whose offsets decrease or leave [0, text_bytes] is not read, has an empty
+ * image and is counted by rr_gate_status.  n_docs = 0 gives d_plane_off = [0].
+ *
+ * THE MATCH, per batch: rr_gate_factors_dev.  d_rows [n_queries x pool] int64 GLOBAL rows; candidate row r reads document
+ * r - row_offset.  The batch's terms, packed (gate.pack_groups): d_term_bytes, d_term_off int32 [T + 1], d_term_group int32
+ * [T] (the group 0..5 of each term), d_q_term int32 [n_queries + 1] (query q owns terms d_q_term[q] .. d_q_term[q + 1]),
+ * d_q_groups int32 [n_queries] (its number of groups, 0..6), d_factor float32 [n_queries x 7]: d_factor[q][m] = the factor
+ * of m missed groups, filled by the host with the reference's arithmetic (a Python float, factor *= penalty left to right,
+ * one float32 cast).  Writes d_gate [n_queries x pool] float32 = d_factor[q][groups missed] -- the kernel does no floating
+ * point, the value is bitwise the reference's -- and, when d_hits is not NULL, d_hits [n_queries x pool] int32 = the bit
+ * mask of the groups that hit.  A query with 0 groups gives d_factor[q][0] (1.0) and reads no text.  A row outside
+ * [row_offset, row_offset + n_docs) reads no text, misses every group and is counted by rr_gate_status; so is a query whose
+ * packing exceeds rr_gate_limits, has a zero-length term, a byte >= 0x80 or a group outside [0, groups): it is answered
+ * d_factor[q][0] (the Python side checks all of that before the call and gates such a query on the host).
+ * One wave per (query, candidate), four candidates of a query per workgroup, the terms in LDS; the image is read in aligned
+ * 16-byte words, and the bytes of a boundary word that belong to a neighbouring document are replaced by FF before anything
+ * is compared, so a match never runs into the next or the previous document.  No result depends on scheduling.
+ * Asynchronous on `stream`; no host wait, no allocation. */
+typedef struct rr_gate rr_gate;
+int rr_gate_create(int32_t device, rr_gate** out);
+int rr_gate_destroy(rr_gate* g);
+/* Bytes of a document per step of the plane kernels, bytes of an image per step of a wave of the match, consecutive bytes per
+ * thread (both), the longest term in bytes, term bytes per query, terms per query, readable bytes the plane needs behind
+ * its last document. */
+int rr_gate_limits(int32_t* out_plane_step, int32_t* out_match_step, int32_t* out_per_thread, int32_t* out_max_term,
+                   int32_t* out_term_bytes, int32_t* out_max_terms, int32_t* out_slack);
+int rr_gate_measure_dev(rr_gate* g, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off, int32_t n_docs,
+                        int32_t max_chars, int64_t* d_plane_off, int64_t* d_total, void* stream);
+int rr_gate_write_dev(rr_gate* g, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off, int32_t n_docs,
+                      int32_t max_chars, const int64_t* d_plane_off, uint8_t* d_plane, int64_t plane_bytes, void* stream);
+/* plane_bytes = the images' total (d_plane_off[n_docs]); d_plane must be 16-byte aligned and readable for the slack behind
+ * it.  d_plane, d_term_bytes and d_term_group must not be NULL even when they hold nothing. */
+int rr_gate_factors_dev(rr_gate* g, const uint8_t* d_plane, const int64_t* d_plane_off, int64_t plane_bytes, int32_t n_docs,
+                        int64_t row_offset, const int64_t* d_rows, int32_t n_queries, int32_t pool, const uint8_t* d_term_bytes,
+                        const int32_t* d_term_off, const int32_t* d_term_group, const int32_t* d_q_term,
+                        const int32_t* d_q_groups, const float* d_factor, float* d_gate, int32_t* d_hits, void* stream);
+/* Waits for the device; RR_E_INVALID when a call since the last one refused a document, a plane buffer, a candidate row or a
+ * query's packing (*out_bad = how many). */
+int rr_gate_status(rr_gate* g, int32_t* out_bad);
+
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard
  * that selects on its own rescoring ~8x the candidates the merged answer needs.  Instead:

@@ -129,6 +129,13 @@ PROTOTYPES = {
     "rr_doctok_vocab_dev": (C.c_int, [c_vp, c_i32, c_vp, c_vp]),
     "rr_doctok_copy_vocab": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "rr_doctok_copy_tokens": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "rr_gate_create": (C.c_int, [c_i32, P(c_vp)]),
+    "rr_gate_destroy": (C.c_int, [c_vp]),
+    "rr_gate_limits": (C.c_int, [P(c_i32)] * 7),
+    "rr_gate_measure_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rr_gate_write_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "rr_gate_factors_dev": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_i32] + [c_vp] * 9),
+    "rr_gate_status": (C.c_int, [c_vp, P(c_i32)]),
     "rr_index_stream": (C.c_int, [c_vp, P(c_vp)]),
     "rr_index_synchronize": (C.c_int, [c_vp]),
 }

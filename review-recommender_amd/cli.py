@@ -54,6 +54,10 @@ def parse_args(argv=None):
     ap.add_argument("--ce-precision", choices=["fp32", "bf16"], default="fp32",
                     help="arithmetic of the two GPU encoders: fp32 = the reference's (logits / embeddings within 1e-5 of "
                          "transformers; ~6x the time of bf16), bf16 = the fast path (2.5e-2 on logits)")
+    ap.add_argument("--gate", choices=["host", "device"], default="host",
+                    help="where the attribute gate's terms are matched: host = str.lower() and substring searches in Python "
+                         "(the reference's way), device = a gate plane of agg_text[:6000] on the GPU (csrc/rr_gate.hip; up to "
+                         "6 KB of device memory per product); the same results")
     ap.add_argument("--allow-hub", action="store_true",
                     help="opt in to sentence-transformers by model name (EMB_MODEL / RERANK_MODEL, app/test.py:28-29) for "
                          "whatever model no local directory was given; off by default: the product path is the GPU one")
@@ -99,7 +103,7 @@ def main(argv=None) -> int:
                          "--qvec-npy (or opt in to the hub loader with --allow-hub)")          # app/test.py:234-235
     try:
         engine = SearchEngine.from_artifacts(args.data_dir, encoder=enc, cross_encoder=ce, flavour="cli",
-                                             device=args.device)
+                                             device=args.device, gate=args.gate)
     except ArtifactError as e:
         raise SystemExit(f"[ERR] {e}")
     # snippets are scored whenever the review file exists and --no-snippets is absent (app/test.py:271-276)

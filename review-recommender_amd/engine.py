@@ -10,7 +10,8 @@ Boundary kept:
 
 Per query batch the device does K1 (dense scan + exact top-pool), K2 (BM25 at the
 pool), K3 (min-max, priors, trust, blend, gate, top-k) back to back on one HIP stream;
-the host only tokenises, matches gate strings and builds the result frame.
+the host only tokenises and builds the result frame.  The attribute gate is matched on the device between K2 and K3
+(gate="device": gate.py, csrc/rr_gate.hip) or, by default, by the host function between the two.
 torch is used for device buffers and streams only.
 """
 from __future__ import annotations
@@ -100,10 +101,11 @@ class StagedBatch:
 class HybridSearcher:
     """K1 -> K2 -> K3 on one GPU over a ProductIndex (+ optional BM25Index)."""
 
-    def __init__(self, index: ProductIndex, bm25: Optional[BM25Index] = None):
+    def __init__(self, index: ProductIndex, bm25: Optional[BM25Index] = None, gate_text=None):
+        """``gate_text``: a gate.GateText over the index's rows, for ``search_batch(gate_groups=...)``."""
         if not index.has_meta:
             raise ValueError("the index needs metadata (ProductIndex.set_meta) before searching")
-        self.index, self.bm25 = index, bm25
+        self.index, self.bm25, self.gate_text = index, bm25, gate_text
         self.lib = _lib.load()
         torch = _torch()
         if not torch.cuda.is_available():
@@ -378,10 +380,16 @@ class HybridSearcher:
                      gate_fn: Optional[Callable[[np.ndarray], np.ndarray]] = None,
                      rerank_fn: Optional[Callable[[np.ndarray], np.ndarray]] = None,
                      bm25_mode: str = "forward", reviews=None, max_scan: int = 0,
-                     bm25_f64: bool = False) -> BatchResult:
+                     bm25_f64: bool = False, gate_groups=None,
+                     gate_host: Optional[Callable[[int, np.ndarray], np.ndarray]] = None) -> BatchResult:
         """qvecs (B, dim) float32; term_id_lists: per-query BM25 token ids (None = no BM25).
         gate_fn / rerank_fn map the (B, pool) pool rows to (B, pool) float32 gate factors /
         (B, rr_k) raw reranker scores; they run on the host between K2 and K3.
+        ``gate_groups`` (instead of gate_fn): per query its gate groups (text.build_gate_groups); they are matched against
+        the searcher's ``gate_text`` on the device (rr_gate_factors_dev, queued between K2 and K3; the penalty is
+        ``weights.gate_penalty``) and the rows stay on the device.  A query over a limit of that kernel (gate.pack_groups:
+        ``host_queries``) gets its row of the gate tensor from ``gate_host(b, rows[b]) -> (pool,) float32`` instead; only
+        then are the rows copied to the host.
         ``bm25_f64``: the CLI flavour without a BM25 artefact (float64 zeros column, app/test.py:252)."""
         torch = _torch()
         w = weights or FusionWeights()
@@ -396,8 +404,23 @@ class HybridSearcher:
             raise ValueError(f"pool {pool} exceeds the kernels' limit {MAX_POOL}")
         k_eff = min(k, pool)
         rr_k = min(rerank_k, pool)
+        packed = None
+        if gate_groups is not None:
+            from .gate import pack_groups
+            if gate_fn is not None:
+                raise ValueError("pass either gate_fn or gate_groups")
+            if self.gate_text is None:
+                raise ValueError("gate_groups need a gate plane: HybridSearcher(..., gate_text=GateText...)")
+            if len(gate_groups) != B:
+                raise ValueError(f"{len(gate_groups)} gate groups for {B} queries")
+            packed = pack_groups(gate_groups, w.gate_penalty)
+            if packed.host_queries and gate_host is None:
+                raise ValueError(f"queries {packed.host_queries} exceed the gate kernel's limits and no gate_host was given")
+            if not packed.any_groups and not packed.host_queries:
+                packed = None                    # nothing to match: no gate, as with gate_fn=None
         with torch.cuda.device(self.device):
             q_dev = torch.from_numpy(q).to(self.device)
+            staged_groups = self.gate_text.upload(packed) if packed is not None else None    # (ahead of the kernels)
             rows, dense = self.dense_pool(q_dev, pool)
             tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
             bm = self.bm25_at(tl, rows, bm25_mode)
@@ -413,6 +436,8 @@ class HybridSearcher:
                     reviews.handle, C.c_void_p(q_dev.data_ptr()), B, C.c_void_p(rows.data_ptr()), pool,
                     self.index.row_offset, int(max_scan), C.c_void_p(best.data_ptr()),
                     C.c_void_p(best_ids.data_ptr()), self._stream()), "rr_reviews_best_cut_dev")
+            if packed is not None:
+                gate = self.gate_text.gate(rows, packed, gate_host, staged_groups)
             if gate_fn is not None or (rerank_fn is not None and rr_k > 0):
                 rows_h = rows.cpu().numpy() if rows_h is None else rows_h
                 if gate_fn is not None:
@@ -442,12 +467,16 @@ class SearchEngine:
     cross_encoder: object with ``predict(pairs, batch_size=64, show_progress_bar=False)``.
     bm25_build: "device" builds the BM25 index on the GPU (bm25.build_bm25_index), "host" with
     BM25Corpus.from_corpus; the two give bitwise the same index.
+    gate: "host" (the default) matches the gate terms with `text.calculate_gate_factor` between K2 and K3; "device" builds a
+    gate plane of ``meta["agg_text"]`` on the GPU (gate.GateText, up to 6 KB of device memory per product; ``gate_max_bytes``
+    refuses a larger one) and matches there (csrc/rr_gate.hip).  The two give bitwise the same frames.
     """
 
     def __init__(self, meta: pd.DataFrame, embeddings: np.ndarray, bm25_blob: Optional[dict] = None,
                  *, encoder=None, cross_encoder=None, device: int = 0, normalize: bool = True,
                  flavour: str = "app", dtype: str = "f32", reviews: Optional[Tuple] = None,
-                 bm25_build: str = "device", index: Optional[ProductIndex] = None, bm25_ids: Optional[Tuple] = None):
+                 bm25_build: str = "device", index: Optional[ProductIndex] = None, bm25_ids: Optional[Tuple] = None,
+                 gate: str = "host", gate_max_bytes: Optional[int] = None):
         """``index``: a ready ProductIndex (embed.build_product_embeddings) to use instead of uploading ``embeddings``
         (then None); it is taken as it is -- ``normalize`` and ``dtype`` describe an upload only.
         ``bm25_ids``: ``(skus, tok, doc_off, vocab)`` instead of ``bm25_blob`` -- the corpus as token ids (numpy arrays or
@@ -456,6 +485,8 @@ class SearchEngine:
             raise ValueError("flavour must be 'app' or 'cli'")
         if bm25_build not in ("device", "host"):
             raise ValueError("bm25_build must be 'device' or 'host'")
+        if gate not in ("device", "host"):
+            raise ValueError("gate must be 'device' or 'host'")
         if (index is None) == (embeddings is None):
             raise ValueError("pass either an embedding matrix or a ready index")
         n_emb = embeddings.shape[0] if index is None else index.n_rows
@@ -500,7 +531,13 @@ class SearchEngine:
             else:
                 self._bm25_corpus = BM25Corpus.from_corpus(bm25_blob["corpus"])
                 bm25_index = self._bm25_corpus.select(order).to_device(device)
-        self.searcher = HybridSearcher(self.index, bm25_index)
+        self.gate = gate
+        gate_text = None
+        if gate == "device":
+            from .gate import GateText
+            gate_text = GateText.from_texts(self._texts.tolist(), self.index.device, max_bytes=gate_max_bytes,
+                                            row_offset=self.index.row_offset)
+        self.searcher = HybridSearcher(self.index, bm25_index, gate_text)
         # reviews = (frame with sku/text/stars, (n_reviews, dim) embeddings): reviews_with_embeddings.parquet
         self.reviews = None
         if reviews is not None:
@@ -590,19 +627,34 @@ class SearchEngine:
             raise ValueError("no query encoder was given; use search_by_vector / pass qvec")
         return np.asarray(self.encoder.encode([query], normalize_embeddings=True)[0], dtype=np.float32)
 
-    def _gate_fn(self, query: str, penalty: float):
-        groups = text.build_gate_groups(query)
+    def _gate_rows(self, groups, penalty: float, rows: np.ndarray) -> np.ndarray:
+        """The host gate: float32 (len(rows),) factors of one query's groups at these rows."""
+        if not groups:
+            return np.ones(len(rows), dtype=np.float32)
+        texts = self._texts.iloc[rows].str.slice(0, 6000).tolist()
+        return np.array([text.calculate_gate_factor(t, groups, penalty)[0] for t in texts], dtype=np.float32)
+
+    def _gate_args(self, groups_per_query, penalty: float) -> dict:
+        """search_batch's gate arguments for these queries' groups: the device match when the engine has a gate plane,
+        else the host function, each query's groups on its own row of the pool."""
+        if not any(groups_per_query):
+            return {}
+        if self.searcher.gate_text is not None:
+            return {"gate_groups": groups_per_query,
+                    "gate_host": lambda b, rows: self._gate_rows(groups_per_query[b], penalty, rows)}
+        return {"gate_fn": lambda rows: np.stack([self._gate_rows(g, penalty, r) for g, r in zip(groups_per_query, rows)])}
+
+    def _rerank_batch_fn(self, queries: Sequence[str]):
+        if self.cross_encoder is None:
+            return None   # model missing -> zeros (app/app_product_search.py:275)
 
         def fn(rows: np.ndarray) -> np.ndarray:
-            out = np.ones(rows.shape, dtype=np.float32)
-            if not groups:
-                return out
-            for b in range(rows.shape[0]):
-                texts = self._texts.iloc[rows[b]].str.slice(0, 6000).tolist()
-                out[b] = np.array([text.calculate_gate_factor(t, groups, penalty)[0] for t in texts],
-                                  dtype=np.float32)
-            return out
-        return groups, fn
+            # the (query, text[:2000]) pairs of EVERY query of the batch in one predict call
+            texts = self._texts.iloc[rows.reshape(-1)].str.slice(0, 2000).tolist()
+            pairs = [(queries[i // rows.shape[1]], t) for i, t in enumerate(texts)]
+            scores = np.asarray(self.cross_encoder.predict(pairs, batch_size=64, show_progress_bar=False), dtype=np.float32)
+            return scores.reshape(rows.shape)
+        return fn
 
     def _rerank_fn(self, query: str):
         if self.cross_encoder is None:
@@ -635,16 +687,15 @@ class SearchEngine:
         term_ids = None
         if self.searcher.bm25 is not None:
             term_ids = [self.searcher.bm25.term_ids(toks)]
-        groups, gate_fn = self._gate_fn(query, gate_penalty)
+        groups = text.build_gate_groups(query)
         w = FusionWeights(w_dense, w_bm25, w_rerank, w_prior, w_best, prior_C, min_reviews,
                           gate_penalty, APP_TRUST_SAT, app)
         res = self.searcher.search_batch(
             qv[None, :], term_ids, k, rerank_k, w,
             pool_floor=APP_POOL_FLOOR if app else CLI_POOL_FLOOR,
-            gate_fn=gate_fn if groups else None,
             rerank_fn=self._rerank_fn(query) if rerank_k > 0 else None,
             reviews=self.reviews if use_snips else None, max_scan=max_scan,
-            bm25_f64=not app)
+            bm25_f64=not app, **self._gate_args([groups], gate_penalty))
         frame = self._frame(res, 0, rerank_k > 0)
         snips = {}
         if res.best_ids is not None:
@@ -654,6 +705,52 @@ class SearchEngine:
                "groups": [list(g) for g in groups], "pool": max(k, rerank_k,
                                                               APP_POOL_FLOOR if app else CLI_POOL_FLOOR)}
         return frame, snips, dbg
+
+    def run_search_batch(self, queries: Sequence[str], k: int, rerank_k: int, w_dense: float, w_bm25: float,
+                         w_rerank: float, w_prior: float, w_best: float, prior_C: float,
+                         use_snips: bool = False, max_scan: int = 0, min_reviews: int = 8,
+                         gate_penalty: float = 0.5, *, qvecs: Optional[np.ndarray] = None
+                         ) -> List[Tuple[pd.DataFrame, Dict, Dict]]:
+        """`run_search` for a batch of queries with the same parameters: per query the triple `run_search` returns.
+        The queries are encoded in ONE encoder call (unless ``qvecs`` (B, dim) is given), searched in one `search_batch`
+        -- with gate="device" the gate terms of all of them are matched in one kernel launch -- and the reranker pairs of
+        all of them go through one `predict`."""
+        app = self.flavour == "app"
+        queries = list(queries)
+        if not queries:
+            return []
+        if qvecs is None:
+            if self.encoder is None:
+                raise ValueError("no query encoder was given; pass qvecs")
+            qv = np.asarray(self.encoder.encode(queries, normalize_embeddings=True), dtype=np.float32)
+        else:
+            qv = np.asarray(qvecs, dtype=np.float32)
+        if qv.shape[0] != len(queries):
+            raise ValueError(f"{qv.shape[0]} query vectors for {len(queries)} queries")
+        toks = [text.tokenize_query(q) for q in queries]
+        term_ids = None
+        if self.searcher.bm25 is not None:
+            term_ids = [self.searcher.bm25.term_ids(t) for t in toks]
+        groups = [text.build_gate_groups(q) for q in queries]
+        w = FusionWeights(w_dense, w_bm25, w_rerank, w_prior, w_best, prior_C, min_reviews,
+                          gate_penalty, APP_TRUST_SAT, app)
+        floor = APP_POOL_FLOOR if app else CLI_POOL_FLOOR
+        res = self.searcher.search_batch(
+            qv, term_ids, k, rerank_k, w, pool_floor=floor,
+            rerank_fn=self._rerank_batch_fn(queries) if rerank_k > 0 else None,
+            reviews=self.reviews if use_snips else None, max_scan=max_scan,
+            bm25_f64=not app, **self._gate_args(groups, gate_penalty))
+        out = []
+        for b in range(len(queries)):
+            frame = self._frame(res, b, rerank_k > 0)
+            snips = {}
+            if res.best_ids is not None:
+                skus = self.meta["sku"].astype(str).iloc[res.pool_rows[b]].tolist()
+                snips = self.reviews.snippets(skus, res.best_ids[b], res.best_raw[b], 600 if app else 400)
+            dbg = {"bm25_active": self.searcher.bm25 is not None, "tokens": toks[b],
+                   "groups": [list(g) for g in groups[b]], "pool": max(k, rerank_k, floor)}
+            out.append((frame, snips, dbg))
+        return out
 
     def _frame(self, res: BatchResult, b: int, rerank_active: bool = False) -> pd.DataFrame:
         top = res.order[b].astype(np.int64)

@@ -1,8 +1,10 @@
 """Host-side query text handling of the hot path (a4, a10, a11).
 
-These are string operations on one query and <= pool short texts; they stay on
-the host (the reference does them in Python too) and feed the HIP kernels with
-token ids and one gate factor per candidate.
+String operations on one query: tokens, gate groups.  They stay on the host (the reference does them in Python too) and
+feed the HIP kernels with token ids and gate terms.  `calculate_gate_factor`, the one function here that reads product
+texts (<= pool of them per query, 6000 characters each), is the host form of the gate (SearchEngine(gate="host"), the
+default, and ShardedSearcher); gate.py / csrc/rr_gate.hip match the same terms on the device (gate="device") and give
+bitwise the same factors.
 
   tokenize_query        utils.py:57-60   (= _tokenize app/app_product_search.py:189-190)
   tokenize_document     nlp/12_product_prep.py:75-78  (index-time tokenizer)

@@ -329,8 +329,9 @@ int rr_reviews_best_cut_dev(rr_reviews* rv, const float* d_queries, int32_t n_qu
  *     (BAAI/bge-small-en-v1.5: BertModel of the same block shape, 12 layers, CLS pooling; the l2 normalisation is the caller's)
  * The kernels are built for hidden 384 / 12 heads x 32 / FFN 1536; layer count, vocabulary, positions (<= 512) are free.
  * Tokenisation (WordPiece): rr_wp_encode_dev below turns documents (ASCII, or UTF-8 on a handle of rr_wp_create_utf8) into
- * the packed ids this call takes, on the device (csrc/rr_wordpiece.hip); what it flags and text PAIRS (the reranker) are tokenised on the host
- * (review-recommender_amd/wordpiece.py). */
+ * the packed ids this call takes, on the device (csrc/rr_wordpiece.hip); what it flags is tokenised on the host
+ * (review-recommender_amd/wordpiece.py).  Text PAIRS (the reranker): rr_pairs_measure_dev / rr_pairs_write_dev below assemble
+ * them on the device from the token plane of an index and the queries' ids; without a plane they are tokenised on the host. */
 typedef struct rr_ce rr_ce;
 typedef struct rr_ce_config {
     int32_t hidden, n_layers, n_heads, ffn;       /* 384, L, 12, 1536 */
@@ -646,6 +647,56 @@ int rr_gate_factors_dev(rr_gate* g, const uint8_t* d_plane, const int64_t* d_pla
 /* Waits for the device; RR_E_INVALID when a call since the last one refused a document, a plane buffer, a candidate row or a
  * query's packing (*out_bad = how many). */
 int rr_gate_status(rr_gate* g, int32_t* out_bad);
+
+/* ------------------------------------------------------------ the reranker's pairs: token plane and assembly (csrc/rr_pairs.hip) */
+
+/* What CrossEncoder.predict does in front of the model as run_search calls it (app/app_product_search.py:272-278,
+ * app/test.py:223-225): the pairs (query, agg_text[:2000]) as `[CLS] query [SEP] text [SEP]`, truncated `longest_first` to
+ * max_length, packed as rr_ce_forward_dev takes them.  rerank.model_plane / rerank.model_pairs state both halves in numpy.
+ * The calls of one handle must be stream-ordered.
+ *
+ * THE TOKEN PLANE, once per index (rerank.RerankText builds it with rr_wp_encode_dev): for every document the WordPiece ids
+ * of its first 2000 code points, the first max_length - 3 of them (no longer text side survives the truncation), as uint16
+ * back to back in d_plane_tok, with int64 offsets d_plane_off [n_docs + 1].  Document i is the product of global row
+ * row_offset + i.
+ *
+ * THE ASSEMBLY, per batch.  d_rows [n_queries x pool] int64 GLOBAL rows, of which the first rr_k <= pool of every query are
+ * reranked: pair p of the flattened list is (query b = p / rr_k, candidate j = p % rr_k) and reads d_rows[b * pool + j].  A
+ * call serves the pairs [first_pair, first_pair + n_pairs), any range of the n_queries x rr_k, one that begins and ends
+ * inside a query included (the caller chunks with it).  The queries' ids: d_q_tok int32, d_q_off int32 [n_queries + 1].
+ *   rr_pairs_measure_dev  d_keep [n_pairs][2] int32 = the query and text tokens pair first_pair + i keeps, by the rule of
+ *                         `longest_first` as wordpiece.py states it, with avail = max_length - 3: cut only when
+ *                         n_a + n_b > avail; n1 = the shorter side, n2 = the longer (the text on a tie); n2 = n1 if
+ *                         n1 > avail else max(n1, avail - n1); if n1 + n2 > avail still, n1 = avail / 2 and
+ *                         n2 = n1 + avail % 2.  d_cu [n_pairs + 1] int32 = the exclusive sum of the sequence lengths
+ *                         keep_a + keep_b + 3.  The host reads back ONE number, d_cu[n_pairs]: it sizes the three id arrays
+ *                         and is the n_tokens of rr_ce_forward_dev.  n_b is what the plane holds, min(tokens, avail): the
+ *                         rule answers the same for both whenever n_a <= avail, so a query of more than avail tokens is
+ *                         not for this call (rerank.pack_queries hands it to the host).
+ *   rr_pairs_write_dev    the sequences into d_tok / d_typ / d_pos (capacity n_tokens each): [CLS], the kept query ids,
+ *                         [SEP], the kept text ids widened from uint16, [SEP]; type 0 up to and including the first [SEP],
+ *                         1 behind it; position = index inside the sequence.  One wave per pair, lanes striding over the
+ *                         sequence: the text reads and the three int32 stores are contiguous per wave.
+ * A row outside [row_offset, row_offset + n_docs) reads no text, gives [CLS] query [SEP] [SEP] and is counted by
+ * rr_pairs_status; a pair whose d_keep / d_cu do not fit the offsets or n_tokens is not written and counted too.  Limits the
+ * host can check are RR_E_INVALID with nothing written: rr_k outside 1..pool, a range outside n_queries x rr_k,
+ * max_length < 3, n_pairs * max_length beyond int32, n_tokens above 2^27 (rr_ce_forward_dev's fp32 call limit).
+ * Asynchronous on `stream`; no host wait, except that the first measure of a larger n_pairs grows the scan's scratch. */
+typedef struct rr_pairs rr_pairs;
+int rr_pairs_create(int32_t device, rr_pairs** out);
+int rr_pairs_destroy(rr_pairs* h);
+int rr_pairs_measure_dev(rr_pairs* h, const int64_t* d_plane_off, int32_t n_docs, int64_t row_offset, const int64_t* d_rows,
+                         int32_t pool, int32_t rr_k, const int32_t* d_q_off, int32_t n_queries, int32_t max_length,
+                         int64_t first_pair, int32_t n_pairs, int32_t* d_keep, int32_t* d_cu, void* stream);
+/* d_plane_tok and d_q_tok must not be NULL even when they hold nothing. */
+int rr_pairs_write_dev(rr_pairs* h, const uint16_t* d_plane_tok, const int64_t* d_plane_off, int32_t n_docs, int64_t row_offset,
+                       const int64_t* d_rows, int32_t pool, int32_t rr_k, const int32_t* d_q_tok, const int32_t* d_q_off,
+                       int32_t n_queries, int32_t cls_id, int32_t sep_id, int64_t first_pair, int32_t n_pairs,
+                       const int32_t* d_keep, const int32_t* d_cu, int64_t n_tokens, int32_t* d_tok, int32_t* d_typ,
+                       int32_t* d_pos, void* stream);
+/* Waits for the device; RR_E_INVALID when a call since the last one met a row outside the plane or refused a pair
+ * (*out_bad = how many). */
+int rr_pairs_status(rr_pairs* h, int32_t* out_bad);
 
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard

@@ -136,6 +136,13 @@ PROTOTYPES = {
     "rr_gate_write_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "rr_gate_factors_dev": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_i32] + [c_vp] * 9),
     "rr_gate_status": (C.c_int, [c_vp, P(c_i32)]),
+    "rr_pairs_create": (C.c_int, [c_i32, P(c_vp)]),
+    "rr_pairs_destroy": (C.c_int, [c_vp]),
+    "rr_pairs_measure_dev": (C.c_int, [c_vp, c_vp, c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, c_vp, c_vp,
+                                       c_vp]),
+    "rr_pairs_write_dev": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64,
+                                     c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rr_pairs_status": (C.c_int, [c_vp, P(c_i32)]),
     "rr_index_stream": (C.c_int, [c_vp, P(c_vp)]),
     "rr_index_synchronize": (C.c_int, [c_vp]),
 }

@@ -182,7 +182,7 @@ class BertEncoderGPU:
     def forward_packed_dev(self, tok, typ, pos, cu, n_seqs: int, max_len: int, mode: int = OUT_LOGITS):
         """Forward over sequences that are already packed ON THE DEVICE (int32 torch tensors: token ids, type ids,
         position ids per token; cu_seqlens per sequence): returns a device tensor, no host hop.  Asynchronous on
-        torch's current stream.  Used where the pairs are assembled on the GPU (bench.py's rerank mode).  `max_len` must
+        torch's current stream.  Used where the pairs are assembled on the GPU (rerank.RerankText.scores, bench.py's rerank mode).  `max_len` must
         be at least every sequence's length (`out_of_range` reports a shorter one as a ValueError)."""
         torch = self._torch
         n_tokens = int(tok.numel())

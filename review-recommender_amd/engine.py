@@ -11,7 +11,8 @@ Boundary kept:
 Per query batch the device does K1 (dense scan + exact top-pool), K2 (BM25 at the
 pool), K3 (min-max, priors, trust, blend, gate, top-k) back to back on one HIP stream;
 the host only tokenises and builds the result frame.  The attribute gate is matched on the device between K2 and K3
-(gate="device": gate.py, csrc/rr_gate.hip) or, by default, by the host function between the two.
+(gate="device": gate.py, csrc/rr_gate.hip) or, by default, by the host function between the two; the reranker's pairs are
+assembled and scored on the device (rerank="device": rerank.py, csrc/rr_pairs.hip) or, by default, by `predict` on the host.
 torch is used for device buffers and streams only.
 """
 from __future__ import annotations
@@ -101,11 +102,12 @@ class StagedBatch:
 class HybridSearcher:
     """K1 -> K2 -> K3 on one GPU over a ProductIndex (+ optional BM25Index)."""
 
-    def __init__(self, index: ProductIndex, bm25: Optional[BM25Index] = None, gate_text=None):
-        """``gate_text``: a gate.GateText over the index's rows, for ``search_batch(gate_groups=...)``."""
+    def __init__(self, index: ProductIndex, bm25: Optional[BM25Index] = None, gate_text=None, rerank_text=None):
+        """``gate_text``: a gate.GateText over the index's rows, for ``search_batch(gate_groups=...)``.
+        ``rerank_text``: a rerank.RerankText over the index's rows, for ``search_batch(rerank_pairs=...)``."""
         if not index.has_meta:
             raise ValueError("the index needs metadata (ProductIndex.set_meta) before searching")
-        self.index, self.bm25, self.gate_text = index, bm25, gate_text
+        self.index, self.bm25, self.gate_text, self.rerank_text = index, bm25, gate_text, rerank_text
         self.lib = _lib.load()
         torch = _torch()
         if not torch.cuda.is_available():
@@ -381,7 +383,8 @@ class HybridSearcher:
                      rerank_fn: Optional[Callable[[np.ndarray], np.ndarray]] = None,
                      bm25_mode: str = "forward", reviews=None, max_scan: int = 0,
                      bm25_f64: bool = False, gate_groups=None,
-                     gate_host: Optional[Callable[[int, np.ndarray], np.ndarray]] = None) -> BatchResult:
+                     gate_host: Optional[Callable[[int, np.ndarray], np.ndarray]] = None,
+                     rerank_pairs: Optional[Tuple] = None) -> BatchResult:
         """qvecs (B, dim) float32; term_id_lists: per-query BM25 token ids (None = no BM25).
         gate_fn / rerank_fn map the (B, pool) pool rows to (B, pool) float32 gate factors /
         (B, rr_k) raw reranker scores; they run on the host between K2 and K3.
@@ -390,6 +393,12 @@ class HybridSearcher:
         ``weights.gate_penalty``) and the rows stay on the device.  A query over a limit of that kernel (gate.pack_groups:
         ``host_queries``) gets its row of the gate tensor from ``gate_host(b, rows[b]) -> (pool,) float32`` instead; only
         then are the rows copied to the host.
+        ``rerank_pairs`` (instead of rerank_fn): ``(cross_encoder, packed_queries, rerank_host)`` -- the pairs of the first
+        rr_k candidates of every query are assembled from the searcher's ``rerank_text`` and scored on the device
+        (RerankText.scores); the (B, pool) rerank tensor, zeros beyond rr_k, goes straight into K3: no row leaves the device
+        and no score is uploaded.  A query of more than max_length - 3 tokens (rerank.pack_queries: ``host_queries``) gets
+        its rr_k scores from ``rerank_host(b, rows[b, :rr_k]) -> (rr_k,) float32`` instead; only then are the rows copied to
+        the host.
         ``bm25_f64``: the CLI flavour without a BM25 artefact (float64 zeros column, app/test.py:252)."""
         torch = _torch()
         w = weights or FusionWeights()
@@ -418,6 +427,16 @@ class HybridSearcher:
                 raise ValueError(f"queries {packed.host_queries} exceed the gate kernel's limits and no gate_host was given")
             if not packed.any_groups and not packed.host_queries:
                 packed = None                    # nothing to match: no gate, as with gate_fn=None
+        if rerank_pairs is not None:
+            if rerank_fn is not None:
+                raise ValueError("pass either rerank_fn or rerank_pairs")
+            if self.rerank_text is None:
+                raise ValueError("rerank_pairs need a token plane: HybridSearcher(..., rerank_text=RerankText...)")
+            rr_ce, rr_queries, rerank_host = rerank_pairs
+            if rr_queries.n_queries != B:
+                raise ValueError(f"{rr_queries.n_queries} packed queries for {B} queries")
+            if rr_queries.host_queries and rerank_host is None:
+                raise ValueError(f"queries {rr_queries.host_queries} exceed the pair kernel's limit and no rerank_host was given")
         with torch.cuda.device(self.device):
             q_dev = torch.from_numpy(q).to(self.device)
             staged_groups = self.gate_text.upload(packed) if packed is not None else None    # (ahead of the kernels)
@@ -447,6 +466,14 @@ class HybridSearcher:
                     r = np.zeros((B, pool), dtype=np.float32)
                     r[:, :rr_k] = np.asarray(rerank_fn(rows_h[:, :rr_k]), dtype=np.float32)
                     rerank = torch.from_numpy(r).to(self.device)
+            if rerank_pairs is not None and rr_k > 0:
+                rerank = torch.zeros((B, pool), dtype=torch.float32, device=self.device)
+                rerank[:, :rr_k] = self.rerank_text.scores(rr_ce, rows, rr_k, rr_queries)
+                if rr_queries.host_queries:
+                    rows_h = rows.cpu().numpy() if rows_h is None else rows_h
+                    for b in rr_queries.host_queries:
+                        r = np.ascontiguousarray(rerank_host(b, rows_h[b, :rr_k]), dtype=np.float32).reshape(rr_k)
+                        rerank[b, :rr_k].copy_(torch.from_numpy(r))
             params = self.make_params(w, k_eff, pool, pool, rr_k, bm25_f64=bm25_f64 and self.bm25 is None)
             out_rows, cols, order = self.fuse(params, B, rows, dense, None if params.bm25_f64 else bm, None,
                                               rerank, best, gate)
@@ -470,13 +497,18 @@ class SearchEngine:
     gate: "host" (the default) matches the gate terms with `text.calculate_gate_factor` between K2 and K3; "device" builds a
     gate plane of ``meta["agg_text"]`` on the GPU (gate.GateText, up to 6 KB of device memory per product; ``gate_max_bytes``
     refuses a larger one) and matches there (csrc/rr_gate.hip).  The two give bitwise the same frames.
+    rerank: "host" (the default) builds the reranker's pairs as strings and scores them with ``cross_encoder.predict``;
+    "device" builds a token plane of ``meta["agg_text"]`` on the GPU (rerank.RerankText, up to about 1 KB of device memory per
+    product; ``rerank_max_bytes`` refuses a larger one), assembles the pairs there (csrc/rr_pairs.hip) and leaves the scores
+    on the device.  It needs a ``cross_encoder`` that is this package's `CrossEncoder` with a tokenizer.
     """
 
     def __init__(self, meta: pd.DataFrame, embeddings: np.ndarray, bm25_blob: Optional[dict] = None,
                  *, encoder=None, cross_encoder=None, device: int = 0, normalize: bool = True,
                  flavour: str = "app", dtype: str = "f32", reviews: Optional[Tuple] = None,
                  bm25_build: str = "device", index: Optional[ProductIndex] = None, bm25_ids: Optional[Tuple] = None,
-                 gate: str = "host", gate_max_bytes: Optional[int] = None):
+                 gate: str = "host", gate_max_bytes: Optional[int] = None, rerank: str = "host",
+                 rerank_max_bytes: Optional[int] = None):
         """``index``: a ready ProductIndex (embed.build_product_embeddings) to use instead of uploading ``embeddings``
         (then None); it is taken as it is -- ``normalize`` and ``dtype`` describe an upload only.
         ``bm25_ids``: ``(skus, tok, doc_off, vocab)`` instead of ``bm25_blob`` -- the corpus as token ids (numpy arrays or
@@ -487,6 +519,13 @@ class SearchEngine:
             raise ValueError("bm25_build must be 'device' or 'host'")
         if gate not in ("device", "host"):
             raise ValueError("gate must be 'device' or 'host'")
+        if rerank not in ("device", "host"):
+            raise ValueError("rerank must be 'device' or 'host'")
+        if rerank == "device":
+            from .cross_encoder import CrossEncoder
+            if not isinstance(cross_encoder, CrossEncoder) or cross_encoder.tokenizer is None:
+                raise ValueError("rerank=\"device\" needs a cross_encoder that is this package's CrossEncoder with a tokenizer "
+                                 "(its ids are what the token plane holds); any other object is served by rerank=\"host\"")
         if (index is None) == (embeddings is None):
             raise ValueError("pass either an embedding matrix or a ready index")
         n_emb = embeddings.shape[0] if index is None else index.n_rows
@@ -537,7 +576,14 @@ class SearchEngine:
             from .gate import GateText
             gate_text = GateText.from_texts(self._texts.tolist(), self.index.device, max_bytes=gate_max_bytes,
                                             row_offset=self.index.row_offset)
-        self.searcher = HybridSearcher(self.index, bm25_index, gate_text)
+        self.rerank = rerank
+        rerank_text = None
+        if rerank == "device":
+            from .rerank import RerankText
+            rerank_text = RerankText.from_texts(self._texts.tolist(), cross_encoder.tokenizer, cross_encoder.max_length,
+                                                self.index.device, max_bytes=rerank_max_bytes, row_offset=self.index.row_offset)
+            rerank_text.check_model(cross_encoder)
+        self.searcher = HybridSearcher(self.index, bm25_index, gate_text, rerank_text)
         # reviews = (frame with sku/text/stars, (n_reviews, dim) embeddings): reviews_with_embeddings.parquet
         self.reviews = None
         if reviews is not None:
@@ -656,6 +702,18 @@ class SearchEngine:
             return scores.reshape(rows.shape)
         return fn
 
+    def _rerank_args(self, queries: Sequence[str], rerank_k: int, batch: bool) -> dict:
+        """search_batch's rerank arguments for these queries: the device pairs when the engine has a token plane (the B
+        queries are tokenised here, B short strings), else the host function over all of them."""
+        if rerank_k <= 0:
+            return {}
+        if self.searcher.rerank_text is not None:
+            from .rerank import pack_queries
+            ce = self.cross_encoder
+            packed = pack_queries([ce.tokenizer.text_ids(str(q)) for q in queries], ce.max_length)
+            return {"rerank_pairs": (ce, packed, lambda b, rows: self._rerank_fn(queries[b])(rows[None, :])[0])}
+        return {"rerank_fn": self._rerank_batch_fn(queries) if batch else self._rerank_fn(queries[0])}
+
     def _rerank_fn(self, query: str):
         if self.cross_encoder is None:
             return None   # model missing -> zeros (app/app_product_search.py:275)
@@ -693,9 +751,8 @@ class SearchEngine:
         res = self.searcher.search_batch(
             qv[None, :], term_ids, k, rerank_k, w,
             pool_floor=APP_POOL_FLOOR if app else CLI_POOL_FLOOR,
-            rerank_fn=self._rerank_fn(query) if rerank_k > 0 else None,
             reviews=self.reviews if use_snips else None, max_scan=max_scan,
-            bm25_f64=not app, **self._gate_args([groups], gate_penalty))
+            bm25_f64=not app, **self._rerank_args([query], rerank_k, False), **self._gate_args([groups], gate_penalty))
         frame = self._frame(res, 0, rerank_k > 0)
         snips = {}
         if res.best_ids is not None:
@@ -714,7 +771,7 @@ class SearchEngine:
         """`run_search` for a batch of queries with the same parameters: per query the triple `run_search` returns.
         The queries are encoded in ONE encoder call (unless ``qvecs`` (B, dim) is given), searched in one `search_batch`
         -- with gate="device" the gate terms of all of them are matched in one kernel launch -- and the reranker pairs of
-        all of them go through one `predict`."""
+        all of them go through one `predict` (with rerank="device": through the pair kernels and the packed forward)."""
         app = self.flavour == "app"
         queries = list(queries)
         if not queries:
@@ -737,9 +794,8 @@ class SearchEngine:
         floor = APP_POOL_FLOOR if app else CLI_POOL_FLOOR
         res = self.searcher.search_batch(
             qv, term_ids, k, rerank_k, w, pool_floor=floor,
-            rerank_fn=self._rerank_batch_fn(queries) if rerank_k > 0 else None,
             reviews=self.reviews if use_snips else None, max_scan=max_scan,
-            bm25_f64=not app, **self._gate_args(groups, gate_penalty))
+            bm25_f64=not app, **self._rerank_args(queries, rerank_k, True), **self._gate_args(groups, gate_penalty))
         out = []
         for b in range(len(queries)):
             frame = self._frame(res, b, rerank_k > 0)

@@ -1,0 +1,356 @@
+"""The reranker's pairs on the GPU (csrc/rr_pairs.hip), and the plane's and the two kernels' model on the CPU.
+
+Stands in for what `CrossEncoder.predict` does in front of the model as run_search calls it (app/app_product_search.py:272-278,
+app/test.py:223-225): the pairs ``(query, agg_text[:2000])`` through the model's BertTokenizer, `[CLS] query [SEP] text [SEP]`
+truncated `longest_first` to ``max_length``.
+
+`RerankText` is the token plane of an index on the device: per product the WordPiece ids of ``agg_text[:2000]`` -- the cut is
+in code points and is made BEFORE tokenising, so a word cut in half is tokenised as the half -- of which the first
+``max_length - 3`` are kept (no longer text side survives the truncation), uint16, back to back.  It is tokenised once per
+index (embed.DeviceWordPiece; what that hands back, by wordpiece.py); per batch `RerankText.scores` assembles the packed
+sequences of the candidates on the device (rr_pairs_measure_dev / rr_pairs_write_dev), runs `forward_packed_dev` on them and
+leaves the scores on the device.  `pack_queries` turns a batch's query ids into the arrays the kernels read.  `model_plane` /
+`model_pairs` state in numpy what the plane and the two kernels hold, as gate.model_gate_plane / model_gate_hits do for theirs.
+
+The plane holds ``min(n_b, avail)`` text tokens, ``avail = max_length - 3``, not ``n_b``.  `keep_lengths` (the rule of
+`WordPieceTokenizer.encode_pair`) answers the same for both whenever the query has ``n_a <= avail`` tokens
+(tests/test_rerank_model.py sweeps it) and differs for some longer queries: those are `PackedQueries.host_queries`, scored
+through the host `predict`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+
+MAX_CHARS = 2000            # app/app_product_search.py:276, app/test.py:224: agg_text[:2000]
+MAX_VOCAB = 1 << 16         # the plane's ids are uint16
+CHUNK_DOCS = 8192           # documents per call of the device tokenizer while the plane is built
+STAGE_BYTES = 64 << 20
+
+
+# ---------------------------------------------------------------------------------- the models
+def keep_lengths(n_a: int, n_b: int, max_length: int) -> Tuple[int, int]:
+    """(query tokens, text tokens) a pair keeps: `longest_first` as `WordPieceTokenizer.encode_pair` states it."""
+    avail = max(int(max_length) - 3, 0)
+    if n_a + n_b > avail:
+        swap = n_a > n_b                           # (a tie: the text is the longer side)
+        n1, n2 = (n_b, n_a) if swap else (n_a, n_b)
+        n2 = n1 if n1 > avail else max(n1, avail - n1)
+        if n1 + n2 > avail:
+            n1 = avail // 2
+            n2 = n1 + avail % 2
+        n_a, n_b = (n2, n1) if swap else (n1, n2)
+    return n_a, n_b
+
+
+def model_plane(texts: Sequence[str], tokenizer, max_length: int, max_chars: int = MAX_CHARS) -> List[np.ndarray]:
+    """What `RerankText.from_texts` holds per document: the ids of ``text[:max_chars]``, the first ``max_length - 3``."""
+    keep = max(int(max_length) - 3, 0)
+    return [np.asarray(tokenizer.text_ids(str(t)[:max_chars])[:keep], dtype=np.uint16) for t in texts]
+
+
+def model_pairs(plane: Sequence[np.ndarray], rows, pool: int, rr_k: int, q_ids: Sequence[Sequence[int]], max_length: int,
+                cls: int, sep: int, first_pair: int, n_pairs: int, row_offset: int = 0):
+    """What rr_pairs_measure_dev / rr_pairs_write_dev make of the pairs [first_pair, first_pair + n_pairs) of a batch:
+    (tok, typ, pos, cu) int32.  ``rows``: (B, pool) global rows, ``q_ids``: the B queries' ids.  A row outside the plane
+    gives ``[CLS] query [SEP] [SEP]``."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, pool)
+    avail = max(int(max_length) - 3, 0)
+    tok: List[int] = []
+    typ: List[int] = []
+    pos: List[int] = []
+    cu = [0]
+    for p in range(first_pair, first_pair + n_pairs):
+        b, j = divmod(p, rr_k)
+        r = int(rows[b, j]) - row_offset
+        text = [int(t) for t in plane[r][:avail]] if 0 <= r < len(plane) else []
+        q = [int(t) for t in q_ids[b]]
+        ka, kb = keep_lengths(len(q), len(text), max_length)
+        ids = [cls] + q[:ka] + [sep] + text[:kb] + [sep]
+        tok += ids
+        typ += [0] * (ka + 2) + [1] * (kb + 1)
+        pos += list(range(len(ids)))
+        cu.append(len(tok))
+    a = lambda x: np.asarray(x, dtype=np.int32)
+    return a(tok), a(typ), a(pos), a(cu)
+
+
+class PackedQueries:
+    """A batch's query ids as the kernels read them (include/rr_hip.h: rr_pairs_measure_dev): ``ids`` int32, ``off`` int32
+    [B + 1].  ``host_queries``: the queries of more than ``max_length - 3`` tokens; they are packed with no ids and their
+    rows must be scored through the host `predict`."""
+
+    def __init__(self, ids, off, host_queries, max_length):
+        self.ids, self.off, self.host_queries, self.max_length = ids, off, list(host_queries), int(max_length)
+        self.n_queries = len(off) - 1
+
+    def buffer(self):
+        """(one int32 array: the offsets, then the ids (at least one element), offset of the ids)."""
+        n_off = len(self.off)
+        buf = np.zeros(n_off + max(len(self.ids), 1), dtype=np.int32)
+        buf[:n_off] = self.off
+        buf[n_off:n_off + len(self.ids)] = self.ids
+        return buf, n_off
+
+
+def pack_queries(id_lists: Sequence[Sequence[int]], max_length: int) -> PackedQueries:
+    """id_lists[q] = ``tokenizer.text_ids(query)``."""
+    avail = max(int(max_length) - 3, 0)
+    host = [q for q, ids in enumerate(id_lists) if len(ids) > avail]
+    kept = [np.zeros(0, dtype=np.int32) if len(ids) > avail else np.asarray(ids, dtype=np.int32).reshape(-1) for ids in id_lists]
+    off = np.zeros(len(kept) + 1, dtype=np.int32)
+    np.cumsum([len(k) for k in kept], out=off[1:])
+    flat = np.concatenate(kept) if off[-1] else np.zeros(0, dtype=np.int32)
+    return PackedQueries(flat, off, host, max_length)
+
+
+def _narrow(ids):
+    """int32 / int64 ids 0..65535 (a torch tensor) as the int16 tensor with the same low 16 bits."""
+    import torch
+    return ((ids.to(torch.int32) + 32768) % 65536 - 32768).to(torch.int16)
+
+
+# ---------------------------------------------------------------------------------- the plane on the device
+class RerankText:
+    """The token plane of one index on one GPU: ``d_tok`` the ids back to back (uint16 in memory; held in a torch.int16
+    tensor, `tokens()` gives them as numpy uint16), ``d_off`` int64 [n + 1], ``n`` documents, ``n_tokens``; document i is the
+    product of global row ``row_offset + i``.  ``max_length``: the cross-encoder's, which decided the cap of ``max_length - 3``
+    ids per document."""
+
+    def __init__(self, device: int = 0, row_offset: int = 0):
+        import torch
+        if not torch.cuda.is_available():
+            raise _lib.HipLibraryError("no GPU visible: the token plane lives on the device only")
+        self.device = getattr(device, "index", device) or 0
+        self.row_offset = int(row_offset)
+        h = C.c_void_p()
+        _lib.check(_lib.load().rr_pairs_create(self.device, C.byref(h)), "rr_pairs_create")
+        self._h = h
+        self.d_tok = self.d_off = None
+        self.n = self.n_tokens = self.max_length = 0
+        self.cls_id = self.sep_id = self.vocab_size = 0
+        self.host_docs: List[int] = []
+
+    # ------------------------------------------------------------------ building
+    @classmethod
+    def from_texts(cls, texts: Sequence[str], tokenizer, max_length: int, device: int = 0, *, max_chars: int = MAX_CHARS,
+                   max_bytes: Optional[int] = None, row_offset: int = 0, chunk_docs: int = CHUNK_DOCS,
+                   stage_bytes: int = STAGE_BYTES) -> "RerankText":
+        """From a column of str.  The first ``max_chars`` characters of every text are uploaded as UTF-8 (in row blocks through
+        two pinned buffers, embed._stage_rows) and tokenised ``chunk_docs`` documents at a time by the device tokenizer
+        (``[CLS]``, the first ``max_length - 3`` pieces, ``[SEP]``); the pieces are narrowed to uint16 and appended.  What
+        the device tokenizer hands back (a hard code point, malformed bytes, more than 4 096 bytes of text without enough
+        pieces in them or of mapped text: ``host_docs``) is tokenised by ``tokenizer.text_ids`` and placed at its own
+        offsets: the plane is dense and in row order.  The raw heads are dropped once the plane stands.
+        ``max_bytes``: refuse (MemoryError) a plane that needs more device memory than this -- up to about 1 KB per
+        product: 10M products of about 450 tokens are about 9 GB."""
+        import torch
+        from .embed import DeviceWordPiece, _stage_rows, _utf8_column
+        L = int(max_length)
+        if L < 3:
+            raise ValueError(f"max_length {L} leaves no room for [CLS] [SEP] [SEP]")
+        vocab_size = max(tokenizer.vocab.values()) + 1
+        if vocab_size > MAX_VOCAB:
+            raise ValueError(f"a vocabulary of {vocab_size} pieces does not fit the plane's uint16 ids: use rerank=\"host\"")
+        if int(chunk_docs) < 1:
+            raise ValueError("chunk_docs must be at least 1")
+        self = cls(device, row_offset)
+        self.max_length, self.vocab_size = L, vocab_size
+        self.cls_id, self.sep_id = int(tokenizer.cls_id), int(tokenizer.sep_id)
+        keep = L - 3
+        heads = [str(t)[:max_chars] for t in texts]
+        raw, off = _utf8_column(heads)
+        n, total = len(off) - 1, int(off[-1])
+
+        def room(tokens: int) -> None:
+            need = 2 * max(tokens, 1) + 8 * (n + 1)
+            if max_bytes is not None and need > max_bytes:
+                raise MemoryError(f"the token plane of {n} products needs {need} bytes of device memory or more, more than the "
+                                  f"{max_bytes} allowed: use rerank=\"host\" (or raise rerank_max_bytes)")
+
+        room(0)
+        dev = torch.device("cuda", self.device)
+        wp = DeviceWordPiece(tokenizer, self.device, unicode=True)
+        parts, lens_all, done = [], np.zeros(n, dtype=np.int64), [0]
+        try:
+            with torch.cuda.device(dev):
+                main = torch.cuda.current_stream(dev)
+                d_text = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+                d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64)).to(dev)
+
+                def block(c0: int, c1: int) -> None:
+                    nd, base = c1 - c0, int(off[c0])
+                    packed, info, _, cap, _keep = wp.queue_dev(d_text.data_ptr() + base, int(off[c1]) - base,
+                                                               d_off[c0:c1 + 1] - base, L - 1)
+                    main.synchronize()
+                    h = info.numpy()
+                    tok, _, pos, cu = wp.views(packed, nd, cap, int(h[0]))
+                    cu_h = cu.cpu().numpy().astype(np.int64)
+                    lens = cu_h[1:] - cu_h[:-1] - 2                     # (a handed-back document: the placeholder, 0)
+                    host = np.flatnonzero(h[1:nd + 1]).tolist()
+                    host_ids = [np.asarray(tokenizer.text_ids(heads[c0 + i])[:keep], dtype=np.int64) for i in host]
+                    for i, ids in zip(host, host_ids):
+                        lens[i] = len(ids)
+                    new_off = np.zeros(nd + 1, dtype=np.int64)
+                    np.cumsum(lens, out=new_off[1:])
+                    m = int(new_off[-1])
+                    room(done[0] + m)
+                    out = torch.empty(m, dtype=torch.int16, device=dev)
+                    if m:
+                        # the pieces without [CLS] / [SEP], each to its document's new offset + its place in the document
+                        is_piece = pos > 0
+                        is_piece[(cu[1:] - 1).long()] = False
+                        doc = torch.repeat_interleave(torch.arange(nd, device=dev), (cu[1:] - cu[:-1]).long(), output_size=int(h[0]))
+                        where = torch.from_numpy(new_off).to(dev)[doc[is_piece]] + pos[is_piece].long() - 1
+                        out[where] = _narrow(tok[is_piece])
+                        for i, ids in zip(host, host_ids):
+                            if len(ids):
+                                out[int(new_off[i]):int(new_off[i + 1])] = _narrow(torch.from_numpy(ids).to(dev))
+                    parts.append(out)
+                    lens_all[c0:c1] = lens
+                    done[0] += m
+                    self.host_docs += [c0 + i for i in host]
+
+                def on_rows(a: int, b: int) -> None:
+                    for c0 in range(a, b, int(chunk_docs)):
+                        block(c0, min(b, c0 + int(chunk_docs)))
+
+                _stage_rows(raw, off, d_text, main, stage_bytes, on_rows)
+                wp.check()
+                plane_off = np.zeros(n + 1, dtype=np.int64)
+                np.cumsum(lens_all, out=plane_off[1:])
+                self.d_tok = torch.cat(parts) if done[0] else torch.zeros(1, dtype=torch.int16, device=dev)
+                self.d_off = torch.from_numpy(plane_off).to(dev)
+                self.n, self.n_tokens = int(n), int(done[0])
+                main.synchronize()
+        finally:
+            wp.close()
+        return self
+
+    def tokens(self) -> List[np.ndarray]:
+        """The plane on the host: per document its uint16 ids (tests)."""
+        flat = self.d_tok[:self.n_tokens].cpu().numpy().view(np.uint16)
+        off = self.d_off.cpu().numpy()
+        return [flat[off[i]:off[i + 1]] for i in range(self.n)]
+
+    def check_model(self, ce) -> None:
+        """Raises ValueError unless ``ce`` (a cross_encoder.CrossEncoder) can score this plane's ids."""
+        if self.vocab_size > ce.model.vocab:
+            raise ValueError(f"the tokenizer's vocabulary ({self.vocab_size} pieces) is larger than the model's embedding table "
+                             f"({ce.model.vocab} rows)")
+        if ce.max_length != self.max_length:
+            raise ValueError(f"the plane was cut for max_length {self.max_length}, the cross-encoder has {ce.max_length}")
+        if ce.model.n_labels != 1:
+            raise ValueError(f"the device rerank path scores single-label models; this one has {ce.model.n_labels} labels")
+        if ce.model.device != self.device:
+            raise ValueError(f"the plane lives on GPU {self.device}, the cross-encoder on GPU {ce.model.device}")
+
+    # ------------------------------------------------------------------ per batch
+    def upload(self, packed: PackedQueries):
+        """The packed queries on the device: (int32 tensor, offset of the ids).  One copy."""
+        import torch
+        buf, at = packed.buffer()
+        return torch.from_numpy(buf).to(torch.device("cuda", self.device)), at
+
+    def _check_rows(self, rows, rr_k: int, packed: PackedQueries):
+        import torch
+        B, pool = rows.shape
+        if B != packed.n_queries:
+            raise ValueError(f"{packed.n_queries} packed queries for {B} rows of candidates")
+        if not rows.is_contiguous() or rows.dtype != torch.int64:
+            raise ValueError("rows must be a contiguous int64 tensor")
+        if packed.max_length != self.max_length:
+            raise ValueError(f"queries packed for max_length {packed.max_length}, the plane was cut for {self.max_length}")
+        return B, pool
+
+    def pairs(self, rows, rr_k: int, packed: PackedQueries, first_pair: int = 0, n_pairs: Optional[int] = None, staged=None):
+        """rr_pairs_measure_dev, the read-back of the token count, rr_pairs_write_dev, on the current stream: the packed
+        sequences of the pairs [first_pair, first_pair + n_pairs) of ``rows`` ((B, pool) int64 device tensor of global rows,
+        the first ``rr_k`` of every query) -> (tok, typ, pos, cu) int32 device tensors, as `forward_packed_dev` takes them."""
+        import torch
+        B, pool = self._check_rows(rows, rr_k, packed)
+        n_pairs = B * int(rr_k) - int(first_pair) if n_pairs is None else int(n_pairs)
+        lib = _lib.load()
+        d_q, at = staged if staged is not None else self.upload(packed)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        st = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
+        keep = torch.empty((max(n_pairs, 1), 2), dtype=torch.int32, device=rows.device)
+        cu = torch.empty(max(n_pairs, 0) + 1, dtype=torch.int32, device=rows.device)
+        _lib.check(lib.rr_pairs_measure_dev(self._h, p(self.d_off), self.n, self.row_offset, p(rows), pool, int(rr_k), p(d_q), B,
+                                            self.max_length, int(first_pair), n_pairs, p(keep), p(cu), st), "rr_pairs_measure_dev")
+        n_tokens = int(cu[n_pairs].item())                 # the only number read back: it sizes the three id arrays
+        ids = torch.empty(3 * max(n_tokens, 1), dtype=torch.int32, device=rows.device)
+        tok, typ, pos = ids[:n_tokens], ids[n_tokens:2 * n_tokens], ids[2 * n_tokens:3 * n_tokens]
+        _lib.check(lib.rr_pairs_write_dev(self._h, p(self.d_tok), p(self.d_off), self.n, self.row_offset, p(rows), pool, int(rr_k),
+                                          C.c_void_p(d_q.data_ptr() + 4 * at), p(d_q), B, self.cls_id, self.sep_id, int(first_pair),
+                                          n_pairs, p(keep), p(cu), n_tokens, p(ids), C.c_void_p(ids.data_ptr() + 4 * n_tokens),
+                                          C.c_void_p(ids.data_ptr() + 8 * n_tokens), st), "rr_pairs_write_dev")
+        return tok, typ, pos, cu
+
+    def scores(self, ce, rows, rr_k: int, packed: PackedQueries):
+        """The reranker's scores of the first ``rr_k`` candidates of every query: (B, rr_k) float32 on the device, what
+        ``ce.predict`` gives for the pairs ``(query, agg_text[:2000])``.  The pairs go through the model in chunks of
+        ``n_pairs * max_length <= min(ce.model.max_tokens_per_call, FP32_MAX_TOKENS)`` (a bound that needs no lengths on the
+        host); per chunk `pairs` and `forward_packed_dev`.  A pass of the fp32 mode that leaves the fp16 range poisons its
+        call's logits with NaN (include/rr_hip.h): after all chunks ONE ``isnan`` over the scores decides whether the handle
+        switches to the wide-range kernels and the chunks run again, once.  The rows of ``packed.host_queries`` hold the
+        scores of the EMPTY query: the caller overwrites them (HybridSearcher.search_batch does)."""
+        import torch
+        from .cross_encoder import FP32_MAX_TOKENS, OUT_LOGITS
+        self.check_model(ce)
+        B, pool = self._check_rows(rows, rr_k, packed)
+        rr_k = int(rr_k)
+        if not 1 <= rr_k <= pool:
+            raise ValueError(f"rr_k {rr_k} outside 1..pool = {pool}")
+        L = self.max_length
+        total = B * rr_k
+        step = max(1, min(int(ce.model.max_tokens_per_call), FP32_MAX_TOKENS) // L)
+        with torch.cuda.device(rows.device):
+            staged = self.upload(packed)
+            out = torch.empty(total, dtype=torch.float32, device=rows.device)
+
+            def run():
+                for a in range(0, total, step):
+                    m = min(step, total - a)
+                    tok, typ, pos, cu = self.pairs(rows, rr_k, packed, a, m, staged)
+                    out[a:a + m] = ce.model.forward_packed_dev(tok, typ, pos, cu, m, L, OUT_LOGITS)[:, 0]
+
+            run()
+            if bool(torch.isnan(out).any()):
+                if ce.model.precision != "fp32" or ce.model.wide_range:
+                    raise _lib.HipLibraryError("the cross-encoder answered NaN scores")
+                ce.model.set_wide_range(True)              # as forward_ids: the handle continues on the wide-range kernels
+                run()
+                if bool(torch.isnan(out).any()):
+                    raise _lib.HipLibraryError("the cross-encoder answered NaN scores on the wide-range kernels")
+            self.check()
+            if ce.activation == "sigmoid":                 # CrossEncoder._post: float64, rounded once to float32
+                out = (1.0 / (1.0 + torch.exp(-out.to(torch.float64)))).to(torch.float32)
+        return out.view(B, rr_k)
+
+    def check(self) -> None:
+        """Raises ValueError when a call since the last check met a candidate row outside the plane or refused a pair
+        (waits for the device)."""
+        bad = C.c_int32()
+        _lib.check(_lib.load().rr_pairs_status(self._h, C.byref(bad)), "rr_pairs_status")
+
+    @property
+    def nbytes(self) -> int:
+        """Device memory the plane holds."""
+        return 0 if self.d_tok is None else int(2 * self.d_tok.numel() + 8 * self.d_off.numel())
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.load().rr_pairs_destroy(self._h)
+            self._h = None
+        self.d_tok = self.d_off = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

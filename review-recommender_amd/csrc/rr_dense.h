@@ -18,8 +18,8 @@ struct rr_scan_geom {
     int32_t n_waves;          // waves of the launch; every one owns at least one tile
     int32_t qs;               // 0: scores are [query][n_pad], tile maxima [query][n_tiles] (rr_scan_f32)
                               // Q: scores are [row / 16][Q][16], tile maxima [tile][Q], group maxima [wave][Q]
-                              //    (rr_scan_mfma_f32 with Q = 16 * NQT query slots: every store of a wave is
-                              //    one contiguous block of whole 128-B lines)
+                              //    (the stored pass of rr_scan_mfma_x3 with Q = 16 query slots, of rr_scan_x3w with
+                              //    32 or 64: every store of a wave is one contiguous block of whole 128-B lines)
     int64_t n_pad;            // 64 * n_tiles
     int32_t mm_pairs;         // M-tile maxima of the two-pass path: 0 = [tile][Q][4] (rr_scan_mfma_x3),
                               // 1 = [32-row tile][Q][2] (rr_scan_x3w: whole lines per store),
@@ -33,7 +33,7 @@ struct rr_scan_geom {
 // Splits the tiles into equal contiguous runs, one per wave of (at most) `resident_blocks` x 4 waves.
 rr_scan_geom rr_make_geom(const rr_index* ix, int resident_blocks);
 // Which kernel a scan launch ran (rr_index_last_scan_info): 1 rr_scan_f32, 2 rr_scan_bf16, 3 rr_scan_mfma_x3,
-// 4 rr_scan_x3w, 5 rr_scan_flt, 6 rr_scan_mfma_f32, 7 rr_scan_mfma_bf16; terms = bf16 MFMA terms per dimension.
+// 4 rr_scan_x3w, 5 rr_scan_flt (6 and 7 are retired: the removed f32-input MFMA scans); terms = bf16 MFMA terms per dimension.
 static inline void rr_scan_note(rr_index* ix, int kernel, int variant, int nq, int terms, int elem_bytes = 0) {
     ix->last_scan[0] = kernel; ix->last_scan[1] = variant; ix->last_scan[2] = nq; ix->last_scan[3] = terms;
     ix->last_scan[4] = elem_bytes ? elem_bytes : (ix->dtype == RR_DTYPE_BF16 ? 2 : 4);
@@ -84,11 +84,9 @@ void rr_launch_group_kth(rr_index* ix, const rr_scan_geom& G, int nq_a, int nq_b
                          int64_t smax_set_stride, hipStream_t st);
 // Waves a kernel can keep resident on the device (occupancy x CUs x waves per workgroup).
 int rr_resident_waves(const void* kernel, int threads, int device);
-// bf16-storage scans (rr_dense_bf16.hip): up to 8 (VALU) or 9..64 (matrix cores) queries.
+// bf16-storage VALU scan (rr_dense_bf16.hip): up to 8 queries.
 int rr_dense_chunk_bf16(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                         float* d_scores, hipStream_t st);
-int rr_dense_chunk_mfma_bf16(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
-                             float* d_scores, hipStream_t st);
 // l2_normalize of rows [first, first + n) of an fp32 index, in place
 int rr_l2norm_rows_f32(rr_index* ix, int64_t first_row, int64_t n, float eps, hipStream_t st);
 // ... of n padded rows anywhere on the device (a staging copy): the same kernel

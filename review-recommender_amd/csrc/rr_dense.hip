@@ -241,137 +241,6 @@ __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_f32_generic(
     }
 }
 
-// ------------------------------------------------------------------ batched scan (MFMA)
-// rr_scan_mfma_f32<NQT>: the same scan for 16*NQT queries per launch (NQT = 1, 2, 4) on the
-// f32-input matrix cores.  v_mfma_f32_16x16x4_f32 is exact f32 (a k-ordered fmaf chain) at the
-// f32 vector rate, but one MFMA reuses each operand dword 16 times, so operand traffic per
-// FLOP drops 16x and the kernel stays HBM-bound up to ~32 queries per pass
-// (2*B flop/byte against a ~20 flop/byte f32 ridge), compute-bound beyond.
-//
-// Like rr_scan_f32 every wave is an independent stream over its own contiguous run of
-// 64-row tiles: no barriers, no inter-wave traffic after the prologue.  Measured on this
-// chip the scan rate follows the bytes in flight per CU (Little's law at ~5-8 us loaded
-// latency), and only the register file can hold ~190 KB per CU: LDS-staged variants
-// (register or LDS-DMA staging, 64-96 KB in flight) stopped at 4.6-5.2 TB/s.  So:
-//   A operand  matrix rows go straight to VGPRs in fragment shape: lane (r = lane&15,
-//              g = lane>>4) loads float4 (g + 4j), j = 0..23, of row r of a 16-row M-tile.
-//              The 24 registers are a ring: as soon as the MFMAs of step j have consumed
-//              a register, the load of the same j of the NEXT M-tile is issued into it, so a
-//              wave keeps 24 KB in flight continuously (8 waves per CU: 192 KB).
-//   B operand  the 16*NQT queries sit in LDS for the whole launch, XOR-swizzled
-//              (slot = (f & ~15) | ((f ^ query) & 15)) so the fragment ds_read_b128 is
-//              conflict-free; one read feeds four MFMAs.
-// Lane (r, g) feeds MFMA (j, c) with component c of float4 (g + 4j) of row r / query r.
-// The 384 dims are cut into four quarters (j in [6q, 6q+6)), each with its own accumulator;
-// every score is (acc0 + acc1) + (acc2 + acc3), each acc a fixed fmaf chain, whatever NQT is
-// and wherever the row sits: scores do not depend on batch size (within this kernel),
-// sharding or grid.  (The order differs from rr_scan_f32's: the two kernels agree to f32
-// rounding, ~1e-8, not bit for bit.)
-template <int NQT>
-__global__ __launch_bounds__((NQT == 4 ? 512 : 256), 2) void rr_scan_mfma_f32(
-    const f32x4* __restrict__ mat, rr_scan_geom G, const float* __restrict__ queries,  // (16*NQT) x 384
-    float* __restrict__ sims, float* __restrict__ gmax, uint32_t* __restrict__ smax) {
-    constexpr int ROWF4 = 96;
-    __shared__ f32x4 qs[NQT * 16 * ROWF4];
-    constexpr int THREADS = NQT == 4 ? 512 : 256;   // 64 queries = 96 KB of LDS: one workgroup per CU, 8 waves
-    const int tid = threadIdx.x;
-    for (int i = tid; i < NQT * 16 * ROWF4; i += THREADS) {
-        const int q = i / ROWF4, f = i % ROWF4;
-        qs[q * ROWF4 + ((f & ~15) | ((f ^ q) & 15))] = reinterpret_cast<const f32x4*>(queries)[i];
-    }
-    __syncthreads();
-
-    const int lane = tid & 63;
-    const int r = lane & 15;
-    const int g = lane >> 4;
-    const int64_t wave = (int64_t)blockIdx.x * (THREADS / 64) + (tid >> 6);
-    if (wave >= G.n_waves) return;
-    const int64_t t0 = wave * G.tiles_per_wave;
-    const int64_t t1 = t0 + G.tiles_per_wave < G.n_tiles ? t0 + G.tiles_per_wave : G.n_tiles;
-    const int64_t m0 = t0 * 4, m1 = t1 * 4;          // 16-row M-tiles of this wave
-
-    auto row_ptr = [&](int64_t mt) {
-        int64_t row = mt * 16 + r;
-        row = row < G.n_rows ? row : G.n_rows - 1;   // tail rows re-read the last row; masked later
-        return mat + row * ROWF4 + g;
-    };
-
-    // The ring loads are issued from inline asm so that they stay interleaved with the MFMAs
-    // (hipcc sinks plain loads to the end of the iteration and waits vmcnt(0) at its top);
-    // the waits are therefore counted by hand.  RR_RING_WAIT(j) ties the wait to the register
-    // it guards ("+v"), so the MFMAs that read it cannot be scheduled above it.
-#define RR_RING_LOAD(dst, ptr, byteoff) \
-    asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(ptr), "n"(byteoff) : "memory")
-    // younger memory operations when the load of (M-tile, j) is needed: the 23 other ring loads
-    // plus the NQT score stores of the previous M-tile (its occasional tile-maximum stores only
-    // make the wait conservative)
-#define RR_RING_WAIT(reg) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(reg) : "n"(23 + NQT) : "memory")
-    f32x4 a[24];
-    {
-        const f32x4* p = row_ptr(m0);
-#pragma unroll
-        for (int j = 0; j < 24; ++j) RR_RING_LOAD(a[j], p, 64 * j);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // first M-tile: nothing older to count against
-    }
-    float tile_max[NQT], gm[NQT];
-#pragma unroll
-    for (int t = 0; t < NQT; ++t) tile_max[t] = gm[t] = -INFINITY;
-
-#pragma unroll 1
-    for (int64_t mt = m0; mt < m1; ++mt) {
-        const f32x4* pn = row_ptr(mt + 1 < m1 ? mt + 1 : mt);
-        f32x4 acc[NQT][4];
-#pragma unroll
-        for (int t = 0; t < NQT; ++t)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) acc[t][qd] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 24; ++j) {
-            const int f = g + 4 * j;
-            const int qd = j / 6;
-            RR_RING_WAIT(a[j]);
-            const f32x4 x = a[j];
-#pragma unroll
-            for (int t = 0; t < NQT; ++t) {
-                const f32x4 b = qs[(16 * t + r) * ROWF4 + ((f & ~15) | ((f ^ r) & 15))];
-                acc[t][qd] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.x, b.x, acc[t][qd], 0, 0, 0);
-                acc[t][qd] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.y, b.y, acc[t][qd], 0, 0, 0);
-                acc[t][qd] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.z, b.z, acc[t][qd], 0, 0, 0);
-                acc[t][qd] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.w, b.w, acc[t][qd], 0, 0, 0);
-            }
-            // the same j of the next M-tile goes into the register just consumed
-            asm volatile("global_load_dwordx4 %0, %1, off offset:%2"
-                         : "=v"(a[j]) : "v"(pn), "n"(64 * j), "v"(acc[NQT - 1][qd]) : "memory");
-        }
-        // lane (r, g) holds rows 4*g .. 4*g+3 of the M-tile for query 16*t + r
-        const int64_t row0 = mt * 16 + 4 * g;
-        const bool tile_end = (mt & 3) == 3;
-#pragma unroll
-        for (int t = 0; t < NQT; ++t) {
-            f32x4 v = (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]);
-            v.x = (row0 + 0 < G.n_rows && v.x == v.x) ? v.x : -INFINITY;   // NaN scores and pad rows rank last
-            v.y = (row0 + 1 < G.n_rows && v.y == v.y) ? v.y : -INFINITY;
-            v.z = (row0 + 2 < G.n_rows && v.z == v.z) ? v.z : -INFINITY;
-            v.w = (row0 + 3 < G.n_rows && v.w == v.w) ? v.w : -INFINITY;
-            // [M-tile][query slot][16 rows]: the wave's 16*NQT queries x 64 B form one contiguous block
-            *reinterpret_cast<f32x4*>(sims + ((mt * (16 * NQT) + 16 * t + r) * 16 + 4 * g)) = v;
-            float m4 = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
-            m4 = fmaxf(m4, __shfl_xor(m4, 16, 64));
-            m4 = fmaxf(m4, __shfl_xor(m4, 32, 64));
-            tile_max[t] = fmaxf(tile_max[t], m4);
-            if (tile_end) {                              // fourth M-tile: the 64-row tile is complete
-                if (g == 0) gmax[(mt >> 2) * (16 * NQT) + 16 * t + r] = tile_max[t];
-                gm[t] = fmaxf(gm[t], tile_max[t]);
-                tile_max[t] = -INFINITY;
-            }
-        }
-    }
-    if (g == 0) {
-#pragma unroll
-        for (int t = 0; t < NQT; ++t) smax[wave * (16 * NQT) + 16 * t + r] = rr_f2key(gm[t]);
-    }
-}
-
 // ------------------------------------------------------------------ select
 // Suffix scan over a 256-bin histogram: finds the bin holding the k-th largest
 // element (counting from the top bin) and the count strictly above it.
@@ -1374,8 +1243,7 @@ static rr_scan_geom rr_launch_scan(rr_index* ix, const float* d_q, hipStream_t s
 // one returns; their flags come down.  More than eight: all of them go on to the split-operand pass.  fp32 storage, dim 384.
 int rr_dense_listed_fallback(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores,
                              int32_t* flags, hipStream_t st) {
-    static const bool off = getenv("RR_NO_CHAIN_FALLBACK") != nullptr;
-    if (off || ix->dtype != RR_DTYPE_F32 || ix->dim_pad != 384 || !ix->d_flag_list) return RR_OK;
+    if (ix->dtype != RR_DTYPE_F32 || ix->dim_pad != 384 || !ix->d_flag_list) return RR_OK;
     static int cap = 0;
     if (!cap) cap = rr_resident_grid(rr_scan_f32<6, 8, true>, ix->device);
     rr_scan_geom G = rr_make_geom(ix, cap);
@@ -1393,8 +1261,7 @@ int rr_dense_listed_fallback(rr_index* ix, const float* d_q, int nq, int pool, i
 static int rr_dense_chunk(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                           float* d_scores, hipStream_t st, bool time_it) {
     if (time_it) hipEventRecord(ix->ev0, st);
-    const int slot = (int)(ix->ring_head % rr_index::kRing);
-    hipEventRecord(ix->ring0[slot], st);
+    const int slot = rr_scan_events_begin(ix, st);
     rr_scan_note(ix, 1, nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8, nq, 0);
     rr_scan_geom G;
     switch (nq) {
@@ -1403,9 +1270,7 @@ static int rr_dense_chunk(rr_index* ix, const float* d_q, int nq, int pool, int6
         case 3: case 4: G = rr_launch_scan<4>(ix, d_q, st); break;
         default: G = rr_launch_scan<8>(ix, d_q, st); break;
     }
-    hipEventRecord(ix->ring1[slot], st);
-    ix->ring_head++;
-    if (ix->ring_head - ix->ring_tail > rr_index::kRing) ix->ring_tail = ix->ring_head - rr_index::kRing;
+    rr_scan_events_end(ix, slot, st);
     if (time_it) {
         hipEventRecord(ix->ev1, st);
         ix->timing_valid = true;
@@ -1417,52 +1282,17 @@ static int rr_dense_chunk(rr_index* ix, const float* d_q, int nq, int pool, int6
     return RR_OK;
 }
 
-// Scan + select for 9..64 queries on the matrix cores (fp32 storage, dim 384 only).
-template <int NQT>
-static int rr_dense_chunk_mfma(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
-                               float* d_scores, hipStream_t st) {
-    constexpr int THREADS = NQT == 4 ? 512 : 256;
-    static int cap_waves = 0;
-    if (!cap_waves) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rr_scan_mfma_f32<NQT>, THREADS, 0) != hipSuccess ||
-            per_cu < 1)
-            per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->device) != hipSuccess || cus < 1)
-            cus = 256;
-        cap_waves = per_cu * cus * (THREADS / 64);
-        if (cap_waves > RR_MAX_SCAN_WAVES) cap_waves = RR_MAX_SCAN_WAVES;
-    }
-    rr_scan_geom G = rr_make_geom(ix, cap_waves / 4);  // one run of tiles per wave, like rr_scan_f32
-    G.qs = 16 * NQT;
-    const int slot = (int)(ix->ring_head % rr_index::kRing);
-    hipEventRecord(ix->ring0[slot], st);
-    rr_scan_note(ix, 6, NQT, nq, 0);
-    hipLaunchKernelGGL((rr_scan_mfma_f32<NQT>), dim3((G.n_waves + THREADS / 64 - 1) / (THREADS / 64)), dim3(THREADS), 0, st,
-                       reinterpret_cast<const f32x4*>(ix->d_matrix), G, d_q, ix->d_sims, ix->d_gmax, ix->d_smax);
-    hipEventRecord(ix->ring1[slot], st);
-    ix->ring_head++;
-    if (ix->ring_head - ix->ring_tail > rr_index::kRing) ix->ring_tail = ix->ring_head - rr_index::kRing;
-    hipLaunchKernelGGL(rr_select, dim3(nq), dim3(RR_SEL_THREADS), 0, st, G, ix->d_sims, ix->d_gmax,
-                       ix->d_smax, pool, ix->row_offset, d_rows, d_scores, ix->d_sel_trace, (const int32_t*)nullptr, nq, (int64_t)0, (int64_t)0, (int64_t)0,
-                       (const int32_t*)nullptr, (int32_t*)nullptr);
-    RR_HIP_TRY(hipGetLastError());
-    return RR_OK;
-}
-
 // Orders this call's use of the handle's scratch behind the previous call's when the stream changed.  Two resources:
 // the ACTIVE slot's scan state (written by its scan, read -- and, by the fallbacks, overwritten -- by the parts of its
 // selection) and the selection scratch all slots share (M-tile lists, rescored rows, stored scores): `select` says whether
 // the call touches the second.  Each records the last launch sequence that used it; a call on another stream waits for it.
-static int rr_scratch_enter(rr_index* ix, hipStream_t st, bool scan = true, bool select = true) {
-    (void)scan;
+static int rr_scratch_enter(rr_index* ix, hipStream_t st, bool select = true) {
     const int s = ix->cur_slot;
     if (ix->slot_has[s] && ix->slot_stream[s] != st) RR_HIP_TRY(hipStreamWaitEvent(st, ix->slot_ev[s], 0));
     if (select && ix->has_done && st != ix->last_stream) RR_HIP_TRY(hipStreamWaitEvent(st, ix->ev_done, 0));
     return RR_OK;
 }
-static int rr_scratch_leave(rr_index* ix, hipStream_t st, bool scan = true, bool select = true) {
-    (void)scan;
+static int rr_scratch_leave(rr_index* ix, hipStream_t st, bool select = true) {
     const int s = ix->cur_slot;
     RR_HIP_TRY(hipEventRecord(ix->slot_ev[s], st));
     ix->slot_stream[s] = st;
@@ -1480,9 +1310,7 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
     RR_HIP_TRY(hipSetDevice(ix->device));
     const bool bf16 = ix->dtype == RR_DTYPE_BF16;
     const bool mfma_ok = ix->dim_pad == 384 && ix->n_rows >= 64;
-    // batches run on the bf16 matrix cores with exactly-split operands (rr_dense_x3.hip);
-    // RR_SCAN_F32_CHAIN=1 selects the f32-input MFMA kernels (scores = pure fmaf chains) instead
-    static const bool f32_chain = getenv("RR_SCAN_F32_CHAIN") != nullptr;
+    // batches run on the bf16 matrix cores with exactly-split operands (rr_dense_x3.hip)
     static const bool exact_scan = getenv("RR_SCAN_EXACT") != nullptr;
     // measured crossover (10M rows): the per-row-chain VALU scans win up to 4 queries per read
     // (2.4-2.5 ms fp32, 1.3-1.5 ms bf16); from 5 on the matrix-core scan does (2.7-2.9 / 1.8 ms
@@ -1501,7 +1329,7 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
         float* scores = d_scores + (int64_t)q0 * pool;
         int n;
         bool small = false;        // the filter path declined: too few tiles
-        if (mfma_ok && left > valu_max && !f32_chain && !exact_scan && ix->scan_mode == RR_SCAN_MODE_DEFAULT &&
+        if (mfma_ok && left > valu_max && !exact_scan && ix->scan_mode == RR_SCAN_MODE_DEFAULT &&
             (ix->n_rows + 63) / 64 < 8 * (int64_t)pool)
             small = true;
         if (mfma_ok && left > valu_max && !small) {
@@ -1510,7 +1338,7 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
             // RR_SCAN_MODE_STORED, the exact split-operand scans, 64 queries per read
             n = left < RR_MFMA_MAXQ ? left : RR_MFMA_MAXQ;
             bool done = false;
-            if (!f32_chain && !exact_scan && ix->scan_mode == RR_SCAN_MODE_DEFAULT) {
+            if (!exact_scan && ix->scan_mode == RR_SCAN_MODE_DEFAULT) {
                 // up to 128 queries per scan launch; 193 .. 256 remaining queries go as a PAIR of launches that share one
                 // selection / rescoring sequence (the second part must still use the 128-slot kernel: > 64 queries)
                 static const bool no_pair = getenv("RR_NO_PAIR") != nullptr;
@@ -1522,12 +1350,7 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
                     n = nf;
                 }
             }
-            if (done) {
-            } else if (!f32_chain) rc = rr_dense_chunk_x3(ix, q, n, pool, rows, scores, st);
-            else if (bf16) rc = rr_dense_chunk_mfma_bf16(ix, q, n, pool, rows, scores, st);
-            else if (n <= 16) rc = rr_dense_chunk_mfma<1>(ix, q, n, pool, rows, scores, st);
-            else if (n <= 32) rc = rr_dense_chunk_mfma<2>(ix, q, n, pool, rows, scores, st);
-            else rc = rr_dense_chunk_mfma<4>(ix, q, n, pool, rows, scores, st);
+            if (!done) rc = rr_dense_chunk_x3(ix, q, n, pool, rows, scores, st);
         } else {
             // the VALU scan kernels read NB = 1/2/4/8 query slots; slots past n hold zeros
             const int vmax = small ? 8 : valu_max;
@@ -1564,9 +1387,9 @@ extern "C" int rr_dense_scan_slot_dev(rr_index* ix, int32_t slot, const float* d
     RR_HIP_TRY(hipSetDevice(ix->device));
     // only the batched filter path has a scan that can be split from its selection (5 .. 256 queries, matrix-core
     // kernels, default scan mode); everything else answers "not applied" and is served by rr_dense_topk_dev
-    static const bool exact_scan = getenv("RR_SCAN_EXACT") != nullptr, f32_chain = getenv("RR_SCAN_F32_CHAIN") != nullptr;
+    static const bool exact_scan = getenv("RR_SCAN_EXACT") != nullptr;
     const bool mfma_ok = ix->dim_pad == 384 && ix->n_rows >= 64;
-    if (!mfma_ok || n_queries <= 4 || n_queries > RR_SEL_MAXQ || exact_scan || f32_chain || ix->scan_mode != RR_SCAN_MODE_DEFAULT ||
+    if (!mfma_ok || n_queries <= 4 || n_queries > RR_SEL_MAXQ || exact_scan || ix->scan_mode != RR_SCAN_MODE_DEFAULT ||
         (n_queries > RR_FLT_MAXQ && n_queries <= RR_FLT_MAXQ + RR_MFMA_MAXQ))       // (129 .. 192 go as two chunks)
         return RR_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -1576,7 +1399,7 @@ extern "C" int rr_dense_scan_slot_dev(rr_index* ix, int32_t slot, const float* d
     d_queries = static_cast<const float*>(q_vis);
     rc = rr_slot_activate(ix, slot);
     if (rc) return rc;
-    rc = rr_scratch_enter(ix, st, true, false);
+    rc = rr_scratch_enter(ix, st, false);
     if (rc) return rc;
     rc = rr_ensure_scratch(ix, (int)rr_round_up(n_queries, RR_MFMA_MAXQ));
     if (rc) return rc;
@@ -1587,10 +1410,10 @@ extern "C" int rr_dense_scan_slot_dev(rr_index* ix, int32_t slot, const float* d
         hipLaunchKernelGGL(rr_pad_queries, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                            d_queries, ix->d_q, n_queries, ix->dim, ix->dim_pad, slots);
     rc = rr_dense_chunk_flt(ix, ix->d_q, n_queries, pool, nullptr, nullptr, st, 1, kth, d_bound, nullptr);
-    if (rc == RR_FLT_NO_BOUND || rc == RR_FLT_SMALL) return rr_scratch_leave(ix, st, true, false);     // not applied
+    if (rc == RR_FLT_NO_BOUND || rc == RR_FLT_SMALL) return rr_scratch_leave(ix, st, false);     // not applied
     if (rc) return rc;
     *applied = 1;
-    return rr_scratch_leave(ix, st, true, false);
+    return rr_scratch_leave(ix, st, false);
 }
 
 // phase 2 = selection / rescoring / ordering of the scan phase 1 left in `slot`, M-tiles opened no further down than `d_floor`.
@@ -1605,13 +1428,13 @@ extern "C" int rr_dense_select_part_dev(rr_index* ix, int32_t slot, int32_t part
     hipStream_t st = (hipStream_t)stream;
     int rc = rr_slot_activate(ix, slot);
     if (rc) return rc;
-    rc = rr_scratch_enter(ix, st, false, true);
+    rc = rr_scratch_enter(ix, st);
     if (rc) return rc;
     rc = rr_dense_chunk_flt(ix, ix->d_q, n_queries, pool, d_out_rows, d_out_scores, st, 2, 0, nullptr, d_floor, parts);
     RR_REQUIRE(rc != RR_FLT_SMALL, "rr_dense_select_dev: no scan of these %d queries (pool %d) is pending in slot %d: call "
                "rr_dense_scan_dev first and use its `applied` answer", n_queries, pool, slot);
     if (rc) return rc;
-    return rr_scratch_leave(ix, st, false, true);
+    return rr_scratch_leave(ix, st);
 }
 
 extern "C" int rr_dense_select_slot_dev(rr_index* ix, int32_t slot, int32_t n_queries, int32_t pool, const float* d_floor,
@@ -1659,8 +1482,8 @@ extern "C" int rr_dense_topk_slot_dev(rr_index* ix, int32_t slot, const float* d
     const int slots = (int)rr_round_up(n_queries, RR_MFMA_MAXQ);   // kernels read whole query tiles
     const int64_t total = (int64_t)slots * ix->dim_pad;
     // a call the batched filter path will serve in one chunk: padding + bf16 planes + bounds in ONE launch
-    static const bool plain_front = getenv("RR_SCAN_EXACT") != nullptr || getenv("RR_SCAN_F32_CHAIN") != nullptr;
-    const bool filter_call = ix->dim_pad == 384 && ix->n_rows >= 64 && n_queries > 4 && n_queries <= RR_SEL_MAXQ && !plain_front &&
+    static const bool exact_scan = getenv("RR_SCAN_EXACT") != nullptr;
+    const bool filter_call = ix->dim_pad == 384 && ix->n_rows >= 64 && n_queries > 4 && n_queries <= RR_SEL_MAXQ && !exact_scan &&
                              ix->scan_mode == RR_SCAN_MODE_DEFAULT && (ix->n_rows + 63) / 64 >= 8 * (int64_t)pool;
     if (!filter_call || rr_flt_pad_prep(ix, d_queries, n_queries, slots, st) != RR_OK)
         hipLaunchKernelGGL(rr_pad_queries, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,

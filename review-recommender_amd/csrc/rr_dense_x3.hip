@@ -14,15 +14,23 @@
 // other scan, and every score is still independent of where the row sits, of the shard and of
 // the grid (one fixed instruction sequence per 16-row M-tile x 16-query tile).
 //
-// Stream structure = rr_scan_mfma_f32: every wave walks its own run of 64-row tiles, fragment
-// loads straight into a VGPR ring (fp32: for each of the 12 K-blocks lane (r, kg) loads floats
-// [32b+4kg, +4) and [32b+16+4kg, +4) of row r, so the four lanes of a row read 64 contiguous bytes
-// per instruction; the query planes are permuted to the same k order), inline-asm loads with
-// counted waits, M-tile-major scores.  The queries are
-// split once per launch by rr_split_queries into three bf16 planes that each workgroup copies
-// to LDS, XOR-swizzled in 16-B units (unit u of query q sits at u ^ (q & 15)) so the B-fragment
-// ds_read_b128 is conflict-free.  64 queries x 3 planes = 144 KB: one 512-thread workgroup per
-// CU, 8 waves x 24 KB in flight.
+// Stream structure: every wave is an independent stream over its own contiguous run of 64-row
+// tiles, with no barrier and no inter-wave traffic after the prologue.  The matrix goes straight
+// into a ring of VGPRs, in fragment shape, and never through LDS: measured on this chip the scan
+// rate follows the bytes in flight per CU (Little's law at ~5-8 us loaded latency), and only the
+// register file can hold the ~190 KB per CU that takes; LDS-staged variants (register or LDS-DMA
+// staging, 64-96 KB in flight) stopped at 4.6-5.2 TB/s.  A register of the ring is loaded again,
+// for the next M-tile, as soon as the MFMAs that read it are issued.  The ring loads are inline
+// asm so that they stay interleaved with the MFMAs (hipcc sinks plain loads to the end of the
+// iteration and waits vmcnt(0) at its top); the waits are therefore counted by hand, and each is
+// tied ("+v") to the registers it guards so that no MFMA reading them is scheduled above it.
+// fp32: for each of the 12 K-blocks lane (r, kg) takes floats [32b+4kg, +4) and [32b+16+4kg, +4)
+// of row r, so the four lanes of a row read 64 contiguous bytes per instruction; the query planes
+// are permuted to the same k order.  Stored scores are M-tile-major ([row / 16][query][16]).
+// The 16 queries of a launch are split once by rr_split_queries into three bf16 planes that each
+// workgroup copies to LDS (3 x 16 x 768 B = 36 KB), XOR-swizzled in 16-B units (unit u of query q
+// sits at u ^ (q & 15)) so the B-fragment ds_read_b128 is conflict-free.  17..64 queries take the
+// wide-tile kernel of rr_dense_x3w.hip.
 #include "rr_x3.h"
 
 // queries (slots x 384 fp32) -> planes[3][slots][384] bf16 (truncating split, exact sum), in the k
@@ -74,25 +82,30 @@ __device__ __forceinline__ void rr_x3_mma(const rr_x3_afrag& f, bf16x8 q1, bf16x
 // writes only the maxima: the score stores cost more than a third of the scan time
 // (tools/x3 ablation: 3.35 -> 2.52 ms at 64 queries, 2.78 -> 2.43 ms at 16), the candidate tiles are
 // rescored afterwards by rr_rescore_x3 instead (~1 % of the matrix per 64 queries).
-template <int NQT, bool A_BF16, bool STORE>
-__global__ __launch_bounds__((NQT == 4 ? 512 : 256), 2) void rr_scan_mfma_x3(
-    const u32x4* __restrict__ mat, rr_scan_geom G, const u32x4* __restrict__ planes,  // [3][16*NQT][48] units
+// One 16-query tile per launch, 256 threads: two workgroups per CU, 8 waves x 24 KB (fp32) in flight.
+// (NQT = 1 with the accumulator and the maxima as arrays of NQT and loops over them is what is left of a
+// kernel that took 1, 2 or 4 query tiles: written as plain scalars the same arithmetic gets another
+// register allocation from hipcc, and this kernel's instruction stream is what its timings were taken on.)
+template <bool A_BF16, bool STORE>
+__global__ __launch_bounds__(256, 2) void rr_scan_mfma_x3(
+    const u32x4* __restrict__ mat, rr_scan_geom G, const u32x4* __restrict__ planes,  // [3][16][48] units
     float* __restrict__ sims, float* __restrict__ gmax, uint32_t* __restrict__ smax,
     const int32_t* __restrict__ fallback, int n_flags) {
-    constexpr int THREADS = NQT == 4 ? 512 : 256;
+    constexpr int NQT = 1;
+    constexpr int THREADS = 256;
     if (STORE && fallback) {
         int any = 0;
         for (int i = 0; i < n_flags; ++i) any |= fallback[i];
         if (!any) return;                                  // wave-uniform: nobody needs the stored scores
     }
-    constexpr int QN = 16 * NQT;
+    constexpr int QN = 16;
     constexpr int ROWU = A_BF16 ? 48 : 96;            // 16-byte units per matrix row
     constexpr int RING = A_BF16 ? 12 : 24;            // units a lane holds per M-tile
     __shared__ u32x4 qs[3 * QN * RR_X3_UNITS];
     const int tid = threadIdx.x;
     for (int i = tid; i < 3 * QN * RR_X3_UNITS; i += THREADS) {
         const int u = i % RR_X3_UNITS, pq = i / RR_X3_UNITS;      // pq = plane * QN + query
-        qs[pq * RR_X3_UNITS + (u ^ (pq & 15))] = planes[i];       // QN % 16 == 0: pq & 15 == query & 15
+        qs[pq * RR_X3_UNITS + (u ^ (pq & 15))] = planes[i];       // QN == 16: pq & 15 == query
     }
     __syncthreads();
 
@@ -141,8 +154,7 @@ __global__ __launch_bounds__((NQT == 4 ? 512 : 256), 2) void rr_scan_mfma_x3(
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     float tile_max[NQT], gm[NQT];
-#pragma unroll
-    for (int t = 0; t < NQT; ++t) tile_max[t] = gm[t] = -INFINITY;
+    tile_max[0] = gm[0] = -INFINITY;
 
 #pragma unroll 1
     for (int64_t mt = m0; mt < m1; ++mt) {
@@ -154,23 +166,19 @@ __global__ __launch_bounds__((NQT == 4 ? 512 : 256), 2) void rr_scan_mfma_x3(
 #pragma unroll
         for (int b = 0; b < 12; ++b) {
             // B fragments first: their LDS latency hides behind the wait for the matrix units and
-            // (fp32) the operand split.  TB query tiles at a time (register budget), the next
-            // group's reads issued before the current group's MFMAs.
-            constexpr int TB = (!A_BF16 && NQT == 4) ? 2 : NQT;
+            // (fp32) the operand split.
             const int u = 4 * b + kg;                         // 16-byte unit of the query planes
-            bf16x8 qf[NQT][3];
+            bf16x8 qf[3];
 #pragma unroll
-            for (int t = 0; t < TB; ++t)
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl)
-                    qf[t][pl] = __builtin_bit_cast(bf16x8, qs[(pl * QN + 16 * t + r) * RR_X3_UNITS + (u ^ r)]);
+            for (int pl = 0; pl < 3; ++pl)
+                qf[pl] = __builtin_bit_cast(bf16x8, qs[(pl * QN + r) * RR_X3_UNITS + (u ^ r)]);
             if (b % 6 == 0) {
                 // The ring is refilled in two bursts per M-tile (units of K-blocks 0-5 after block 5,
                 // of K-blocks 6-11 after block 11): a burst asks for 6 adjacent 128-B lines of each
                 // of the 16 rows at once, which keeps the DRAM pages open, where one line per row
                 // every K-block does not.  Younger operations than the burst this half needs: the
-                // other half's burst, and the NQT stores of the previous M-tile's epilogue (score
-                // stores when STORE -- its maxima only make the wait conservative --, else the
+                // other half's burst, and the one store of the previous M-tile's epilogue (the score
+                // store when STORE -- its maxima only make the wait conservative --, else the
                 // M-tile maxima written after every fourth M-tile).
                 constexpr int H = RING / 2;
                 if (STORE || maxima_pending) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(H + NQT) : "memory");
@@ -183,14 +191,7 @@ __global__ __launch_bounds__((NQT == 4 ? 512 : 256), 2) void rr_scan_mfma_x3(
                                                                to_mfma_lanes(a[A_BF16 ? b : 2 * b + 1]));
 #pragma unroll
             for (int t = 0; t < NQT; ++t) {
-                if (t % TB == 0 && t + TB < NQT) {            // prefetch the next group of query tiles
-#pragma unroll
-                    for (int t2 = t + TB; t2 < t + 2 * TB; ++t2)
-#pragma unroll
-                        for (int pl = 0; pl < 3; ++pl)
-                            qf[t2][pl] = __builtin_bit_cast(bf16x8, qs[(pl * QN + 16 * t2 + r) * RR_X3_UNITS + (u ^ r)]);
-                }
-                rr_x3_mma<A_BF16>(af, qf[t][0], qf[t][1], qf[t][2], acc[t]);
+                rr_x3_mma<A_BF16>(af, qf[0], qf[1], qf[2], acc[t]);
             }
             if (b % 6 == 5) {
                 // this half's units of the next M-tile, as one burst, into the registers just consumed
@@ -203,7 +204,7 @@ __global__ __launch_bounds__((NQT == 4 ? 512 : 256), 2) void rr_scan_mfma_x3(
                 }
             }
         }
-        // lane (r, kg) holds rows 4*kg .. 4*kg+3 of the M-tile for query 16*t + r
+        // lane (r, kg) holds rows 4*kg .. 4*kg+3 of the M-tile for query r
         const int64_t row0 = mt * 16 + 4 * kg;
         const bool tile_end = (mt & 3) == 3;
 #pragma unroll
@@ -212,7 +213,7 @@ __global__ __launch_bounds__((NQT == 4 ? 512 : 256), 2) void rr_scan_mfma_x3(
             if (STORE) *reinterpret_cast<f32x4*>(sims + ((mt * QN + 16 * t + r) * 16 + 4 * kg)) = v;
             float m4 = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
             m4 = fmaxf(m4, __shfl_xor(m4, 16, 64));
-            m4 = fmaxf(m4, __shfl_xor(m4, 32, 64));      // maximum of the M-tile for query 16*t + r, in all four kg lanes
+            m4 = fmaxf(m4, __shfl_xor(m4, 32, 64));      // maximum of the M-tile for query r, in all four kg lanes
             if (STORE) {
                 tile_max[t] = fmaxf(tile_max[t], m4);
                 if (tile_end) {
@@ -286,23 +287,13 @@ __global__ __launch_bounds__(256) void rr_rescore_x3(
     }
 }
 
-bool rr_x3_stored_path(const rr_index* ix) {
-    if (ix->scan_mode == RR_SCAN_MODE_STORED) return true;
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("RR_X3_STORED");       // diagnostic: single-pass scan that stores every score
-        v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
-}
-
-template <int NQT, bool A_BF16>
+template <bool A_BF16>
 static int rr_dense_chunk_x3_t(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                                float* d_scores, hipStream_t st) {
-    constexpr int THREADS = NQT == 4 ? 512 : 256;
-    constexpr int QN = 16 * NQT;
+    constexpr int THREADS = 256;
+    constexpr int QN = 16;
     static int waves = 0;
-    if (!waves) waves = rr_resident_waves((const void*)rr_scan_mfma_x3<NQT, A_BF16, false>, THREADS, ix->device);
+    if (!waves) waves = rr_resident_waves((const void*)rr_scan_mfma_x3<A_BF16, false>, THREADS, ix->device);
     rr_scan_geom G = rr_make_geom(ix, waves / 4);
     G.qs = QN;
     // the split query planes live behind the staged queries in the index's query buffer
@@ -314,8 +305,8 @@ static int rr_dense_chunk_x3_t(rr_index* ix, const float* d_q, int nq, int pool,
     rr_launch_split_queries(d_q, planes, QN, A_BF16 ? RR_X3_ORDER_NATURAL : RR_X3_ORDER_PAIR64, st);
     if (rr_x3_stored_path(ix)) {
         const int slot = rr_scan_events_begin(ix, st);
-    rr_scan_note(ix, 3, NQT, nq, A_BF16 ? 3 : 6);
-        hipLaunchKernelGGL((rr_scan_mfma_x3<NQT, A_BF16, true>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
+        rr_scan_note(ix, 3, 1, nq, A_BF16 ? 3 : 6);
+        hipLaunchKernelGGL((rr_scan_mfma_x3<A_BF16, true>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
                            ix->d_gmax, ix->d_smax, (const int32_t*)nullptr, 0);
         rr_scan_events_end(ix, slot, st);
         rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st);
@@ -323,8 +314,8 @@ static int rr_dense_chunk_x3_t(rr_index* ix, const float* d_q, int nq, int pool,
         return RR_OK;
     }
     const int slot = rr_scan_events_begin(ix, st);
-    rr_scan_note(ix, 3, NQT, nq, A_BF16 ? 3 : 6);
-    hipLaunchKernelGGL((rr_scan_mfma_x3<NQT, A_BF16, false>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
+    rr_scan_note(ix, 3, 1, nq, A_BF16 ? 3 : 6);
+    hipLaunchKernelGGL((rr_scan_mfma_x3<A_BF16, false>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
                        ix->d_gmax, ix->d_smax, (const int32_t*)nullptr, 0);
     rr_scan_events_end(ix, slot, st);
     rr_launch_select_mtiles(ix, G, nq, pool, st);
@@ -332,29 +323,17 @@ static int rr_dense_chunk_x3_t(rr_index* ix, const float* d_q, int nq, int pool,
                        X.mtiles, X.count, X.fb, X.sc);
     rr_launch_select_rescored(ix, G, nq, pool, d_rows, d_scores, st);
     // Fallback for the queries that raised their flag: both launches return at once otherwise.
-    hipLaunchKernelGGL((rr_scan_mfma_x3<NQT, A_BF16, true>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
+    hipLaunchKernelGGL((rr_scan_mfma_x3<A_BF16, true>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
                        ix->d_gmax, ix->d_smax, (const int32_t*)X.fb, nq);
     rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st, X.fb);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }
 
+// 5..16 queries: the 16x16x32 tile here; 17..64: the 32x32x16 tile of rr_dense_x3w.hip
 int rr_dense_chunk_x3(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                       float* d_scores, hipStream_t st) {
-    const bool b = ix->dtype == RR_DTYPE_BF16;
-    static int narrow = -1;
-    if (narrow < 0) {
-        const char* e = getenv("RR_X3_NARROW");       // diagnostic: 16x16x32 tiles for every batch size
-        narrow = (e && e[0] == '1') ? 1 : 0;
-    }
-    if (nq > 16 && !narrow) return rr_dense_chunk_x3w(ix, d_q, nq, pool, d_rows, d_scores, st);
-    if (nq <= 16)
-        return b ? rr_dense_chunk_x3_t<1, true>(ix, d_q, nq, pool, d_rows, d_scores, st)
-                 : rr_dense_chunk_x3_t<1, false>(ix, d_q, nq, pool, d_rows, d_scores, st);
-    if (nq <= 32)
-        return b ? rr_dense_chunk_x3_t<2, true>(ix, d_q, nq, pool, d_rows, d_scores, st)
-                 : rr_dense_chunk_x3_t<2, false>(ix, d_q, nq, pool, d_rows, d_scores, st);
-    return b ? rr_dense_chunk_x3_t<4, true>(ix, d_q, nq, pool, d_rows, d_scores, st)
-             : rr_dense_chunk_x3_t<4, false>(ix, d_q, nq, pool, d_rows, d_scores, st);
+    if (nq > 16) return rr_dense_chunk_x3w(ix, d_q, nq, pool, d_rows, d_scores, st);
+    return ix->dtype == RR_DTYPE_BF16 ? rr_dense_chunk_x3_t<true>(ix, d_q, nq, pool, d_rows, d_scores, st)
+                                      : rr_dense_chunk_x3_t<false>(ix, d_q, nq, pool, d_rows, d_scores, st);
 }
-

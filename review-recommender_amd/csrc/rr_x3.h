@@ -58,8 +58,8 @@ __device__ __forceinline__ rr_x3_afrag rr_x3_split(u32x4 lo_unit, u32x4 hi_unit)
 #define RR_X3_ORDER_PAIR64 1     // rr_scan_mfma_x3 on an fp32 matrix: slot (kg, j) = dim 4kg + j | 16 + 4kg + (j - 4)
 #define RR_X3_ORDER_WIDE_BF16 2  // rr_scan_x3w on a bf16 matrix: K-step v, slot (h, j) = dim 16h + 8v + j
 void rr_launch_split_queries(const float* d_q, unsigned short* planes, int slots, int order, hipStream_t st);
-// RR_SCAN_MODE_STORED on the handle (or RR_X3_STORED=1 in the environment): single stored-score pass
-bool rr_x3_stored_path(const rr_index* ix);
+// RR_SCAN_MODE_STORED on the handle: single stored-score pass
+static inline bool rr_x3_stored_path(const rr_index* ix) { return ix->scan_mode == RR_SCAN_MODE_STORED; }
 // 32x32x16-tile scan for 17..64 queries (rr_dense_x3w.hip)
 int rr_dense_chunk_x3w(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                        float* d_scores, hipStream_t st);

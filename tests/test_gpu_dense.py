@@ -451,37 +451,6 @@ def test_adopted_matrix_changed_behind_the_index():
     ix.close(); fresh.close()
 
 
-def test_f32_chain_matrix_core_path_in_a_subprocess():
-    """RR_SCAN_F32_CHAIN=1 selects the f32-input MFMA kernels (scores = pure fmaf chains) for
-    batches; the switch is read once per process, so the check runs in a child process."""
-    import os
-    import subprocess
-    import sys
-    code = r'''
-import sys; sys.path.insert(0, "tests"); sys.path.insert(0, ".")
-import numpy as np
-from oracle import dense as OD
-from parity import assert_topk_matches
-from review_recommender_amd import synth
-from review_recommender_amd.index import ProductIndex
-for dtype in ("f32", "bf16"):
-    V = synth.unit_rows(20001, 384, 71)
-    Vo = OD.round_to_bf16(V) if dtype == "bf16" else V
-    Q = synth.unit_rows(40, 384, 72)
-    ix = ProductIndex.from_rows(V, dtype=dtype)
-    rows, scores = ix.dense_topk(Q, 150)
-    for i in range(len(Q)):
-        assert_topk_matches(rows[i], scores[i], OD.sims_float64(Vo, Q[i]), 150)
-    r2, s2 = ix.dense_topk(np.concatenate([Q[5:12], Q[:1]]), 150)      # batch-invariant, bitwise
-    assert np.array_equal(r2[-1], rows[0]) and np.array_equal(s2[-1], scores[0])
-print("chain-ok")
-'''
-    env = dict(os.environ, RR_SCAN_F32_CHAIN="1")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "chain-ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
-
-
 def test_exact_split_operand_scans_in_a_subprocess():
     """RR_SCAN_EXACT=1 turns the filter scan off: batches run the split-operand scans (16x16x32 tiles up
     to 16 queries, 32x32x16 beyond) with their own two-pass selection and bit-exact rescoring -- the
@@ -501,15 +470,23 @@ for dtype in ("f32", "bf16"):
     V[149_990:150_030] = V[7]                     # ties in the ragged tail
     Vo = OD.round_to_bf16(V) if dtype == "bf16" else V
     ix = ProductIndex.from_rows(V, dtype=dtype)
+    def routed(batch):                                # 5..16 queries: rr_scan_mfma_x3 (one tile); 17..64: rr_scan_x3w
+        info = ix.last_scan_info()
+        if batch == 9:
+            assert info[0] == 3 and info[1] == 1, (dtype, batch, info)
+        else:
+            assert info[0] == 4 and (batch != 64 or info[1] == 2), (dtype, batch, info)
     for batch in (9, 40, 64):
         Q = synth.unit_rows(batch, 384, 172 + batch)
         Q[2] = V[7]
         rows, scores = ix.dense_topk(Q, 150)
+        routed(batch)
         assert ix.select_trace()[0] == 2, ix.select_trace()[:4]       # two-pass, no stored scores
         for i in (0, 2, batch - 1):
             assert_topk_matches(rows[i], scores[i], OD.sims_float64(Vo, Q[i]), 150)
         ix.set_scan_mode(True)
         r1, s1 = ix.dense_topk(Q, 150)                                # the stored-score pass: bit-equal
+        routed(batch)
         ix.set_scan_mode(False)
         assert np.array_equal(r1, rows) and np.array_equal(s1.view(np.uint32), scores.view(np.uint32))
 print("exact-ok")

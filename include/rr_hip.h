@@ -262,7 +262,20 @@ int rr_fuse_topk_dev(rr_index* ix, const rr_fuse_params* p, int32_t n_queries,
                      const double* d_n_reviews, const double* d_avg_stars, const double* d_log1p_n,
                      const float* d_rerank, const float* d_best, const float* d_gate,
                      int64_t* d_out_rows, double* d_out_cols, int32_t* d_out_order, void* stream);
-/* Host-buffer form of the same call. */
+/* The same call with a CANDIDATE-aligned gate column that survives the merge: d_cand_gate holds one factor per candidate,
+ * addressed exactly like d_dense -- [query][n_candidates] when cand_per_rank == 0, gathered blocks
+ * [rank][query][cand_per_rank], cand_rank_stride_bytes apart, otherwise -- so a row shard can gate the candidates it owns
+ * BEFORE the exchange and ship the factor in its payload (sharded.py): whichever branch of the merge places a candidate
+ * (the binary-search merge of ordered lists, the bitonic sort of an unordered one), its factor is read through the same
+ * slot map as its dense and BM25 scores, once, where the blend applies the gate.  No first pass is needed to learn the pool
+ * order.  NULL = ones.  d_gate and d_cand_gate both non-NULL is RR_E_INVALID with nothing launched.
+ * rr_fuse_topk_dev is this call with d_cand_gate = NULL. */
+int rr_fuse_topk_cand_dev(rr_index* ix, const rr_fuse_params* p, int32_t n_queries,
+                          const int64_t* d_rows, const float* d_dense, const float* d_bm25,
+                          const double* d_n_reviews, const double* d_avg_stars, const double* d_log1p_n,
+                          const float* d_rerank, const float* d_best, const float* d_gate, const float* d_cand_gate,
+                          int64_t* d_out_rows, double* d_out_cols, int32_t* d_out_order, void* stream);
+/* Host-buffer form of rr_fuse_topk_dev. */
 int rr_fuse_topk(rr_index* ix, const rr_fuse_params* p, int32_t n_queries,
                  const int64_t* h_rows, const float* h_dense, const float* h_bm25,
                  const double* h_n_reviews, const double* h_avg_stars, const double* h_log1p_n,

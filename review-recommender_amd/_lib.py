@@ -82,6 +82,7 @@ PROTOTYPES = {
     "rr_bm25_set_idf": (C.c_int, [c_vp, c_vp, c_f64]),
     "rr_bm25_copy_csr": (C.c_int, [c_vp] + [c_vp] * 7),
     "rr_fuse_topk_dev": (C.c_int, [c_vp, P(FuseParams), c_i32] + [c_vp] * 9 + [c_vp] * 3 + [c_vp]),
+    "rr_fuse_topk_cand_dev": (C.c_int, [c_vp, P(FuseParams), c_i32] + [c_vp] * 10 + [c_vp] * 3 + [c_vp]),
     "rr_fuse_topk": (C.c_int, [c_vp, P(FuseParams), c_i32] + [c_vp] * 9 + [c_vp] * 3),
     "rr_index_gather_meta_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rr_copy_segments_dev": (C.c_int, [c_vp, c_i32, c_i32, c_vp]),

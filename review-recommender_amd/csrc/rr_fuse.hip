@@ -158,7 +158,8 @@ __global__ __launch_bounds__(RR_FUSE_THREADS) void rr_fuse(
     rr_fuse_dev_params fp, const int64_t* __restrict__ g_rows, const float* __restrict__ g_dense,
     const float* __restrict__ g_bm25, const double* __restrict__ g_n, const double* __restrict__ g_avg,
     const double* __restrict__ g_l1p, const float* __restrict__ g_rerank, const float* __restrict__ g_best,
-    const float* __restrict__ g_gate, const double* __restrict__ ix_n, const double* __restrict__ ix_avg,
+    const float* __restrict__ g_gate, const float* __restrict__ g_cand_gate, const double* __restrict__ ix_n,
+    const double* __restrict__ ix_avg,
     const double* __restrict__ ix_l1p, int64_t* __restrict__ out_rows, double* __restrict__ out_cols,
     int32_t* __restrict__ out_order) {
     extern __shared__ __align__(16) unsigned char lds[];
@@ -326,7 +327,8 @@ __global__ __launch_bounds__(RR_FUSE_THREADS) void rr_fuse(
         sat = (sat != sat) ? sat : (1.0 < sat ? 1.0 : sat);     // np.minimum propagates NaN
         const float trust = fp.p.apply_trust ? (float)(0.6 * ramp + 0.4 * sat) : 1.0f;
         c_trust[i] = trust;
-        const float gate = g_gate ? g_gate[(int64_t)q * pool + i] : 1.0f;
+        // pool-aligned factor, or the candidate's own: it came in beside dense / bm25 and is read through the slot map once
+        const float gate = g_gate ? g_gate[(int64_t)q * pool + i] : (g_cand_gate ? at.get(g_cand_gate, c_src[i]) : 1.0f);
 
         const float t_dense = fp.w_dense32 * c_dense[i];
         const float t_bm25 = fp.w_bm2532 * c_bm25[i];
@@ -440,15 +442,16 @@ static int rr_fuse_check(const rr_index* ix, const rr_fuse_params* p, int32_t nq
     return RR_OK;
 }
 
-extern "C" int rr_fuse_topk_dev(rr_index* ix, const rr_fuse_params* p, int32_t n_queries,
-                                const int64_t* d_rows, const float* d_dense, const float* d_bm25,
-                                const double* d_n_reviews, const double* d_avg_stars,
-                                const double* d_log1p_n, const float* d_rerank, const float* d_best,
-                                const float* d_gate, int64_t* d_out_rows, double* d_out_cols,
-                                int32_t* d_out_order, void* stream) {
+extern "C" int rr_fuse_topk_cand_dev(rr_index* ix, const rr_fuse_params* p, int32_t n_queries,
+                                     const int64_t* d_rows, const float* d_dense, const float* d_bm25,
+                                     const double* d_n_reviews, const double* d_avg_stars,
+                                     const double* d_log1p_n, const float* d_rerank, const float* d_best,
+                                     const float* d_gate, const float* d_cand_gate, int64_t* d_out_rows,
+                                     double* d_out_cols, int32_t* d_out_order, void* stream) {
     int rc = rr_fuse_check(ix, p, n_queries, d_rows, d_dense, d_n_reviews, d_avg_stars, d_log1p_n);
     if (rc) return rc;
     RR_REQUIRE(d_out_rows && d_out_cols && d_out_order, "rr_fuse_topk_dev: NULL output");
+    RR_REQUIRE(!(d_gate && d_cand_gate), "rr_fuse_topk_cand_dev: pass the pool-aligned gate or the candidate-aligned one, not both");
     RR_HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;  // NULL = the device's default stream
     rr_fuse_dev_params fp;
@@ -474,11 +477,21 @@ extern "C" int rr_fuse_topk_dev(rr_index* ix, const rr_fuse_params* p, int32_t n
         }
     }
     hipLaunchKernelGGL(rr_fuse, dim3(n_queries), dim3(RR_FUSE_THREADS), lds, st, fp, d_rows, d_dense,
-                       d_bm25, d_n_reviews, d_avg_stars, d_log1p_n, d_rerank, d_best, d_gate,
+                       d_bm25, d_n_reviews, d_avg_stars, d_log1p_n, d_rerank, d_best, d_gate, d_cand_gate,
                        ix->d_n_reviews, ix->d_avg_stars, ix->d_log1p_n, d_out_rows, d_out_cols,
                        d_out_order);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
+}
+
+extern "C" int rr_fuse_topk_dev(rr_index* ix, const rr_fuse_params* p, int32_t n_queries,
+                                const int64_t* d_rows, const float* d_dense, const float* d_bm25,
+                                const double* d_n_reviews, const double* d_avg_stars,
+                                const double* d_log1p_n, const float* d_rerank, const float* d_best,
+                                const float* d_gate, int64_t* d_out_rows, double* d_out_cols,
+                                int32_t* d_out_order, void* stream) {
+    return rr_fuse_topk_cand_dev(ix, p, n_queries, d_rows, d_dense, d_bm25, d_n_reviews, d_avg_stars, d_log1p_n, d_rerank,
+                                 d_best, d_gate, NULL, d_out_rows, d_out_cols, d_out_order, stream);
 }
 
 namespace {

@@ -230,10 +230,11 @@ class GateText:
         buf, where = packed.buffer()
         return torch.from_numpy(buf).to(torch.device("cuda", self.device)), where
 
-    def factors(self, rows, packed: PackedGroups, staged=None, want_hits: bool = False):
+    def factors(self, rows, packed: PackedGroups, staged=None, want_hits: bool = False, out=None):
         """rr_gate_factors_dev on the current stream: ``rows`` (B, pool) int64 device tensor of global rows ->
         float32 (B, pool) gate factors on the device (and the int32 hit masks with ``want_hits``).  ``staged``: what
-        `upload(packed)` returned, when the caller uploaded ahead of the kernels in front of this one."""
+        `upload(packed)` returned, when the caller uploaded ahead of the kernels in front of this one.  ``out``: a contiguous
+        float32 (B, pool) device tensor to write the factors into (e.g. the gate column of a shard payload)."""
         import torch
         B, pool = rows.shape
         if B != packed.n_queries:
@@ -241,7 +242,10 @@ class GateText:
         if not rows.is_contiguous() or rows.dtype != torch.int64:
             raise ValueError("rows must be a contiguous int64 tensor")
         d_buf, where = staged if staged is not None else self.upload(packed)
-        gate = torch.empty((B, pool), dtype=torch.float32, device=rows.device)
+        if out is not None and (out.shape != rows.shape or out.dtype != torch.float32 or not out.is_contiguous()
+                                or out.device != rows.device):
+            raise ValueError("out must be a contiguous float32 tensor of the rows' shape, on their device")
+        gate = out if out is not None else torch.empty((B, pool), dtype=torch.float32, device=rows.device)
         hits = torch.empty((B, pool), dtype=torch.int32, device=rows.device) if want_hits else None
         at = lambda name: C.c_void_p(d_buf.data_ptr() + where[name])
         _lib.check(_lib.load().rr_gate_factors_dev(
@@ -252,11 +256,11 @@ class GateText:
             C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)), "rr_gate_factors_dev")
         return (gate, hits) if want_hits else gate
 
-    def gate(self, rows, packed: PackedGroups, gate_host=None, staged=None):
+    def gate(self, rows, packed: PackedGroups, gate_host=None, staged=None, out=None):
         """`factors`, and for the queries the kernel cannot hold (``packed.host_queries``) their rows of the gate tensor from
         ``gate_host(b, rows[b] as numpy) -> (pool,) float32``: only then are the candidate rows copied to the host."""
         import torch
-        gate = self.factors(rows, packed, staged)
+        gate = self.factors(rows, packed, staged, out=out)
         if packed.host_queries:
             if gate_host is None:
                 raise ValueError(f"queries {packed.host_queries} exceed the gate kernel's limits and no gate_host was given")

@@ -114,6 +114,22 @@ def _narrow(ids):
     return ((ids.to(torch.int32) + 32768) % 65536 - 32768).to(torch.int16)
 
 
+def join_planes(toks, offs):
+    """[ids of plane r (its n_tokens, any integer dtype)], [offsets of plane r, int64 [n_r + 1]] -> (ids, offsets) of the
+    planes back to back: plane r's offsets without their leading 0, rebased by the tokens in front of it.  torch tensors on
+    any one device (the GPU for `RerankText.concat`, the host in the collective's CPU test)."""
+    import torch
+    if len(toks) != len(offs) or not toks:
+        raise ValueError("join_planes: one id tensor and one offset tensor per plane")
+    parts, base = [offs[0][:1].to(torch.int64)], 0
+    for t, o in zip(toks, offs):
+        if int(o.numel()) < 1:
+            raise ValueError("join_planes: an offset tensor holds at least the leading 0")
+        parts.append(o[1:].to(torch.int64) + base)
+        base += int(t.numel())
+    return torch.cat(list(toks)), torch.cat(parts)
+
+
 # ---------------------------------------------------------------------------------- the plane on the device
 class RerankText:
     """The token plane of one index on one GPU: ``d_tok`` the ids back to back (uint16 in memory; held in a torch.int16
@@ -231,6 +247,40 @@ class RerankText:
             wp.close()
         return self
 
+    @classmethod
+    def concat(cls, planes: Sequence["RerankText"]) -> "RerankText":
+        """The planes of consecutive row shards, in rank order, as ONE plane with the first shard's ``row_offset``: the ids
+        appended, the offsets rebased, all on the device (`join_planes`) -- bitwise the plane `from_texts` builds from all
+        the texts at once (a document's ids do not depend on its neighbours).  The planes must live on one GPU."""
+        if not planes:
+            raise ValueError("no planes to join")
+        first = planes[0]
+        at = first.row_offset
+        for p in planes:
+            if p.row_offset != at:
+                raise ValueError(f"the planes are not consecutive row shards: one begins at row {p.row_offset}, expected {at}")
+            if (p.max_length, p.cls_id, p.sep_id, p.vocab_size, p.device) != (first.max_length, first.cls_id, first.sep_id,
+                                                                               first.vocab_size, first.device):
+                raise ValueError("the planes were cut for different models or live on different GPUs")
+            at += p.n
+        tok, off = join_planes([p.d_tok[:p.n_tokens] for p in planes], [p.d_off for p in planes])
+        host_docs = [p.row_offset - first.row_offset + i for p in planes for i in p.host_docs]
+        return cls.from_arrays(tok, off, first, host_docs)
+
+    @classmethod
+    def from_arrays(cls, tok, off, like: "RerankText", host_docs: Sequence[int] = ()) -> "RerankText":
+        """A plane over ready device tensors (``tok`` int16 ids back to back, ``off`` int64 [n + 1]) with the model constants,
+        the device and the row offset of ``like``."""
+        import torch
+        self = cls(like.device, like.row_offset)
+        self.max_length, self.vocab_size, self.cls_id, self.sep_id = like.max_length, like.vocab_size, like.cls_id, like.sep_id
+        dev = torch.device("cuda", self.device)
+        self.n, self.n_tokens = int(off.numel()) - 1, int(tok.numel())
+        self.d_tok = tok.to(dev).contiguous() if self.n_tokens else torch.zeros(1, dtype=torch.int16, device=dev)
+        self.d_off = off.to(dev).contiguous()
+        self.host_docs = list(host_docs)
+        return self
+
     def tokens(self) -> List[np.ndarray]:
         """The plane on the host: per document its uint16 ids (tests)."""
         flat = self.d_tok[:self.n_tokens].cpu().numpy().view(np.uint16)
@@ -291,14 +341,17 @@ class RerankText:
                                           C.c_void_p(ids.data_ptr() + 8 * n_tokens), st), "rr_pairs_write_dev")
         return tok, typ, pos, cu
 
-    def scores(self, ce, rows, rr_k: int, packed: PackedQueries):
+    def scores(self, ce, rows, rr_k: int, packed: PackedQueries, first_pair: int = 0, n_pairs: Optional[int] = None):
         """The reranker's scores of the first ``rr_k`` candidates of every query: (B, rr_k) float32 on the device, what
         ``ce.predict`` gives for the pairs ``(query, agg_text[:2000])``.  The pairs go through the model in chunks of
         ``n_pairs * max_length <= min(ce.model.max_tokens_per_call, FP32_MAX_TOKENS)`` (a bound that needs no lengths on the
         host); per chunk `pairs` and `forward_packed_dev`.  A pass of the fp32 mode that leaves the fp16 range poisons its
         call's logits with NaN (include/rr_hip.h): after all chunks ONE ``isnan`` over the scores decides whether the handle
         switches to the wide-range kernels and the chunks run again, once.  The rows of ``packed.host_queries`` hold the
-        scores of the EMPTY query: the caller overwrites them (HybridSearcher.search_batch does)."""
+        scores of the EMPTY query: the caller overwrites them (HybridSearcher.search_batch does).
+        ``first_pair`` / ``n_pairs``: only the range [first_pair, first_pair + n_pairs) of the flattened B x rr_k pair list
+        (a rank's share, sharded.split_pairs; it may begin and end inside a query) -> a flat (n_pairs,) tensor.  An empty
+        range launches nothing and returns an empty tensor."""
         import torch
         from .cross_encoder import FP32_MAX_TOKENS, OUT_LOGITS
         self.check_model(ce)
@@ -307,7 +360,13 @@ class RerankText:
         if not 1 <= rr_k <= pool:
             raise ValueError(f"rr_k {rr_k} outside 1..pool = {pool}")
         L = self.max_length
-        total = B * rr_k
+        whole = n_pairs is None and int(first_pair) == 0
+        first = int(first_pair)
+        total = B * rr_k - first if n_pairs is None else int(n_pairs)
+        if first < 0 or total < 0 or first + total > B * rr_k:
+            raise ValueError(f"pairs [{first}, {first + total}) outside the batch's {B * rr_k}")
+        if total == 0:
+            return torch.empty(0, dtype=torch.float32, device=rows.device)
         step = max(1, min(int(ce.model.max_tokens_per_call), FP32_MAX_TOKENS) // L)
         with torch.cuda.device(rows.device):
             staged = self.upload(packed)
@@ -316,7 +375,7 @@ class RerankText:
             def run():
                 for a in range(0, total, step):
                     m = min(step, total - a)
-                    tok, typ, pos, cu = self.pairs(rows, rr_k, packed, a, m, staged)
+                    tok, typ, pos, cu = self.pairs(rows, rr_k, packed, first + a, m, staged)
                     out[a:a + m] = ce.model.forward_packed_dev(tok, typ, pos, cu, m, L, OUT_LOGITS)[:, 0]
 
             run()
@@ -330,7 +389,7 @@ class RerankText:
             self.check()
             if ce.activation == "sigmoid":                 # CrossEncoder._post: float64, rounded once to float32
                 out = (1.0 / (1.0 + torch.exp(-out.to(torch.float64)))).to(torch.float32)
-        return out.view(B, rr_k)
+        return out.view(B, rr_k) if whole else out
 
     def check(self) -> None:
         """Raises ValueError when a call since the last check met a candidate row outside the plane or refused a pair

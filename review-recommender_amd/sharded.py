@@ -13,6 +13,13 @@ merges world x pool candidates to the global top-pool by (dense desc, row asc) a
 Every rank ends with the same result.  The global top-pool is contained in the union of
 the local top-pools, and a row's score does not depend on the shard it sits in
 (csrc/rr_dense.hip), so the answer equals the single-GPU answer bit for bit.
+
+The attribute gate depends on (query, product text) only: with ``gate_groups`` every rank matches its OWN candidates against
+the gate plane of its own rows (gate.GateText, 1/world of the corpus) between K2 and the all-gather, the factor rides in the
+payload as one more float32 column (44 B/candidate), and K3 reads it through the merge's slot map (rr_fuse_topk_cand_dev):
+one K3 pass, no host wait, no replicated texts.  The reranker scores the MERGED pool, so its token plane (about 1 KB per
+product) is replicated once per index (`exchange_plane`); per batch every rank assembles and scores its share of the pairs
+on the device (``rerank_pairs``).
 """
 from __future__ import annotations
 
@@ -42,6 +49,7 @@ class PayloadLayout:
     """Byte offsets of the candidate payload one rank contributes (all 16-B aligned)."""
     n_queries: int
     pool: int
+    gate: bool = False          # a float32 column of gate factors behind bm25 (44 B/candidate instead of 40)
 
     @property
     def count(self) -> int:
@@ -63,16 +71,21 @@ class PayloadLayout:
     @property
     def off_bm25(self) -> int: return self.off_dense + self._al(self.count * 4)
     @property
-    def nbytes(self) -> int: return self.off_bm25 + self._al(self.count * 4)
+    def off_gate(self) -> int: return self.off_bm25 + self._al(self.count * 4)
+    @property
+    def nbytes(self) -> int: return self.off_gate + (self._al(self.count * 4) if self.gate else 0)
 
     def views(self, buf):
         """Typed (n_queries, pool) views into one rank's uint8 buffer (torch tensor)."""
         import torch
         c, shape = self.count, (self.n_queries, self.pool)
         v = lambda off, n, dt: buf[off:off + n].view(dt).view(shape)
-        return {"rows": v(self.off_rows, c * 8, torch.int64), "n": v(self.off_n, c * 8, torch.float64),
-                "avg": v(self.off_avg, c * 8, torch.float64), "l1p": v(self.off_l1p, c * 8, torch.float64),
-                "dense": v(self.off_dense, c * 4, torch.float32), "bm25": v(self.off_bm25, c * 4, torch.float32)}
+        out = {"rows": v(self.off_rows, c * 8, torch.int64), "n": v(self.off_n, c * 8, torch.float64),
+               "avg": v(self.off_avg, c * 8, torch.float64), "l1p": v(self.off_l1p, c * 8, torch.float64),
+               "dense": v(self.off_dense, c * 4, torch.float32), "bm25": v(self.off_bm25, c * 4, torch.float32)}
+        if self.gate:
+            out["gate"] = v(self.off_gate, c * 4, torch.float32)
+        return out
 
 
 class PendingExchange:
@@ -195,6 +208,50 @@ def exchange_scores(local, n_pairs: int, world: int, group=None):
     return torch.cat(parts)
 
 
+def exchange_plane_arrays(tok, off, world: int, group=None):
+    """The collective half of `exchange_plane`: every rank contributes the ids (int16, its n_tokens) and the offsets (int64
+    [n + 1]) of its shard's token plane; all ranks end with the same joined (ids, offsets) of the whole corpus
+    (rerank.join_planes).  Three all-gathers: the sizes, then the id and the offset tensors padded to the longest."""
+    import torch
+    import torch.distributed as dist
+    from .rerank import join_planes
+    if world == 1:
+        return join_planes([tok], [off])
+    via_host = tok.is_cuda and dist.get_backend(group) != "nccl"        # gloo rehearsal on a GPU box: gloo gathers host tensors
+
+    def gather(x):
+        src = x.cpu() if via_host else x
+        out = torch.empty((world,) + tuple(src.shape), dtype=src.dtype, device=src.device)
+        if dist.get_backend(group) == "nccl":
+            dist.all_gather_into_tensor(out, src.contiguous(), group=group)
+        else:
+            dist.all_gather([out[r] for r in range(world)], src.contiguous(), group=group)
+        return out.to(x.device) if via_host else out
+
+    sizes = gather(torch.tensor([int(tok.numel()), int(off.numel())], dtype=torch.int64, device=tok.device)).cpu().tolist()
+    n_tok, n_off = max(s[0] for s in sizes), max(s[1] for s in sizes)
+    tok_pad = torch.zeros(max(n_tok, 1), dtype=tok.dtype, device=tok.device)
+    tok_pad[:tok.numel()] = tok
+    off_pad = torch.zeros(n_off, dtype=torch.int64, device=off.device)
+    off_pad[:off.numel()] = off
+    # (the ids travel as bytes: gloo has no 16-bit integers)
+    toks, offs = gather(tok_pad.view(torch.uint8)).view(tok.dtype), gather(off_pad)
+    return join_planes([toks[r, :sizes[r][0]] for r in range(world)], [offs[r, :sizes[r][1]] for r in range(world)])
+
+
+def exchange_plane(local, world: int, group=None):
+    """Replicates the reranker's token plane: ``local`` is this rank's rerank.RerankText over its own rows; returns the plane
+    of the whole corpus (row_offset 0: rank 0's), identical on every rank.  A collective, once per index, not per batch: about
+    1 KB per product crosses the wire, where the gate plane (6 KB per product) stays sharded."""
+    from .rerank import RerankText
+    if world == 1:
+        return local
+    tok, off = exchange_plane_arrays(local.d_tok[:local.n_tokens], local.d_off, world, group)
+    whole = RerankText.from_arrays(tok, off, local)
+    whole.row_offset = 0                # (shard_bounds: rank 0's rows begin at 0)
+    return whole
+
+
 @dataclass
 class PendingBatch:
     """What ShardedSearcher.submit leaves for finish: the batch's parameters, its payload and the started all-gather."""
@@ -209,6 +266,10 @@ class PendingBatch:
     pending: "PendingExchange"
     gate_fn: object = None
     rerank_fn: object = None
+    packed: object = None         # gate_groups: the batch's gate.PackedGroups (the payload then carries the gate column),
+    gate_host: object = None      # the host function of its over-limit queries,
+    staged: object = None         # and the packed groups on the device (overlapped form: uploaded at submit, ahead of K1)
+    rerank_pairs: object = None   # (cross_encoder, rerank.PackedQueries, rerank_host)
     # the overlapped form (ShardedSearcher.enable_overlap): stage 0 = scanned (K1's scan on the scans' stream, the floor's
     # all-reduce started), 1 = payload built and its all-gather started, 2 = finished
     stage: int = 1
@@ -267,13 +328,17 @@ class _Overlap:
 class ShardedSearcher:
     """K1 + K2 per shard, one all-gather, K3 on the merged pool."""
 
-    def __init__(self, searcher: HybridSearcher, n_total_rows: int, rank: int, world: int, group=None):
+    def __init__(self, searcher: HybridSearcher, n_total_rows: int, rank: int, world: int, group=None, rerank_text=None):
+        """``searcher.gate_text``: the gate plane of THIS shard's rows (``GateText.from_texts(texts[lo:hi], ...,
+        row_offset=lo)``), for ``gate_groups``.  ``rerank_text``: the token plane of the WHOLE corpus (`exchange_plane` of
+        the shards' planes), for ``rerank_pairs``; one rank takes its searcher's."""
         lo, hi = shard_bounds(n_total_rows, world, rank)
         ix = searcher.index
         if ix.row_offset != lo or ix.n_rows != hi - lo:
             raise ValueError(f"rank {rank} must hold rows [{lo}, {hi}); its index holds "
                              f"[{ix.row_offset}, {ix.row_offset + ix.n_rows})")
         self.s, self.rank, self.world, self.group, self.n_total = searcher, rank, world, group, n_total_rows
+        self.rerank_text = rerank_text if rerank_text is not None else (searcher.rerank_text if world == 1 else None)
         # diagnostic: run the payload + exchange + merge path even with one rank (bench.py --force-payload)
         self.force_payload = False
         # row shards select against a corpus-wide floor (two-phase K1 + exchange_floor); RR_NO_SHARD_FLOOR=1: every shard
@@ -327,18 +392,26 @@ class ShardedSearcher:
         kth = max((pool_local + self.world - 1) // self.world, (pool_local + 7) // 8 + 1)
         return self.s.dense_scan(q_dev, pool_local, min(kth, pool_local))
 
-    def local_payload(self, q_dev, term_id_lists, pool_local: int, bm25_mode: str = "forward", floor=None, buf=None):
+    def local_payload(self, q_dev, term_id_lists, pool_local: int, bm25_mode: str = "forward", floor=None, buf=None,
+                      gate=None, gate_host=None):
         """K1 (+ the floor exchange when there is more than one shard) + K2 + metadata gather into the payload buffer of
         this rank.  ``floor``: tests that play several shards in one process pass the minimum they formed themselves
-        (after calling local_scan on every shard); ``False`` = plain K1."""
+        (after calling local_scan on every shard); ``False`` = plain K1.
+        ``gate``: the batch's gate.PackedGroups -- the layout then has the gate column, and behind K2, on the same stream,
+        this rank's candidates are matched against the gate plane of its own rows into it (every candidate of a shard's
+        list, fill entries included, is a row of the shard: DESIGN.md section 5).  The packed terms are uploaded ahead of K1.
+        ``gate_host(b, rows)``: for the queries of ``gate.host_queries``, on this rank's own rows."""
         import torch
         self._flush_overlap()
         s = self.s
         B = q_dev.shape[0]
-        lay = PayloadLayout(B, pool_local)
+        if gate is not None and s.gate_text is None:
+            raise ValueError("gate groups need the gate plane of this shard's rows: HybridSearcher(..., gate_text=GateText...)")
+        lay = PayloadLayout(B, pool_local, gate=gate is not None)
         if buf is None:                 # (``buf``: a caller-owned uint8 buffer of lay.nbytes to build the payload in)
             buf = torch.empty(lay.nbytes, dtype=torch.uint8, device=s.device)
         v = lay.views(buf)
+        staged = s.gate_text.upload(gate) if gate is not None else None
         import torch.distributed as dist
         if floor is None and self.world > 1 and self.use_floor and dist.is_available() and dist.is_initialized():
             bound = self.local_scan(q_dev, pool_local)
@@ -354,6 +427,8 @@ class ShardedSearcher:
         else:
             s.dense_select(q_dev, pool_local, floor, out=(v["rows"], v["dense"]))
         s.bm25_at(term_id_lists, v["rows"], bm25_mode, out=v["bm25"])  # K2 too
+        if gate is not None:
+            s.gate_text.gate(v["rows"], gate, gate_host, staged, out=v["gate"])
         _lib.check(s.lib.rr_index_gather_meta_dev(
             s.index.handle, C.c_void_p(v["rows"].data_ptr()), B * pool_local,
             C.c_void_p(v["n"].data_ptr()), C.c_void_p(v["avg"].data_ptr()),
@@ -362,8 +437,19 @@ class ShardedSearcher:
 
     def search_batch_dev(self, q_dev, term_id_lists: Optional[Sequence[Sequence[int]]], k: int,
                          weights: Optional[FusionWeights] = None, pool_floor: int = 150,
-                         bm25_mode: str = "forward", rerank_k: int = 0, gate_fn=None, rerank_fn=None):
+                         bm25_mode: str = "forward", rerank_k: int = 0, gate_fn=None, rerank_fn=None,
+                         gate_groups=None, gate_host=None, rerank_pairs=None):
         """Device-resident queries in, device tensors out: (pool_rows, columns, order).
+
+        ``gate_groups`` / ``gate_host`` (instead of gate_fn; names and meaning of HybridSearcher.search_batch): per query
+        its gate groups, matched on the device against the gate plane of this rank's OWN rows before the exchange; the
+        factor travels in the payload and K3 runs once (rr_fuse_topk_cand_dev).  ``gate_host(b, rows)`` is called for the
+        queries over the match kernel's limits only, with this rank's own candidate rows of query b.
+        ``rerank_pairs`` = ``(cross_encoder, packed_queries, rerank_host)`` (instead of rerank_fn): after the merge pass every
+        rank assembles and scores its share of the B x rr_k pairs on the device against the replicated token plane
+        (``self.rerank_text``), the scores are all-gathered and K3 runs again with them.  ``rerank_host(b, rows)`` is called
+        for the queries of ``packed_queries.host_queries`` only, with the rows of this rank's share of query b's pairs, and
+        returns one score per row.
 
         ``gate_fn(rows (B, pool) global rows, numpy) -> (B, pool) float32`` and
         ``rerank_fn(query_idx (n,), rows (n,)) -> (n,) float32`` (scores of the (query, product) pairs given) are
@@ -383,21 +469,27 @@ class ShardedSearcher:
             assert pool_local == pool, "each shard needs at least `pool` rows"
         tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
         s = self.s
-        two_pass = gate_fn is not None or (rerank_fn is not None and rr_k > 0)
         if self.world == 1 and not self.force_payload:
-            # nothing to exchange: K1 -> K2 -> K3 straight through, metadata read from the index
+            # nothing to exchange: K1 -> K2 -> gate -> K3 straight through, metadata read from the index
+            packed = self._check_columns(B, w, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs)
+            two_pass = gate_fn is not None or ((rerank_fn is not None or rerank_pairs is not None) and rr_k > 0)
             self._flush_overlap()
+            staged = s.gate_text.upload(packed) if packed is not None else None      # (ahead of the kernels)
             rows, dense = s.dense_pool(q_dev, pool)
             bm = s.bm25_at(tl, rows, bm25_mode)
             gate = rerank = None
             if two_pass:
-                gate, rerank = self._pool_columns(rows, B, pool, rr_k, gate_fn, rerank_fn)
+                gate, rerank = self._pool_columns(rows, B, pool, rr_k, gate_fn, rerank_fn, rerank_pairs)
+            if packed is not None:
+                gate = s.gate_text.gate(rows, packed, gate_host, staged)      # pool-aligned: the pool order is K1's already
             return s.fuse(HybridSearcher.make_params(w, min(k, pool), pool, pool, rr_k), B, rows, dense, bm,
                           None, rerank, None, gate)
-        return self.finish(self.submit(q_dev, term_id_lists, k, weights, pool_floor, bm25_mode, rerank_k, gate_fn, rerank_fn))
+        return self.finish(self.submit(q_dev, term_id_lists, k, weights, pool_floor, bm25_mode, rerank_k, gate_fn, rerank_fn,
+                                       gate_groups, gate_host, rerank_pairs))
 
     def submit(self, q_dev, term_id_lists, k: int, weights: Optional[FusionWeights] = None, pool_floor: int = 150,
-               bm25_mode: str = "forward", rerank_k: int = 0, gate_fn=None, rerank_fn=None) -> "PendingBatch":
+               bm25_mode: str = "forward", rerank_k: int = 0, gate_fn=None, rerank_fn=None,
+               gate_groups=None, gate_host=None, rerank_pairs=None) -> "PendingBatch":
         """First half of search_batch_dev for row shards: K1 (+ floor exchange) + K2 + metadata gather on this rank, then the
         payload all-gather is STARTED (exchange_start) and the call returns.  `finish(ticket)` waits for the collective on
         the stream and runs the merge (K3).  Calling submit(batch i + 1) before finish(batch i) puts batch i's all-gather
@@ -420,16 +512,50 @@ class ShardedSearcher:
         if self.world > 1:
             assert pool_local == pool, "each shard needs at least `pool` rows"
         tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
-        two_pass = gate_fn is not None or (rerank_fn is not None and rr_k > 0)
+        packed = self._check_columns(B, w, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs)
+        # (a gate matched on the device is a payload column: such a batch is an ordinary one-pass batch)
+        two_pass = gate_fn is not None or ((rerank_fn is not None or rerank_pairs is not None) and rr_k > 0)
         if self._ov is not None:
             if not two_pass:
-                t = self._submit_overlapped(q_dev, tl, B, k, pool, pool_local, w, bm25_mode)
+                t = self._submit_overlapped(q_dev, tl, B, k, pool, pool_local, w, bm25_mode, packed, gate_host)
                 if t is not None:
                     return t
             self._flush_overlap()      # a batch the pipeline does not take (host columns, a call K1 cannot split): in order, behind it
-        lay, buf = self.local_payload(q_dev, tl, pool_local, bm25_mode)
+        lay, buf = self.local_payload(q_dev, tl, pool_local, bm25_mode, gate=packed, gate_host=gate_host)
         pending = exchange_start(buf, self.world, self.group)
-        return PendingBatch(B, k, pool, pool_local, rr_k, w, lay, buf, pending, gate_fn, rerank_fn)
+        return PendingBatch(B, k, pool, pool_local, rr_k, w, lay, buf, pending, gate_fn, rerank_fn, packed=packed,
+                            gate_host=gate_host, rerank_pairs=rerank_pairs)
+
+    def _check_columns(self, B: int, w: FusionWeights, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs):
+        """The checks of the gate / rerank arguments, before any launch or collective (every rank computes the same tests on
+        the same batch, so no rank is left waiting in a collective the others never join).  Returns the batch's
+        gate.PackedGroups, or None when there is nothing to match (no gate, as with gate_fn=None)."""
+        packed = None
+        if gate_groups is not None:
+            from .gate import pack_groups
+            if gate_fn is not None:
+                raise ValueError("pass either gate_fn or gate_groups")
+            if self.s.gate_text is None:
+                raise ValueError("gate_groups need the gate plane of this shard's rows: HybridSearcher(..., gate_text=GateText...)")
+            if len(gate_groups) != B:
+                raise ValueError(f"{len(gate_groups)} gate groups for {B} queries")
+            packed = pack_groups(gate_groups, w.gate_penalty)
+            if packed.host_queries and gate_host is None:
+                raise ValueError(f"queries {packed.host_queries} exceed the gate kernel's limits and no gate_host was given")
+            if not packed.any_groups and not packed.host_queries:
+                packed = None
+        if rerank_pairs is not None:
+            if rerank_fn is not None:
+                raise ValueError("pass either rerank_fn or rerank_pairs")
+            if self.rerank_text is None:
+                raise ValueError("rerank_pairs need the token plane of the whole corpus: "
+                                 "ShardedSearcher(..., rerank_text=exchange_plane(...))")
+            _, rr_queries, rerank_host = rerank_pairs
+            if rr_queries.n_queries != B:
+                raise ValueError(f"{rr_queries.n_queries} packed queries for {B} queries")
+            if rr_queries.host_queries and rerank_host is None:
+                raise ValueError(f"queries {rr_queries.host_queries} exceed the pair kernel's limit and no rerank_host was given")
+        return packed
 
     def _check_merge_size(self, pool: int) -> None:
         """K3 merges world x pool candidates per query and takes at most MAX_CANDIDATES (include/rr_hip.h:
@@ -448,7 +574,7 @@ class ShardedSearcher:
             t, ov.pending = ov.pending, None
             self._build_payload(t)
 
-    def _submit_overlapped(self, q_dev, tl, B, k, pool, pool_local, w, bm25_mode):
+    def _submit_overlapped(self, q_dev, tl, B, k, pool, pool_local, w, bm25_mode, packed=None, gate_host=None):
         import torch
         import torch.distributed as dist
         ov, s = self._ov, self.s
@@ -460,6 +586,7 @@ class ShardedSearcher:
         if with_floor:       # (local_scan's rule)
             kth = min(max((pool_local + self.world - 1) // self.world, (pool_local + 7) // 8 + 1), pool_local)
         cur = torch.cuda.current_stream(s.device)
+        staged = s.gate_text.upload(packed) if packed is not None else None     # (ahead of K1; the copy has finished on return)
         ready = torch.cuda.Event()
         ready.record(cur)                                   # (the caller's stream produced q_dev)
         with torch.cuda.stream(ov.scan_stream):
@@ -480,9 +607,10 @@ class ShardedSearcher:
             work = exchange_floor_start(bound, self.world, self.group) if with_floor else None
         ov.seq += 1
         ov.unfinished += 1
-        lay = PayloadLayout(B, pool_local)
+        lay = PayloadLayout(B, pool_local, gate=packed is not None)
         t = PendingBatch(B, k, pool, pool_local, 0, w, lay, None, None, stage=0, slot=slot,
-                         bound=bound if with_floor else None, floor_work=work, terms=tl, bm25_mode=bm25_mode, plain_q=plain_q)
+                         bound=bound if with_floor else None, floor_work=work, terms=tl, bm25_mode=bm25_mode, plain_q=plain_q,
+                         packed=packed, gate_host=gate_host, staged=staged)
         prev, ov.pending = ov.pending, t
         if prev is not None:
             self._build_payload(prev)                       # batch i - 1's tail goes to its stream beside this scan
@@ -507,6 +635,8 @@ class ShardedSearcher:
             else:
                 s.dense_select_slot(t.slot, B, pool_local, floor=t.bound, out=(v["rows"], v["dense"]))
             s.bm25_at(t.terms, v["rows"], t.bm25_mode, out=v["bm25"])
+            if t.packed is not None:                        # this rank's own candidates against its own plane, into the payload
+                s.gate_text.gate(v["rows"], t.packed, t.gate_host, t.staged, out=v["gate"])
             _lib.check(s.lib.rr_index_gather_meta_dev(
                 s.index.handle, C.c_void_p(v["rows"].data_ptr()), B * pool_local,
                 C.c_void_p(v["n"].data_ptr()), C.c_void_p(v["avg"].data_ptr()),
@@ -534,28 +664,30 @@ class ShardedSearcher:
             ptr = lambda off: C.c_void_p(base + off)
             params = HybridSearcher.make_params(w, k_out, pool, self.world * pool_local, 0,
                                                 cand_per_rank=pool_local, stride_bytes=lay.nbytes)
-            _lib.check(s.lib.rr_fuse_topk_dev(
+            _lib.check(s.lib.rr_fuse_topk_cand_dev(
                 s.index.handle, C.byref(params), B, ptr(lay.off_rows), ptr(lay.off_dense), ptr(lay.off_bm25),
                 ptr(lay.off_n), ptr(lay.off_avg), ptr(lay.off_l1p), None, None, None,
+                ptr(lay.off_gate) if lay.gate else None,
                 C.c_void_p(out_rows.data_ptr()), C.c_void_p(cols.data_ptr()), C.c_void_p(order.data_ptr()), s._stream()),
-                "rr_fuse_topk_dev")
+                "rr_fuse_topk_cand_dev")
             done = torch.cuda.Event()
             done.record(ov.tail_stream)
         cur.wait_event(done)                                # the caller's stream may read the answer
-        t.stage = 2
+        t.stage, t.staged = 2, None
         ov.unfinished -= 1
         # (the answer lives in the slot's ring buffers: valid until three more batches have been submitted)
         return out_rows, cols, order
 
     def finish(self, t: "PendingBatch"):
-        """Second half: the gathered payload is merged and fused (K3; with a gate / reranker: merge, host columns, K3 again)."""
+        """Second half: the gathered payload is merged and fused (K3, with the payload's gate column when the batch has one;
+        with a host gate or a reranker: merge, pool-aligned columns, K3 again)."""
         import torch
         if t.slot >= 0:
             return self._finish_overlapped(t)
         s = self.s
         B, k, pool, pool_local, rr_k, w, lay = t.B, t.k, t.pool, t.pool_local, t.rr_k, t.w, t.lay
         gate_fn, rerank_fn = t.gate_fn, t.rerank_fn
-        two_pass = gate_fn is not None or (rerank_fn is not None and rr_k > 0)
+        two_pass = gate_fn is not None or ((rerank_fn is not None or t.rerank_pairs is not None) and rr_k > 0)
         gathered = t.pending.wait()
         base = gathered.data_ptr()
         ptr = lambda off: C.c_void_p(base + off)
@@ -567,28 +699,49 @@ class ShardedSearcher:
             out_rows = torch.empty((B, pool), dtype=torch.int64, device=s.device)
             cols = torch.empty((B, 8, pool), dtype=torch.float64, device=s.device)
             order = torch.empty((B, params.k), dtype=torch.int32, device=s.device)
-            _lib.check(s.lib.rr_fuse_topk_dev(
+            _lib.check(s.lib.rr_fuse_topk_cand_dev(
                 s.index.handle, C.byref(params), B, ptr(lay.off_rows), ptr(lay.off_dense), ptr(lay.off_bm25),
                 ptr(lay.off_n), ptr(lay.off_avg), ptr(lay.off_l1p), p(rerank), None, p(gate),
-                p(out_rows), p(cols), p(order), s._stream()), "rr_fuse_topk_dev")
+                ptr(lay.off_gate) if lay.gate else None,          # (gate_fn and gate_groups exclude each other)
+                p(out_rows), p(cols), p(order), s._stream()), "rr_fuse_topk_cand_dev")
             return out_rows, cols, order
 
         if not two_pass:
             res = fuse(min(k, pool), None, None, 0)
         else:
             merged_rows, _, _ = fuse(pool, None, None, 0)           # pass A: the merge alone fixes the pool order
-            gate, rerank = self._pool_columns(merged_rows, B, pool, rr_k, gate_fn, rerank_fn)
+            gate, rerank = self._pool_columns(merged_rows, B, pool, rr_k, gate_fn, rerank_fn, t.rerank_pairs)
             res = fuse(min(k, pool), rerank, gate, rr_k)             # pass B: same payload + pool-aligned columns
         self._keep = (gathered, t.buf)   # alive until the stream has consumed them
         return res
 
-    def _pool_columns(self, rows_dev, B: int, pool: int, rr_k: int, gate_fn, rerank_fn):
-        """Gate factors (every rank, all pairs: string work on replicated texts) and reranker scores (this rank's
-        share of the B x rr_k pairs + the score all-gather) for the merged pool; device tensors or None."""
+    def _pool_columns(self, rows_dev, B: int, pool: int, rr_k: int, gate_fn, rerank_fn, rerank_pairs=None):
+        """Host gate factors (gate_fn: every rank, all pairs: string work on replicated texts) and reranker scores (this
+        rank's share of the B x rr_k pairs + the score all-gather) for the merged pool; device tensors or None.  With
+        ``rerank_pairs`` the share is assembled and scored on the device and the rows stay there, unless a query of the
+        batch is over the pair kernel's limit."""
         import torch
         s = self.s
-        rows_h = rows_dev.cpu().numpy()
         gate = rerank = None
+        if rerank_pairs is not None and rr_k > 0:
+            ce, rr_queries, rerank_host = rerank_pairs
+            n_pairs = B * rr_k
+            lo, hi = split_pairs(n_pairs, self.world, self.rank)
+            with torch.cuda.device(s.device):
+                mine = self.rerank_text.scores(ce, rows_dev, rr_k, rr_queries, lo, hi - lo)
+                if rr_queries.host_queries:                      # (a property of the batch: every rank branches alike)
+                    rows_h = rows_dev.cpu().numpy()
+                    for b in rr_queries.host_queries:
+                        a, e = max(lo, b * rr_k), min(hi, (b + 1) * rr_k)
+                        if a < e:                                # this rank's pairs of query b only
+                            r = np.ascontiguousarray(rerank_host(b, rows_h[b, a - b * rr_k:e - b * rr_k]), dtype=np.float32)
+                            mine[a - lo:e - lo].copy_(torch.from_numpy(r.reshape(e - a)))
+                full = exchange_scores(mine, n_pairs, self.world, self.group)
+                rerank = torch.zeros((B, pool), dtype=torch.float32, device=s.device)
+                rerank[:, :rr_k] = full.view(B, rr_k)
+        if gate_fn is None and (rerank_fn is None or rr_k <= 0):
+            return gate, rerank
+        rows_h = rows_dev.cpu().numpy()
         if gate_fn is not None:
             g = np.ascontiguousarray(gate_fn(rows_h), dtype=np.float32)
             gate = torch.from_numpy(g).to(s.device)

@@ -99,6 +99,40 @@ class StagedBatch:
         self.q, self.terms, self.ready, self.slot = q, terms, ready, slot
 
 
+def check_columns(B: int, w: FusionWeights, gate_text, rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs):
+    """The checks of a batch's gate / rerank arguments against the searcher's planes, before any launch or collective (on row
+    shards every rank computes the same tests on the same batch, so no rank is left waiting in a collective the others never
+    join).  ``gate_text``: the gate plane of the searcher's own rows; ``rerank_text``: the token plane of every row a merged
+    pool can hold (sharded.exchange_plane on row shards).  Returns the batch's gate.PackedGroups, or None when there is
+    nothing to match (no gate, as with gate_fn=None)."""
+    packed = None
+    if gate_groups is not None:
+        from .gate import pack_groups
+        if gate_fn is not None:
+            raise ValueError("pass either gate_fn or gate_groups")
+        if gate_text is None:
+            raise ValueError("gate_groups need the gate plane of the searcher's rows: HybridSearcher(..., gate_text=GateText...)")
+        if len(gate_groups) != B:
+            raise ValueError(f"{len(gate_groups)} gate groups for {B} queries")
+        packed = pack_groups(gate_groups, w.gate_penalty)
+        if packed.host_queries and gate_host is None:
+            raise ValueError(f"queries {packed.host_queries} exceed the gate kernel's limits and no gate_host was given")
+        if not packed.any_groups and not packed.host_queries:
+            packed = None
+    if rerank_pairs is not None:
+        if rerank_fn is not None:
+            raise ValueError("pass either rerank_fn or rerank_pairs")
+        if rerank_text is None:
+            raise ValueError("rerank_pairs need the token plane of the whole corpus: HybridSearcher(..., rerank_text=RerankText...), "
+                             "on row shards ShardedSearcher(..., rerank_text=exchange_plane(...))")
+        _, rr_queries, rerank_host = rerank_pairs
+        if rr_queries.n_queries != B:
+            raise ValueError(f"{rr_queries.n_queries} packed queries for {B} queries")
+        if rr_queries.host_queries and rerank_host is None:
+            raise ValueError(f"queries {rr_queries.host_queries} exceed the pair kernel's limit and no rerank_host was given")
+    return packed
+
+
 class HybridSearcher:
     """K1 -> K2 -> K3 on one GPU over a ProductIndex (+ optional BM25Index)."""
 
@@ -149,18 +183,19 @@ class HybridSearcher:
             segs[i] = _lib.CopySeg(dst.data_ptr(), src.data_ptr(), row_bytes, rows, dp, sp)
         _lib.check(self.lib.rr_copy_segments_dev(segs, len(pairs), self.device.index, self._stream()), "rr_copy_segments_dev")
 
+    def _pool_pair(self, B: int, pool: int):
+        """K1's output pair: fresh (rows int64 (B, pool), scores float32 (B, pool)) device tensors."""
+        torch = _torch()
+        return (torch.empty((B, pool), dtype=torch.int64, device=self.device),
+                torch.empty((B, pool), dtype=torch.float32, device=self.device))
+
     def dense_pool(self, q_dev, pool: int, out=None, slot: int = 0):
         """K1 on device tensors: (rows int64 (B,pool), scores float32 (B,pool)).  ``q_dev``: (B, dim) float32 on the
         device -- or in PINNED host memory (K1's first kernel then reads the queries over PCIe itself: no copy command).
         ``out`` = (rows, scores) tensors to write into (e.g. views of a shard payload).  ``slot``: the scan slot whose state
         the call uses (rr_dense_topk_slot_dev; 0 unless other batches have scans parked)."""
-        torch = _torch()
         B = q_dev.shape[0]
-        if out is not None:
-            rows, dense = out
-        else:
-            rows = torch.empty((B, pool), dtype=torch.int64, device=self.device)
-            dense = torch.empty((B, pool), dtype=torch.float32, device=self.device)
+        rows, dense = out if out is not None else self._pool_pair(B, pool)
         _lib.check(self.lib.rr_dense_topk_slot_dev(self.index.handle, int(slot), C.c_void_p(q_dev.data_ptr()), B, pool,
                                                    C.c_void_p(rows.data_ptr()), C.c_void_p(dense.data_ptr()),
                                                    self._stream()), "rr_dense_topk_dev")
@@ -182,13 +217,8 @@ class HybridSearcher:
     def dense_select(self, q_dev, pool: int, floor, out=None):
         """Phase 2 (rr_dense_select_dev): the selection of the scan dense_scan left behind, with the floor the shards
         agreed on (float32 (B,) device tensor).  Lists of `pool` rows: see include/rr_hip.h."""
-        torch = _torch()
         B = q_dev.shape[0]
-        if out is not None:
-            rows, dense = out
-        else:
-            rows = torch.empty((B, pool), dtype=torch.int64, device=self.device)
-            dense = torch.empty((B, pool), dtype=torch.float32, device=self.device)
+        rows, dense = out if out is not None else self._pool_pair(B, pool)
         _lib.check(self.lib.rr_dense_select_dev(self.index.handle, C.c_void_p(q_dev.data_ptr()), B, pool,
                                                 C.c_void_p(floor.data_ptr()), C.c_void_p(rows.data_ptr()),
                                                 C.c_void_p(dense.data_ptr()), self._stream()), "rr_dense_select_dev")
@@ -217,14 +247,9 @@ class HybridSearcher:
         """Phase 2 (rr_dense_select_part_dev) on the CURRENT stream -- which may be another one than the scan's, and another
         one per part (SELECT_LIST | SELECT_RESCORE | SELECT_ORDER): the library orders them with events.  Returns
         (rows, dense) when SELECT_ORDER is among the parts, else None."""
-        torch = _torch()
         rows = dense = None
         if parts & self.SELECT_ORDER:
-            if out is not None:
-                rows, dense = out
-            else:
-                rows = torch.empty((B, pool), dtype=torch.int64, device=self.device)
-                dense = torch.empty((B, pool), dtype=torch.float32, device=self.device)
+            rows, dense = out if out is not None else self._pool_pair(B, pool)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         _lib.check(self.lib.rr_dense_select_part_dev(self.index.handle, int(slot), int(parts), B, pool, p(floor), p(rows), p(dense),
                                                      self._stream()), "rr_dense_select_part_dev")
@@ -413,30 +438,7 @@ class HybridSearcher:
             raise ValueError(f"pool {pool} exceeds the kernels' limit {MAX_POOL}")
         k_eff = min(k, pool)
         rr_k = min(rerank_k, pool)
-        packed = None
-        if gate_groups is not None:
-            from .gate import pack_groups
-            if gate_fn is not None:
-                raise ValueError("pass either gate_fn or gate_groups")
-            if self.gate_text is None:
-                raise ValueError("gate_groups need a gate plane: HybridSearcher(..., gate_text=GateText...)")
-            if len(gate_groups) != B:
-                raise ValueError(f"{len(gate_groups)} gate groups for {B} queries")
-            packed = pack_groups(gate_groups, w.gate_penalty)
-            if packed.host_queries and gate_host is None:
-                raise ValueError(f"queries {packed.host_queries} exceed the gate kernel's limits and no gate_host was given")
-            if not packed.any_groups and not packed.host_queries:
-                packed = None                    # nothing to match: no gate, as with gate_fn=None
-        if rerank_pairs is not None:
-            if rerank_fn is not None:
-                raise ValueError("pass either rerank_fn or rerank_pairs")
-            if self.rerank_text is None:
-                raise ValueError("rerank_pairs need a token plane: HybridSearcher(..., rerank_text=RerankText...)")
-            rr_ce, rr_queries, rerank_host = rerank_pairs
-            if rr_queries.n_queries != B:
-                raise ValueError(f"{rr_queries.n_queries} packed queries for {B} queries")
-            if rr_queries.host_queries and rerank_host is None:
-                raise ValueError(f"queries {rr_queries.host_queries} exceed the pair kernel's limit and no rerank_host was given")
+        packed = check_columns(B, w, self.gate_text, self.rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs)
         with torch.cuda.device(self.device):
             q_dev = torch.from_numpy(q).to(self.device)
             staged_groups = self.gate_text.upload(packed) if packed is not None else None    # (ahead of the kernels)
@@ -467,6 +469,7 @@ class HybridSearcher:
                     r[:, :rr_k] = np.asarray(rerank_fn(rows_h[:, :rr_k]), dtype=np.float32)
                     rerank = torch.from_numpy(r).to(self.device)
             if rerank_pairs is not None and rr_k > 0:
+                rr_ce, rr_queries, rerank_host = rerank_pairs
                 rerank = torch.zeros((B, pool), dtype=torch.float32, device=self.device)
                 rerank[:, :rr_k] = self.rerank_text.scores(rr_ce, rows, rr_k, rr_queries)
                 if rr_queries.host_queries:
@@ -690,19 +693,7 @@ class SearchEngine:
                     "gate_host": lambda b, rows: self._gate_rows(groups_per_query[b], penalty, rows)}
         return {"gate_fn": lambda rows: np.stack([self._gate_rows(g, penalty, r) for g, r in zip(groups_per_query, rows)])}
 
-    def _rerank_batch_fn(self, queries: Sequence[str]):
-        if self.cross_encoder is None:
-            return None   # model missing -> zeros (app/app_product_search.py:275)
-
-        def fn(rows: np.ndarray) -> np.ndarray:
-            # the (query, text[:2000]) pairs of EVERY query of the batch in one predict call
-            texts = self._texts.iloc[rows.reshape(-1)].str.slice(0, 2000).tolist()
-            pairs = [(queries[i // rows.shape[1]], t) for i, t in enumerate(texts)]
-            scores = np.asarray(self.cross_encoder.predict(pairs, batch_size=64, show_progress_bar=False), dtype=np.float32)
-            return scores.reshape(rows.shape)
-        return fn
-
-    def _rerank_args(self, queries: Sequence[str], rerank_k: int, batch: bool) -> dict:
+    def _rerank_args(self, queries: Sequence[str], rerank_k: int) -> dict:
         """search_batch's rerank arguments for these queries: the device pairs when the engine has a token plane (the B
         queries are tokenised here, B short strings), else the host function over all of them."""
         if rerank_k <= 0:
@@ -711,18 +702,18 @@ class SearchEngine:
             from .rerank import pack_queries
             ce = self.cross_encoder
             packed = pack_queries([ce.tokenizer.text_ids(str(q)) for q in queries], ce.max_length)
-            return {"rerank_pairs": (ce, packed, lambda b, rows: self._rerank_fn(queries[b])(rows[None, :])[0])}
-        return {"rerank_fn": self._rerank_batch_fn(queries) if batch else self._rerank_fn(queries[0])}
+            return {"rerank_pairs": (ce, packed, lambda b, rows: self._rerank_fn(queries[b:b + 1])(rows[None, :])[0])}
+        return {"rerank_fn": self._rerank_fn(queries)}
 
-    def _rerank_fn(self, query: str):
+    def _rerank_fn(self, queries: Sequence[str]):
         if self.cross_encoder is None:
             return None   # model missing -> zeros (app/app_product_search.py:275)
 
         def fn(rows: np.ndarray) -> np.ndarray:
-            # every (query, text[:2000]) pair of the batch in ONE predict call: the packed forward has no use for
-            # per-query mini-batches (app/app_product_search.py:272-278 builds the pairs the same way, per query)
+            # the (query, text[:2000]) pairs of EVERY query of the batch in ONE predict call: the packed forward has no use
+            # for per-query mini-batches (app/app_product_search.py:272-278 builds the pairs the same way, per query)
             texts = self._texts.iloc[rows.reshape(-1)].str.slice(0, 2000).tolist()
-            pairs = [(query, t) for t in texts]
+            pairs = [(queries[i // rows.shape[1]], t) for i, t in enumerate(texts)]
             scores = np.asarray(self.cross_encoder.predict(pairs, batch_size=64, show_progress_bar=False), dtype=np.float32)
             return scores.reshape(rows.shape)
         return fn
@@ -739,29 +730,9 @@ class SearchEngine:
         index (``reviews=`` of the constructor) ``snips`` and ``_best`` are filled like
         _best_snippets does (app/app_product_search.py:285-294, 320-370); otherwise ``snips`` is {}
         and ``_best`` zeros, as in the reference when the review file is absent."""
-        app = self.flavour == "app"
         qv = self.encode(query) if qvec is None else np.asarray(qvec, dtype=np.float32)
-        toks = text.tokenize_query(query)
-        term_ids = None
-        if self.searcher.bm25 is not None:
-            term_ids = [self.searcher.bm25.term_ids(toks)]
-        groups = text.build_gate_groups(query)
-        w = FusionWeights(w_dense, w_bm25, w_rerank, w_prior, w_best, prior_C, min_reviews,
-                          gate_penalty, APP_TRUST_SAT, app)
-        res = self.searcher.search_batch(
-            qv[None, :], term_ids, k, rerank_k, w,
-            pool_floor=APP_POOL_FLOOR if app else CLI_POOL_FLOOR,
-            reviews=self.reviews if use_snips else None, max_scan=max_scan,
-            bm25_f64=not app, **self._rerank_args([query], rerank_k, False), **self._gate_args([groups], gate_penalty))
-        frame = self._frame(res, 0, rerank_k > 0)
-        snips = {}
-        if res.best_ids is not None:
-            skus = self.meta["sku"].astype(str).iloc[res.pool_rows[0]].tolist()
-            snips = self.reviews.snippets(skus, res.best_ids[0], res.best_raw[0], 600 if app else 400)
-        dbg = {"bm25_active": self.searcher.bm25 is not None, "tokens": toks,
-               "groups": [list(g) for g in groups], "pool": max(k, rerank_k,
-                                                              APP_POOL_FLOOR if app else CLI_POOL_FLOOR)}
-        return frame, snips, dbg
+        return self.run_search_batch([query], k, rerank_k, w_dense, w_bm25, w_rerank, w_prior, w_best, prior_C, use_snips,
+                                     max_scan, min_reviews, gate_penalty, qvecs=qv[None, :])[0]
 
     def run_search_batch(self, queries: Sequence[str], k: int, rerank_k: int, w_dense: float, w_bm25: float,
                          w_rerank: float, w_prior: float, w_best: float, prior_C: float,
@@ -795,7 +766,7 @@ class SearchEngine:
         res = self.searcher.search_batch(
             qv, term_ids, k, rerank_k, w, pool_floor=floor,
             reviews=self.reviews if use_snips else None, max_scan=max_scan,
-            bm25_f64=not app, **self._rerank_args(queries, rerank_k, True), **self._gate_args(groups, gate_penalty))
+            bm25_f64=not app, **self._rerank_args(queries, rerank_k), **self._gate_args(groups, gate_penalty))
         out = []
         for b in range(len(queries)):
             frame = self._frame(res, b, rerank_k > 0)

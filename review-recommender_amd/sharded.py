@@ -31,7 +31,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .engine import FusionWeights, HybridSearcher
+from .engine import FusionWeights, HybridSearcher, check_columns
 from .index import MAX_CANDIDATES
 
 
@@ -106,61 +106,39 @@ class PendingExchange:
         return self.out
 
 
+def _gather(src, world: int, group=None, out=None, start: bool = False):
+    """The one all-gather of this module and its three transports: every rank contributes ``src`` (contiguous, the same shape
+    and dtype on all ranks) and ends with the (world,) + src.shape tensor ``out`` (allocated beside ``src`` unless given).
+    ``start``: returns the started PendingExchange instead of waiting for it."""
+    import torch
+    import torch.distributed as dist
+    if out is None:
+        out = torch.empty((world,) + tuple(src.shape), dtype=src.dtype, device=src.device)
+    if world == 1:
+        out[0].copy_(src)
+        pend = PendingExchange(out)
+    elif dist.get_backend(group) == "nccl":                       # RCCL over xGMI
+        pend = PendingExchange(out, dist.all_gather_into_tensor(out, src, group=group, async_op=True))
+    elif src.is_cuda:                                             # gloo rehearsal on a GPU box: gloo gathers host tensors
+        host = torch.empty(out.shape, dtype=src.dtype)
+        work = dist.all_gather([host[r] for r in range(world)], src.cpu(), group=group, async_op=True)
+        pend = PendingExchange(out, work, lambda: out.copy_(host))
+    else:                                                         # gloo (CPU tests)
+        pend = PendingExchange(out, dist.all_gather([out[r] for r in range(world)], src, group=group, async_op=True))
+    return pend if start else pend.wait()
+
+
 def exchange_start(buf, world: int, group=None, out=None) -> PendingExchange:
     """Starts the path's one collective (all-gather of every rank's payload buffer) without waiting for it: what lets
     batch i's exchange run under K1 of batch i + 1 (ShardedSearcher.submit / finish).  ``out``: a caller-owned
     (world, nbytes) uint8 buffer to gather into."""
-    import torch
-    import torch.distributed as dist
-    if out is None:
-        out = torch.empty((world, buf.numel()), dtype=torch.uint8, device=buf.device)
-    if world == 1:
-        out[0].copy_(buf)
-        return PendingExchange(out)
-    if dist.get_backend(group) == "nccl":
-        return PendingExchange(out, dist.all_gather_into_tensor(out, buf, group=group, async_op=True))   # RCCL over xGMI
-    if buf.is_cuda:                                               # gloo rehearsal on a GPU box: gloo gathers host tensors
-        host = torch.empty((world, buf.numel()), dtype=torch.uint8)
-        work = dist.all_gather([host[r] for r in range(world)], buf.cpu(), group=group, async_op=True)
-        return PendingExchange(out, work, lambda: out.copy_(host))
-    return PendingExchange(out, dist.all_gather([out[r] for r in range(world)], buf, group=group, async_op=True))
+    return _gather(buf, world, group, out, start=True)
 
 
 def exchange(buf, world: int, group=None):
     """The path's one collective: all-gather of every rank's payload buffer.
     Returns a (world, nbytes) uint8 tensor, identical on every rank."""
-    import torch
-    import torch.distributed as dist
-    out = torch.empty((world, buf.numel()), dtype=torch.uint8, device=buf.device)
-    if world == 1:
-        out[0].copy_(buf)
-        return out
-    if dist.get_backend(group) == "nccl":
-        dist.all_gather_into_tensor(out, buf, group=group)       # RCCL over xGMI
-    elif buf.is_cuda:                                             # gloo rehearsal on a GPU box: gloo gathers host tensors
-        host = torch.empty((world, buf.numel()), dtype=torch.uint8)
-        dist.all_gather([host[r] for r in range(world)], buf.cpu(), group=group)
-        out.copy_(host)
-    else:                                                         # gloo (CPU tests)
-        parts = [out[r] for r in range(world)]
-        dist.all_gather(parts, buf, group=group)
-    return out
-
-
-def exchange_floor(bound, world: int, group=None):
-    """The tiny collective in front of the shards' selection (DESIGN.md section 5): element-wise MINIMUM over the ranks
-    of the per-query bounds of HybridSearcher.dense_scan -- a lower bound of the corpus-wide pool-th best score.
-    In place; B floats."""
-    import torch.distributed as dist
-    if world == 1:
-        return bound
-    if dist.get_backend(group) == "nccl" or not bound.is_cuda:
-        dist.all_reduce(bound, op=dist.ReduceOp.MIN, group=group)
-    else:                                                         # gloo rehearsal on a GPU box
-        host = bound.cpu()
-        dist.all_reduce(host, op=dist.ReduceOp.MIN, group=group)
-        bound.copy_(host)
-    return bound
+    return exchange_start(buf, world, group).wait()
 
 
 def exchange_floor_start(bound, world: int, group=None):
@@ -171,8 +149,29 @@ def exchange_floor_start(bound, world: int, group=None):
         return None
     if dist.get_backend(group) == "nccl":
         return dist.all_reduce(bound, op=dist.ReduceOp.MIN, group=group, async_op=True)
-    exchange_floor(bound, world, group)
+    host = bound.cpu()                                            # gloo reduces host tensors (a CPU tensor is its own copy)
+    dist.all_reduce(host, op=dist.ReduceOp.MIN, group=group)
+    if host is not bound:                                         # gloo rehearsal on a GPU box
+        bound.copy_(host)
     return None
+
+
+def exchange_floor(bound, world: int, group=None):
+    """The tiny collective in front of the shards' selection (DESIGN.md section 5): element-wise MINIMUM over the ranks
+    of the per-query bounds of HybridSearcher.dense_scan -- a lower bound of the corpus-wide pool-th best score.
+    In place; B floats."""
+    work = exchange_floor_start(bound, world, group)
+    if work is not None:
+        work.wait()
+    return bound
+
+
+def floor_kth(pool_local: int, world: int) -> int:
+    """The rank of the row whose score a shard reports as its bound for the floor.  The shards' kth best rows together hold
+    >= pool rows for any kth >= ceil(pool / world).  A shard is only sure of ~8 kth rescored rows (kth opened 8-row M-tiles):
+    with kth >= ceil(pool / 8) + 1 its own list of `pool` rows fills without the exact fallback also at world >= 8
+    (ceil(150 / 8) = 19 M-tiles = 152 rows would just do)."""
+    return min(max((pool_local + world - 1) // world, (pool_local + 7) // 8 + 1), pool_local)
 
 
 def split_pairs(n_pairs: int, world: int, rank: int) -> Tuple[int, int]:
@@ -186,26 +185,14 @@ def exchange_scores(local, n_pairs: int, world: int, group=None):
     reranker scores of its share of the pairs (float32 tensor of split_pairs' length); returns the full
     (n_pairs,) tensor, identical on every rank."""
     import torch
-    import torch.distributed as dist
     if world == 1:
         return local
     share = (n_pairs + world - 1) // world                     # shares differ by at most one pair: pad to the longest
     buf = torch.zeros(share, dtype=torch.float32, device=local.device)
     buf[:local.numel()] = local
-    out = torch.empty(world * share, dtype=torch.float32, device=local.device)
-    if dist.get_backend(group) == "nccl":
-        dist.all_gather_into_tensor(out, buf, group=group)
-    elif buf.is_cuda:                                             # gloo rehearsal on a GPU box
-        host = torch.empty(world * share, dtype=torch.float32)
-        dist.all_gather([host[r * share:(r + 1) * share] for r in range(world)], buf.cpu(), group=group)
-        out.copy_(host)
-    else:
-        dist.all_gather([out[r * share:(r + 1) * share] for r in range(world)], buf, group=group)
-    parts = []
-    for r in range(world):
-        lo, hi = split_pairs(n_pairs, world, r)
-        parts.append(out[r * share:r * share + (hi - lo)])
-    return torch.cat(parts)
+    out = _gather(buf, world, group)
+    bounds = [split_pairs(n_pairs, world, r) for r in range(world)]
+    return torch.cat([out[r, :hi - lo] for r, (lo, hi) in enumerate(bounds)])
 
 
 def exchange_plane_arrays(tok, off, world: int, group=None):
@@ -213,29 +200,18 @@ def exchange_plane_arrays(tok, off, world: int, group=None):
     [n + 1]) of its shard's token plane; all ranks end with the same joined (ids, offsets) of the whole corpus
     (rerank.join_planes).  Three all-gathers: the sizes, then the id and the offset tensors padded to the longest."""
     import torch
-    import torch.distributed as dist
     from .rerank import join_planes
     if world == 1:
         return join_planes([tok], [off])
-    via_host = tok.is_cuda and dist.get_backend(group) != "nccl"        # gloo rehearsal on a GPU box: gloo gathers host tensors
-
-    def gather(x):
-        src = x.cpu() if via_host else x
-        out = torch.empty((world,) + tuple(src.shape), dtype=src.dtype, device=src.device)
-        if dist.get_backend(group) == "nccl":
-            dist.all_gather_into_tensor(out, src.contiguous(), group=group)
-        else:
-            dist.all_gather([out[r] for r in range(world)], src.contiguous(), group=group)
-        return out.to(x.device) if via_host else out
-
-    sizes = gather(torch.tensor([int(tok.numel()), int(off.numel())], dtype=torch.int64, device=tok.device)).cpu().tolist()
+    sizes = _gather(torch.tensor([int(tok.numel()), int(off.numel())], dtype=torch.int64, device=tok.device),
+                        world, group).cpu().tolist()
     n_tok, n_off = max(s[0] for s in sizes), max(s[1] for s in sizes)
     tok_pad = torch.zeros(max(n_tok, 1), dtype=tok.dtype, device=tok.device)
     tok_pad[:tok.numel()] = tok
     off_pad = torch.zeros(n_off, dtype=torch.int64, device=off.device)
     off_pad[:off.numel()] = off
     # (the ids travel as bytes: gloo has no 16-bit integers)
-    toks, offs = gather(tok_pad.view(torch.uint8)).view(tok.dtype), gather(off_pad)
+    toks, offs = _gather(tok_pad.view(torch.uint8), world, group).view(tok.dtype), _gather(off_pad, world, group)
     return join_planes([toks[r, :sizes[r][0]] for r in range(world)], [offs[r, :sizes[r][1]] for r in range(world)])
 
 
@@ -279,6 +255,7 @@ class PendingBatch:
     terms: object = None
     bm25_mode: str = "forward"
     plain_q: object = None        # set when K1 could not be split on this rank: the queries of the whole K1 stage 1 then runs
+    two_pass: bool = False        # a host gate or a reranker: finish merges, forms the pool-aligned columns, runs K3 again
 
 
 class _Overlap:
@@ -385,12 +362,8 @@ class ShardedSearcher:
 
     def local_scan(self, q_dev, pool_local: int):
         """Phase 1 of K1 on this rank: the scan and this shard's bound per query (None: the call cannot be split)."""
-        # the shards' kth best rows together hold >= pool rows for any kth >= ceil(pool / world).  A shard is only sure of
-        # ~8 kth rescored rows (kth opened 8-row M-tiles): with kth >= ceil(pool / 8) + 1 its own list of `pool` rows
-        # fills without the exact fallback also at world >= 8 (ceil(150 / 8) = 19 M-tiles = 152 rows would just do)
         self._flush_overlap()
-        kth = max((pool_local + self.world - 1) // self.world, (pool_local + 7) // 8 + 1)
-        return self.s.dense_scan(q_dev, pool_local, min(kth, pool_local))
+        return self.s.dense_scan(q_dev, pool_local, floor_kth(pool_local, self.world))
 
     def local_payload(self, q_dev, term_id_lists, pool_local: int, bm25_mode: str = "forward", floor=None, buf=None,
                       gate=None, gate_host=None):
@@ -426,14 +399,20 @@ class ShardedSearcher:
             s.dense_pool(q_dev, pool_local, out=(v["rows"], v["dense"]))   # K1 writes the payload in place
         else:
             s.dense_select(q_dev, pool_local, floor, out=(v["rows"], v["dense"]))
-        s.bm25_at(term_id_lists, v["rows"], bm25_mode, out=v["bm25"])  # K2 too
-        if gate is not None:
-            s.gate_text.gate(v["rows"], gate, gate_host, staged, out=v["gate"])
+        self._payload_tail(v, term_id_lists, bm25_mode, gate, gate_host, staged)
+        return lay, buf
+
+    def _payload_tail(self, v, terms, bm25_mode: str, packed, gate_host, staged) -> None:
+        """Behind K1, on the current stream, into the payload views ``v``: K2 at the candidate rows, the gate match of this
+        rank's own candidates against its own plane when the batch has packed groups, and the metadata gather."""
+        s = self.s
+        s.bm25_at(terms, v["rows"], bm25_mode, out=v["bm25"])          # K2 writes the payload in place too
+        if packed is not None:
+            s.gate_text.gate(v["rows"], packed, gate_host, staged, out=v["gate"])
         _lib.check(s.lib.rr_index_gather_meta_dev(
-            s.index.handle, C.c_void_p(v["rows"].data_ptr()), B * pool_local,
+            s.index.handle, C.c_void_p(v["rows"].data_ptr()), v["rows"].numel(),
             C.c_void_p(v["n"].data_ptr()), C.c_void_p(v["avg"].data_ptr()),
             C.c_void_p(v["l1p"].data_ptr()), s._stream()), "rr_index_gather_meta_dev")
-        return lay, buf
 
     def search_batch_dev(self, q_dev, term_id_lists: Optional[Sequence[Sequence[int]]], k: int,
                          weights: Optional[FusionWeights] = None, pool_floor: int = 150,
@@ -457,22 +436,11 @@ class ShardedSearcher:
         merged first (K3 with k = pool gives the pool order), gate strings are matched on the host, the
         B x rr_k reranker pairs are split evenly across the ranks, their scores gathered with a second tiny
         all-gather, and K3 runs again on the same gathered payload with the pool-aligned columns."""
-        import torch
-        w = weights or FusionWeights()
-        B = q_dev.shape[0]
-        pool = min(max(k, rerank_k, pool_floor), self.n_total)
-        self._check_merge_size(pool)
-        pool_local = min(pool, self.s.index.n_rows)
-        rr_k = min(rerank_k, pool)
-        if self.world > 1:
-            # every rank must contribute the same count for the strided addressing
-            assert pool_local == pool, "each shard needs at least `pool` rows"
-        tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
         s = self.s
         if self.world == 1 and not self.force_payload:
             # nothing to exchange: K1 -> K2 -> gate -> K3 straight through, metadata read from the index
-            packed = self._check_columns(B, w, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs)
-            two_pass = gate_fn is not None or ((rerank_fn is not None or rerank_pairs is not None) and rr_k > 0)
+            B, w, pool, _, rr_k, tl, packed, two_pass = self._plan(q_dev, term_id_lists, k, weights, pool_floor, rerank_k,
+                                                                   gate_fn, rerank_fn, gate_groups, gate_host, rerank_pairs)
             self._flush_overlap()
             staged = s.gate_text.upload(packed) if packed is not None else None      # (ahead of the kernels)
             rows, dense = s.dense_pool(q_dev, pool)
@@ -503,18 +471,8 @@ class ShardedSearcher:
             res[n - 1] = s.finish(t)
 
         Every answer is bit for bit the one search_batch_dev gives (same kernels, same order per batch)."""
-        w = weights or FusionWeights()
-        B = q_dev.shape[0]
-        pool = min(max(k, rerank_k, pool_floor), self.n_total)
-        self._check_merge_size(pool)
-        pool_local = min(pool, self.s.index.n_rows)
-        rr_k = min(rerank_k, pool)
-        if self.world > 1:
-            assert pool_local == pool, "each shard needs at least `pool` rows"
-        tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
-        packed = self._check_columns(B, w, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs)
-        # (a gate matched on the device is a payload column: such a batch is an ordinary one-pass batch)
-        two_pass = gate_fn is not None or ((rerank_fn is not None or rerank_pairs is not None) and rr_k > 0)
+        B, w, pool, pool_local, rr_k, tl, packed, two_pass = self._plan(
+            q_dev, term_id_lists, k, weights, pool_floor, rerank_k, gate_fn, rerank_fn, gate_groups, gate_host, rerank_pairs)
         if self._ov is not None:
             if not two_pass:
                 t = self._submit_overlapped(q_dev, tl, B, k, pool, pool_local, w, bm25_mode, packed, gate_host)
@@ -524,47 +482,31 @@ class ShardedSearcher:
         lay, buf = self.local_payload(q_dev, tl, pool_local, bm25_mode, gate=packed, gate_host=gate_host)
         pending = exchange_start(buf, self.world, self.group)
         return PendingBatch(B, k, pool, pool_local, rr_k, w, lay, buf, pending, gate_fn, rerank_fn, packed=packed,
-                            gate_host=gate_host, rerank_pairs=rerank_pairs)
+                            gate_host=gate_host, rerank_pairs=rerank_pairs, two_pass=two_pass)
 
-    def _check_columns(self, B: int, w: FusionWeights, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs):
-        """The checks of the gate / rerank arguments, before any launch or collective (every rank computes the same tests on
-        the same batch, so no rank is left waiting in a collective the others never join).  Returns the batch's
-        gate.PackedGroups, or None when there is nothing to match (no gate, as with gate_fn=None)."""
-        packed = None
-        if gate_groups is not None:
-            from .gate import pack_groups
-            if gate_fn is not None:
-                raise ValueError("pass either gate_fn or gate_groups")
-            if self.s.gate_text is None:
-                raise ValueError("gate_groups need the gate plane of this shard's rows: HybridSearcher(..., gate_text=GateText...)")
-            if len(gate_groups) != B:
-                raise ValueError(f"{len(gate_groups)} gate groups for {B} queries")
-            packed = pack_groups(gate_groups, w.gate_penalty)
-            if packed.host_queries and gate_host is None:
-                raise ValueError(f"queries {packed.host_queries} exceed the gate kernel's limits and no gate_host was given")
-            if not packed.any_groups and not packed.host_queries:
-                packed = None
-        if rerank_pairs is not None:
-            if rerank_fn is not None:
-                raise ValueError("pass either rerank_fn or rerank_pairs")
-            if self.rerank_text is None:
-                raise ValueError("rerank_pairs need the token plane of the whole corpus: "
-                                 "ShardedSearcher(..., rerank_text=exchange_plane(...))")
-            _, rr_queries, rerank_host = rerank_pairs
-            if rr_queries.n_queries != B:
-                raise ValueError(f"{rr_queries.n_queries} packed queries for {B} queries")
-            if rr_queries.host_queries and rerank_host is None:
-                raise ValueError(f"queries {rr_queries.host_queries} exceed the pair kernel's limit and no rerank_host was given")
-        return packed
-
-    def _check_merge_size(self, pool: int) -> None:
-        """K3 merges world x pool candidates per query and takes at most MAX_CANDIDATES (include/rr_hip.h:
-        RR_MAX_CANDIDATES).  Checked before any launch or collective; every rank computes the same test, so no rank
-        is left waiting in a collective the others never join."""
-        if self.world * pool > MAX_CANDIDATES:
+    def _plan(self, q_dev, term_id_lists, k: int, weights, pool_floor: int, rerank_k: int, gate_fn, rerank_fn,
+              gate_groups, gate_host, rerank_pairs):
+        """The batch's plan, with every check that can refuse it, before any launch or collective (every rank computes the
+        same tests on the same batch, so no rank is left waiting in a collective the others never join):
+        (B, weights, pool, pool_local, rr_k, term lists, the gate's PackedGroups or None, two_pass).  ``two_pass``: a host
+        gate or a reranker needs the merged pool first (merge, pool-aligned columns, K3 again); a gate matched on the device
+        is a payload column, such a batch is an ordinary one-pass batch."""
+        w = weights or FusionWeights()
+        B = q_dev.shape[0]
+        pool = min(max(k, rerank_k, pool_floor), self.n_total)
+        if self.world * pool > MAX_CANDIDATES:      # K3 merges world x pool candidates per query (include/rr_hip.h: RR_MAX_CANDIDATES)
             raise ValueError(f"{self.world} shards x pool {pool} = {self.world * pool} candidates per query exceed "
                              f"the merge limit of {MAX_CANDIDATES}: the pool may be at most "
                              f"{MAX_CANDIDATES // self.world} with {self.world} shards")
+        pool_local = min(pool, self.s.index.n_rows)
+        rr_k = min(rerank_k, pool)
+        if self.world > 1:
+            # every rank must contribute the same count for the strided addressing
+            assert pool_local == pool, "each shard needs at least `pool` rows"
+        tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
+        packed = check_columns(B, w, self.s.gate_text, self.rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs)
+        two_pass = gate_fn is not None or ((rerank_fn is not None or rerank_pairs is not None) and rr_k > 0)
+        return B, w, pool, pool_local, rr_k, tl, packed, two_pass
 
     # ------------------------------------------------------------------ the overlapped form
     def _flush_overlap(self) -> None:
@@ -582,9 +524,7 @@ class ShardedSearcher:
             raise RuntimeError("the overlapped pipeline is three batches deep: finish() earlier tickets before submitting more")
         slot = ov.seq % ov.SLOTS
         with_floor = self.world > 1 and self.use_floor and dist.is_available() and dist.is_initialized()
-        kth = 0
-        if with_floor:       # (local_scan's rule)
-            kth = min(max((pool_local + self.world - 1) // self.world, (pool_local + 7) // 8 + 1), pool_local)
+        kth = floor_kth(pool_local, self.world) if with_floor else 0
         cur = torch.cuda.current_stream(s.device)
         staged = s.gate_text.upload(packed) if packed is not None else None     # (ahead of K1; the copy has finished on return)
         ready = torch.cuda.Event()
@@ -634,13 +574,7 @@ class ShardedSearcher:
                 s.dense_pool(t.plain_q, pool_local, out=(v["rows"], v["dense"]), slot=t.slot)
             else:
                 s.dense_select_slot(t.slot, B, pool_local, floor=t.bound, out=(v["rows"], v["dense"]))
-            s.bm25_at(t.terms, v["rows"], t.bm25_mode, out=v["bm25"])
-            if t.packed is not None:                        # this rank's own candidates against its own plane, into the payload
-                s.gate_text.gate(v["rows"], t.packed, t.gate_host, t.staged, out=v["gate"])
-            _lib.check(s.lib.rr_index_gather_meta_dev(
-                s.index.handle, C.c_void_p(v["rows"].data_ptr()), B * pool_local,
-                C.c_void_p(v["n"].data_ptr()), C.c_void_p(v["avg"].data_ptr()),
-                C.c_void_p(v["l1p"].data_ptr()), s._stream()), "rr_index_gather_meta_dev")
+            self._payload_tail(v, t.terms, t.bm25_mode, t.packed, t.gate_host, t.staged)
             t.pending = exchange_start(buf, self.world, self.group, out=gathered)
         t.buf, t.stage, t.terms, t.plain_q = buf, 1, None, None
 
@@ -659,17 +593,7 @@ class ShardedSearcher:
             torch.empty((B, k_out), dtype=torch.int32, device=s.device)))[t.slot]
         cur = torch.cuda.current_stream(s.device)
         with torch.cuda.stream(ov.tail_stream):
-            gathered = t.pending.wait()
-            base = gathered.data_ptr()
-            ptr = lambda off: C.c_void_p(base + off)
-            params = HybridSearcher.make_params(w, k_out, pool, self.world * pool_local, 0,
-                                                cand_per_rank=pool_local, stride_bytes=lay.nbytes)
-            _lib.check(s.lib.rr_fuse_topk_cand_dev(
-                s.index.handle, C.byref(params), B, ptr(lay.off_rows), ptr(lay.off_dense), ptr(lay.off_bm25),
-                ptr(lay.off_n), ptr(lay.off_avg), ptr(lay.off_l1p), None, None, None,
-                ptr(lay.off_gate) if lay.gate else None,
-                C.c_void_p(out_rows.data_ptr()), C.c_void_p(cols.data_ptr()), C.c_void_p(order.data_ptr()), s._stream()),
-                "rr_fuse_topk_cand_dev")
+            self.merge(lay, t.pending.wait(), B, k_out, pool, pool_local, w, out=(out_rows, cols, order))
             done = torch.cuda.Event()
             done.record(ov.tail_stream)
         cur.wait_event(done)                                # the caller's stream may read the answer
@@ -681,39 +605,44 @@ class ShardedSearcher:
     def finish(self, t: "PendingBatch"):
         """Second half: the gathered payload is merged and fused (K3, with the payload's gate column when the batch has one;
         with a host gate or a reranker: merge, pool-aligned columns, K3 again)."""
-        import torch
         if t.slot >= 0:
             return self._finish_overlapped(t)
-        s = self.s
-        B, k, pool, pool_local, rr_k, w, lay = t.B, t.k, t.pool, t.pool_local, t.rr_k, t.w, t.lay
-        gate_fn, rerank_fn = t.gate_fn, t.rerank_fn
-        two_pass = gate_fn is not None or ((rerank_fn is not None or t.rerank_pairs is not None) and rr_k > 0)
+        B, pool, pool_local, rr_k, w, lay = t.B, t.pool, t.pool_local, t.rr_k, t.w, t.lay
+        k_out = min(t.k, pool)
         gathered = t.pending.wait()
+        if not t.two_pass:
+            res = self.merge(lay, gathered, B, k_out, pool, pool_local, w)
+        else:
+            # pass A: the merge alone fixes the pool order; pass B: the same payload + the pool-aligned columns
+            merged_rows, _, _ = self.merge(lay, gathered, B, pool, pool, pool_local, w)
+            gate, rerank = self._pool_columns(merged_rows, B, pool, rr_k, t.gate_fn, t.rerank_fn, t.rerank_pairs)
+            res = self.merge(lay, gathered, B, k_out, pool, pool_local, w, rr_k, rerank, gate)
+        self._keep = (gathered, t.buf)   # alive until the stream has consumed them
+        return res
+
+    def merge(self, lay: PayloadLayout, gathered, B: int, k_out: int, pool: int, pool_local: int, w: FusionWeights,
+              rr_k: int = 0, rerank=None, gate=None, out=None):
+        """K3 over a gathered payload, on the current stream: ``gathered`` holds ``self.world`` blocks of layout ``lay``
+        ([rank][query][pool_local] addressing); they are merged to the top ``pool`` by (dense desc, row asc) and fused ->
+        (out_rows (B, pool), cols (B, 8, pool) f64, order (B, k_out)).  The payload's gate column is read through the merge
+        when the layout has one; ``rerank`` / ``gate``: pool-aligned (B, pool) float32 columns of a second pass (a host gate
+        and the payload's column exclude each other).  ``out``: the three tensors to write into instead of fresh ones."""
+        import torch
+        s = self.s
+        params = HybridSearcher.make_params(w, k_out, pool, self.world * pool_local, rr_k,
+                                            cand_per_rank=pool_local, stride_bytes=lay.nbytes)
+        if out is None:
+            out = (torch.empty((B, pool), dtype=torch.int64, device=s.device),
+                   torch.empty((B, 8, pool), dtype=torch.float64, device=s.device),
+                   torch.empty((B, k_out), dtype=torch.int32, device=s.device))
         base = gathered.data_ptr()
         ptr = lambda off: C.c_void_p(base + off)
         p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
-
-        def fuse(k_out, rerank, gate, rr):
-            params = HybridSearcher.make_params(w, k_out, pool, self.world * pool_local, rr,
-                                                cand_per_rank=pool_local, stride_bytes=lay.nbytes)
-            out_rows = torch.empty((B, pool), dtype=torch.int64, device=s.device)
-            cols = torch.empty((B, 8, pool), dtype=torch.float64, device=s.device)
-            order = torch.empty((B, params.k), dtype=torch.int32, device=s.device)
-            _lib.check(s.lib.rr_fuse_topk_cand_dev(
-                s.index.handle, C.byref(params), B, ptr(lay.off_rows), ptr(lay.off_dense), ptr(lay.off_bm25),
-                ptr(lay.off_n), ptr(lay.off_avg), ptr(lay.off_l1p), p(rerank), None, p(gate),
-                ptr(lay.off_gate) if lay.gate else None,          # (gate_fn and gate_groups exclude each other)
-                p(out_rows), p(cols), p(order), s._stream()), "rr_fuse_topk_cand_dev")
-            return out_rows, cols, order
-
-        if not two_pass:
-            res = fuse(min(k, pool), None, None, 0)
-        else:
-            merged_rows, _, _ = fuse(pool, None, None, 0)           # pass A: the merge alone fixes the pool order
-            gate, rerank = self._pool_columns(merged_rows, B, pool, rr_k, gate_fn, rerank_fn, t.rerank_pairs)
-            res = fuse(min(k, pool), rerank, gate, rr_k)             # pass B: same payload + pool-aligned columns
-        self._keep = (gathered, t.buf)   # alive until the stream has consumed them
-        return res
+        _lib.check(s.lib.rr_fuse_topk_cand_dev(
+            s.index.handle, C.byref(params), B, ptr(lay.off_rows), ptr(lay.off_dense), ptr(lay.off_bm25),
+            ptr(lay.off_n), ptr(lay.off_avg), ptr(lay.off_l1p), p(rerank), None, p(gate),
+            ptr(lay.off_gate) if lay.gate else None, p(out[0]), p(out[1]), p(out[2]), s._stream()), "rr_fuse_topk_cand_dev")
+        return out
 
     def _pool_columns(self, rows_dev, B: int, pool: int, rr_k: int, gate_fn, rerank_fn, rerank_pairs=None):
         """Host gate factors (gate_fn: every rank, all pairs: string work on replicated texts) and reranker scores (this
@@ -723,10 +652,17 @@ class ShardedSearcher:
         import torch
         s = self.s
         gate = rerank = None
+        n_pairs = B * rr_k
+        lo, hi = split_pairs(n_pairs, self.world, self.rank)
+
+        def spread(mine):                                        # my share -> all ranks' scores -> (B, pool), zeros beyond rr_k
+            full = exchange_scores(mine, n_pairs, self.world, self.group)
+            col = torch.zeros((B, pool), dtype=torch.float32, device=s.device)
+            col[:, :rr_k] = full.view(B, rr_k)
+            return col
+
         if rerank_pairs is not None and rr_k > 0:
             ce, rr_queries, rerank_host = rerank_pairs
-            n_pairs = B * rr_k
-            lo, hi = split_pairs(n_pairs, self.world, self.rank)
             with torch.cuda.device(s.device):
                 mine = self.rerank_text.scores(ce, rows_dev, rr_k, rr_queries, lo, hi - lo)
                 if rr_queries.host_queries:                      # (a property of the batch: every rank branches alike)
@@ -736,9 +672,7 @@ class ShardedSearcher:
                         if a < e:                                # this rank's pairs of query b only
                             r = np.ascontiguousarray(rerank_host(b, rows_h[b, a - b * rr_k:e - b * rr_k]), dtype=np.float32)
                             mine[a - lo:e - lo].copy_(torch.from_numpy(r.reshape(e - a)))
-                full = exchange_scores(mine, n_pairs, self.world, self.group)
-                rerank = torch.zeros((B, pool), dtype=torch.float32, device=s.device)
-                rerank[:, :rr_k] = full.view(B, rr_k)
+                rerank = spread(mine)
         if gate_fn is None and (rerank_fn is None or rr_k <= 0):
             return gate, rerank
         rows_h = rows_dev.cpu().numpy()
@@ -746,14 +680,10 @@ class ShardedSearcher:
             g = np.ascontiguousarray(gate_fn(rows_h), dtype=np.float32)
             gate = torch.from_numpy(g).to(s.device)
         if rerank_fn is not None and rr_k > 0:
-            n_pairs = B * rr_k
-            lo, hi = split_pairs(n_pairs, self.world, self.rank)
             idx = np.arange(lo, hi)
             qi, ci = idx // rr_k, idx % rr_k
             mine = np.asarray(rerank_fn(qi, rows_h[qi, ci]), dtype=np.float32).reshape(-1)
             if mine.shape[0] != hi - lo:
                 raise ValueError("rerank_fn must return one score per pair")
-            full = exchange_scores(torch.from_numpy(mine).to(s.device), n_pairs, self.world, self.group)
-            rerank = torch.zeros((B, pool), dtype=torch.float32, device=s.device)
-            rerank[:, :rr_k] = full.view(B, rr_k)
+            rerank = spread(torch.from_numpy(mine).to(s.device))
         return gate, rerank

@@ -70,6 +70,10 @@ def test_sharded_equals_unsharded_bitwise(world, batch):
     assert np.array_equal(out_rows.cpu().numpy(), want_rows)
     assert np.array_equal(cols.cpu().numpy(), want_cols, equal_nan=True)
     assert np.array_equal(order.cpu().numpy(), want_order)
+    # ShardedSearcher.merge (what finish runs) on the same gathered buffer: the raw call's three arrays, bit for bit
+    for got, raw in zip(shards[0].merge(lay, gathered, batch, k, pool, pool, w), (out_rows, cols, order)):
+        assert got.dtype == raw.dtype and got.shape == raw.shape and got.data_ptr() != raw.data_ptr()
+        assert got.cpu().numpy().tobytes() == raw.cpu().numpy().tobytes()
     r0 = want_rows[0].tolist()
     assert r0.index(1000) + 1 == r0.index(39_000)      # tie: ascending global row
 
@@ -109,17 +113,7 @@ def test_eight_shards_merge_up_to_the_candidate_limit_and_refuse_more():
     for r, sh in enumerate(shards):
         _, buf = sh.local_payload(q_dev, tl, pool)
         gathered[r].copy_(buf)
-    s0 = shards[0].s
-    params = HybridSearcher.make_params(w, pool, pool, world * pool, 0, cand_per_rank=pool, stride_bytes=lay.nbytes)
-    out_rows = torch.empty((batch, pool), dtype=torch.int64, device="cuda")
-    cols = torch.empty((batch, 8, pool), dtype=torch.float64, device="cuda")
-    order = torch.empty((batch, pool), dtype=torch.int32, device="cuda")
-    base = gathered.data_ptr()
-    p = lambda off: C.c_void_p(base + off)
-    _lib.check(s0.lib.rr_fuse_topk_dev(
-        s0.index.handle, C.byref(params), batch, p(lay.off_rows), p(lay.off_dense), p(lay.off_bm25),
-        p(lay.off_n), p(lay.off_avg), p(lay.off_l1p), None, None, None, C.c_void_p(out_rows.data_ptr()),
-        C.c_void_p(cols.data_ptr()), C.c_void_p(order.data_ptr()), s0._stream()), "rr_fuse_topk_dev")
+    out_rows, cols, order = shards[0].merge(lay, gathered, batch, pool, pool, pool, w)
     torch.cuda.synchronize()
     assert np.array_equal(out_rows.cpu().numpy(), want[0])
     assert np.array_equal(cols.cpu().numpy(), want[1], equal_nan=True)
@@ -157,17 +151,7 @@ def test_config4_shape_bf16_batch_256_sharded_equals_unsharded(dtype):
         gathered[r].copy_(buf)
         torch.cuda.synchronize()
         first = first or sh
-    s0 = first.s
-    params = HybridSearcher.make_params(w, k, pool, world * pool, 0, cand_per_rank=pool, stride_bytes=lay.nbytes)
-    out_rows = torch.empty((batch, pool), dtype=torch.int64, device="cuda")
-    cols = torch.empty((batch, 8, pool), dtype=torch.float64, device="cuda")
-    order = torch.empty((batch, k), dtype=torch.int32, device="cuda")
-    base = gathered.data_ptr()
-    p = lambda off: C.c_void_p(base + off)
-    _lib.check(s0.lib.rr_fuse_topk_dev(
-        s0.index.handle, C.byref(params), batch, p(lay.off_rows), p(lay.off_dense), p(lay.off_bm25),
-        p(lay.off_n), p(lay.off_avg), p(lay.off_l1p), None, None, None, C.c_void_p(out_rows.data_ptr()),
-        C.c_void_p(cols.data_ptr()), C.c_void_p(order.data_ptr()), s0._stream()), "rr_fuse_topk_dev")
+    out_rows, cols, order = first.merge(lay, gathered, batch, k, pool, pool, w)
     torch.cuda.synchronize()
     assert np.array_equal(out_rows.cpu().numpy(), want[0])
     assert np.array_equal(cols.cpu().numpy(), want[1], equal_nan=True)
@@ -258,17 +242,7 @@ def test_shards_select_against_a_corpus_wide_floor(dtype):
         assert sh.s.index.select_trace()[0] == 2
         opened.append(sh.s.index.select_trace()[2])
     assert sum(opened) * 3 < sum(own), (opened, own)              # (query 0's M-tile lists: ~1/8 expected)
-    s0 = shards[0].s
-    params = HybridSearcher.make_params(w, k, pool, world * pool, 0, cand_per_rank=pool, stride_bytes=lay.nbytes)
-    out_rows = torch.empty((batch, pool), dtype=torch.int64, device="cuda")
-    cols = torch.empty((batch, 8, pool), dtype=torch.float64, device="cuda")
-    order = torch.empty((batch, k), dtype=torch.int32, device="cuda")
-    base = gathered.data_ptr()
-    p = lambda off: C.c_void_p(base + off)
-    _lib.check(s0.lib.rr_fuse_topk_dev(
-        s0.index.handle, C.byref(params), batch, p(lay.off_rows), p(lay.off_dense), p(lay.off_bm25),
-        p(lay.off_n), p(lay.off_avg), p(lay.off_l1p), None, None, None, C.c_void_p(out_rows.data_ptr()),
-        C.c_void_p(cols.data_ptr()), C.c_void_p(order.data_ptr()), s0._stream()), "rr_fuse_topk_dev")
+    out_rows, cols, order = shards[0].merge(lay, gathered, batch, k, pool, pool, w)
     torch.cuda.synchronize()
     assert np.array_equal(out_rows.cpu().numpy(), want[0])
     assert np.array_equal(cols.cpu().numpy(), want[1], equal_nan=True)

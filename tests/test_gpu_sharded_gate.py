@@ -118,16 +118,8 @@ def merge(shards, lay, bufs, weights, k, batch, pool):
     gathered = torch.empty((size, lay.nbytes), dtype=torch.uint8, device="cuda")
     for r, buf in enumerate(bufs):
         gathered[r].copy_(buf)
-    s0 = shards[0].s
-    params = HybridSearcher.make_params(weights, k, pool, size * pool, 0, cand_per_rank=pool, stride_bytes=lay.nbytes)
-    out_rows = torch.empty((batch, pool), dtype=torch.int64, device="cuda")
-    cols = torch.empty((batch, 8, pool), dtype=torch.float64, device="cuda")
-    order = torch.empty((batch, k), dtype=torch.int32, device="cuda")
-    p = lambda off: C.c_void_p(gathered.data_ptr() + off)
-    _lib.check(s0.lib.rr_fuse_topk_cand_dev(
-        s0.index.handle, C.byref(params), batch, p(lay.off_rows), p(lay.off_dense), p(lay.off_bm25), p(lay.off_n),
-        p(lay.off_avg), p(lay.off_l1p), None, None, None, p(lay.off_gate), C.c_void_p(out_rows.data_ptr()),
-        C.c_void_p(cols.data_ptr()), C.c_void_p(order.data_ptr()), s0._stream()), "rr_fuse_topk_cand_dev")
+    assert lay.gate
+    out_rows, cols, order = shards[0].merge(lay, gathered, batch, k, pool, pool, weights)
     torch.cuda.synchronize()
     return out_rows.cpu().numpy(), cols.cpu().numpy(), order.cpu().numpy()
 

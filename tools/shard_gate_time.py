@@ -27,7 +27,6 @@ Also the bytes of gate plane per shard, and that the three gated forms answer bi
 device_gate_batch_faster: gate_groups_s < gate_fn_s (medians) on the same corpus in the same run; the ratio and the gate's
 added time over the ungated batch are recorded, not gated."""
 import argparse
-import ctypes as C
 import json
 import pathlib
 import sys
@@ -55,7 +54,7 @@ def main():
     a = ap.parse_args()
     import pandas as pd
     import torch
-    from review_recommender_amd import _lib, gate as G, synth, text as T
+    from review_recommender_amd import gate as G, synth, text as T
     from review_recommender_amd.bm25 import BM25Corpus
     from review_recommender_amd.engine import FusionWeights, HybridSearcher
     from review_recommender_amd.index import ProductIndex
@@ -106,18 +105,9 @@ def main():
     gate_fn = lambda rows: np.stack([gate_rows(g, r) for g, r in zip(groups, rows)])
     lays = {False: PayloadLayout(B, pool), True: PayloadLayout(B, pool, gate=True)}
     gathered = {g: torch.empty((world, lay.nbytes), dtype=torch.uint8, device="cuda") for g, lay in lays.items()}
-    s0 = shards[0].s
 
     def fuse(lay, buf, k_out, gate=None):
-        params = HybridSearcher.make_params(w, k_out, pool, world * pool, 0, cand_per_rank=pool, stride_bytes=lay.nbytes)
-        out = (torch.empty((B, pool), dtype=torch.int64, device="cuda"), torch.empty((B, 8, pool), dtype=torch.float64, device="cuda"),
-               torch.empty((B, k_out), dtype=torch.int32, device="cuda"))
-        p = lambda off: C.c_void_p(buf.data_ptr() + off)
-        _lib.check(s0.lib.rr_fuse_topk_cand_dev(
-            s0.index.handle, C.byref(params), B, p(lay.off_rows), p(lay.off_dense), p(lay.off_bm25), p(lay.off_n), p(lay.off_avg),
-            p(lay.off_l1p), None, None, C.c_void_p(gate.data_ptr()) if gate is not None else None,
-            p(lay.off_gate) if lay.gate else None, *[C.c_void_p(t.data_ptr()) for t in out], s0._stream()), "rr_fuse_topk_cand_dev")
-        return out
+        return shards[0].merge(lay, buf, B, k_out, pool, pool, w, gate=gate)
 
     def batch(mode):
         gated = mode == "gate_groups"

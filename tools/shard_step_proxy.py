@@ -87,7 +87,7 @@ def overlapped_rank_step():
     torch.cuda.synchronize()
     s0 = shards[0].sharded
     s0.force_payload = True
-    kth = min(max((POOL + world - 1) // world, (POOL + 7) // 8 + 1), POOL)
+    kth = S.floor_kth(POOL, world)
 
     # the two collectives, replayed: rank 0's own bound is computed live and then overwritten by the corpus-wide minimum; its
     # payload block is gathered beside the seven recorded ones

@@ -711,6 +711,78 @@ int rr_pairs_write_dev(rr_pairs* h, const uint16_t* d_plane_tok, const int64_t* 
  * (*out_bad = how many). */
 int rr_pairs_status(rr_pairs* h, int32_t* out_bad);
 
+/* ------------------------------------------------------------ the query front: ids, gate groups, reranker ids (csrc/rr_query.hip) */
+
+/* What run_search does with the query STRING before the kernels (utils.py:57-86, app/app_product_search.py:189-227), for a
+ * whole batch on the device: the BM25 term ids of text.tokenize_query, the gate groups of text.build_gate_groups packed as
+ * gate.pack_groups packs them, the reranker's query ids packed as rerank.pack_queries packs them -- each in the layout its
+ * consumer reads (the BM25 scores at the candidates, the gate match, the pair assembly).  querytext.model_front states in
+ * plain Python what the kernels compute.  The calls of one handle must be stream-ordered.
+ *
+ * THE TABLES, once per index (the create call uploads them; the kernel source holds no word list):
+ *   the vocabulary  bytes + int64 offsets [n_vocab + 1] in id order, hashed ON THE HOST into an open-addressing table (the
+ *                   build_table call; the table_slots call gives its size: a power of two, at least 64 and at least twice
+ *                   the entries): a slot = 4 int32 = hash, first byte, length, id (-1 = empty).  Entries that are not 1 .. 64
+ *                   bytes of [a-z0-9'] are left out: no query token can equal them.  A lookup compares the hash, then the bytes;
+ *   the stop words  bytes + int32 offsets [n_stop + 1], 1 .. 8 ASCII bytes each;
+ *   the static gate groups  n_colors colour groups, then n_syn synonym groups: the terms' bytes + int32 offsets, SORTED inside
+ *                   a group, h_group_off int32 [n_colors + n_syn + 1] = first term of each group; the synonym groups' keys as
+ *                   bytes + int32 offsets [n_syn + 1].  Terms and keys are 1 .. 64 ASCII bytes.  max_groups (1 .. 6) groups
+ *                   of the largest static group must fit the gate's 64 terms and 1024 term bytes per query, so that no query
+ *                   the kernel answers can exceed a limit of the gate match.
+ *
+ * THE BATCH.  d_text = the UTF-8 bytes of n_queries (1 .. 65535) queries back to back, d_text_off = n_queries + 1 int64
+ * offsets (the layout rr_wp_encode_dev reads, so one staged buffer serves both).  Per query:
+ *   tokens      the matches of [a-z0-9]+(?:'[a-z0-9]+)? (greedy, left to right) over the bytes after A-Z -> a-z,
+ *               E2 84 AA -> k, C4 B0 -> i + separator, NUL and every other byte >= 0x80 -> separator; minus the stop words;
+ *   d_ids       one vocabulary id per token, in order, duplicates kept, -1 for a token the table lacks; query q owns
+ *               d_ids[d_ids_off[q] .. d_ids_off[q + 1]), d_ids_off int32 [n_queries + 1];
+ *   gate groups colour groups in table order, present when one of their terms is a SUBSTRING of the lower-cased query (the
+ *               gate plane's byte image of it); then per token its synonym group when the token is that group's key, else
+ *               {token} when it has min_keyword_len bytes or more; groups equal as sets are dropped, the first stays; the first
+ *               max_groups are kept.  Written as the gate match reads them: d_term_bytes, d_term_off int32 [T + 1],
+ *               d_term_group int32 [T], d_q_term int32 [n_queries + 1], d_q_groups int32 [n_queries]; the factor table
+ *               stays the host's (no floating point here);
+ *   d_needs_host int32 [n_queries], one bit per reason: 1 = the query has more than 1024 bytes, 2 = a token has more than 64
+ *               bytes, 4 = more than max_length - 3 reranker ids, 8 = the WordPiece kernel handed it back, 16 = its offsets
+ *               decrease or leave the text (also counted by the status call).  A flagged query gets no ids, no groups and
+ *               no reranker ids: the caller serves it through the host functions.
+ * d_wp_cu / d_wp_needs_host (both or neither): cu_seqlens and needs_host of rr_wp_encode_dev over the SAME text and offsets
+ * with the cross-encoder's vocabulary and max_length = the cross-encoder's (then a query of max_length - 2 pieces or more
+ * shows as such); they decide bits 4 and 8 and the reranker counts.  d_counts int32 [n_queries x 4] (ids, terms, term bytes,
+ * reranker ids per query) is scratch between the two launches and the input of the strip call.
+ * Two launches, a wave per query: `measure` writes d_counts and d_needs_host, `write` sums the counts of the queries in front
+ * of its own and writes.  Capacities (cap_ids ids, cap_terms terms -- d_term_off holds cap_terms + 1 --, cap_term_bytes):
+ * every store is checked first; one that does not fit is not made and counted by the status call.  Upper bounds: a query
+ * of b bytes has at most (b + 1) / 2 tokens, max_groups groups have at most 64 terms and 1024 term bytes.
+ *
+ * The strip call: d_rr_ids / d_rr_off int32 [n_queries + 1] = the pieces of every unflagged query without [CLS] and [SEP],
+ * back to back (d_wp_tok of capacity wp_capacity and d_wp_cu as rr_wp_encode_dev wrote them, d_counts as the front call
+ * left it).  Asynchronous on `stream`; no host wait, no allocation, nothing read back. */
+typedef struct rr_query rr_query;
+/* Bytes of a query, bytes of a token, groups per query, bytes of a stop word the kernels hold. */
+int rr_query_limits(int32_t* out_max_query, int32_t* out_max_token, int32_t* out_max_groups, int32_t* out_max_stop);
+int rr_query_table_slots(int32_t n_entries, int32_t* out_slots);
+/* Host only (no device needed): h_slots [n_slots][4] int32, *out_kept = the entries kept. */
+int rr_query_build_table(const uint8_t* h_bytes, const int64_t* h_off, int32_t n_entries, int32_t n_slots, int32_t* h_slots,
+                         int32_t* out_kept);
+int rr_query_create(int32_t device, const uint8_t* h_vocab_bytes, const int64_t* h_vocab_off, int32_t n_vocab,
+                    const uint8_t* h_stop_bytes, const int32_t* h_stop_off, int32_t n_stop, const uint8_t* h_term_bytes,
+                    const int32_t* h_term_off, const int32_t* h_group_off, int32_t n_colors, int32_t n_syn,
+                    const uint8_t* h_key_bytes, const int32_t* h_key_off, int32_t max_groups, int32_t min_keyword_len,
+                    rr_query** out);
+int rr_query_destroy(rr_query* h);
+int rr_query_front_dev(rr_query* h, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                       int32_t n_queries, const int32_t* d_wp_cu, const int32_t* d_wp_needs_host, int32_t max_length,
+                       int32_t* d_counts, int32_t* d_needs_host, int32_t* d_ids, int32_t* d_ids_off, int64_t cap_ids,
+                       int32_t* d_term_off, int32_t* d_term_group, int32_t* d_q_term, int32_t* d_q_groups,
+                       uint8_t* d_term_bytes, int64_t cap_terms, int64_t cap_term_bytes, void* stream);
+int rr_query_strip_dev(rr_query* h, const int32_t* d_wp_tok, const int32_t* d_wp_cu, int64_t wp_capacity, int32_t n_queries,
+                       const int32_t* d_counts, int32_t* d_rr_off, int32_t* d_rr_ids, int64_t cap_rr, void* stream);
+/* Waits for the device; RR_E_INVALID when a call since the last one met offsets that decrease or leave the text or a store
+ * beyond a capacity (*out_bad = how many). */
+int rr_query_status(rr_query* h, int32_t* out_bad);
+
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard
  * that selects on its own rescoring ~8x the candidates the merged answer needs.  Instead:

@@ -144,6 +144,16 @@ PROTOTYPES = {
     "rr_pairs_write_dev": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64,
                                      c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rr_pairs_status": (C.c_int, [c_vp, P(c_i32)]),
+    "rr_query_limits": (C.c_int, [P(c_i32)] * 4),
+    "rr_query_table_slots": (C.c_int, [c_i32, P(c_i32)]),
+    "rr_query_build_table": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, P(c_i32)]),
+    "rr_query_create": (C.c_int, [c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32,
+                                  c_i32, P(c_vp)]),
+    "rr_query_destroy": (C.c_int, [c_vp]),
+    "rr_query_front_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    "rr_query_strip_dev": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rr_query_status": (C.c_int, [c_vp, P(c_i32)]),
     "rr_index_stream": (C.c_int, [c_vp, P(c_vp)]),
     "rr_index_synchronize": (C.c_int, [c_vp]),
 }

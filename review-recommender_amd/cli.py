@@ -58,6 +58,10 @@ def parse_args(argv=None):
                     help="where the attribute gate's terms are matched: host = str.lower() and substring searches in Python "
                          "(the reference's way), device = a gate plane of agg_text[:6000] on the GPU (csrc/rr_gate.hip; up to "
                          "6 KB of device memory per product); the same results")
+    ap.add_argument("--query-text", choices=["host", "device"], default="host",
+                    help="where the query string is tokenised, its BM25 ids looked up and its gate groups built: host = in "
+                         "Python (the reference's way), device = on the GPU for the whole batch (csrc/rr_query.hip); the same "
+                         "results")
     ap.add_argument("--allow-hub", action="store_true",
                     help="opt in to sentence-transformers by model name (EMB_MODEL / RERANK_MODEL, app/test.py:28-29) for "
                          "whatever model no local directory was given; off by default: the product path is the GPU one")
@@ -103,7 +107,7 @@ def main(argv=None) -> int:
                          "--qvec-npy (or opt in to the hub loader with --allow-hub)")          # app/test.py:234-235
     try:
         engine = SearchEngine.from_artifacts(args.data_dir, encoder=enc, cross_encoder=ce, flavour="cli",
-                                             device=args.device, gate=args.gate)
+                                             device=args.device, gate=args.gate, query_text=args.query_text)
     except ArtifactError as e:
         raise SystemExit(f"[ERR] {e}")
     # snippets are scored whenever the review file exists and --no-snippets is absent (app/test.py:271-276)

@@ -64,6 +64,7 @@ class BatchResult:
     k: int
     best_ids: Optional[np.ndarray] = None    # (B, pool) best review id per candidate, -1 = none
     best_raw: Optional[np.ndarray] = None    # (B, pool) its raw score
+    needs_host: Optional[np.ndarray] = None  # (B,) with query_front: the queries the front end handed back (querytext.FLAG_*)
 
     def topk_rows(self) -> np.ndarray:
         return np.take_along_axis(self.pool_rows, self.order.astype(np.int64), axis=1)
@@ -99,13 +100,23 @@ class StagedBatch:
         self.q, self.terms, self.ready, self.slot = q, terms, ready, slot
 
 
-def check_columns(B: int, w: FusionWeights, gate_text, rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs):
+def check_columns(B: int, w: FusionWeights, gate_text, rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs,
+                  query_front=None):
     """The checks of a batch's gate / rerank arguments against the searcher's planes, before any launch or collective (on row
     shards every rank computes the same tests on the same batch, so no rank is left waiting in a collective the others never
     join).  ``gate_text``: the gate plane of the searcher's own rows; ``rerank_text``: the token plane of every row a merged
     pool can hold (sharded.exchange_plane on row shards).  Returns the batch's gate.PackedGroups, or None when there is
-    nothing to match (no gate, as with gate_fn=None)."""
+    nothing to match (no gate, as with gate_fn=None).  ``query_front`` (a querytext.QueryFront): the batch's groups and
+    packed queries are already on the device; its sizes are checked and it is returned in the PackedGroups' place when the
+    searcher has a gate plane and no gate_fn was given (which of its queries have groups is not known on the host)."""
     packed = None
+    if query_front is not None:
+        if gate_groups is not None or (rerank_pairs is not None and rerank_pairs[1] is not None):
+            raise ValueError("pass either query_front or gate_groups / packed queries in rerank_pairs")
+        if query_front.n_queries != B:
+            raise ValueError(f"a query front of {query_front.n_queries} queries for {B} queries")
+        if gate_text is not None and gate_fn is None:
+            packed = query_front
     if gate_groups is not None:
         from .gate import pack_groups
         if gate_fn is not None:
@@ -126,6 +137,10 @@ def check_columns(B: int, w: FusionWeights, gate_text, rerank_text, gate_fn, gat
             raise ValueError("rerank_pairs need the token plane of the whole corpus: HybridSearcher(..., rerank_text=RerankText...), "
                              "on row shards ShardedSearcher(..., rerank_text=exchange_plane(...))")
         _, rr_queries, rerank_host = rerank_pairs
+        if rr_queries is None:
+            rr_queries = query_front
+            if rr_queries is None or rr_queries.rerank_staged is None:
+                raise ValueError("rerank_pairs without packed queries need a query_front made with a reranker's tokenizer")
         if rr_queries.n_queries != B:
             raise ValueError(f"{rr_queries.n_queries} packed queries for {B} queries")
         if rr_queries.host_queries and rerank_host is None:
@@ -409,7 +424,8 @@ class HybridSearcher:
                      bm25_mode: str = "forward", reviews=None, max_scan: int = 0,
                      bm25_f64: bool = False, gate_groups=None,
                      gate_host: Optional[Callable[[int, np.ndarray], np.ndarray]] = None,
-                     rerank_pairs: Optional[Tuple] = None) -> BatchResult:
+                     rerank_pairs: Optional[Tuple] = None, query_front=None,
+                     on_queued: Optional[Callable[[], None]] = None) -> BatchResult:
         """qvecs (B, dim) float32; term_id_lists: per-query BM25 token ids (None = no BM25).
         gate_fn / rerank_fn map the (B, pool) pool rows to (B, pool) float32 gate factors /
         (B, rr_k) raw reranker scores; they run on the host between K2 and K3.
@@ -424,6 +440,12 @@ class HybridSearcher:
         and no score is uploaded.  A query of more than max_length - 3 tokens (rerank.pack_queries: ``host_queries``) gets
         its rr_k scores from ``rerank_host(b, rows[b, :rr_k]) -> (rr_k,) float32`` instead; only then are the rows copied to
         the host.
+        ``query_front`` (instead of term_id_lists, gate_groups and the packed queries of rerank_pairs -- pass
+        ``rerank_pairs=(cross_encoder, None, rerank_host)``): a querytext.QueryFront, the batch's query text already on the
+        device.  K2 reads its ids, the gate match its groups (when the searcher has a gate plane and no gate_fn is given),
+        the pair kernels its query ids.  Its ``needs_host`` flags come back in ``BatchResult.needs_host`` with the answer:
+        the rows of a flagged query were computed from an EMPTY query text and are the caller's to replace.
+        ``on_queued``: called once when every kernel of the batch is queued, before the answer is waited for.
         ``bm25_f64``: the CLI flavour without a BM25 artefact (float64 zeros column, app/test.py:252)."""
         torch = _torch()
         w = weights or FusionWeights()
@@ -438,12 +460,20 @@ class HybridSearcher:
             raise ValueError(f"pool {pool} exceeds the kernels' limit {MAX_POOL}")
         k_eff = min(k, pool)
         rr_k = min(rerank_k, pool)
-        packed = check_columns(B, w, self.gate_text, self.rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs)
+        if query_front is not None and term_id_lists is not None:
+            raise ValueError("pass either query_front or term_id_lists")
+        packed = check_columns(B, w, self.gate_text, self.rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs,
+                               query_front)
         with torch.cuda.device(self.device):
             q_dev = torch.from_numpy(q).to(self.device)
-            staged_groups = self.gate_text.upload(packed) if packed is not None else None    # (ahead of the kernels)
+            if packed is query_front:
+                staged_groups = query_front.gate_staged if packed is not None else None
+            else:
+                staged_groups = self.gate_text.upload(packed) if packed is not None else None    # (ahead of the kernels)
             rows, dense = self.dense_pool(q_dev, pool)
             tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
+            if query_front is not None and self.bm25 is not None:
+                tl = query_front.terms
             bm = self.bm25_at(tl, rows, bm25_mode)
             gate = rerank = best = None
             best_ids = None
@@ -471,7 +501,11 @@ class HybridSearcher:
             if rerank_pairs is not None and rr_k > 0:
                 rr_ce, rr_queries, rerank_host = rerank_pairs
                 rerank = torch.zeros((B, pool), dtype=torch.float32, device=self.device)
-                rerank[:, :rr_k] = self.rerank_text.scores(rr_ce, rows, rr_k, rr_queries)
+                if rr_queries is None:
+                    rr_queries = query_front
+                    rerank[:, :rr_k] = self.rerank_text.scores(rr_ce, rows, rr_k, rr_queries, staged=query_front.rerank_staged)
+                else:
+                    rerank[:, :rr_k] = self.rerank_text.scores(rr_ce, rows, rr_k, rr_queries)
                 if rr_queries.host_queries:
                     rows_h = rows.cpu().numpy() if rows_h is None else rows_h
                     for b in rr_queries.host_queries:
@@ -480,10 +514,14 @@ class HybridSearcher:
             params = self.make_params(w, k_eff, pool, pool, rr_k, bm25_f64=bm25_f64 and self.bm25 is None)
             out_rows, cols, order = self.fuse(params, B, rows, dense, None if params.bm25_f64 else bm, None,
                                               rerank, best, gate)
+            if on_queued is not None:
+                on_queued()
             res = BatchResult(out_rows.cpu().numpy(), cols.cpu().numpy(), order.cpu().numpy(),
                               dense.cpu().numpy(), bm.cpu().numpy(), pool, k_eff)
             if best_ids is not None:
                 res.best_ids, res.best_raw = best_ids.cpu().numpy(), best.cpu().numpy()
+            if query_front is not None:
+                res.needs_host = query_front.needs_host.cpu().numpy()
         return res
 
 
@@ -504,6 +542,11 @@ class SearchEngine:
     "device" builds a token plane of ``meta["agg_text"]`` on the GPU (rerank.RerankText, up to about 1 KB of device memory per
     product; ``rerank_max_bytes`` refuses a larger one), assembles the pairs there (csrc/rr_pairs.hip) and leaves the scores
     on the device.  It needs a ``cross_encoder`` that is this package's `CrossEncoder` with a tokenizer.
+    query_text: "host" (the default) tokenises the queries, looks their BM25 ids up, builds and packs their gate groups and
+    their reranker ids in Python, query by query; "device" stages the batch's bytes once and does all of that on the GPU
+    (querytext.QueryText, csrc/rr_query.hip) for the consumers that are on the device (K2; the gate with gate="device"; the
+    pairs with rerank="device").  The queries the kernels hand back are searched again through the host functions.  The two
+    give bitwise the same frames, snips and dbg.
     """
 
     def __init__(self, meta: pd.DataFrame, embeddings: np.ndarray, bm25_blob: Optional[dict] = None,
@@ -511,7 +554,7 @@ class SearchEngine:
                  flavour: str = "app", dtype: str = "f32", reviews: Optional[Tuple] = None,
                  bm25_build: str = "device", index: Optional[ProductIndex] = None, bm25_ids: Optional[Tuple] = None,
                  gate: str = "host", gate_max_bytes: Optional[int] = None, rerank: str = "host",
-                 rerank_max_bytes: Optional[int] = None):
+                 rerank_max_bytes: Optional[int] = None, query_text: str = "host"):
         """``index``: a ready ProductIndex (embed.build_product_embeddings) to use instead of uploading ``embeddings``
         (then None); it is taken as it is -- ``normalize`` and ``dtype`` describe an upload only.
         ``bm25_ids``: ``(skus, tok, doc_off, vocab)`` instead of ``bm25_blob`` -- the corpus as token ids (numpy arrays or
@@ -524,6 +567,8 @@ class SearchEngine:
             raise ValueError("gate must be 'device' or 'host'")
         if rerank not in ("device", "host"):
             raise ValueError("rerank must be 'device' or 'host'")
+        if query_text not in ("device", "host"):
+            raise ValueError("query_text must be 'device' or 'host'")
         if rerank == "device":
             from .cross_encoder import CrossEncoder
             if not isinstance(cross_encoder, CrossEncoder) or cross_encoder.tokenizer is None:
@@ -587,6 +632,14 @@ class SearchEngine:
                                                 self.index.device, max_bytes=rerank_max_bytes, row_offset=self.index.row_offset)
             rerank_text.check_model(cross_encoder)
         self.searcher = HybridSearcher(self.index, bm25_index, gate_text, rerank_text)
+        self.query_text = query_text
+        self._query_text = None
+        if query_text == "device":
+            from .querytext import QueryText
+            vocab = {} if bm25_index is None else bm25_index.corpus.vocab      # (None: refused with term_ids' message)
+            self._query_text = QueryText(vocab, rerank_tokenizer=cross_encoder.tokenizer if rerank == "device" else None,
+                                         max_length=cross_encoder.max_length if rerank == "device" else 512,
+                                         device=self.index.device)
         # reviews = (frame with sku/text/stars, (n_reviews, dim) embeddings): reviews_with_embeddings.parquet
         self.reviews = None
         if reviews is not None:
@@ -755,18 +808,26 @@ class SearchEngine:
             qv = np.asarray(qvecs, dtype=np.float32)
         if qv.shape[0] != len(queries):
             raise ValueError(f"{qv.shape[0]} query vectors for {len(queries)} queries")
-        toks = [text.tokenize_query(q) for q in queries]
-        term_ids = None
-        if self.searcher.bm25 is not None:
-            term_ids = [self.searcher.bm25.term_ids(t) for t in toks]
-        groups = [text.build_gate_groups(q) for q in queries]
         w = FusionWeights(w_dense, w_bm25, w_rerank, w_prior, w_best, prior_C, min_reviews,
                           gate_penalty, APP_TRUST_SAT, app)
         floor = APP_POOL_FLOOR if app else CLI_POOL_FLOOR
-        res = self.searcher.search_batch(
-            qv, term_ids, k, rerank_k, w, pool_floor=floor,
-            reviews=self.reviews if use_snips else None, max_scan=max_scan,
-            bm25_f64=not app, **self._rerank_args(queries, rerank_k), **self._gate_args(groups, gate_penalty))
+        common = dict(pool_floor=floor, reviews=self.reviews if use_snips else None, max_scan=max_scan, bm25_f64=not app)
+
+        def host_text(qs):
+            return [text.tokenize_query(q) for q in qs], [text.build_gate_groups(q) for q in qs]
+
+        def search_host(qs, vecs, toks, groups):
+            term_ids = None
+            if self.searcher.bm25 is not None:
+                term_ids = [self.searcher.bm25.term_ids(t) for t in toks]
+            return self.searcher.search_batch(vecs, term_ids, k, rerank_k, w, **common, **self._rerank_args(qs, rerank_k),
+                                              **self._gate_args(groups, gate_penalty))
+
+        if self._query_text is None:
+            toks, groups = host_text(queries)
+            res = search_host(queries, qv, toks, groups)
+        else:
+            res, toks, groups = self._search_device_text(queries, qv, k, rerank_k, w, gate_penalty, common, host_text, search_host)
         out = []
         for b in range(len(queries)):
             frame = self._frame(res, b, rerank_k > 0)
@@ -778,6 +839,40 @@ class SearchEngine:
                    "groups": [list(g) for g in groups[b]], "pool": max(k, rerank_k, floor)}
             out.append((frame, snips, dbg))
         return out
+
+    def _search_device_text(self, queries, qv, k, rerank_k, w, gate_penalty, common, host_text, search_host):
+        """One batch with query_text="device": the bytes are staged once and the front end is queued ahead of K1; the
+        consumers that are on the device read its buffers, a host gate / host reranker keeps its host function.  The dbg
+        lists (tokens, groups) are built while the kernels run.  The queries the front end flags are searched again through
+        the host functions, in one batch of their own, and their results put in place."""
+        qs = [str(q) for q in queries]
+        front = self._query_text.front(qs, gate_penalty)
+        made = {}
+        args = {}
+        if self.searcher.gate_text is None:                    # the host gate reads the groups: they are built first
+            made["toks"], made["groups"] = host_text(queries)
+            args.update(self._gate_args(made["groups"], gate_penalty))
+        if rerank_k > 0:
+            if self.searcher.rerank_text is not None:
+                args["rerank_pairs"] = (self.cross_encoder, None,
+                                        lambda b, rows: self._rerank_fn(queries[b:b + 1])(rows[None, :])[0])
+            else:
+                args.update(self._rerank_args(queries, rerank_k))
+
+        def on_queued():
+            if not made:
+                made["toks"], made["groups"] = host_text(queries)
+
+        res = self.searcher.search_batch(qv, None, k, rerank_k, w, **common, query_front=front, on_queued=on_queued, **args)
+        self._query_text.check()
+        flagged = np.flatnonzero(res.needs_host)
+        if len(flagged):
+            sub = search_host([queries[i] for i in flagged], qv[flagged], [made["toks"][i] for i in flagged],
+                              [made["groups"][i] for i in flagged])
+            for name in ("pool_rows", "columns", "order", "dense_raw", "bm25_raw", "best_ids", "best_raw"):
+                if getattr(res, name) is not None:
+                    getattr(res, name)[flagged] = getattr(sub, name)
+        return res, made["toks"], made["groups"]
 
     def _frame(self, res: BatchResult, b: int, rerank_active: bool = False) -> pd.DataFrame:
         top = res.order[b].astype(np.int64)

@@ -1,0 +1,364 @@
+"""The query text of a batch on the GPU (csrc/rr_query.hip), and the kernels' model on the CPU.
+
+Stands in for what `SearchEngine.run_search_batch` does per query in Python before the kernels run: `text.tokenize_query` +
+`BM25Index.term_ids`, `text.build_gate_groups` + `gate.pack_groups`, `tokenizer.text_ids` + `rerank.pack_queries`.
+
+`QueryText` is the per-index object: the BM25 vocabulary as an open-addressing table, the stop words and the static gate groups
+of text.py (uploaded once; the kernel source holds no word list) and, with a reranker, the device WordPiece tokenizer of the
+cross-encoder's vocabulary.  `QueryText.front(queries, penalty)` stages the batch's bytes with ONE upload, queues the kernels
+on the current stream and returns a `QueryFront`: device buffers in the layouts `rr_bm25_scores_at_dev`, `rr_gate_factors_dev`
+and `rr_pairs_*_dev` read, and the ``needs_host`` flags, which travel to the host with the batch's answer (nothing is read back
+before it).  A flagged query (FLAG_*) has no ids, no groups and no reranker ids on the device and is served by the host
+functions.  `model_front` states in plain Python, without ``re``, what the kernels compute for one query, as
+doctok.model_tokenize does for the document tokenizer.
+
+The byte rules are doctok.py's (tests/test_doctok_model.py proves them against ``str.lower()`` and ``re``) with the query-time
+stop list, one-byte tokens kept and no cap; the colour groups are substring matches against the gate plane's byte image of
+the query (gate.model_gate_plane), in which an ASCII string occurs exactly when it occurs in ``query.lower()``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+from collections import namedtuple
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib, text
+from .gate import MAX_GROUPS, MAX_TERM_BYTES, MAX_TERMS, QUERY_TERM_BYTES, _utf8, factor_table, model_gate_plane
+
+MAX_QUERY_BYTES = 1024      # rr_query_limits (QueryText checks these against the library): bytes of a query,
+MAX_TOKEN_BYTES = 64        # of a token,
+MAX_STOP_BYTES = 8          # of a stop word the kernels hold
+FLAG_QUERY, FLAG_TOKEN, FLAG_RERANK, FLAG_WP, FLAG_SPAN = 1, 2, 4, 8, 16     # needs_host bits (include/rr_hip.h)
+HASH_BASE = 0x01000193
+
+# alnums and the apostrophe stay, everything else (NUL and every byte >= 0x80 included) is a separator
+_MAP = bytes(c if (48 <= c <= 57 or 97 <= c <= 122 or c == 39) else 32 for c in range(256))
+
+FrontModel = namedtuple("FrontModel", "tokens ids groups terms rerank_ids flag")
+
+
+# ---------------------------------------------------------------------------------- the static tables
+@functools.lru_cache(maxsize=None)
+def static_tables():
+    """text.py's word lists as `rr_query_create` takes them: (stop words, groups, n_colors, keys) -- the groups are the colour
+    groups in COLORS order, then the synonym groups in SYNONYMS order, each a SORTED list of terms; keys = SYNONYMS' keys."""
+    groups = [sorted(g) for g in text.COLORS.values()] + [sorted(g) for g in text.SYNONYMS.values()]
+    return sorted(text.QUERY_STOP_WORDS), groups, len(text.COLORS), list(text.SYNONYMS)
+
+
+def _strings(items: Sequence[str], dtype=np.int32) -> Tuple[np.ndarray, np.ndarray]:
+    blobs = [s.encode("utf-8") for s in items]
+    off = np.zeros(len(blobs) + 1, dtype=dtype)
+    np.cumsum([len(b) for b in blobs], out=off[1:])
+    data = np.frombuffer(b"".join(blobs), dtype=np.uint8).copy() if off[-1] else np.zeros(1, dtype=np.uint8)
+    return data, off
+
+
+def vocab_arrays(vocab: Dict[str, int]) -> Tuple[np.ndarray, np.ndarray]:
+    """(bytes, int64 offsets) of the vocabulary in id order; an id no string has is an empty entry."""
+    n = max(vocab.values()) + 1 if vocab else 0
+    entries = [""] * n
+    for s, i in vocab.items():
+        if i < 0:
+            raise ValueError(f"vocabulary id {i} of {s!r} is negative")
+        entries[i] = s
+    return _strings(entries, np.int64)
+
+
+def model_hash(token: bytes) -> int:
+    h = 0
+    for b in token:
+        h = (h * HASH_BASE + b) & 0xFFFFFFFF
+    return h
+
+
+def model_slot(token: bytes, n_slots: int) -> int:
+    """The slot a token's walk through the table starts at."""
+    h = model_hash(token) ^ ((len(token) * 0x9E3779B1) & 0xFFFFFFFF)
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
+    h ^= h >> 16
+    return h & (n_slots - 1)
+
+
+def build_vocab_table(vocab: Dict[str, int]):
+    """The open-addressing table the device looks tokens up in, built by the library ON THE HOST (rr_query_build_table; no
+    GPU needed): (slots [n_slots][4] int32 = hash, first byte, length, id or -1; vocabulary bytes; entries kept)."""
+    lib = _lib.load()
+    blob, off = vocab_arrays(vocab)
+    n_slots, kept = C.c_int32(), C.c_int32()
+    _lib.check(lib.rr_query_table_slots(len(off) - 1, C.byref(n_slots)), "rr_query_table_slots")
+    slots = np.empty((n_slots.value, 4), dtype=np.int32)
+    _lib.check(lib.rr_query_build_table(_lib.ptr(blob), _lib.ptr(off), len(off) - 1, n_slots.value, _lib.ptr(slots),
+                                        C.byref(kept)), "rr_query_build_table")
+    return slots, blob, kept.value
+
+
+def table_lookup(slots: np.ndarray, blob: np.ndarray, token: bytes) -> int:
+    """The kernel's walk: from the token's slot to the first empty one, the hash compared first, then the bytes."""
+    n_slots, h = len(slots), model_hash(token)
+    s = model_slot(token, n_slots)
+    for _ in range(n_slots):
+        hash_, first, length, id_ = (int(v) for v in slots[s])
+        if id_ < 0:
+            return -1
+        if (hash_ & 0xFFFFFFFF) == h and length == len(token) and blob[first:first + length].tobytes() == token:
+            return id_
+        s = (s + 1) & (n_slots - 1)
+    return -1
+
+
+# ---------------------------------------------------------------------------------- the model
+def model_tokens(image: bytes) -> List[bytes]:
+    """The tokens of a query's image, stop words included: doctok.model_tokenize's walk."""
+    out: List[bytes] = []
+    for chunk in image.translate(_MAP).split():    # maximal pieces of alnums and apostrophes
+        runs = chunk.split(b"'")                   # an empty run = two apostrophes in a row, or one at either end
+        i = 0
+        while i < len(runs):
+            if not runs[i]:
+                i += 1
+            elif i + 1 < len(runs) and runs[i + 1]:  # one apostrophe, then a run: the token takes both
+                out.append(runs[i] + b"'" + runs[i + 1])
+                i += 2
+            else:
+                out.append(runs[i])
+                i += 1
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _model_tables():
+    """static_tables() as bytes: (stop words, groups, n_colors, keys)."""
+    stop, groups, n_colors, keys = static_tables()
+    return (frozenset(s.encode("ascii") for s in stop), [[w.encode("ascii") for w in g] for g in groups], n_colors,
+            [k.encode("ascii") for k in keys])
+
+
+def model_front(query_bytes, vocab: Dict[str, int], *, rerank_tokenizer=None, max_length: int = 512) -> FrontModel:
+    """What rr_query_front_dev / rr_query_strip_dev answer for one query (a str, or its UTF-8 bytes): ``tokens`` (str),
+    ``ids`` (vocabulary ids, -1 = unknown), ``groups`` (each a sorted list of terms), ``terms`` ((group, bytes) in packing
+    order), ``rerank_ids`` (None without a tokenizer) and ``flag`` (FLAG_* bits).  A flagged query has nothing but its flag."""
+    raw = _utf8(query_bytes)
+    stop_b, static, n_colors, key_b = _model_tables()
+    flag = 0
+    toks: List[bytes] = []
+    image = b""
+    if len(raw) > MAX_QUERY_BYTES:
+        flag |= FLAG_QUERY
+    else:
+        image = model_gate_plane(raw, max_chars=len(raw) + 1)          # (no cut: a query is taken whole)
+        every = model_tokens(image)
+        if any(len(t) > MAX_TOKEN_BYTES for t in every):
+            flag |= FLAG_TOKEN
+        toks = [t for t in every if t not in stop_b]
+    rr: Optional[List[int]] = None
+    if rerank_tokenizer is not None:
+        from .wp_unicode import model_tokenize
+        ids, needs_host, _ = model_tokenize(bytes(raw), rerank_tokenizer, int(max_length))
+        if needs_host:
+            flag |= FLAG_WP
+            rr = []
+        else:
+            rr = [int(t) for t in ids[1:-1]]
+            if len(rr) > int(max_length) - 3:
+                flag |= FLAG_RERANK
+    if flag:
+        return FrontModel([], [], [], [], None if rr is None else [], flag)
+    ids_out = [vocab.get(t.decode("ascii"), -1) for t in toks]
+    groups: List[List[bytes]] = []
+    for g in static[:n_colors]:                                        # a substring of the image, not a token
+        if any(w in image for w in g):
+            groups.append(g)
+    for t in toks:
+        if t in key_b:
+            groups.append(static[n_colors + key_b.index(t)])
+        elif len(t) >= text.MIN_KEYWORD_LEN:
+            groups.append([t])
+    unique: List[List[bytes]] = []
+    for g in groups:                                                   # (sorted lists of distinct terms: equal as sets = equal)
+        if g not in unique:
+            unique.append(g)
+    unique = unique[:text.MAX_GATE_GROUPS]
+    terms = [(i, w) for i, g in enumerate(unique) for w in g]
+    return FrontModel([t.decode("ascii") for t in toks], ids_out, [[w.decode("ascii") for w in g] for g in unique], terms, rr,
+                      flag)
+
+
+# ---------------------------------------------------------------------------------- the batch on the device
+class QueryFront:
+    """One batch's query text on the device (QueryText.front).  ``terms``: an engine.StagedTerms (``n_ids`` is an upper
+    bound); ``gate_staged``: ``(buffer, offsets)`` as `GateText.factors(staged=)` takes them; ``rerank_staged``: ``(int32
+    tensor, offset of the ids)`` as `RerankText.pairs(staged=)` takes them, or None; ``needs_host``: int32 (B,) device tensor
+    of FLAG_* bits.  It also stands where a gate.PackedGroups / rerank.PackedQueries is asked only for its sizes:
+    ``n_queries``, ``max_length``, and ``host_queries`` (empty: the flags are not known on the host before the answer)."""
+
+    def __init__(self, n_queries, terms, gate_staged, rerank_staged, needs_host, max_length, keep):
+        self.n_queries, self.terms, self.gate_staged, self.rerank_staged = int(n_queries), terms, gate_staged, rerank_staged
+        self.needs_host, self.max_length, self._keep = needs_host, int(max_length), keep
+        self.host_queries: List[int] = []
+
+    def _i32(self, name: str, count: int):
+        buf, where = self._keep["buf"], self._keep["where"]
+        import torch
+        return buf[where[name]:where[name] + 4 * count].view(torch.int32)
+
+    def host_arrays(self) -> dict:
+        """The device-made arrays on the host, cut to their lengths (tests; waits for the device)."""
+        B = self.n_queries
+        out = {"needs_host": self.needs_host.cpu().numpy(), "ids_off": self._i32("ids_off", B + 1).cpu().numpy(),
+               "q_term": self._i32("q_term", B + 1).cpu().numpy(), "q_groups": self._i32("q_groups", B).cpu().numpy()}
+        out["ids"] = self._i32("ids", int(out["ids_off"][B])).cpu().numpy()
+        T = int(out["q_term"][B])
+        out["term_off"] = self._i32("term_off", T + 1).cpu().numpy()
+        out["term_group"] = self._i32("term_group", T).cpu().numpy()
+        buf, where = self._keep["buf"], self._keep["where"]
+        out["term_bytes"] = buf[where["term_bytes"]:where["term_bytes"] + int(out["term_off"][T])].cpu().numpy()
+        if self.rerank_staged is not None:
+            out["rr_off"] = self._i32("rr_off", B + 1).cpu().numpy()
+            out["rr_ids"] = self._i32("rr_ids", int(out["rr_off"][B])).cpu().numpy()
+        return out
+
+
+class QueryText:
+    """The query front end of one index on one GPU.  ``vocab``: the BM25 vocabulary (token -> id; {} when the index has no
+    BM25 leg); ``rerank_tokenizer``: the cross-encoder's WordPieceTokenizer when the reranker's query ids are wanted too,
+    with the cross-encoder's ``max_length``."""
+
+    def __init__(self, vocab: Optional[Dict[str, int]], *, rerank_tokenizer=None, max_length: int = 512, device: int = 0):
+        import torch
+        if vocab is None:
+            raise ValueError("this corpus was built from integer ids; pass ids directly")
+        if not torch.cuda.is_available():
+            raise _lib.HipLibraryError("no GPU visible: the query front end runs on the device only")
+        lib = _lib.load()
+        lim = [C.c_int32() for _ in range(4)]
+        _lib.check(lib.rr_query_limits(*[C.byref(v) for v in lim]), "rr_query_limits")
+        if tuple(v.value for v in lim) != (MAX_QUERY_BYTES, MAX_TOKEN_BYTES, MAX_GROUPS, MAX_STOP_BYTES) \
+                or MAX_TOKEN_BYTES != MAX_TERM_BYTES or text.MAX_GATE_GROUPS > MAX_GROUPS:
+            raise _lib.HipLibraryError("querytext.py, gate.py and csrc/rr_query.hip disagree on the kernels' limits")
+        self.device = getattr(device, "index", device) or 0
+        self.max_length = int(max_length)
+        stop, groups, n_colors, keys = static_tables()
+        v_bytes, v_off = vocab_arrays(vocab)
+        s_bytes, s_off = _strings(stop)
+        t_bytes, t_off = _strings([w for g in groups for w in g])
+        g_off = np.zeros(len(groups) + 1, dtype=np.int32)
+        np.cumsum([len(g) for g in groups], out=g_off[1:])
+        k_bytes, k_off = _strings(keys)
+        # what a query can need of the gate's arrays: max_groups groups, each a static group or one token
+        self.terms_per_query = text.MAX_GATE_GROUPS * max([len(g) for g in groups] + [1])
+        self.term_bytes_per_query = text.MAX_GATE_GROUPS * max([sum(len(w) for w in g) for g in groups] + [MAX_TOKEN_BYTES])
+        if self.terms_per_query > MAX_TERMS or self.term_bytes_per_query > QUERY_TERM_BYTES:
+            raise ValueError("text.py's gate groups do not fit the gate kernel's limits")
+        h = C.c_void_p()
+        _lib.check(lib.rr_query_create(self.device, _lib.ptr(v_bytes), _lib.ptr(v_off), len(v_off) - 1, _lib.ptr(s_bytes),
+                                       _lib.ptr(s_off), len(stop), _lib.ptr(t_bytes), _lib.ptr(t_off), _lib.ptr(g_off), n_colors,
+                                       len(groups) - n_colors, _lib.ptr(k_bytes), _lib.ptr(k_off), text.MAX_GATE_GROUPS,
+                                       text.MIN_KEYWORD_LEN, C.byref(h)), "rr_query_create")
+        self._h = h
+        self.wp = None
+        if rerank_tokenizer is not None:
+            if self.max_length < 3:
+                raise ValueError(f"max_length {self.max_length} leaves no room for [CLS] [SEP] [SEP]")
+            from .embed import DeviceWordPiece
+            self.wp = DeviceWordPiece(rerank_tokenizer, self.device, unicode=True)
+
+    def front(self, queries: Sequence, penalty=0.5) -> QueryFront:
+        """Queues the front end of ``queries`` (str, or UTF-8 bytes) on the current stream: one pinned buffer with the
+        offsets, the gate's factor table (``penalty``: one, or one per query) and the bytes, ONE copy to the device, the
+        WordPiece kernels (with a reranker), rr_query_front_dev and rr_query_strip_dev.  Nothing is read back."""
+        raws = [_utf8(q) for q in queries]
+        B = len(raws)
+        if B < 1:
+            raise ValueError("no queries")
+        pens = [float(penalty)] * B if np.isscalar(penalty) else [float(p) for p in penalty]
+        if len(pens) != B:
+            raise ValueError(f"{len(pens)} penalties for {B} queries")
+        off = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in raws], out=off[1:])
+        return self.front_bytes(np.frombuffer(b"".join(raws), dtype=np.uint8), off, pens)
+
+    def front_bytes(self, raw: np.ndarray, off: np.ndarray, penalties: Sequence[float]) -> QueryFront:
+        """`front` for bytes and int64 offsets that are already packed (the offsets are the kernel's to check)."""
+        import torch
+        from .engine import StagedTerms
+        B, total = len(off) - 1, int(raw.size)
+        L = self.max_length
+        cap_ids = max((total + B) // 2, 1)
+        cap_terms, cap_tb = B * self.terms_per_query, B * self.term_bytes_per_query
+        cap_rr = max(min(total, B * max(L - 3, 0)), 1) if self.wp is not None else 1
+        where, at = {}, 0
+        for name, nbytes in (("text_off", 8 * (B + 1)), ("factor", 4 * B * (MAX_GROUPS + 1)), ("text", total),
+                             ("counts", 16 * B), ("needs_host", 4 * B), ("ids_off", 4 * (B + 1)), ("ids", 4 * cap_ids),
+                             ("term_off", 4 * (cap_terms + 1)), ("term_group", 4 * cap_terms), ("q_term", 4 * (B + 1)),
+                             ("q_groups", 4 * B), ("term_bytes", cap_tb), ("rr_off", 4 * (B + 1)), ("rr_ids", 4 * cap_rr)):
+            where[name] = at
+            at += (max(nbytes, 1) + 15) // 16 * 16
+            if name == "text":
+                n_in = at
+        dev = torch.device("cuda", self.device)
+        stage = torch.empty(n_in, dtype=torch.uint8, pin_memory=True)
+        host = stage.numpy()
+        host[:8 * (B + 1)] = np.ascontiguousarray(off, dtype=np.int64).view(np.uint8)
+        factor = np.stack([factor_table(p) for p in penalties]) if len(set(penalties)) > 1 else \
+            np.broadcast_to(factor_table(penalties[0]), (B, MAX_GROUPS + 1))
+        host[where["factor"]:where["factor"] + 4 * B * (MAX_GROUPS + 1)] = np.ascontiguousarray(factor, dtype=np.float32).view(np.uint8).reshape(-1)
+        host[where["text"]:where["text"] + total] = raw
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            buf = torch.empty(at, dtype=torch.uint8, device=dev)
+            buf[:n_in].copy_(stage, non_blocking=True)
+            base = buf.data_ptr()
+            p = lambda name: C.c_void_p(base + where[name])
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            wp_out = None
+            if self.wp is not None:
+                d_off = buf[:8 * (B + 1)].view(torch.int64)
+                cap = min(B * L, total + 2 * B)
+                packed, _info, _, cap, _ = self.wp.queue_dev(base + where["text"], total, d_off, L, cap)
+                wp_out = packed
+                wp_cu, wp_needs = C.c_void_p(packed.data_ptr() + 12 * cap), C.c_void_p(packed.data_ptr() + 4 * (3 * cap + B + 1))
+            else:
+                wp_cu = wp_needs = None
+            _lib.check(lib.rr_query_front_dev(self._h, p("text"), total, p("text_off"), B, wp_cu, wp_needs, L, p("counts"),
+                                              p("needs_host"), p("ids"), p("ids_off"), cap_ids, p("term_off"), p("term_group"),
+                                              p("q_term"), p("q_groups"), p("term_bytes"), cap_terms, cap_tb, st),
+                       "rr_query_front_dev")
+            rerank_staged = None
+            if self.wp is not None:
+                _lib.check(lib.rr_query_strip_dev(self._h, C.c_void_p(packed.data_ptr()), wp_cu, cap, B, p("counts"), p("rr_off"),
+                                                  p("rr_ids"), cap_rr, st), "rr_query_strip_dev")
+                rerank_staged = (buf[where["rr_off"]:where["rr_ids"] + 4 * cap_rr].view(torch.int32),
+                                 (where["rr_ids"] - where["rr_off"]) // 4)
+            i32 = lambda name, count: buf[where[name]:where[name] + 4 * count].view(torch.int32)
+            terms = StagedTerms(i32("ids", cap_ids), i32("ids_off", B + 1), None, cap_ids if total else 0)
+        return QueryFront(B, terms, (buf, where), rerank_staged, i32("needs_host", B), L,
+                          {"buf": buf, "where": where, "stage": stage, "wp": wp_out})
+
+    def check(self) -> None:
+        """Raises ValueError when a batch since the last check had offsets that decrease or leave the text, or a store that
+        did not fit its buffer (waits for the device)."""
+        bad = C.c_int32()
+        _lib.check(_lib.load().rr_query_status(self._h, C.byref(bad)), "rr_query_status")
+        if self.wp is not None:
+            self.wp.check()
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.load().rr_query_destroy(self._h)
+            self._h = None
+        if getattr(self, "wp", None) is not None:
+            self.wp.close()
+            self.wp = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -341,7 +341,8 @@ class RerankText:
                                           C.c_void_p(ids.data_ptr() + 8 * n_tokens), st), "rr_pairs_write_dev")
         return tok, typ, pos, cu
 
-    def scores(self, ce, rows, rr_k: int, packed: PackedQueries, first_pair: int = 0, n_pairs: Optional[int] = None):
+    def scores(self, ce, rows, rr_k: int, packed: PackedQueries, first_pair: int = 0, n_pairs: Optional[int] = None,
+               staged=None):
         """The reranker's scores of the first ``rr_k`` candidates of every query: (B, rr_k) float32 on the device, what
         ``ce.predict`` gives for the pairs ``(query, agg_text[:2000])``.  The pairs go through the model in chunks of
         ``n_pairs * max_length <= min(ce.model.max_tokens_per_call, FP32_MAX_TOKENS)`` (a bound that needs no lengths on the
@@ -351,7 +352,8 @@ class RerankText:
         scores of the EMPTY query: the caller overwrites them (HybridSearcher.search_batch does).
         ``first_pair`` / ``n_pairs``: only the range [first_pair, first_pair + n_pairs) of the flattened B x rr_k pair list
         (a rank's share, sharded.split_pairs; it may begin and end inside a query) -> a flat (n_pairs,) tensor.  An empty
-        range launches nothing and returns an empty tensor."""
+        range launches nothing and returns an empty tensor.  ``staged``: the packed queries already on the device, as `pairs`
+        takes them (then ``packed`` is asked for its sizes only)."""
         import torch
         from .cross_encoder import FP32_MAX_TOKENS, OUT_LOGITS
         self.check_model(ce)
@@ -369,7 +371,7 @@ class RerankText:
             return torch.empty(0, dtype=torch.float32, device=rows.device)
         step = max(1, min(int(ce.model.max_tokens_per_call), FP32_MAX_TOKENS) // L)
         with torch.cuda.device(rows.device):
-            staged = self.upload(packed)
+            staged = staged if staged is not None else self.upload(packed)
             out = torch.empty(total, dtype=torch.float32, device=rows.device)
 
             def run():

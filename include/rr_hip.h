@@ -746,7 +746,8 @@ int rr_pairs_status(rr_pairs* h, int32_t* out_bad);
  *   d_needs_host int32 [n_queries], one bit per reason: 1 = the query has more than 1024 bytes, 2 = a token has more than 64
  *               bytes, 4 = more than max_length - 3 reranker ids, 8 = the WordPiece kernel handed it back, 16 = its offsets
  *               decrease or leave the text (also counted by the status call).  A flagged query gets no ids, no groups and
- *               no reranker ids: the caller serves it through the host functions.
+ *               no reranker ids: the caller serves it through the host functions.  (32 is not this call's: the flag call
+ *               below sets it for a query the QUERY ENCODER's WordPiece kernel handed back.)
  * d_wp_cu / d_wp_needs_host (both or neither): cu_seqlens and needs_host of rr_wp_encode_dev over the SAME text and offsets
  * with the cross-encoder's vocabulary and max_length = the cross-encoder's (then a query of max_length - 2 pieces or more
  * shows as such); they decide bits 4 and 8 and the reranker counts.  d_counts int32 [n_queries x 4] (ids, terms, term bytes,
@@ -782,6 +783,35 @@ int rr_query_strip_dev(rr_query* h, const int32_t* d_wp_tok, const int32_t* d_wp
 /* Waits for the device; RR_E_INVALID when a call since the last one met offsets that decrease or leave the text or a store
  * beyond a capacity (*out_bad = how many). */
 int rr_query_status(rr_query* h, int32_t* out_bad);
+
+/* The query VECTORS of a batch: the encoder's CLS rows (rr_ce_forward_dev with RR_CE_OUT_CLS over the WordPiece ids of the
+ * same staged bytes) to the unit vectors K1 reads.  Row q of d_out = d_rows[q] / max(||d_rows[q]||, eps) in float32, every
+ * rounding the one numpy makes in `e / np.maximum(np.linalg.norm(e, axis=1, keepdims=True), eps)` on a C-contiguous float32
+ * array (cross_encoder.QueryEncoder.encode_ids), so the result equals the host's bit for bit (querytext.model_query_vectors
+ * states the same in plain Python; tests/test_query_vectors_model.py proves it against numpy):
+ *   squares      each x * x is rounded to float32 BEFORE it is summed: no FMA forms across the square and the add.  The
+ *                library is built with -ffp-contract=off and the kernel is correct under it; it also carries the pragma;
+ *   sum order    numpy's pairwise sum of the n = dim squares.  n < 8: sequential from 0.  8 <= n <= 128: eight accumulators
+ *                r[j] = a[j]; for i = 8, 16, ... while i < n - n % 8: r[j] += a[i + j]; then
+ *                ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)); then the n % 8 tail, added sequentially.  n > 128: split at
+ *                n2 = n / 2 - (n / 2) % 8, sum(left) + sum(right), recursively.  dim 384 = four pieces of 96;
+ *   sqrt, divide correctly rounded (HIP's default; the library does not turn it off);
+ *   max          numpy's maximum: a NaN norm stays NaN and makes the row NaN (fmaxf would drop it).  eps is the caller's
+ *                float32 (the encoder's: float32(1e-12));
+ *   edges        an Inf norm gives 0 (signed) for finite elements and NaN for infinite ones; a zero row stays zero;
+ *                denormal squares and quotients are kept, as numpy on x86 keeps them.
+ * d_needs_host (may be NULL) int32 [n_queries]: row q is written as ZEROS where d_needs_host[q] != 0, so that K1 runs on a
+ * defined vector; the caller replaces that query's answer.  d_out == d_rows is allowed (a row is read in full before it is
+ * written).  n_queries 0 .. 65535 (0 does nothing), dim 1 .. 8192 (what rr_index_create accepts): outside that, a NULL
+ * d_rows / d_out or a NaN eps is RR_E_INVALID with nothing launched.  A wave per query, one launch, no scratch memory; the
+ * pointers belong to the CURRENT device.  Asynchronous on `stream`. */
+int rr_query_vectors_dev(const float* d_rows, int32_t n_queries, int32_t dim, float eps, const int32_t* d_needs_host,
+                         float* d_out, void* stream);
+/* d_needs_host[q] |= bit where d_src[q] != 0 (both int32 [n_queries], n_queries 0 .. 65535; bit = one bit, 1 .. 2^30).  How
+ * the flags of a SECOND rr_wp_encode_dev over the batch -- the query encoder's vocabulary -- join the front call's: bit
+ * 32 = the query encoder's WordPiece kernel handed the query back (its sequence is the placeholder [CLS] [SEP], its vector
+ * zeros).  Queue it after the front call on the same stream.  Asynchronous on `stream`. */
+int rr_query_flag_dev(const int32_t* d_src, int32_t n_queries, int32_t bit, int32_t* d_needs_host, void* stream);
 
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard

@@ -30,6 +30,10 @@
 // qf_front<true> runs the same walk, sums the counts of the queries in front of it by itself (B is small) and writes.  A
 // flagged query writes nothing but its (empty) offsets.  qf_strip takes [CLS] / [SEP] off what rr_wp_encode_dev made of the
 // same bytes.  Every store is checked against its capacity first.
+//
+// THE VECTORS.  qv_normalize turns the query encoder's CLS rows into the unit vectors K1 reads, with numpy's float32
+// roundings bit for bit (the only floating point of this file; see its own comment below); qv_flag joins the flags of the
+// encoder's WordPiece pass to needs_host.
 #include <vector>
 
 #include "rr_prims.h"
@@ -446,6 +450,132 @@ __global__ __launch_bounds__(QF_THREADS) void qf_strip(const int32_t* __restrict
         rr_off[q] = (int32_t)base;
         if (q == n_queries - 1) rr_off[n_queries] = (int32_t)(base + n);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ the query vectors
+// The encoder's CLS rows to the unit vectors K1 reads, with the roundings of numpy's float32
+//   e / np.maximum(np.linalg.norm(e, axis=1, keepdims=True), eps)
+// bit for bit (querytext.model_query_vectors states them in plain Python; include/rr_hip.h lists them).  A wave per query:
+//   1. lane 0 walks numpy's pairwise split of `dim` terms (a piece of more than 128 is cut at n/2 - (n/2) % 8) and lists the
+//      pieces left to right with their depth: at most 128 pieces, seven splits deep, for dim <= 8192;
+//   2. eight lanes per piece carry its eight accumulators (lane j adds the squares j, j + 8, ... of the piece in order), three
+//      cross-lane adds make ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)) -- float addition commutes, so every lane of the eight holds
+//      that value -- and lane 0 of the eight adds the piece's tail of n % 8 squares.  Eight pieces per pass: dim 384 is four
+//      pieces of 96 on 32 lanes, one pass;
+//   3. lane 0 folds the pieces' sums in the order of the splits (two neighbours of one depth are the halves of one split:
+//      left + right, one level up), takes the square root and numpy's maximum with eps; every lane divides its elements.
+// No FMA may form between a square and the addition that takes it: the build passes -ffp-contract=off, and the pragma below
+// holds the kernel to it whatever the flags say.  sqrtf and the quotient are HIP's correctly rounded defaults; float32
+// denormals are kept (the default for gfx9 compute kernels).  The row is read in full before anything is written, so it may
+// be normalised in place.
+#define QV_BLOCK 128                               // numpy's PW_BLOCKSIZE
+#define QV_MAX_DIM 8192                            // rr_index_create's widest row
+#define QV_MAX_LEAVES 128                          // a piece of a split has at least 64 terms
+#define QV_MAX_DEPTH 16                            // (seven splits for dim <= 8192)
+
+__global__ __launch_bounds__(QF_THREADS) void qv_normalize(const float* rows, int32_t dim, float eps, const int32_t* needs_host,
+                                                           float* out) {
+#pragma clang fp contract(off)
+    __shared__ int32_t leaf_first[QV_MAX_LEAVES + 1];
+    __shared__ int32_t leaf_depth[QV_MAX_LEAVES];
+    __shared__ float leaf_sum[QV_MAX_LEAVES];
+    __shared__ int32_t st_n[QV_MAX_DEPTH], st_d[QV_MAX_DEPTH];
+    __shared__ float st_s[QV_MAX_DEPTH];
+    __shared__ int32_t n_leaves;
+    __shared__ float denom;
+    const int lane = threadIdx.x, q = blockIdx.x;
+    const float* row = rows + (int64_t)q * dim;
+    float* dst = out + (int64_t)q * dim;
+    if (needs_host && needs_host[q] != 0) {        // (the whole wave: K1 runs on a defined vector, the caller replaces the answer)
+        for (int i = lane; i < dim; i += QF_THREADS) dst[i] = 0.f;
+        return;
+    }
+    if (lane == 0) {
+        int sp = 0, nl = 0, first = 0, m = dim, d = 0;
+        for (;;) {
+            while (m > QV_BLOCK) {                 // the right half waits on the stack
+                int n2 = m / 2;
+                n2 -= n2 % 8;
+                ++d;
+                st_n[sp] = m - n2; st_d[sp] = d; ++sp;
+                m = n2;
+            }
+            leaf_first[nl] = first; leaf_depth[nl] = d; ++nl;
+            first += m;
+            if (sp == 0) break;
+            --sp;
+            m = st_n[sp]; d = st_d[sp];
+        }
+        leaf_first[nl] = first;
+        n_leaves = nl;
+    }
+    __syncthreads();
+    const int nl = n_leaves, j = lane & 7;
+    for (int l = lane >> 3; l < nl; l += QF_THREADS / 8) {
+        const int first = leaf_first[l], m = leaf_first[l + 1] - first;
+        const float* a = row + first;
+        float r = 0.f, x;
+        if (m < 8) {                               // (dim < 8 only: one piece, summed in order from 0)
+            if (j == 0)
+                for (int i = 0; i < m; ++i) { x = a[i]; x = x * x; r = r + x; }
+        } else {
+            const int body = m - (m & 7);
+            x = a[j]; r = x * x;
+            for (int i = 8; i < body; i += 8) { x = a[i + j]; x = x * x; r = r + x; }
+            r = r + __shfl_xor(r, 1);
+            r = r + __shfl_xor(r, 2);
+            r = r + __shfl_xor(r, 4);
+            if (j == 0)
+                for (int i = body; i < m; ++i) { x = a[i]; x = x * x; r = r + x; }
+        }
+        if (j == 0) leaf_sum[l] = r;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        int sp = 0;
+        for (int l = 0; l < nl; ++l) {
+            float s = leaf_sum[l];
+            int d = leaf_depth[l];
+            while (sp > 0 && st_d[sp - 1] == d) { --sp; s = st_s[sp] + s; --d; }
+            st_s[sp] = s; st_d[sp] = d; ++sp;
+        }
+        const float norm = sqrtf(st_s[0]);
+        denom = (norm > eps || norm != norm) ? norm : eps;       // numpy's maximum: a NaN norm stays (fmaxf would drop it)
+    }
+    __syncthreads();
+    const float den = denom;
+    for (int i = lane; i < dim; i += QF_THREADS) dst[i] = row[i] / den;
+}
+
+extern "C" int rr_query_vectors_dev(const float* d_rows, int32_t n_queries, int32_t dim, float eps, const int32_t* d_needs_host,
+                                    float* d_out, void* stream) {
+    RR_REQUIRE(n_queries >= 0 && n_queries <= 65535, "rr_query_vectors_dev: %d queries outside [0, 65535]", n_queries);
+    RR_REQUIRE(dim >= 1 && dim <= QV_MAX_DIM, "rr_query_vectors_dev: dim %d outside [1, %d]", dim, QV_MAX_DIM);
+    RR_REQUIRE(d_rows && d_out, "rr_query_vectors_dev: NULL argument");
+    RR_REQUIRE(eps == eps, "rr_query_vectors_dev: eps is NaN");
+    if (n_queries == 0) return RR_OK;
+    hipLaunchKernelGGL(qv_normalize, dim3((unsigned)n_queries), dim3(QF_THREADS), 0, (hipStream_t)stream, d_rows, dim, eps,
+                       d_needs_host, d_out);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+// needs_host[q] |= bit where src[q] != 0: the flags of the query encoder's WordPiece pass join the front's.
+__global__ __launch_bounds__(QF_THREADS) void qv_flag(const int32_t* __restrict__ src, int32_t n, int32_t bit,
+                                                      int32_t* __restrict__ needs_host) {
+    const int q = blockIdx.x * QF_THREADS + threadIdx.x;
+    if (q < n && src[q] != 0) needs_host[q] |= bit;
+}
+
+extern "C" int rr_query_flag_dev(const int32_t* d_src, int32_t n_queries, int32_t bit, int32_t* d_needs_host, void* stream) {
+    RR_REQUIRE(n_queries >= 0 && n_queries <= 65535, "rr_query_flag_dev: %d queries outside [0, 65535]", n_queries);
+    RR_REQUIRE(d_src && d_needs_host, "rr_query_flag_dev: NULL argument");
+    RR_REQUIRE(bit >= 1 && bit <= (1 << 30) && (bit & (bit - 1)) == 0, "rr_query_flag_dev: %d is not one bit of 1 .. 2^30", bit);
+    if (n_queries == 0) return RR_OK;
+    hipLaunchKernelGGL(qv_flag, dim3((unsigned)((n_queries + QF_THREADS - 1) / QF_THREADS)), dim3(QF_THREADS), 0,
+                       (hipStream_t)stream, d_src, n_queries, bit, d_needs_host);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI

@@ -426,7 +426,9 @@ class HybridSearcher:
                      gate_host: Optional[Callable[[int, np.ndarray], np.ndarray]] = None,
                      rerank_pairs: Optional[Tuple] = None, query_front=None,
                      on_queued: Optional[Callable[[], None]] = None) -> BatchResult:
-        """qvecs (B, dim) float32; term_id_lists: per-query BM25 token ids (None = no BM25).
+        """qvecs (B, dim) float32: a numpy array (uploaded here), a float32 torch tensor on the searcher's device (read where it
+        is), or None with a ``query_front`` that carries ``qvecs`` (QueryText with an encoder): K1 and the best-review pick
+        then read that tensor.  term_id_lists: per-query BM25 token ids (None = no BM25).
         gate_fn / rerank_fn map the (B, pool) pool rows to (B, pool) float32 gate factors /
         (B, rr_k) raw reranker scores; they run on the host between K2 and K3.
         ``gate_groups`` (instead of gate_fn): per query its gate groups (text.build_gate_groups); they are matched against
@@ -449,10 +451,21 @@ class HybridSearcher:
         ``bm25_f64``: the CLI flavour without a BM25 artefact (float64 zeros column, app/test.py:252)."""
         torch = _torch()
         w = weights or FusionWeights()
-        q = np.ascontiguousarray(qvecs, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.index.dim:
-            raise ValueError(f"qvecs must be (B, {self.index.dim}); got {q.shape}")
-        B = q.shape[0]
+        q = q_dev = None
+        if qvecs is None:
+            q_dev = getattr(query_front, "qvecs", None)
+            if q_dev is None:
+                raise ValueError("qvecs=None needs a query_front that carries the query vectors (QueryText with an encoder)")
+        elif isinstance(qvecs, torch.Tensor):
+            if qvecs.device != self.device or qvecs.dtype != torch.float32:
+                raise ValueError(f"a tensor as qvecs must be float32 on {self.device}; got {qvecs.dtype} on {qvecs.device}")
+            q_dev = qvecs.contiguous()
+        else:
+            q = np.ascontiguousarray(qvecs, dtype=np.float32)
+        shape = tuple(q.shape if q is not None else q_dev.shape)
+        if len(shape) != 2 or shape[1] != self.index.dim:
+            raise ValueError(f"qvecs must be (B, {self.index.dim}); got {shape}")
+        B = shape[0]
         if k < 1:
             raise ValueError("k must be >= 1")
         pool = min(max(k, rerank_k, pool_floor), self.index.n_rows)
@@ -465,7 +478,8 @@ class HybridSearcher:
         packed = check_columns(B, w, self.gate_text, self.rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs,
                                query_front)
         with torch.cuda.device(self.device):
-            q_dev = torch.from_numpy(q).to(self.device)
+            if q_dev is None:
+                q_dev = torch.from_numpy(q).to(self.device)
             if packed is query_front:
                 staged_groups = query_front.gate_staged if packed is not None else None
             else:
@@ -547,6 +561,11 @@ class SearchEngine:
     (querytext.QueryText, csrc/rr_query.hip) for the consumers that are on the device (K2; the gate with gate="device"; the
     pairs with rerank="device").  The queries the kernels hand back are searched again through the host functions.  The two
     give bitwise the same frames, snips and dbg.
+    query_vectors: "host" (the default) encodes the queries with ``encoder.encode`` (Python WordPiece per query, ids up, CLS
+    rows down, numpy's l2 normalisation, vectors up again); "device" makes them in the query front from the staged bytes
+    (device WordPiece of the encoder's vocabulary, the forward, rr_query_vectors_dev) and K1 reads them where they are.  It
+    needs query_text="device" and an ``encoder`` that is this package's `QueryEncoder` with a tokenizer.  The queries the
+    front hands back are encoded with ``encoder.encode``, those only.  The two give bitwise the same frames, snips and dbg.
     """
 
     def __init__(self, meta: pd.DataFrame, embeddings: np.ndarray, bm25_blob: Optional[dict] = None,
@@ -554,7 +573,7 @@ class SearchEngine:
                  flavour: str = "app", dtype: str = "f32", reviews: Optional[Tuple] = None,
                  bm25_build: str = "device", index: Optional[ProductIndex] = None, bm25_ids: Optional[Tuple] = None,
                  gate: str = "host", gate_max_bytes: Optional[int] = None, rerank: str = "host",
-                 rerank_max_bytes: Optional[int] = None, query_text: str = "host"):
+                 rerank_max_bytes: Optional[int] = None, query_text: str = "host", query_vectors: str = "host"):
         """``index``: a ready ProductIndex (embed.build_product_embeddings) to use instead of uploading ``embeddings``
         (then None); it is taken as it is -- ``normalize`` and ``dtype`` describe an upload only.
         ``bm25_ids``: ``(skus, tok, doc_off, vocab)`` instead of ``bm25_blob`` -- the corpus as token ids (numpy arrays or
@@ -574,6 +593,16 @@ class SearchEngine:
             if not isinstance(cross_encoder, CrossEncoder) or cross_encoder.tokenizer is None:
                 raise ValueError("rerank=\"device\" needs a cross_encoder that is this package's CrossEncoder with a tokenizer "
                                  "(its ids are what the token plane holds); any other object is served by rerank=\"host\"")
+        if query_vectors not in ("device", "host"):
+            raise ValueError("query_vectors must be 'device' or 'host'")
+        if query_vectors == "device":
+            from .cross_encoder import QueryEncoder
+            if query_text != "device":
+                raise ValueError("query_vectors=\"device\" needs query_text=\"device\" (the vectors are made from the bytes the "
+                                 "query front stages); with query_text=\"host\" the queries are encoded by query_vectors=\"host\"")
+            if not isinstance(encoder, QueryEncoder) or encoder.tokenizer is None:
+                raise ValueError("query_vectors=\"device\" needs an encoder that is this package's QueryEncoder with a tokenizer "
+                                 "(its ids are what the forward reads); any other object is served by query_vectors=\"host\"")
         if (index is None) == (embeddings is None):
             raise ValueError("pass either an embedding matrix or a ready index")
         n_emb = embeddings.shape[0] if index is None else index.n_rows
@@ -639,7 +668,8 @@ class SearchEngine:
             vocab = {} if bm25_index is None else bm25_index.corpus.vocab      # (None: refused with term_ids' message)
             self._query_text = QueryText(vocab, rerank_tokenizer=cross_encoder.tokenizer if rerank == "device" else None,
                                          max_length=cross_encoder.max_length if rerank == "device" else 512,
-                                         device=self.index.device)
+                                         device=self.index.device, encoder=encoder if query_vectors == "device" else None)
+        self.query_vectors = query_vectors
         # reviews = (frame with sku/text/stars, (n_reviews, dim) embeddings): reviews_with_embeddings.parquet
         self.reviews = None
         if reviews is not None:
@@ -793,7 +823,8 @@ class SearchEngine:
                          gate_penalty: float = 0.5, *, qvecs: Optional[np.ndarray] = None
                          ) -> List[Tuple[pd.DataFrame, Dict, Dict]]:
         """`run_search` for a batch of queries with the same parameters: per query the triple `run_search` returns.
-        The queries are encoded in ONE encoder call (unless ``qvecs`` (B, dim) is given), searched in one `search_batch`
+        The queries are encoded in ONE encoder call (unless ``qvecs`` (B, dim) is given; with query_vectors="device" in the
+        query front on the GPU, and nothing is encoded on the host but the queries the front hands back), searched in one `search_batch`
         -- with gate="device" the gate terms of all of them are matched in one kernel launch -- and the reranker pairs of
         all of them go through one `predict` (with rerank="device": through the pair kernels and the packed forward)."""
         app = self.flavour == "app"
@@ -803,10 +834,12 @@ class SearchEngine:
         if qvecs is None:
             if self.encoder is None:
                 raise ValueError("no query encoder was given; pass qvecs")
-            qv = np.asarray(self.encoder.encode(queries, normalize_embeddings=True), dtype=np.float32)
+            # query_vectors="device": nothing is encoded here -- the query front makes the vectors (qv stays None)
+            qv = None if self.query_vectors == "device" else \
+                np.asarray(self.encoder.encode(queries, normalize_embeddings=True), dtype=np.float32)
         else:
             qv = np.asarray(qvecs, dtype=np.float32)
-        if qv.shape[0] != len(queries):
+        if qv is not None and qv.shape[0] != len(queries):
             raise ValueError(f"{qv.shape[0]} query vectors for {len(queries)} queries")
         w = FusionWeights(w_dense, w_bm25, w_rerank, w_prior, w_best, prior_C, min_reviews,
                           gate_penalty, APP_TRUST_SAT, app)
@@ -846,7 +879,7 @@ class SearchEngine:
         lists (tokens, groups) are built while the kernels run.  The queries the front end flags are searched again through
         the host functions, in one batch of their own, and their results put in place."""
         qs = [str(q) for q in queries]
-        front = self._query_text.front(qs, gate_penalty)
+        front = self._query_text.front(qs, gate_penalty, vectors=qv is None)
         made = {}
         args = {}
         if self.searcher.gate_text is None:                    # the host gate reads the groups: they are built first
@@ -865,9 +898,16 @@ class SearchEngine:
 
         res = self.searcher.search_batch(qv, None, k, rerank_k, w, **common, query_front=front, on_queued=on_queued, **args)
         self._query_text.check()
+        if qv is None and self._query_text.redo_vectors(front):
+            # the forward left fp16's range (NaN vectors went into K1): the vectors were made again on the wide-range
+            # kernels, as the host path's forward_ids does, and the batch is searched again with them
+            res = self.searcher.search_batch(None, None, k, rerank_k, w, **common, query_front=front, **args)
         flagged = np.flatnonzero(res.needs_host)
         if len(flagged):
-            sub = search_host([queries[i] for i in flagged], qv[flagged], [made["toks"][i] for i in flagged],
+            # (query_vectors="device": the host encoder for the queries the front handed back, those only)
+            sub_qv = qv[flagged] if qv is not None else \
+                np.asarray(self.encoder.encode([qs[i] for i in flagged], normalize_embeddings=True), dtype=np.float32)
+            sub = search_host([queries[i] for i in flagged], sub_qv, [made["toks"][i] for i in flagged],
                               [made["groups"][i] for i in flagged])
             for name in ("pool_rows", "columns", "order", "dense_raw", "bm25_raw", "best_ids", "best_raw"):
                 if getattr(res, name) is not None:

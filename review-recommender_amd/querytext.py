@@ -12,6 +12,11 @@ before it).  A flagged query (FLAG_*) has no ids, no groups and no reranker ids 
 functions.  `model_front` states in plain Python, without ``re``, what the kernels compute for one query, as
 doctok.model_tokenize does for the document tokenizer.
 
+With a `QueryEncoder` the front also makes the query VECTORS K1 reads (`QueryFront.qvecs`): the device WordPiece tokenizer
+of the encoder's vocabulary over the same staged bytes, the forward with CLS output and `rr_query_vectors_dev`, which
+normalises the rows with numpy's float32 roundings, bit for bit.  `model_query_vectors` states that kernel in plain Python,
+the pairwise order of the additions written out.
+
 The byte rules are doctok.py's (tests/test_doctok_model.py proves them against ``str.lower()`` and ``re``) with the query-time
 stop list, one-byte tokens kept and no cap; the colour groups are substring matches against the gate plane's byte image of
 the query (gate.model_gate_plane), in which an ASCII string occurs exactly when it occurs in ``query.lower()``.
@@ -32,6 +37,7 @@ MAX_QUERY_BYTES = 1024      # rr_query_limits (QueryText checks these against th
 MAX_TOKEN_BYTES = 64        # of a token,
 MAX_STOP_BYTES = 8          # of a stop word the kernels hold
 FLAG_QUERY, FLAG_TOKEN, FLAG_RERANK, FLAG_WP, FLAG_SPAN = 1, 2, 4, 8, 16     # needs_host bits (include/rr_hip.h)
+FLAG_ENCODER = 32           # needs_host bit: the QUERY ENCODER's WordPiece kernel handed the query back (rr_query_flag_dev)
 HASH_BASE = 0x01000193
 
 # alnums and the apostrophe stay, everything else (NUL and every byte >= 0x80 included) is a separator
@@ -190,18 +196,97 @@ def model_front(query_bytes, vocab: Dict[str, int], *, rerank_tokenizer=None, ma
                       flag)
 
 
+# ---------------------------------------------------------------------------------- the model of the query vectors
+PAIRWISE_BLOCK = 128        # numpy's pairwise sum: a piece of at most this many terms is summed on eight accumulators
+VECTOR_EPS = 1e-12          # QueryEncoder.encode_ids: e / maximum(norm, 1e-12)
+
+
+def model_pairwise_leaves(n: int) -> List[Tuple[int, int, int]]:
+    """The pieces numpy's pairwise sum cuts ``n`` terms into, left to right: (first term, terms, depth).  A piece of more
+    than PAIRWISE_BLOCK terms is split at ``n2 = n // 2 - (n // 2) % 8``; two neighbours of one depth are the halves of one
+    split (the tree is full), so the list states the whole order of the additions."""
+    out: List[Tuple[int, int, int]] = []
+    todo = [(0, int(n), 0)]
+    while todo:
+        first, m, depth = todo.pop()
+        while m > PAIRWISE_BLOCK:
+            n2 = m // 2
+            n2 -= n2 % 8
+            todo.append((first + n2, m - n2, depth + 1))
+            m, depth = n2, depth + 1
+        out.append((first, m, depth))
+    return out
+
+
+def _model_leaf_sum(a: Sequence[np.float32]) -> np.float32:
+    n = len(a)
+    if n < 8:
+        res = np.float32(0.0)
+        for v in a:
+            res = res + v
+        return res
+    r = list(a[:8])
+    body = n - n % 8
+    for i in range(8, body, 8):
+        for j in range(8):
+            r[j] = r[j] + a[i + j]
+    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+    for v in a[body:]:
+        res = res + v
+    return res
+
+
+def model_pairwise_sum(a: Sequence[np.float32]) -> np.float32:
+    """``np.add.reduce`` of float32 terms that lie contiguous in memory, one float32 rounding per addition: the leaves of
+    `model_pairwise_leaves`, folded in the order of the splits (left + right)."""
+    stack: List[Tuple[np.float32, int]] = []
+    for first, m, depth in model_pairwise_leaves(len(a)):
+        s = _model_leaf_sum(a[first:first + m])
+        while stack and stack[-1][1] == depth:             # the left half of the same split is waiting
+            left, _ = stack.pop()
+            s, depth = left + s, depth - 1
+        stack.append((s, depth))
+    return stack[0][0]
+
+
+def model_query_vectors(rows, eps: float = VECTOR_EPS) -> np.ndarray:
+    """What rr_query_vectors_dev answers: row q = rows[q] / maximum(norm(rows[q]), float32(eps)), every operation rounded to
+    float32 once -- ``(e / np.maximum(np.linalg.norm(e, axis=1, keepdims=True), eps)).astype(np.float32)`` bit for bit
+    (tests/test_query_vectors_model.py, every width class of the split).  Each square is rounded before it is summed, the
+    sum runs in numpy's pairwise order, the square root and the quotients are correctly rounded, and the maximum keeps a NaN
+    norm (numpy's ``maximum``, not C's fmaxf)."""
+    e = np.ascontiguousarray(rows, dtype=np.float32)
+    if e.ndim != 2 or e.shape[1] < 1:
+        raise ValueError(f"rows must be (n, dim >= 1); got {e.shape}")
+    out = np.empty_like(e)
+    eps32 = np.float32(eps)
+    with np.errstate(all="ignore"):
+        for q in range(e.shape[0]):
+            row = [np.float32(v) for v in e[q]]
+            norm = np.sqrt(model_pairwise_sum([v * v for v in row]))
+            d = norm if (norm != norm or norm > eps32) else eps32
+            for i, v in enumerate(row):
+                out[q, i] = v / d
+    return out
+
+
 # ---------------------------------------------------------------------------------- the batch on the device
 class QueryFront:
     """One batch's query text on the device (QueryText.front).  ``terms``: an engine.StagedTerms (``n_ids`` is an upper
     bound); ``gate_staged``: ``(buffer, offsets)`` as `GateText.factors(staged=)` takes them; ``rerank_staged``: ``(int32
     tensor, offset of the ids)`` as `RerankText.pairs(staged=)` takes them, or None; ``needs_host``: int32 (B,) device tensor
     of FLAG_* bits.  It also stands where a gate.PackedGroups / rerank.PackedQueries is asked only for its sizes:
-    ``n_queries``, ``max_length``, and ``host_queries`` (empty: the flags are not known on the host before the answer)."""
+    ``n_queries``, ``max_length``, and ``host_queries`` (empty: the flags are not known on the host before the answer).
+    ``qvecs``: with a query encoder, the (B, dim) float32 device tensor of the queries' unit vectors (zeros where a query is
+    flagged), which `HybridSearcher.search_batch(None, ..., query_front=)` hands to K1."""
 
-    def __init__(self, n_queries, terms, gate_staged, rerank_staged, needs_host, max_length, keep):
+    def __init__(self, n_queries, terms, gate_staged, rerank_staged, needs_host, max_length, keep, qvecs=None):
         self.n_queries, self.terms, self.gate_staged, self.rerank_staged = int(n_queries), terms, gate_staged, rerank_staged
         self.needs_host, self.max_length, self._keep = needs_host, int(max_length), keep
         self.host_queries: List[int] = []
+        # (B, dim) float32 device tensor: the queries' unit vectors as K1 reads them (QueryText with an encoder), else None;
+        # zeros in the rows of flagged queries
+        self.qvecs = qvecs
 
     def _i32(self, name: str, count: int):
         buf, where = self._keep["buf"], self._keep["where"]
@@ -228,9 +313,15 @@ class QueryFront:
 class QueryText:
     """The query front end of one index on one GPU.  ``vocab``: the BM25 vocabulary (token -> id; {} when the index has no
     BM25 leg); ``rerank_tokenizer``: the cross-encoder's WordPieceTokenizer when the reranker's query ids are wanted too,
-    with the cross-encoder's ``max_length``."""
+    with the cross-encoder's ``max_length``.  ``encoder``: a cross_encoder.QueryEncoder with a (lower-casing) tokenizer, on
+    this device, when the query VECTORS are wanted too: every front then also tokenises the staged bytes with the encoder's
+    vocabulary (truncated to ``encoder.max_length`` as ``encode_pair(s, None, max_length)`` truncates), runs the forward and
+    normalises the CLS rows as numpy does (rr_query_vectors_dev) into ``QueryFront.qvecs`` -- bit for bit the rows of
+    ``encoder.encode(queries, normalize_embeddings=True)``.  A query the encoder's tokenizer kernel hands back carries
+    FLAG_ENCODER; its sequence is the placeholder [CLS] [SEP].  The row of every flagged query is zeros."""
 
-    def __init__(self, vocab: Optional[Dict[str, int]], *, rerank_tokenizer=None, max_length: int = 512, device: int = 0):
+    def __init__(self, vocab: Optional[Dict[str, int]], *, rerank_tokenizer=None, max_length: int = 512, device: int = 0,
+                 encoder=None):
         import torch
         if vocab is None:
             raise ValueError("this corpus was built from integer ids; pass ids directly")
@@ -268,11 +359,31 @@ class QueryText:
                 raise ValueError(f"max_length {self.max_length} leaves no room for [CLS] [SEP] [SEP]")
             from .embed import DeviceWordPiece
             self.wp = DeviceWordPiece(rerank_tokenizer, self.device, unicode=True)
+        self.encoder, self.enc_wp = None, None
+        if encoder is not None:
+            from .cross_encoder import QueryEncoder
+            from .embed import DeviceWordPiece
+            if not isinstance(encoder, QueryEncoder) or encoder.tokenizer is None:
+                raise ValueError("the query vectors need this package's QueryEncoder with a tokenizer")
+            if encoder.model.device != self.device:
+                raise ValueError(f"the encoder is on device {encoder.model.device}, the query front on {self.device}")
+            if encoder.max_length < 2:
+                raise ValueError(f"encoder.max_length {encoder.max_length} leaves no room for [CLS] [SEP]")
+            if max(encoder.tokenizer.vocab.values()) >= encoder.model.vocab:
+                raise ValueError("the tokenizer's vocabulary has ids beyond the encoder's embedding table")
+            self.enc_wp = DeviceWordPiece(encoder.tokenizer, self.device, unicode=True)
+            self.encoder = encoder
 
-    def front(self, queries: Sequence, penalty=0.5) -> QueryFront:
+    def front(self, queries: Sequence, penalty=0.5, vectors: bool = True) -> QueryFront:
         """Queues the front end of ``queries`` (str, or UTF-8 bytes) on the current stream: one pinned buffer with the
         offsets, the gate's factor table (``penalty``: one, or one per query) and the bytes, ONE copy to the device, the
-        WordPiece kernels (with a reranker), rr_query_front_dev and rr_query_strip_dev.  Nothing is read back."""
+        WordPiece kernels (with a reranker), rr_query_front_dev and rr_query_strip_dev.  Nothing is read back.
+
+        With an encoder (and ``vectors``) the query vectors are queued as well: the encoder's WordPiece kernels FIRST, so that
+        the two host integers the forward's launch needs -- the token count and the longest sequence -- travel back while
+        the kernels above run; they are waited for once (the only wait), then come the forward, rr_query_flag_dev and
+        rr_query_vectors_dev.  The fp32-mode forward writes NaN rows when an activation leaves fp16's range: ask
+        `redo_vectors(front)` once the batch has been waited for."""
         raws = [_utf8(q) for q in queries]
         B = len(raws)
         if B < 1:
@@ -282,9 +393,9 @@ class QueryText:
             raise ValueError(f"{len(pens)} penalties for {B} queries")
         off = np.zeros(B + 1, dtype=np.int64)
         np.cumsum([len(r) for r in raws], out=off[1:])
-        return self.front_bytes(np.frombuffer(b"".join(raws), dtype=np.uint8), off, pens)
+        return self.front_bytes(np.frombuffer(b"".join(raws), dtype=np.uint8), off, pens, vectors)
 
-    def front_bytes(self, raw: np.ndarray, off: np.ndarray, penalties: Sequence[float]) -> QueryFront:
+    def front_bytes(self, raw: np.ndarray, off: np.ndarray, penalties: Sequence[float], vectors: bool = True) -> QueryFront:
         """`front` for bytes and int64 offsets that are already packed (the offsets are the kernel's to check)."""
         import torch
         from .engine import StagedTerms
@@ -317,9 +428,17 @@ class QueryText:
             base = buf.data_ptr()
             p = lambda name: C.c_void_p(base + where[name])
             st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            d_off = buf[:8 * (B + 1)].view(torch.int64)
+            enc = None
+            if self.encoder is not None and vectors:
+                Le = self.encoder.max_length
+                e_packed, e_info, _, e_cap, _ = self.enc_wp.queue_dev(base + where["text"], total, d_off, Le,
+                                                                      min(B * Le, total + 2 * B))
+                e_ready = torch.cuda.Event()
+                e_ready.record(torch.cuda.current_stream(dev))
+                enc = {"packed": e_packed, "info": e_info, "cap": e_cap}
             wp_out = None
             if self.wp is not None:
-                d_off = buf[:8 * (B + 1)].view(torch.int64)
                 cap = min(B * L, total + 2 * B)
                 packed, _info, _, cap, _ = self.wp.queue_dev(base + where["text"], total, d_off, L, cap)
                 wp_out = packed
@@ -338,8 +457,46 @@ class QueryText:
                                  (where["rr_ids"] - where["rr_off"]) // 4)
             i32 = lambda name, count: buf[where[name]:where[name] + 4 * count].view(torch.int32)
             terms = StagedTerms(i32("ids", cap_ids), i32("ids_off", B + 1), None, cap_ids if total else 0)
+            qvecs = None
+            if enc is not None:
+                e_ready.synchronize()                  # the one read-back: the token count and the longest sequence
+                h = enc["info"].numpy()
+                enc["n_tokens"], enc["max_len"] = int(h[0]), int(h[B + 1])
+                _lib.check(lib.rr_query_flag_dev(C.c_void_p(e_packed.data_ptr() + 4 * (3 * e_cap + B + 1)), B, FLAG_ENCODER,
+                                                 p("needs_host"), st), "rr_query_flag_dev")
+                qvecs = self._vectors(enc, B, i32("needs_host", B))
         return QueryFront(B, terms, (buf, where), rerank_staged, i32("needs_host", B), L,
-                          {"buf": buf, "where": where, "stage": stage, "wp": wp_out})
+                          {"buf": buf, "where": where, "stage": stage, "wp": wp_out, "enc": enc}, qvecs)
+
+    def _vectors(self, enc: dict, B: int, needs_host, out=None):
+        """The forward over the encoder's packed ids and numpy's normalisation, queued on the current stream.  ``narrow``
+        records which kernels THIS launch ran on (embed._embed_into does the same): it decides the redo."""
+        model = self.encoder.model
+        tok, typ, pos, cu = self.enc_wp.views(enc["packed"], B, enc["cap"], enc["n_tokens"])
+        enc["narrow"] = model.precision == "fp32" and not model.wide_range
+        rows = self.encoder.encode_dev(tok, typ, pos, cu, B, enc["max_len"])
+        out = rows if out is None else out             # (in place: a row is read in full before it is written)
+        import torch
+        _lib.check(_lib.load().rr_query_vectors_dev(C.c_void_p(rows.data_ptr()), B, rows.shape[1], VECTOR_EPS,
+                                                    C.c_void_p(needs_host.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)),
+                   "rr_query_vectors_dev")
+        return out
+
+    def redo_vectors(self, front: QueryFront) -> bool:
+        """After the batch of ``front`` has been waited for: when its forward ran on the fp16-pair kernels and met an
+        activation beyond fp16's range (``encoder.model.out_of_range()``; its CLS rows, and so ``front.qvecs``, are NaN), the
+        handle is switched to the wide-range kernels as `BertEncoderGPU.forward_ids` switches it (``set_wide_range``), the
+        forward and the normalisation are queued again INTO ``front.qvecs`` and True is returned: the caller searches the
+        batch again.  False (and nothing queued) otherwise."""
+        enc = front._keep.get("enc")
+        if enc is None or not enc["narrow"] or not self.encoder.model.out_of_range():
+            return False
+        self.encoder.model.set_wide_range(True)
+        import torch
+        with torch.cuda.device(front.qvecs.device):
+            self._vectors(enc, front.n_queries, front.needs_host, out=front.qvecs)
+        return True
 
     def check(self) -> None:
         """Raises ValueError when a batch since the last check had offsets that decrease or leave the text, or a store that
@@ -348,6 +505,8 @@ class QueryText:
         _lib.check(_lib.load().rr_query_status(self._h, C.byref(bad)), "rr_query_status")
         if self.wp is not None:
             self.wp.check()
+        if self.enc_wp is not None:
+            self.enc_wp.check()
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -356,6 +515,9 @@ class QueryText:
         if getattr(self, "wp", None) is not None:
             self.wp.close()
             self.wp = None
+        if getattr(self, "enc_wp", None) is not None:
+            self.enc_wp.close()
+            self.enc_wp = None
 
     def __del__(self):
         try:

@@ -332,6 +332,37 @@ int rr_reviews_best_cut_dev(rr_reviews* rv, const float* d_queries, int32_t n_qu
                             const int64_t* d_rows, int32_t pool, int64_t row_offset, int64_t max_rows,
                             float* d_best_score, int32_t* d_best_id, void* stream);
 
+/* A review index over ONE ROW SHARD of a larger review table (sharded.py): the index holds only the reviews of its own
+ * products, its review ids are LOCAL (0 .. n_reviews-1, file order), and h_global_ids[n_reviews] maps them, strictly
+ * ascending, to GLOBAL review ids = positions in the whole table of n_total reviews (n_total < 2^31).  With a map every cut
+ * the index compares with and every best id it writes is a GLOBAL id (rr_reviews_best_dev's max_review_id and
+ * rr_reviews_best_cut_dev included; "keep all" is n_total); scores do not change: a review's score does not depend on the
+ * shard it sits in.  Set once, before the first query; an index without a map behaves as before, local = global. */
+int rr_reviews_set_global_ids(rr_reviews* rv, const int32_t* h_global_ids, int64_t n_total);
+
+/* The `iloc[:max_rows]` cut when the candidates' reviews lie on several ranks: a 256-way narrowing of an interval of
+ * GLOBAL review ids per query, d_state[n_queries][2] int64 = (lo, hi), one launch per round, no host read in between.
+ *   begin:  (lo, hi) = (0, n_total - 1).
+ *   count:  [narrows first with d_sums, the summed counts of the previous round, when d_sums != NULL;] then
+ *           d_counts[q][j] (int64, j = 0..255) = the reviews with global id <= T_j = lo + ((j+1)(hi-lo+1) + 255)/256 - 1
+ *           among the candidates d_rows[q][0..pool) this index owns (rows outside [row_offset, row_offset + n_products): 0).
+ *           The caller sums d_counts over the ranks.
+ *   narrow: with j* the first j whose summed count >= max_rows: lo <- (j* = 0 ? lo : T_{j*-1} + 1), hi <- T_{j*}.
+ *           `first` != 0 marks the sums of round 1: a query with count(T_255) <= max_rows is parked at lo = hi = n_total
+ *           (keep all) and later narrowings leave it alone.  d_cuts != NULL: also writes d_cuts[q] = lo (int32).
+ * After R rounds, R the smallest R >= 1 with 256^R >= n_total, lo = hi = the cut: the max_rows-th smallest global id of
+ * the union of the candidates' lists.  max_rows >= 1 (max_rows <= 0 is the caller's: cut -1, no round). */
+int rr_reviews_cut_begin_dev(rr_reviews* rv, int32_t n_queries, int64_t* d_state, void* stream);
+int rr_reviews_cut_count_dev(rr_reviews* rv, int32_t n_queries, const int64_t* d_rows, int32_t pool, int64_t row_offset,
+                             int64_t max_rows, const int64_t* d_sums, int32_t first, int64_t* d_state, int64_t* d_counts,
+                             void* stream);
+int rr_reviews_cut_narrow_dev(rr_reviews* rv, int32_t n_queries, int64_t max_rows, const int64_t* d_sums, int32_t first,
+                              int64_t* d_state, int32_t* d_cuts, void* stream);
+/* rr_reviews_best_dev with one cut per query in device memory (d_cuts[n_queries], global ids when the index has a map):
+ * best score and best (global) review id per (query, candidate); a row this index does not own gives (0, -1). */
+int rr_reviews_best_at_dev(rr_reviews* rv, const float* d_queries, int32_t n_queries, const int64_t* d_rows, int32_t pool,
+                           int64_t row_offset, const int32_t* d_cuts, float* d_best_score, int32_t* d_best_id, void* stream);
+
 /* ------------------------------------------------------------ K5 cross-encoder / query encoder forward */
 
 /* BERT-family encoder on the matrix cores (csrc/rr_ce.hip).  Stands in for

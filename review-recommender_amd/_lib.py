@@ -92,6 +92,11 @@ PROTOTYPES = {
     "rr_reviews_destroy": (C.c_int, [c_vp]),
     "rr_reviews_best_dev": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "rr_reviews_best_cut_dev": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "rr_reviews_set_global_ids": (C.c_int, [c_vp, c_vp, c_i64]),
+    "rr_reviews_cut_begin_dev": (C.c_int, [c_vp, c_i32, c_vp, c_vp]),
+    "rr_reviews_cut_count_dev": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "rr_reviews_cut_narrow_dev": (C.c_int, [c_vp, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "rr_reviews_best_at_dev": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rr_ce_create": (C.c_int, [c_i32, P(CEConfig), P(c_vp), c_i32, P(c_vp)]),
     "rr_ce_destroy": (C.c_int, [c_vp]),
     "rr_ce_forward_dev": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp]),

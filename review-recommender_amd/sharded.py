@@ -20,6 +20,13 @@ payload as one more float32 column (44 B/candidate), and K3 reads it through the
 one K3 pass, no host wait, no replicated texts.  The reranker scores the MERGED pool, so its token plane (about 1 KB per
 product) is replicated once per index (`exchange_plane`); per batch every rank assembles and scores its share of the pairs
 on the device (``rerank_pairs``).
+
+The best review per candidate (``reviews=True``) also belongs to the MERGED pool, and its review table is sharded with the
+products (reviews.ReviewIndex.shard: 1/world of the embeddings per rank).  The reference's ``iloc[:max_rows]`` cut is an
+order statistic over review ids that lie on different ranks: the ranks find it together in at most four rounds of 256-way
+narrowing, whose (B, 256) counts are summed by an all-reduce (`exchange_counts`); every rank then picks the best review of
+the merged rows it owns, one all-gather of (score bits | id) words combines the picks (`exchange_picks`, `select_by_owner`),
+and K3 runs again with the pool-aligned column.
 """
 from __future__ import annotations
 
@@ -32,7 +39,7 @@ import numpy as np
 
 from . import _lib
 from .engine import FusionWeights, HybridSearcher, check_columns
-from .index import MAX_CANDIDATES
+from .index import MAX_CANDIDATES, MAX_POOL
 
 
 def shard_bounds(n_rows: int, world: int, rank: int) -> Tuple[int, int]:
@@ -195,6 +202,68 @@ def exchange_scores(local, n_pairs: int, world: int, group=None):
     return torch.cat([out[r, :hi - lo] for r, (lo, hi) in enumerate(bounds)])
 
 
+def exchange_counts(counts, world: int, group=None):
+    """The collective of one round of the review cut (reviews.model_cut): element-wise SUM over the ranks of the (B, 256)
+    int64 counts, in place.  Integer sums: the same on every rank whatever order the transport adds in."""
+    import torch.distributed as dist
+    if world == 1:
+        return counts
+    if dist.get_backend(group) == "nccl":
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group, async_op=True).wait()    # (orders the stream, not the host)
+        return counts
+    host = counts.cpu()                                           # gloo reduces host tensors (a CPU tensor is its own copy)
+    dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+    if host is not counts:
+        counts.copy_(host)
+    return counts
+
+
+def owner_of(rows, n_rows: int, world: int):
+    """The rank whose shard holds each row of ``rows`` (int64 tensor of global rows) under `shard_bounds`; rows outside the
+    corpus are given to the nearest rank (none owns them: its pick for them is "no review")."""
+    base, extra = divmod(n_rows, world)
+    head = extra * (base + 1)                                     # rows of the ranks that hold one row more
+    own = rows.div(base + 1, rounding_mode="floor")
+    if base > 0:
+        own = own.where(rows < head, (rows - head).div(base, rounding_mode="floor") + extra)
+    return own.clamp_(0, world - 1)
+
+
+def pack_picks(best_raw, best_ids):
+    """(score float32, review id int32) per candidate as ONE int64 word: score bits << 32 | id.  Bits, not values: the
+    ranks' columns are never added (-0.0 + 0.0 would change a score's bit pattern)."""
+    import torch
+    return torch.stack([best_ids, best_raw.view(torch.int32)], dim=-1).view(torch.int64).squeeze(-1)
+
+
+def unpack_picks(words):
+    """The inverse of pack_picks: (best_raw float32, best_ids int32), contiguous."""
+    import torch
+    pair = words.contiguous().view(torch.int32).view(tuple(words.shape) + (2,))
+    return pair[..., 1].contiguous().view(torch.float32), pair[..., 0].contiguous()
+
+
+def select_by_owner(gathered, rows, n_rows: int):
+    """``gathered``: (world, B, pool) int64 picks of every rank for the same merged ``rows`` (B, pool); returns (B, pool):
+    every candidate's word from the rank that OWNS its row."""
+    world = gathered.shape[0]
+    own = owner_of(rows, n_rows, world)
+    return gathered.view(world, -1).gather(0, own.view(1, -1)).view(rows.shape)
+
+
+def exchange_picks(words, rows, n_rows: int, world: int, group=None):
+    """The all-gather of the best-review step: every rank contributes its (B, pool) int64 picks (pack_picks) of the merged
+    rows; returns (best_raw, best_ids) with every candidate's entry taken from its owner rank, identical on every rank."""
+    return unpack_picks(select_by_owner(_gather(words, world, group), rows, n_rows))
+
+
+def exchange_review_tops(top, world: int, group=None):
+    """Once per index: every rank contributes the largest per-product review counts of its shard (ReviewIndex.top_counts,
+    int64); returns all ranks' counts in one numpy array, replicated -- the numbers the skip rule of the cut's rounds is
+    decided from on the host (reviews.pool_reviews_bound)."""
+    return _gather(top, world, group).cpu().numpy().reshape(-1)
+
+
 def exchange_plane_arrays(tok, off, world: int, group=None):
     """The collective half of `exchange_plane`: every rank contributes the ids (int16, its n_tokens) and the offsets (int64
     [n + 1]) of its shard's token plane; all ranks end with the same joined (ids, offsets) of the whole corpus
@@ -255,7 +324,8 @@ class PendingBatch:
     terms: object = None
     bm25_mode: str = "forward"
     plain_q: object = None        # set when K1 could not be split on this rank: the queries of the whole K1 stage 1 then runs
-    two_pass: bool = False        # a host gate or a reranker: finish merges, forms the pool-aligned columns, runs K3 again
+    two_pass: bool = False        # a host gate, a reranker or reviews: finish merges, forms the pool-aligned columns, runs K3 again
+    reviews: object = None        # (queries, max_scan, best_out) of a batch with the best-review column
 
 
 class _Overlap:
@@ -305,10 +375,14 @@ class _Overlap:
 class ShardedSearcher:
     """K1 + K2 per shard, one all-gather, K3 on the merged pool."""
 
-    def __init__(self, searcher: HybridSearcher, n_total_rows: int, rank: int, world: int, group=None, rerank_text=None):
+    def __init__(self, searcher: HybridSearcher, n_total_rows: int, rank: int, world: int, group=None, rerank_text=None,
+                 reviews=None):
         """``searcher.gate_text``: the gate plane of THIS shard's rows (``GateText.from_texts(texts[lo:hi], ...,
         row_offset=lo)``), for ``gate_groups``.  ``rerank_text``: the token plane of the WHOLE corpus (`exchange_plane` of
-        the shards' planes), for ``rerank_pairs``; one rank takes its searcher's."""
+        the shards' planes), for ``rerank_pairs``; one rank takes its searcher's.  ``reviews``: the review index of THIS
+        shard's rows (``ReviewIndex.shard(..., lo, hi)``; one rank may pass a whole index), for ``reviews=True``.  With more
+        than one rank the constructor then runs one collective (`exchange_review_tops`) when a process group is up; a test
+        that plays the shards in one process sets ``review_tops`` itself."""
         lo, hi = shard_bounds(n_total_rows, world, rank)
         ix = searcher.index
         if ix.row_offset != lo or ix.n_rows != hi - lo:
@@ -322,6 +396,21 @@ class ShardedSearcher:
         # selects on its own threshold (one collective less, ~8x the rescoring at 8 shards)
         self.use_floor = os.environ.get("RR_NO_SHARD_FLOOR") is None
         self._ov: Optional[_Overlap] = None
+        self.reviews = reviews
+        self.review_tops = None         # the ranks' largest per-product review counts (numpy, replicated): the skip rule's input
+        self.review_rounds_run = 0      # rounds of the cut this searcher has launched (tests, tools)
+        if reviews is not None:
+            import torch
+            import torch.distributed as dist
+            if (reviews.row_lo, reviews.row_hi) != (lo, hi):
+                raise ValueError(f"rank {rank} holds rows [{lo}, {hi}); its review index is over rows "
+                                 f"[{reviews.row_lo}, {reviews.row_hi})")
+            top = torch.from_numpy(reviews.top_counts(MAX_POOL))
+            if world == 1:
+                self.review_tops = top.numpy()
+            elif dist.is_available() and dist.is_initialized():
+                self.review_tops = exchange_review_tops(top if dist.get_backend(group) != "nccl" else top.to(searcher.device),
+                                                        world, group)
 
     def enable_overlap(self, scan_cus: Optional[int] = None) -> bool:
         """Runs every batch's tail beside the NEXT batch's scan ("keep K1 -> K2-gather -> allgather -> K3 on-stream
@@ -417,8 +506,17 @@ class ShardedSearcher:
     def search_batch_dev(self, q_dev, term_id_lists: Optional[Sequence[Sequence[int]]], k: int,
                          weights: Optional[FusionWeights] = None, pool_floor: int = 150,
                          bm25_mode: str = "forward", rerank_k: int = 0, gate_fn=None, rerank_fn=None,
-                         gate_groups=None, gate_host=None, rerank_pairs=None):
+                         gate_groups=None, gate_host=None, rerank_pairs=None, reviews: bool = False, max_scan: int = 0,
+                         best_out: Optional[dict] = None):
         """Device-resident queries in, device tensors out: (pool_rows, columns, order).
+
+        ``reviews`` / ``max_scan`` (names and meaning of HybridSearcher.search_batch, with the searcher's own shard index):
+        the `_best` column -- per candidate of the merged pool the best review among the first ``max_scan`` reviews, in file
+        order, of all the pool's candidates.  ``best_out``: a dict that receives ``"best_ids"`` (B, pool) int32 GLOBAL review
+        ids (-1: none) and ``"best_raw"`` (B, pool) float32, device tensors aligned with pool_rows (what
+        ``ReviewIndex.snippets`` takes).  A two-pass batch: the merge, the cut's rounds across the ranks (skipped when no
+        pool of this size can hold more than ``max_scan`` reviews), every rank's picks for the rows it owns, one all-gather
+        of them, K3 again.
 
         ``gate_groups`` / ``gate_host`` (instead of gate_fn; names and meaning of HybridSearcher.search_batch): per query
         its gate groups, matched on the device against the gate plane of this rank's OWN rows before the exchange; the
@@ -440,24 +538,28 @@ class ShardedSearcher:
         if self.world == 1 and not self.force_payload:
             # nothing to exchange: K1 -> K2 -> gate -> K3 straight through, metadata read from the index
             B, w, pool, _, rr_k, tl, packed, two_pass = self._plan(q_dev, term_id_lists, k, weights, pool_floor, rerank_k,
-                                                                   gate_fn, rerank_fn, gate_groups, gate_host, rerank_pairs)
+                                                                   gate_fn, rerank_fn, gate_groups, gate_host, rerank_pairs,
+                                                                   reviews)
             self._flush_overlap()
             staged = s.gate_text.upload(packed) if packed is not None else None      # (ahead of the kernels)
             rows, dense = s.dense_pool(q_dev, pool)
             bm = s.bm25_at(tl, rows, bm25_mode)
-            gate = rerank = None
-            if two_pass:
+            gate = rerank = best = None
+            if reviews:                     # one GPU sees every list: the cut by bisection and the pick, one call
+                best = self._best_whole(q_dev, rows, max_scan, best_out)
+            if gate_fn is not None or ((rerank_fn is not None or rerank_pairs is not None) and rr_k > 0):
                 gate, rerank = self._pool_columns(rows, B, pool, rr_k, gate_fn, rerank_fn, rerank_pairs)
             if packed is not None:
                 gate = s.gate_text.gate(rows, packed, gate_host, staged)      # pool-aligned: the pool order is K1's already
             return s.fuse(HybridSearcher.make_params(w, min(k, pool), pool, pool, rr_k), B, rows, dense, bm,
-                          None, rerank, None, gate)
+                          None, rerank, best, gate)
         return self.finish(self.submit(q_dev, term_id_lists, k, weights, pool_floor, bm25_mode, rerank_k, gate_fn, rerank_fn,
-                                       gate_groups, gate_host, rerank_pairs))
+                                       gate_groups, gate_host, rerank_pairs, reviews, max_scan, best_out))
 
     def submit(self, q_dev, term_id_lists, k: int, weights: Optional[FusionWeights] = None, pool_floor: int = 150,
                bm25_mode: str = "forward", rerank_k: int = 0, gate_fn=None, rerank_fn=None,
-               gate_groups=None, gate_host=None, rerank_pairs=None) -> "PendingBatch":
+               gate_groups=None, gate_host=None, rerank_pairs=None, reviews: bool = False, max_scan: int = 0,
+               best_out: Optional[dict] = None) -> "PendingBatch":
         """First half of search_batch_dev for row shards: K1 (+ floor exchange) + K2 + metadata gather on this rank, then the
         payload all-gather is STARTED (exchange_start) and the call returns.  `finish(ticket)` waits for the collective on
         the stream and runs the merge (K3).  Calling submit(batch i + 1) before finish(batch i) puts batch i's all-gather
@@ -472,7 +574,8 @@ class ShardedSearcher:
 
         Every answer is bit for bit the one search_batch_dev gives (same kernels, same order per batch)."""
         B, w, pool, pool_local, rr_k, tl, packed, two_pass = self._plan(
-            q_dev, term_id_lists, k, weights, pool_floor, rerank_k, gate_fn, rerank_fn, gate_groups, gate_host, rerank_pairs)
+            q_dev, term_id_lists, k, weights, pool_floor, rerank_k, gate_fn, rerank_fn, gate_groups, gate_host, rerank_pairs,
+            reviews)
         if self._ov is not None:
             if not two_pass:
                 t = self._submit_overlapped(q_dev, tl, B, k, pool, pool_local, w, bm25_mode, packed, gate_host)
@@ -482,15 +585,16 @@ class ShardedSearcher:
         lay, buf = self.local_payload(q_dev, tl, pool_local, bm25_mode, gate=packed, gate_host=gate_host)
         pending = exchange_start(buf, self.world, self.group)
         return PendingBatch(B, k, pool, pool_local, rr_k, w, lay, buf, pending, gate_fn, rerank_fn, packed=packed,
-                            gate_host=gate_host, rerank_pairs=rerank_pairs, two_pass=two_pass)
+                            gate_host=gate_host, rerank_pairs=rerank_pairs, two_pass=two_pass,
+                            reviews=(q_dev, int(max_scan), best_out) if reviews else None)
 
     def _plan(self, q_dev, term_id_lists, k: int, weights, pool_floor: int, rerank_k: int, gate_fn, rerank_fn,
-              gate_groups, gate_host, rerank_pairs):
+              gate_groups, gate_host, rerank_pairs, reviews: bool = False):
         """The batch's plan, with every check that can refuse it, before any launch or collective (every rank computes the
         same tests on the same batch, so no rank is left waiting in a collective the others never join):
         (B, weights, pool, pool_local, rr_k, term lists, the gate's PackedGroups or None, two_pass).  ``two_pass``: a host
-        gate or a reranker needs the merged pool first (merge, pool-aligned columns, K3 again); a gate matched on the device
-        is a payload column, such a batch is an ordinary one-pass batch."""
+        gate, a reranker or the best-review column needs the merged pool first (merge, pool-aligned columns, K3 again); a
+        gate matched on the device is a payload column, such a batch is an ordinary one-pass batch."""
         w = weights or FusionWeights()
         B = q_dev.shape[0]
         pool = min(max(k, rerank_k, pool_floor), self.n_total)
@@ -505,7 +609,18 @@ class ShardedSearcher:
             assert pool_local == pool, "each shard needs at least `pool` rows"
         tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
         packed = check_columns(B, w, self.s.gate_text, self.rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs)
-        two_pass = gate_fn is not None or ((rerank_fn is not None or rerank_pairs is not None) and rr_k > 0)
+        if reviews:
+            if self.reviews is None:
+                raise ValueError("reviews=True needs the review index of this shard's rows: ShardedSearcher(..., "
+                                 "reviews=ReviewIndex.shard(...))")
+            lo, hi = shard_bounds(self.n_total, self.world, self.rank)
+            if (self.reviews.row_lo, self.reviews.row_hi) != (lo, hi):
+                raise ValueError(f"the review index is over rows [{self.reviews.row_lo}, {self.reviews.row_hi}), "
+                                 f"not this rank's [{lo}, {hi})")
+            if self.review_tops is None:
+                raise ValueError("the ranks' review counts have not been exchanged (review_tops): construct the searcher "
+                                 "with the process group up")
+        two_pass = gate_fn is not None or ((rerank_fn is not None or rerank_pairs is not None) and rr_k > 0) or bool(reviews)
         return B, w, pool, pool_local, rr_k, tl, packed, two_pass
 
     # ------------------------------------------------------------------ the overlapped form
@@ -616,17 +731,18 @@ class ShardedSearcher:
             # pass A: the merge alone fixes the pool order; pass B: the same payload + the pool-aligned columns
             merged_rows, _, _ = self.merge(lay, gathered, B, pool, pool, pool_local, w)
             gate, rerank = self._pool_columns(merged_rows, B, pool, rr_k, t.gate_fn, t.rerank_fn, t.rerank_pairs)
-            res = self.merge(lay, gathered, B, k_out, pool, pool_local, w, rr_k, rerank, gate)
+            best = self.best_column(*t.reviews[:2], merged_rows, t.reviews[2]) if t.reviews is not None else None
+            res = self.merge(lay, gathered, B, k_out, pool, pool_local, w, rr_k, rerank, gate, best=best)
         self._keep = (gathered, t.buf)   # alive until the stream has consumed them
         return res
 
     def merge(self, lay: PayloadLayout, gathered, B: int, k_out: int, pool: int, pool_local: int, w: FusionWeights,
-              rr_k: int = 0, rerank=None, gate=None, out=None):
+              rr_k: int = 0, rerank=None, gate=None, out=None, best=None):
         """K3 over a gathered payload, on the current stream: ``gathered`` holds ``self.world`` blocks of layout ``lay``
         ([rank][query][pool_local] addressing); they are merged to the top ``pool`` by (dense desc, row asc) and fused ->
         (out_rows (B, pool), cols (B, 8, pool) f64, order (B, k_out)).  The payload's gate column is read through the merge
-        when the layout has one; ``rerank`` / ``gate``: pool-aligned (B, pool) float32 columns of a second pass (a host gate
-        and the payload's column exclude each other).  ``out``: the three tensors to write into instead of fresh ones."""
+        when the layout has one; ``rerank`` / ``best`` / ``gate``: pool-aligned (B, pool) float32 columns of a second pass (a
+        host gate and the payload's column exclude each other).  ``out``: the three tensors to write into instead of fresh ones."""
         import torch
         s = self.s
         params = HybridSearcher.make_params(w, k_out, pool, self.world * pool_local, rr_k,
@@ -640,9 +756,72 @@ class ShardedSearcher:
         p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
         _lib.check(s.lib.rr_fuse_topk_cand_dev(
             s.index.handle, C.byref(params), B, ptr(lay.off_rows), ptr(lay.off_dense), ptr(lay.off_bm25),
-            ptr(lay.off_n), ptr(lay.off_avg), ptr(lay.off_l1p), p(rerank), None, p(gate),
+            ptr(lay.off_n), ptr(lay.off_avg), ptr(lay.off_l1p), p(rerank), p(best), p(gate),
             ptr(lay.off_gate) if lay.gate else None, p(out[0]), p(out[1]), p(out[2]), s._stream()), "rr_fuse_topk_cand_dev")
         return out
+
+    # ------------------------------------------------------------------ the best-review column
+    def _best_whole(self, q_dev, rows, max_scan: int, best_out):
+        """One rank, no payload: rr_reviews_best_cut_dev as HybridSearcher.search_batch calls it."""
+        import torch
+        s = self.s
+        B, pool = rows.shape
+        best = torch.empty((B, pool), dtype=torch.float32, device=s.device)
+        ids = torch.empty((B, pool), dtype=torch.int32, device=s.device)
+        q = q_dev if q_dev.is_cuda else q_dev.to(s.device)
+        _lib.check(s.lib.rr_reviews_best_cut_dev(
+            self.reviews.handle, C.c_void_p(q.data_ptr()), B, C.c_void_p(rows.data_ptr()), pool, s.index.row_offset,
+            int(max_scan), C.c_void_p(best.data_ptr()), C.c_void_p(ids.data_ptr()), s._stream()), "rr_reviews_best_cut_dev")
+        if best_out is not None:
+            best_out["best_ids"], best_out["best_raw"] = ids, best
+        return best
+
+    def review_plan(self, pool: int, max_scan: int) -> str:
+        """What a batch's best-review step runs, decided on the host from replicated numbers (every rank branches alike, no
+        device value is read): "none" -- max_scan <= 0, no review is scored; "skip" -- no pool of ``pool`` products can hold
+        more than max_scan reviews (reviews.pool_reviews_bound of the ranks' exchanged counts), the cut cannot bite, every
+        cut is n_total; "rounds" -- the cut is found across the ranks."""
+        from .reviews import pool_reviews_bound
+        if max_scan <= 0:
+            return "none"
+        return "skip" if pool_reviews_bound(self.review_tops, pool) <= max_scan else "rounds"
+
+    def review_cuts(self, rows, max_scan: int, reduce=None):
+        """The rounds of the cut on the merged ``rows`` (B, pool): int32 (B,) global review ids, identical on every rank.
+        One launch per round (the narrowing with the previous sums rides in front of the counting), one all-reduce of the
+        (B, 256) counts behind it (``reduce``: what sums them instead of `exchange_counts`), one launch at the end."""
+        from .reviews import cut_rounds
+        rv, off = self.reviews, self.s.index.row_offset
+        reduce = reduce or (lambda c: exchange_counts(c, self.world, self.group))
+        state, sums = rv.cut_begin(rows.shape[0]), None
+        R = cut_rounds(rv.n_total)
+        for r in range(R):
+            sums = reduce(rv.cut_counts(state, rows, max_scan, off, sums=sums, first=r == 1))
+            self.review_rounds_run += 1
+        return rv.cut_end(state, sums, max_scan, first=R == 1)
+
+    def best_local(self, q_dev, rows, cuts):
+        """This rank's picks for the merged ``rows``: (B, pool) int64 words (pack_picks); rows of other shards: (0, -1)."""
+        q = q_dev if q_dev.is_cuda else q_dev.to(self.s.device)
+        return pack_picks(*self.reviews.best_at(q, rows, cuts, self.s.index.row_offset))
+
+    def best_column(self, q_dev, max_scan: int, rows, best_out=None):
+        """The pool-aligned `_best` column of a batch, on the current stream: plan, cuts, this rank's picks, the all-gather,
+        every candidate's entry from its owner.  Returns best_raw (B, pool) float32; ``best_out`` gets ids and scores."""
+        import torch
+        s, (B, pool) = self.s, rows.shape
+        with torch.cuda.device(s.device):
+            plan = self.review_plan(pool, max_scan)
+            if plan == "none":
+                raw = torch.zeros((B, pool), dtype=torch.float32, device=s.device)
+                ids = torch.full((B, pool), -1, dtype=torch.int32, device=s.device)
+            else:
+                cuts = (self.review_cuts(rows, max_scan) if plan == "rounds" else
+                        torch.full((B,), self.reviews.n_total, dtype=torch.int32, device=s.device))
+                raw, ids = exchange_picks(self.best_local(q_dev, rows, cuts), rows, self.n_total, self.world, self.group)
+        if best_out is not None:
+            best_out["best_ids"], best_out["best_raw"] = ids, raw
+        return raw
 
     def _pool_columns(self, rows_dev, B: int, pool: int, rr_k: int, gate_fn, rerank_fn, rerank_pairs=None):
         """Host gate factors (gate_fn: every rank, all pairs: string work on replicated texts) and reranker scores (this

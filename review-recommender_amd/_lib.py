@@ -178,6 +178,9 @@ DEBUG_PROTOTYPES = {
     "rr_debug_ce_h2_gemm": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, P(C.c_int32)]),
     "rr_debug_ce_h2_attention": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, P(C.c_int32)]),
     "rr_debug_ce_h2_add_ln": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, P(C.c_int32)]),
+    "rr_debug_ce_x3_gemm": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rr_debug_ce_x3_attention": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp]),
+    "rr_debug_ce_x3_add_ln": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_f32]),
 }
 
 _lib = None

@@ -1689,4 +1689,48 @@ extern "C" int rr_debug_ce_ffn_stamps(unsigned long long* out20) {
     RR_HIP_TRY(hipMemcpyFromSymbol(out20, HIP_SYMBOL(ce_dbg_ffn), sizeof(unsigned long long) * 20));
     return RR_OK;
 }
+
+// tests/test_gpu_k5_x3_kernels.py: the wide-range kernels one launch at a time on caller data (device pointers, fp32
+// row-major), each launched as ce_forward_x3 launches it -- same grid, block, LDS size and scale.
+// out[M][N] = x[M][K] w[N][K]^T + bias, through the exact erf GELU when `gelu` is set
+extern "C" int rr_debug_ce_x3_gemm(int32_t gelu, int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_bias,
+                                   float* d_out) {
+    RR_REQUIRE((gelu == 0 || gelu == 1) && M >= 1 && N >= 128 && N % 128 == 0 && K >= 16 && K % 16 == 0 && d_x && d_w && d_bias && d_out,
+               "rr_debug_ce_x3_gemm: bad arguments");
+    const dim3 grid((unsigned)(N / 128), (unsigned)((M + 127) / 128));
+    if (gelu) hipLaunchKernelGGL((ce_gemm_x3<true>), grid, dim3(256), 0, nullptr, d_x, d_w, d_bias, M, N, K, d_out);
+    else hipLaunchKernelGGL((ce_gemm_x3<false>), grid, dim3(256), 0, nullptr, d_x, d_w, d_bias, M, N, K, d_out);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipDeviceSynchronize());
+    return RR_OK;
+}
+
+// qkv [T][1152] fp32 with Q UNSCALED (the kernel applies log2 e / sqrt 32 itself), cu_seqlens [n_seqs + 1] on the device with
+// cu[0] = 0, cu[n_seqs] = T and every length in [1, 512] (checked here: the kernel trusts them) -> ctx [T][384]
+extern "C" int rr_debug_ce_x3_attention(const float* d_qkv, int32_t T, const int32_t* d_cu, int32_t n_seqs, float* d_ctx) {
+    RR_REQUIRE(T >= 1 && n_seqs >= 1 && n_seqs <= T && d_qkv && d_cu && d_ctx, "rr_debug_ce_x3_attention: bad arguments");
+    int dev = 0;
+    RR_HIP_TRY(hipGetDevice(&dev));
+    if (int rc = ce_set_attributes(dev)) return rc;
+    std::vector<int32_t> cu((size_t)n_seqs + 1);
+    RR_HIP_TRY(hipMemcpy(cu.data(), d_cu, sizeof(int32_t) * cu.size(), hipMemcpyDeviceToHost));
+    RR_REQUIRE(cu[0] == 0 && cu[n_seqs] == T, "rr_debug_ce_x3_attention: cu_seqlens run from %d to %d, not from 0 to %d", cu[0], cu[n_seqs], T);
+    for (int i = 0; i < n_seqs; ++i)
+        RR_REQUIRE(cu[i + 1] - cu[i] >= 1 && cu[i + 1] - cu[i] <= 512, "rr_debug_ce_x3_attention: sequence %d has %d tokens, outside [1, 512]",
+                   i, cu[i + 1] - cu[i]);
+    hipLaunchKernelGGL(ce_attention_x3, dim3((unsigned)n_seqs, CE_HEADS), dim3(512), CE_X3A_LDS, nullptr, d_qkv, d_cu, d_ctx,
+                       0.17677669529663687f /* 1 / sqrt(32) */);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipDeviceSynchronize());
+    return RR_OK;
+}
+
+// h[t] = LayerNorm(y[t] + h[t]) * g + b for T rows of 384, in place as in the forward pass
+extern "C" int rr_debug_ce_x3_add_ln(const float* d_y, float* d_h, int32_t T, const float* d_g, const float* d_b, float eps) {
+    RR_REQUIRE(T >= 1 && d_y && d_h && d_g && d_b, "rr_debug_ce_x3_add_ln: bad arguments");
+    hipLaunchKernelGGL(ce_add_ln_f32, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, nullptr, d_y, d_h, T, d_g, d_b, eps);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipDeviceSynchronize());
+    return RR_OK;
+}
 #endif

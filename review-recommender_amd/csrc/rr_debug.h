@@ -34,5 +34,11 @@ int rr_debug_ce_h2_attention(const float* d_qkv, int32_t n_tokens, const int32_t
                              int32_t kernel, float* d_ctx, int32_t* flag_out);
 int rr_debug_ce_h2_add_ln(const float* d_y, const float* d_h, int32_t T, const float* d_g, const float* d_b, float eps, float* d_out32,
                           float* d_outh2, int32_t* flag_out);
+// tests/test_gpu_k5_x3_kernels.py: the wide-range kernels of rr_ce.hip (ce_gemm_x3, ce_attention_x3, ce_add_ln_f32) one launch
+// at a time on caller data, launched as ce_forward_x3 launches them.  The attention takes qkv [T][1152] with Q unscaled and
+// writes ctx [T][384]; the add-LayerNorm updates d_h in place.  See the definitions.
+int rr_debug_ce_x3_gemm(int32_t gelu, int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_bias, float* d_out);
+int rr_debug_ce_x3_attention(const float* d_qkv, int32_t T, const int32_t* d_cu, int32_t n_seqs, float* d_ctx);
+int rr_debug_ce_x3_add_ln(const float* d_y, float* d_h, int32_t T, const float* d_g, const float* d_b, float eps);
 }
 #endif

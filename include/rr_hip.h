@@ -535,6 +535,33 @@ int rr_textprep_dedup_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_b
 int rr_textprep_compact_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
                             const int32_t* d_len, const int32_t* d_status, int32_t n_docs, uint8_t* d_out_text,
                             int64_t out_bytes, int64_t* d_out_off, int32_t* d_src_row, int64_t* d_count, void* stream);
+/* The HEAD of documents of any length: the first max_chars (0 .. 2^28) code points of what a document gives, normalised
+ * (normalize != 0: Unicode whitespace -> one space, strip; the space counts -- nlp/11's normalize_text read as a prefix) or
+ * verbatim (str[:max_chars]).  textprep.model_head states the rules.  Output document j reads input document
+ * d_doc_rows[j] (int32; NULL = j) of the n_src_docs documents d_text_off [n_src_docs + 1] describes: a row shard or the
+ * survivors of a filter need no copy of their text.  d_out_len[j] = the head's bytes, d_status[j] = RR_TP_SHORT (fewer than
+ * min_chars code points; min_chars 0 = no filter), RR_TP_NEEDS_HOST (malformed UTF-8 met while fewer than max_chars code
+ * points were emitted: bytes behind the point where the walk stops are never examined; length 0) or 0.  Length is never a
+ * reason for RR_TP_NEEDS_HOST: a workgroup streams its document in tiles (rr_textprep_limits) and stops at the cut.
+ * A call with a text offset that decreases or leaves [0, text_bytes], or a d_doc_rows entry outside [0, n_src_docs), reads
+ * no text, answers length 0 and RR_TP_NEEDS_HOST for every document and is reported by rr_textprep_status.  Asynchronous
+ * on `stream`; the head calls of one handle must be stream-ordered. */
+int rr_textprep_head_measure_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                                 int32_t n_src_docs, const int32_t* d_doc_rows, int32_t n_docs, int32_t max_chars,
+                                 int32_t normalize, int32_t min_chars, int32_t* d_out_len, int32_t* d_status, void* stream);
+/* d_out_off [n_docs + 1] = the exclusive scan of the lengths of the documents whose status word is 0 (a document with
+ * another status takes no room); d_out_off[n_docs] = the bytes pass 2 writes.  A device prefix sum; no host wait. */
+int rr_textprep_head_offsets_dev(rr_textprep* tp, const int32_t* d_out_len, const int32_t* d_status, int32_t n_docs,
+                                 int64_t* d_out_off, void* stream);
+/* Pass 2, over the same arguments and what pass 1 answered: the head of every document whose status word is 0 is written at
+ * d_out_text + d_out_off[j] (d_out_off int64 [n_docs + 1]: an exclusive scan of the lengths, or the host's own offsets when
+ * rows it cleaned itself take room between the heads; a document whose status word is not 0 writes nothing).  Refused, as
+ * above and with nothing read or written: output offsets that decrease, leave [0, out_bytes] or give a surviving document
+ * less room than d_out_len[j]. */
+int rr_textprep_head_write_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                               int32_t n_src_docs, const int32_t* d_doc_rows, int32_t n_docs, int32_t max_chars,
+                               int32_t normalize, int32_t min_chars, const int32_t* d_out_len, const int32_t* d_status,
+                               uint8_t* d_out_text, int64_t out_bytes, const int64_t* d_out_off, void* stream);
 
 /* ------------------------------------------------------------ BM25 corpus: tokens and vocabulary ids (csrc/rr_doctok.hip) */
 

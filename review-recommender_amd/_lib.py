@@ -120,6 +120,10 @@ PROTOTYPES = {
     "rr_textprep_status": (C.c_int, [c_vp, P(c_i32)]),
     "rr_textprep_dedup_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "rr_textprep_compact_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rr_textprep_head_measure_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rr_textprep_head_offsets_dev": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "rr_textprep_head_write_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64,
+                                             c_vp, c_vp]),
     "rr_products_create": (C.c_int, [c_i32, P(c_vp)]),
     "rr_products_destroy": (C.c_int, [c_vp]),
     "rr_products_order_dev": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -27,6 +27,7 @@
 //                 on which of them claimed it.
 // rr_tp_rank      survivors' ranks and byte offsets (one workgroup, chunks of 1024, as rr_wp_scan).
 // rr_tp_gather    one workgroup per survivor copies its text behind its predecessor's.
+// rr_tp_head      the first max_chars code points of documents of any length, normalised or raw (see there).
 #include "rr_prims.h"
 
 #define RR_TP_THREADS 256
@@ -38,7 +39,7 @@
 
 struct rr_textprep {
     int device = 0;
-    int32_t* d_bad = nullptr;        // documents whose offsets a kernel refused (rr_textprep_status)
+    int32_t* d_bad = nullptr;        // [0] documents whose offsets a kernel refused (rr_textprep_status), [1] the running head call was refused
     int32_t* d_scratch = nullptr;    // dedup: representative [slots], minimum [slots], slot of document [n]; compact: rank [n]
     int64_t cap_words = 0;
     std::mutex mu;
@@ -205,6 +206,171 @@ __global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_clean(
     if (tid == 0) { out_len[doc] = n; status[doc] = st; }
 }
 
+// ------------------------------------------------------------------------------------------------ heads of long documents
+// The first max_chars code points of a document of ANY length (textprep.model_head states the rules): normalised
+// (nlp/11's normalize_text read as a prefix computation) or raw (str[:k]).  Measure / scan / write, as rr_gate.hip's plane:
+//   rr_tp_head_check      one thread per output document: its source row, its text span and (write) its output span.  One
+//                         refused document sets the call's flag and NO workgroup of the call reads or writes text.
+//   rr_tp_head<false>     one workgroup per document walks it in tiles of RR_TP_TILE bytes, RR_TP_PER consecutive bytes per
+//                         thread.  A tile is classified from LDS with RR_TP_HALO bytes on each side: the character that starts
+//                         in the tile is decoded by the thread that owns its first byte (reading on into the right halo), and
+//                         what a slice needs to know about the bytes in front of it -- is the character before it whitespace,
+//                         how many continuation bytes of it are still due -- is read from the three bytes in front of the slice
+//                         (the left halo for the first thread: the pending space crosses a tile edge there, not in a register).
+//                         One block scan over (emissions << 16 | bytes) places every emission; the emitted count and bytes are
+//                         carried from tile to tile, and "something was emitted" is count > 0.  The walk leaves its loop at the
+//                         first tile in which the count reaches max_chars.  A malformed byte counts only while the emissions in
+//                         front of it are fewer than max_chars: that is "decoded while fewer than max_chars were emitted", and
+//                         it does not depend on where a tile ends.
+//   rr_tp_head<true>      the same walk for the documents whose status word is 0, writing at d_out_off.
+#define RR_TP_HALO 3
+#define RR_TP_HEAD_MAX_CHARS (1 << 28)                  // 4 bytes per code point stay below 2^31
+
+__global__ void rr_tp_head_check(int64_t text_bytes, const int64_t* __restrict__ text_off, const int32_t* __restrict__ doc_rows,
+                                 int32_t n_docs, int32_t n_src_docs, const int32_t* __restrict__ out_len,
+                                 const int32_t* __restrict__ status, const int64_t* __restrict__ out_off, int64_t out_bytes,
+                                 int32_t* __restrict__ bad) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_docs) return;
+    const int64_t src = doc_rows ? (int64_t)doc_rows[j] : j;
+    bool ok = src >= 0 && src < n_src_docs;
+    if (ok) {
+        int64_t b0, len;
+        ok = rr_doc_span(text_off, (int)src, text_bytes, &b0, &len);
+    }
+    if (ok && out_off) {
+        const int64_t o0 = out_off[j], o1 = out_off[j + 1];
+        ok = o0 >= 0 && o1 >= o0 && o1 <= out_bytes && (status[j] != 0 || o1 - o0 >= out_len[j]);
+    }
+    if (!ok) { atomicAdd(bad, 1); bad[1] = 1; }             // (a count and a flag: the same whatever the order)
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(RR_TP_THREADS) void rr_tp_head(
+    const uint8_t* __restrict__ text, const int64_t* __restrict__ text_off, const int32_t* __restrict__ doc_rows, int32_t max_chars,
+    int32_t normalize, int32_t min_chars, int32_t* out_len, int32_t* status, const int64_t* __restrict__ out_off,
+    uint8_t* __restrict__ out, const int32_t* __restrict__ bad) {
+    __shared__ uint8_t s_raw[RR_TP_TILE + 2 * RR_TP_HALO];   // s_raw[RR_TP_HALO + k] = byte base + k of the document
+    __shared__ int s_ws[RR_TP_THREADS / 64];
+    __shared__ int s_len;
+    const int tid = threadIdx.x;
+    const int doc = blockIdx.x;
+    if (bad[1]) {                                             // the call was refused: nothing is read or written
+        if (!WRITE && tid == 0) { out_len[doc] = 0; status[doc] = RR_TP_NEEDS_HOST; }
+        return;
+    }
+    if (WRITE && status[doc] != 0) return;
+    const int src_doc = doc_rows ? doc_rows[doc] : doc;
+    const int64_t b0 = text_off[src_doc], len = text_off[src_doc + 1] - b0;
+    const uint8_t* __restrict__ src = text + b0;
+    uint8_t* dst = nullptr;
+    int room = 0;                                             // bytes this document may write
+    if (WRITE) {
+        dst = out + out_off[doc];
+        const int64_t r = out_off[doc + 1] - out_off[doc];
+        room = r > INT32_MAX ? INT32_MAX : (int)r;
+    }
+    if (tid == 0) s_len = -1;
+    int phantom = 0;                                          // the document begins with whitespace
+    int carry_cp = 0, carry_by = 0;                           // emitted before this tile (the same in every thread)
+    int malformed = 0;
+    for (int64_t base = 0; base < len && carry_cp < max_chars; base += RR_TP_TILE) {
+        __syncthreads();                                      // (the previous tile is still being copied from)
+        for (int i = tid; i < RR_TP_TILE + 2 * RR_TP_HALO; i += RR_TP_THREADS) {
+            const int64_t d = base - RR_TP_HALO + i;
+            s_raw[i] = d >= 0 && d < len ? src[d] : (uint8_t)0;
+        }
+        __syncthreads();
+        const int64_t left = len - base;
+        const int own_end = RR_TP_HALO + (int)(left < RR_TP_TILE ? left : RR_TP_TILE);                    // bytes of this tile
+        const int dec_end = RR_TP_HALO + (int)(left < RR_TP_TILE + RR_TP_HALO ? left : RR_TP_TILE + RR_TP_HALO);
+        const int first = base == 0 ? RR_TP_HALO : 0;        // the first byte of s_raw that belongs to the document
+        if (base == 0) {
+            uint32_t c;
+            phantom = normalize && (s_raw[RR_TP_HALO] & 0xC0u) != 0x80u && rr_utf8_decode(s_raw, RR_TP_HALO, dec_end, &c) &&
+                      rr_tp_is_space(c) ? 1 : 0;
+        }
+        const int p0 = RR_TP_HALO + tid * RR_TP_PER;
+        // the character in front of this slice: is it whitespace, and how many of its bytes lie in the slice?
+        bool prev_ws = false;
+        int due = 0;
+        if (p0 < own_end) {
+            int k = p0 - 1;
+            while (k >= first && k > p0 - 1 - RR_TP_HALO && (s_raw[k] & 0xC0u) == 0x80u) --k;
+            if (k >= first && k >= p0 - RR_TP_HALO && (s_raw[k] & 0xC0u) != 0x80u) {
+                uint32_t c;
+                const int n = rr_utf8_decode(s_raw, k, dec_end, &c);
+                if (n) { prev_ws = normalize && rr_tp_is_space(c); due = k + n - p0 > 0 ? k + n - p0 : 0; }
+            }
+        }
+        uint8_t info[RR_TP_PER];                              // bytes to emit (0 = none) | 8 = a space in front
+        unsigned events = 0;                                  // bit j: byte j is malformed (starts nothing, or a stray 10xxxxxx)
+        int packed = 0;                                       // emissions << 16 | bytes of this slice
+#pragma unroll
+        for (int j = 0; j < RR_TP_PER; ++j) {
+            const int i = p0 + j;
+            info[j] = 0;
+            if (i >= own_end) continue;
+            if ((s_raw[i] & 0xC0u) == 0x80u) {
+                if (due > 0) --due;
+                else events |= 1u << j;
+                continue;
+            }
+            uint32_t c;
+            const int n = rr_utf8_decode(s_raw, i, dec_end, &c);
+            due = n > 0 ? n - 1 : 0;
+            if (n == 0) { events |= 1u << j; prev_ws = false; }
+            else if (normalize && rr_tp_is_space(c)) prev_ws = true;
+            else {
+                info[j] = (uint8_t)(n | (prev_ws ? 8 : 0));
+                packed += ((prev_ws ? 2 : 1) << 16) | (n + (prev_ws ? 1 : 0));
+                prev_ws = false;
+            }
+        }
+        int total;
+        const int at = rr_block_scan<int, RR_TP_THREADS>(packed, s_ws, &total);
+        // the space in front of the document's first character was counted and is not emitted: it and everything behind
+        // it in this tile move up by one
+        const int ph = phantom && carry_cp == 0 ? 1 : 0;
+        int cp = carry_cp + (at >> 16) - ph, by = carry_by + (at & 0xFFFF) - ph;
+#pragma unroll
+        for (int j = 0; j < RR_TP_PER; ++j) {
+            if ((events >> j) & 1u) malformed |= (cp < 0 ? 0 : cp) < max_chars;     // met while the walk was still decoding
+            if (!info[j]) continue;
+            const int n = info[j] & 7;
+            int sp = info[j] >> 3;
+            int c_at = cp, b_at = by;
+            cp += 1 + sp; by += n + sp;                       // what the scan counted for this character
+            if (c_at < 0) { sp = 0; c_at = 0; b_at = 0; }     // the first character of the head: its space is stripped
+            if (sp) {
+                if (c_at < max_chars) {
+                    if (WRITE && b_at + 1 <= room) dst[b_at] = ' ';
+                    if (c_at == max_chars - 1) s_len = b_at + 1;                   // the space is the last emission
+                }
+                ++c_at; ++b_at;
+            }
+            if (c_at < max_chars) {
+                if (WRITE && b_at + n <= room)
+                    for (int k = 0; k < n; ++k) dst[b_at + k] = s_raw[p0 + j + k];
+                if (c_at == max_chars - 1) s_len = b_at + n;
+            }
+        }
+        const int t_cp = total >> 16, t_by = total & 0xFFFF;
+        carry_cp += t_cp - (ph && t_cp > 0 ? 1 : 0);
+        carry_by += t_by - (ph && t_cp > 0 ? 1 : 0);
+    }
+    if (WRITE) return;
+    const int any_bad = __syncthreads_or(malformed);          // (also orders s_len)
+    if (tid == 0) {
+        const int emitted = carry_cp < max_chars ? carry_cp : max_chars;
+        if (any_bad) { out_len[doc] = 0; status[doc] = RR_TP_NEEDS_HOST; }
+        else {
+            out_len[doc] = s_len >= 0 ? s_len : carry_by;
+            status[doc] = min_chars > 0 && emitted < min_chars ? RR_TP_SHORT : 0;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ dedup
 __global__ __launch_bounds__(256) void rr_tp_insert(
     const uint8_t* __restrict__ text, int64_t text_bytes, const int64_t* __restrict__ text_off, const int32_t* __restrict__ lens,
@@ -318,8 +484,8 @@ extern "C" int rr_textprep_create(int32_t device, rr_textprep** out) {
     RR_HIP_TRY(hipSetDevice(device));
     rr_textprep* tp = new rr_textprep();
     tp->device = device;
-    hipError_t e = hipMalloc((void**)&tp->d_bad, 4);
-    if (e == hipSuccess) e = hipMemset(tp->d_bad, 0, 4);
+    hipError_t e = hipMalloc((void**)&tp->d_bad, 8);
+    if (e == hipSuccess) e = hipMemset(tp->d_bad, 0, 8);
     if (e != hipSuccess) {
         rr_set_error("rr_textprep_create: %s", hipGetErrorString(e));
         rr_textprep_destroy(tp);
@@ -365,8 +531,86 @@ extern "C" int rr_textprep_status(rr_textprep* tp, int32_t* out_bad_docs) {
     const int rc = rr_take_bad_docs(tp->d_bad, out_bad_docs);
     if (rc != RR_OK) return rc;
     const int32_t bad = *out_bad_docs;
-    RR_REQUIRE(bad == 0, "rr_textprep_status: %d document(s) had text offsets that decrease or leave the text (no text was "
-               "read or written for them)", bad);
+    RR_REQUIRE(bad == 0, "rr_textprep_status: %d document(s) had text offsets that decrease or leave the text, or (head calls) a source "
+               "row outside the documents or an output span outside its buffer (no text was read or written for them)", bad);
+    return RR_OK;
+}
+
+static int rr_tp_head_args(const char* who, rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                           int32_t n_src_docs, int32_t n_docs, int32_t max_chars, int32_t min_chars, const void* d_out_len,
+                           const void* d_status) {
+    RR_REQUIRE(tp && d_text_off && d_out_len && d_status, "%s: NULL argument", who);
+    RR_REQUIRE(n_docs >= 0 && n_src_docs >= 0 && text_bytes >= 0, "%s: %d of %d documents, %lld bytes", who, n_docs, n_src_docs,
+               (long long)text_bytes);
+    RR_REQUIRE(d_text || text_bytes == 0, "%s: NULL text with %lld bytes", who, (long long)text_bytes);
+    RR_REQUIRE(max_chars >= 0 && max_chars <= RR_TP_HEAD_MAX_CHARS && min_chars >= 0, "%s: max_chars %d outside [0, 2^28] or min_chars %d negative",
+               who, max_chars, min_chars);
+    return RR_OK;
+}
+
+extern "C" int rr_textprep_head_measure_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                                            int32_t n_src_docs, const int32_t* d_doc_rows, int32_t n_docs, int32_t max_chars,
+                                            int32_t normalize, int32_t min_chars, int32_t* d_out_len, int32_t* d_status,
+                                            void* stream) {
+    const int rc = rr_tp_head_args("rr_textprep_head_measure_dev", tp, d_text, text_bytes, d_text_off, n_src_docs, n_docs, max_chars,
+                                   min_chars, d_out_len, d_status);
+    if (rc != RR_OK) return rc;
+    if (n_docs == 0) return RR_OK;
+    std::lock_guard<std::mutex> lk(tp->mu);
+    RR_HIP_TRY(hipSetDevice(tp->device));
+    hipStream_t st = (hipStream_t)stream;
+    RR_HIP_TRY(hipMemsetAsync(tp->d_bad + 1, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(rr_tp_head_check, dim3((unsigned)((n_docs + 255) / 256)), dim3(256), 0, st, text_bytes, d_text_off, d_doc_rows,
+                       n_docs, n_src_docs, (const int32_t*)nullptr, (const int32_t*)nullptr, (const int64_t*)nullptr, (int64_t)0,
+                       tp->d_bad);
+    hipLaunchKernelGGL(rr_tp_head<false>, dim3((unsigned)n_docs), dim3(RR_TP_THREADS), 0, st, d_text, d_text_off, d_doc_rows, max_chars,
+                       normalize ? 1 : 0, min_chars, d_out_len, d_status, (const int64_t*)nullptr, (uint8_t*)nullptr,
+                       (const int32_t*)tp->d_bad);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+struct rr_tp_f_head_len {   // what the scan of the heads' offsets sums: the bytes of a surviving head
+    const int32_t* len;
+    const int32_t* status;
+    __device__ __forceinline__ long long operator()(int64_t i) const { return status[i] == 0 && len[i] > 0 ? len[i] : 0; }
+};
+
+extern "C" int rr_textprep_head_offsets_dev(rr_textprep* tp, const int32_t* d_out_len, const int32_t* d_status, int32_t n_docs,
+                                            int64_t* d_out_off, void* stream) {
+    RR_REQUIRE(tp && d_out_len && d_status && d_out_off && n_docs >= 0, "rr_textprep_head_offsets_dev: NULL argument or %d documents",
+               n_docs);
+    std::lock_guard<std::mutex> lk(tp->mu);
+    RR_HIP_TRY(hipSetDevice(tp->device));
+    const int rc = rr_grow((void**)&tp->d_scratch, &tp->cap_words, 2 * rr_scan_sums_len(n_docs), sizeof(int32_t),
+                           "rr_textprep_head_offsets_dev");
+    if (rc != RR_OK) return rc;
+    rr_scan(rr_tp_f_head_len{d_out_len, d_status}, (int64_t)n_docs, (int64_t*)tp->d_scratch, d_out_off, (int32_t*)nullptr,
+            (int64_t*)nullptr, (hipStream_t)stream);
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+extern "C" int rr_textprep_head_write_dev(rr_textprep* tp, const uint8_t* d_text, int64_t text_bytes, const int64_t* d_text_off,
+                                          int32_t n_src_docs, const int32_t* d_doc_rows, int32_t n_docs, int32_t max_chars,
+                                          int32_t normalize, int32_t min_chars, const int32_t* d_out_len, const int32_t* d_status,
+                                          uint8_t* d_out_text, int64_t out_bytes, const int64_t* d_out_off, void* stream) {
+    const int rc = rr_tp_head_args("rr_textprep_head_write_dev", tp, d_text, text_bytes, d_text_off, n_src_docs, n_docs, max_chars,
+                                   min_chars, d_out_len, d_status);
+    if (rc != RR_OK) return rc;
+    RR_REQUIRE(d_out_off && out_bytes >= 0 && (d_out_text || out_bytes == 0), "rr_textprep_head_write_dev: NULL output with %lld bytes",
+               (long long)out_bytes);
+    if (n_docs == 0) return RR_OK;
+    std::lock_guard<std::mutex> lk(tp->mu);
+    RR_HIP_TRY(hipSetDevice(tp->device));
+    hipStream_t st = (hipStream_t)stream;
+    RR_HIP_TRY(hipMemsetAsync(tp->d_bad + 1, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(rr_tp_head_check, dim3((unsigned)((n_docs + 255) / 256)), dim3(256), 0, st, text_bytes, d_text_off, d_doc_rows,
+                       n_docs, n_src_docs, d_out_len, d_status, d_out_off, out_bytes, tp->d_bad);
+    hipLaunchKernelGGL(rr_tp_head<true>, dim3((unsigned)n_docs), dim3(RR_TP_THREADS), 0, st, d_text, d_text_off, d_doc_rows, max_chars,
+                       normalize ? 1 : 0, min_chars, const_cast<int32_t*>(d_out_len), const_cast<int32_t*>(d_status), d_out_off,
+                       d_out_text, (const int32_t*)tp->d_bad);
+    RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }
 

@@ -24,6 +24,10 @@ device stages (csrc/rr_textprep.hip, textprep.py), because the reference cleans 
     rr_textprep_compact_dev   the survivors' texts back to back + offsets: what rr_wp_encode_dev reads, still on the device
 
 and from there chunk by chunk through the tokenizer, the encoder and the row store (`build_review_embeddings`).
+
+Product text that the products builder left on the device (products.DeviceProductText) needs no strings at all:
+`build_product_embeddings_device` cuts normalize_text's heads there (rr_textprep_head_measure_dev /
+rr_textprep_head_write_dev) and feeds them to the same chain (`--target product --reviews FILE`).
 """
 from __future__ import annotations
 
@@ -437,6 +441,155 @@ def build_product_embeddings(products, encoder, *, text_col: str = "agg_text", r
     return index, meta, emb
 
 
+def build_product_embeddings_device(products, text, encoder, *, rows: Optional[Tuple[int, int]] = None, dtype: str = "f32",
+                                    chunk_tokens: int = 131072, data_dir=None, stats: Optional[dict] = None,
+                                    head_bytes: int = 256 << 20):
+    """`build_product_embeddings` for agg_text that is ALREADY on the device (`text`: a products.DeviceProductText, as
+    ``build_products(..., keep_device=True)`` leaves it; `products`: its frame, row for row) -> (ProductIndex, meta, emb or
+    None, kept).  No string of the text column is made on the host:
+
+        rr_textprep_head_measure_dev   normalize_text's head (4000 code points) of every product: length, status word
+        (the lengths and status words come back: they are the chunk plan and the length filter)
+        rr_textprep_head_write_dev     the heads of the kept rows, back to back, in row blocks of at most `head_bytes`
+        DeviceWordPiece.queue_dev      ... and from there as `embed_texts_into` (`_embed_into`)
+
+    kept = the product rows whose normalised text has at least MIN_TEXT_LEN characters, in order (with rows=(lo, hi): rows
+    [lo, hi) of that list, one row shard of the FILTERED table as in `build_product_embeddings`).  The documents the head
+    kernel leaves to the host (malformed UTF-8 inside the head: ``stats["host_clean_docs"]``) are fetched, cleaned by
+    `normalize_text` and written into their slots.  meta = the rows `kept` of `products` with the columns sku, n_reviews,
+    avg_stars, last_ts; the agg_text column is fetched from the device and added ONLY with `data_dir`
+    (product_emb_meta.parquet holds it), otherwise meta has no agg_text.  stats also receives "host_docs" (kept rows the
+    tokenizer left to the host, whose heads are copied back) and "seconds"."""
+    import time
+    import pandas as pd
+    import torch
+    from . import textprep as T
+    seconds: Dict[str, float] = {}
+    clock = [time.perf_counter()]
+
+    def lap(name):
+        now = time.perf_counter()
+        seconds[name] = seconds.get(name, 0.0) + now - clock[0]
+        clock[0] = now
+
+    if stats is not None:
+        stats["seconds"] = seconds
+    if "sku" not in products.columns:
+        raise ValueError("the product table must have 'sku'")
+    n = int(text.n)
+    if len(products) != n:
+        raise ValueError(f"{len(products)} products for the text of {n}")
+    if encoder.tokenizer is None:
+        raise ValueError("no vocabulary was loaded: the builder tokenises text")
+    model = encoder.model
+    if n and int(text.device) != int(model.device):
+        raise ValueError(f"the text lives on GPU {text.device}, the encoder on GPU {model.device}")
+    if not 1 <= int(head_bytes) < 2 ** 31:
+        raise ValueError("head_bytes must lie in [1, 2^31): the tokenizer's offsets per call are below 2^31")
+    if n == 0:
+        raise RuntimeError("No products left after filtering.")
+    dev = torch.device("cuda", model.device)
+    tp = T.TextPrep(model.device)
+    try:
+        with torch.cuda.device(dev):
+            main = torch.cuda.current_stream(dev)
+            st_ptr = main.cuda_stream
+            p_text = text.d_text.data_ptr() if text.text_bytes else None
+            d_len = torch.empty(n, dtype=torch.int32, device=dev)
+            d_st = torch.empty(n, dtype=torch.int32, device=dev)
+            tp.head_measure(p_text, text.text_bytes, text.d_off.data_ptr(), n, None, n, MAX_TEXT_LEN, True, MIN_TEXT_LEN,
+                            d_len.data_ptr(), d_st.data_ptr(), st_ptr)
+            lens, status = d_len.cpu().numpy().astype(np.int64), d_st.cpu().numpy()
+            tp.check()
+            lap("measure_heads")
+
+            host_clean = np.flatnonzero(status & T.NEEDS_HOST)
+            cleaned: Dict[int, bytes] = {}
+            if len(host_clean):
+                off = text.d_off.cpu().numpy()
+                for i in host_clean.tolist():
+                    raw = text.d_text[int(off[i]):int(off[i + 1])].cpu().numpy().tobytes()
+                    t = normalize_text(raw.decode("utf-8", "surrogatepass"))
+                    cleaned[i] = t.encode("utf-8", "surrogatepass")
+                    lens[i] = len(cleaned[i])
+                    status[i] = T.SHORT if len(t) < MIN_TEXT_LEN else 0
+            kept = np.flatnonzero(status == 0)
+            if stats is not None:
+                stats.update(host_clean_docs=host_clean.tolist(), host_docs=[])
+            if len(kept) == 0:
+                raise RuntimeError("No products left after filtering.")
+            lo, hi = (0, len(kept)) if rows is None else (int(rows[0]), int(rows[1]))
+            if not (0 <= lo < hi <= len(kept)):
+                raise ValueError(f"rows=({lo}, {hi}) outside the {len(kept)} products left after filtering")
+            kept = kept[lo:hi]
+            m = len(kept)
+            lens_k = lens[kept]
+            lap("host_clean")
+
+            index = ProductIndex(None, n_rows=m, dim=HIDDEN, device=model.device, row_offset=lo, dtype=dtype)
+            keep_rows = data_dir is not None and dtype != "f32"
+            emb_parts: List[np.ndarray] = []
+            host_docs: List[int] = []
+            d_kept = torch.from_numpy(kept.astype(np.int32)).to(dev)
+            d_len_k, d_st_k = d_len[d_kept.long()], d_st[d_kept.long()]      # (the device's own status: a host-cleaned row writes nothing)
+            ends = np.cumsum(lens_k)
+            d_heads = None
+            r0 = 0
+            while r0 < m:
+                before = int(ends[r0 - 1]) if r0 else 0
+                r1 = max(r0 + 1, int(np.searchsorted(ends, before + int(head_bytes), side="right")))
+                nb = r1 - r0
+                boff = np.zeros(nb + 1, dtype=np.int64)
+                np.cumsum(lens_k[r0:r1], out=boff[1:])
+                nbytes = int(boff[-1])
+                if nbytes >= 2 ** 31:
+                    raise ValueError(f"the head of product row {int(kept[r0])} alone has {nbytes} bytes")
+                if d_heads is None or d_heads.numel() < nbytes + 16:
+                    d_heads = None
+                    d_heads = torch.empty(nbytes + 16, dtype=torch.uint8, device=dev)
+                d_boff = torch.from_numpy(boff).to(dev)
+                tp.head_write(p_text, text.text_bytes, text.d_off.data_ptr(), n, d_kept.data_ptr() + 4 * r0, nb, MAX_TEXT_LEN, True,
+                              MIN_TEXT_LEN, d_len_k.data_ptr() + 4 * r0, d_st_k.data_ptr() + 4 * r0, d_heads.data_ptr(), nbytes,
+                              d_boff.data_ptr(), st_ptr)
+                mine = [j for j in range(nb) if int(kept[r0 + j]) in cleaned]
+                _write_host_rows(d_heads, boff, mine, [cleaned[int(kept[r0 + j])] for j in mine])
+                tp.check()                            # (waits: the tokenizer's stream reads what this one wrote)
+                lap("write_heads")
+
+                def queue_docs(wp, a, b, L, cap):
+                    return wp.queue_dev(d_heads.data_ptr() + int(boff[a]), int(boff[b] - boff[a]), d_boff[a:b + 1] - int(boff[a]), L, cap)
+
+                def host_text(i):
+                    return d_heads[int(boff[i]):int(boff[i + 1])].cpu().numpy().tobytes().decode("utf-8", "surrogatepass")
+
+                blk: dict = {}
+                part = _embed_into(index, lens_k[r0:r1].tolist(), queue_docs, host_text, encoder, first_row=r0,
+                                   chunk_tokens=chunk_tokens, keep_rows=keep_rows, stats=blk)
+                host_docs += [r0 + i for i in blk["host_docs"]]
+                if keep_rows:
+                    emb_parts.append(part)
+                lap("tokenize_encode_store")
+                r0 = r1
+            if stats is not None:
+                stats["host_docs"] = host_docs
+    finally:
+        tp.close()
+
+    meta = pd.DataFrame({"sku": products["sku"].values[kept]})
+    for c in ("n_reviews", "avg_stars", "last_ts"):
+        meta[c] = products[c].values[kept] if c in products.columns else np.nan
+    emb = np.concatenate(emb_parts) if emb_parts else None
+    if data_dir is not None:
+        from .artifacts import save_artifacts
+        agg = text.agg_text()
+        meta["agg_text"] = np.asarray([agg[int(i)] for i in kept], dtype=object)
+        if emb is None:
+            emb = index.download_rows(0, index.n_rows)
+        save_artifacts(data_dir, meta, emb)
+        lap("write_files")
+    return index, meta, emb, kept
+
+
 def prepare_reviews(reviews):
     """nlp/11_build_product_embeddings.py:99-108: the five columns, id / sku / text as str, stars numeric, ts a UTC time."""
     import pandas as pd
@@ -667,6 +820,10 @@ def parse_args(argv=None):
                                  description="Build product or review embeddings on the GPU (nlp/11_build_product_embeddings.py's flags).")
     ap.add_argument("--target", choices=["product", "review"], required=True)
     ap.add_argument("--input", type=str, default="", help=f"default: {PRODUCT_INPUT} (product), {REVIEW_INPUT} (review)")
+    ap.add_argument("--reviews", type=str, default="",
+                    help="product target only: build from reviews_merged.parquet instead of --input -- products.load_reviews, "
+                         "build_products with agg_text kept on the device, build_product_embeddings_device; writes the same "
+                         "two files.  Not together with --input")
     ap.add_argument("--text-col", type=str, default="")
     ap.add_argument("--model", type=str, required=True, help="LOCAL model directory (weights + vocab.txt); nothing is fetched")
     ap.add_argument("--device", type=str, default="0", help="GPU ordinal (0, cuda:0)")
@@ -682,13 +839,35 @@ def parse_args(argv=None):
     ap.add_argument("--resume", action="store_true",
                     help="refused (exit status 2): the reference's resume reopens the output with a fresh writer and so "
                          "truncates the rows it claims to keep; reproducing that would lose data")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.reviews and args.input:
+        ap.error("--input and --reviews exclude each other: the product table is either read or built")
+    if args.reviews and args.target != "product":
+        ap.error("--reviews belongs to --target product (review embeddings read the review table with --input)")
+    return args
+
+
+def _main_product_from_reviews(args) -> int:
+    from . import products as P
+    from .cross_encoder import QueryEncoder
+    device = int(str(args.device).split(":")[-1])
+    reviews = P.load_reviews(args.reviews)
+    products, _, text = P.build_products(reviews, device=device, keep_device=True)
+    encoder = QueryEncoder.from_pretrained_dir(args.model, device=device, precision=args.precision)
+    index, meta, emb, _ = build_product_embeddings_device(products, text, encoder, chunk_tokens=max(1, args.batch) * 512,
+                                                          data_dir=args.out_dir)
+    print(f"[product] rows={len(meta):,}  batch={args.batch}", flush=True)
+    print(f"[ok] wrote {args.out_dir}/product_emb.npy shape={emb.shape}", flush=True)
+    print(f"[ok] wrote {args.out_dir}/product_emb_meta.parquet rows={len(meta):,}", flush=True)
+    return 0
 
 
 def main(argv=None) -> int:
     args = parse_args(argv)
     if args.target == "review":
         return _main_review(args)
+    if args.reviews:
+        return _main_product_from_reviews(args)
     import pandas as pd
     from .cross_encoder import QueryEncoder
     df = pd.read_parquet(args.input or PRODUCT_INPUT)

@@ -7,7 +7,8 @@ truncated `longest_first` to ``max_length``.
 `RerankText` is the token plane of an index on the device: per product the WordPiece ids of ``agg_text[:2000]`` -- the cut is
 in code points and is made BEFORE tokenising, so a word cut in half is tokenised as the half -- of which the first
 ``max_length - 3`` are kept (no longer text side survives the truncation), uint16, back to back.  It is tokenised once per
-index (embed.DeviceWordPiece; what that hands back, by wordpiece.py); per batch `RerankText.scores` assembles the packed
+index (embed.DeviceWordPiece; what that hands back, by wordpiece.py), from a column of str (`from_texts`) or from agg_text
+already on the device (`from_device`, over the raw heads of csrc/rr_textprep.hip); per batch `RerankText.scores` assembles the packed
 sequences of the candidates on the device (rr_pairs_measure_dev / rr_pairs_write_dev), runs `forward_packed_dev` on them and
 leaves the scores on the device.  `pack_queries` turns a batch's query ids into the arrays the kernels read.  `model_plane` /
 `model_pairs` state in numpy what the plane and the two kernels hold, as gate.model_gate_plane / model_gate_hits do for theirs.
@@ -152,6 +153,81 @@ class RerankText:
         self.host_docs: List[int] = []
 
     # ------------------------------------------------------------------ building
+    @staticmethod
+    def _check_build(tokenizer, max_length: int, chunk_docs: int) -> None:
+        """What a plane cannot be built for, said before anything touches the device."""
+        L = int(max_length)
+        if L < 3:
+            raise ValueError(f"max_length {L} leaves no room for [CLS] [SEP] [SEP]")
+        vocab_size = max(tokenizer.vocab.values()) + 1
+        if vocab_size > MAX_VOCAB:
+            raise ValueError(f"a vocabulary of {vocab_size} pieces does not fit the plane's uint16 ids: use rerank=\"host\"")
+        if int(chunk_docs) < 1:
+            raise ValueError("chunk_docs must be at least 1")
+
+    def _begin(self, tokenizer, max_length: int, n: int, max_bytes: Optional[int]) -> None:
+        self.max_length, self.vocab_size = int(max_length), max(tokenizer.vocab.values()) + 1
+        self.cls_id, self.sep_id = int(tokenizer.cls_id), int(tokenizer.sep_id)
+        self._parts, self._lens_all, self._done, self._max_bytes, self.n = [], np.zeros(n, dtype=np.int64), 0, max_bytes, int(n)
+        self._room(0)
+
+    def _room(self, tokens: int) -> None:
+        need = 2 * max(tokens, 1) + 8 * (self.n + 1)
+        if self._max_bytes is not None and need > self._max_bytes:
+            raise MemoryError(f"the token plane of {self.n} products needs {need} bytes of device memory or more, more than the "
+                              f"{self._max_bytes} allowed: use rerank=\"host\" (or raise rerank_max_bytes)")
+
+    def _block(self, wp, tokenizer, d_text: int, text_bytes: int, d_off, c0: int, host_head, also_host: Sequence[int] = ()) -> None:
+        """Documents [c0, c0 + nd) of the plane: their heads lie on the device at `d_text` (address of the first byte) with
+        the int64 offsets `d_off` [nd + 1] relative to it.  Tokenised by `wp` ([CLS], the first max_length - 3 pieces,
+        [SEP]), narrowed to uint16 and appended; what the device tokenizer hands back, and the documents `also_host` (whose
+        heads on the device are empty), are tokenised from ``host_head(i)`` (document i of the block as a str) and placed at
+        their own offsets."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        L, keep, nd = self.max_length, self.max_length - 3, int(d_off.numel()) - 1
+        packed, info, _, cap, _keep = wp.queue_dev(d_text, int(text_bytes), d_off, L - 1)
+        torch.cuda.current_stream(dev).synchronize()
+        h = info.numpy()
+        tok, _, pos, cu = wp.views(packed, nd, cap, int(h[0]))
+        cu_h = cu.cpu().numpy().astype(np.int64)
+        lens = cu_h[1:] - cu_h[:-1] - 2                     # (a handed-back document: the placeholder, 0)
+        host = sorted(set(np.flatnonzero(h[1:nd + 1]).tolist()) | set(int(i) for i in also_host))
+        host_ids = [np.asarray(tokenizer.text_ids(host_head(i))[:keep], dtype=np.int64) for i in host]
+        for i, ids in zip(host, host_ids):
+            lens[i] = len(ids)
+        new_off = np.zeros(nd + 1, dtype=np.int64)
+        np.cumsum(lens, out=new_off[1:])
+        m = int(new_off[-1])
+        self._room(self._done + m)
+        out = torch.empty(m, dtype=torch.int16, device=dev)
+        if m:
+            # the pieces without [CLS] / [SEP], each to its document's new offset + its place in the document
+            is_piece = pos > 0
+            is_piece[(cu[1:] - 1).long()] = False
+            doc = torch.repeat_interleave(torch.arange(nd, device=dev), (cu[1:] - cu[:-1]).long(), output_size=int(h[0]))
+            where = torch.from_numpy(new_off).to(dev)[doc[is_piece]] + pos[is_piece].long() - 1
+            out[where] = _narrow(tok[is_piece])
+            for i, ids in zip(host, host_ids):
+                if len(ids):
+                    out[int(new_off[i]):int(new_off[i + 1])] = _narrow(torch.from_numpy(ids).to(dev))
+        self._parts.append(out)
+        self._lens_all[c0:c0 + nd] = lens
+        self._done += m
+        self.host_docs += [c0 + i for i in host]
+
+    def _finish(self) -> "RerankText":
+        import torch
+        dev = torch.device("cuda", self.device)
+        plane_off = np.zeros(self.n + 1, dtype=np.int64)
+        np.cumsum(self._lens_all, out=plane_off[1:])
+        self.d_tok = torch.cat(self._parts) if self._done else torch.zeros(1, dtype=torch.int16, device=dev)
+        self.d_off = torch.from_numpy(plane_off).to(dev)
+        self.n_tokens = int(self._done)
+        self._parts = None
+        torch.cuda.current_stream(dev).synchronize()
+        return self
+
     @classmethod
     def from_texts(cls, texts: Sequence[str], tokenizer, max_length: int, device: int = 0, *, max_chars: int = MAX_CHARS,
                    max_bytes: Optional[int] = None, row_offset: int = 0, chunk_docs: int = CHUNK_DOCS,
@@ -166,85 +242,98 @@ class RerankText:
         product: 10M products of about 450 tokens are about 9 GB."""
         import torch
         from .embed import DeviceWordPiece, _stage_rows, _utf8_column
-        L = int(max_length)
-        if L < 3:
-            raise ValueError(f"max_length {L} leaves no room for [CLS] [SEP] [SEP]")
-        vocab_size = max(tokenizer.vocab.values()) + 1
-        if vocab_size > MAX_VOCAB:
-            raise ValueError(f"a vocabulary of {vocab_size} pieces does not fit the plane's uint16 ids: use rerank=\"host\"")
-        if int(chunk_docs) < 1:
-            raise ValueError("chunk_docs must be at least 1")
+        cls._check_build(tokenizer, max_length, chunk_docs)
         self = cls(device, row_offset)
-        self.max_length, self.vocab_size = L, vocab_size
-        self.cls_id, self.sep_id = int(tokenizer.cls_id), int(tokenizer.sep_id)
-        keep = L - 3
         heads = [str(t)[:max_chars] for t in texts]
         raw, off = _utf8_column(heads)
         n, total = len(off) - 1, int(off[-1])
-
-        def room(tokens: int) -> None:
-            need = 2 * max(tokens, 1) + 8 * (n + 1)
-            if max_bytes is not None and need > max_bytes:
-                raise MemoryError(f"the token plane of {n} products needs {need} bytes of device memory or more, more than the "
-                                  f"{max_bytes} allowed: use rerank=\"host\" (or raise rerank_max_bytes)")
-
-        room(0)
+        self._begin(tokenizer, max_length, n, max_bytes)
         dev = torch.device("cuda", self.device)
         wp = DeviceWordPiece(tokenizer, self.device, unicode=True)
-        parts, lens_all, done = [], np.zeros(n, dtype=np.int64), [0]
         try:
             with torch.cuda.device(dev):
                 main = torch.cuda.current_stream(dev)
                 d_text = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
                 d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64)).to(dev)
 
-                def block(c0: int, c1: int) -> None:
-                    nd, base = c1 - c0, int(off[c0])
-                    packed, info, _, cap, _keep = wp.queue_dev(d_text.data_ptr() + base, int(off[c1]) - base,
-                                                               d_off[c0:c1 + 1] - base, L - 1)
-                    main.synchronize()
-                    h = info.numpy()
-                    tok, _, pos, cu = wp.views(packed, nd, cap, int(h[0]))
-                    cu_h = cu.cpu().numpy().astype(np.int64)
-                    lens = cu_h[1:] - cu_h[:-1] - 2                     # (a handed-back document: the placeholder, 0)
-                    host = np.flatnonzero(h[1:nd + 1]).tolist()
-                    host_ids = [np.asarray(tokenizer.text_ids(heads[c0 + i])[:keep], dtype=np.int64) for i in host]
-                    for i, ids in zip(host, host_ids):
-                        lens[i] = len(ids)
-                    new_off = np.zeros(nd + 1, dtype=np.int64)
-                    np.cumsum(lens, out=new_off[1:])
-                    m = int(new_off[-1])
-                    room(done[0] + m)
-                    out = torch.empty(m, dtype=torch.int16, device=dev)
-                    if m:
-                        # the pieces without [CLS] / [SEP], each to its document's new offset + its place in the document
-                        is_piece = pos > 0
-                        is_piece[(cu[1:] - 1).long()] = False
-                        doc = torch.repeat_interleave(torch.arange(nd, device=dev), (cu[1:] - cu[:-1]).long(), output_size=int(h[0]))
-                        where = torch.from_numpy(new_off).to(dev)[doc[is_piece]] + pos[is_piece].long() - 1
-                        out[where] = _narrow(tok[is_piece])
-                        for i, ids in zip(host, host_ids):
-                            if len(ids):
-                                out[int(new_off[i]):int(new_off[i + 1])] = _narrow(torch.from_numpy(ids).to(dev))
-                    parts.append(out)
-                    lens_all[c0:c1] = lens
-                    done[0] += m
-                    self.host_docs += [c0 + i for i in host]
-
                 def on_rows(a: int, b: int) -> None:
                     for c0 in range(a, b, int(chunk_docs)):
-                        block(c0, min(b, c0 + int(chunk_docs)))
+                        c1, base = min(b, c0 + int(chunk_docs)), int(off[c0])
+                        self._block(wp, tokenizer, d_text.data_ptr() + base, int(off[c1]) - base, d_off[c0:c1 + 1] - base, c0,
+                                    lambda i: heads[c0 + i])
 
                 _stage_rows(raw, off, d_text, main, stage_bytes, on_rows)
                 wp.check()
-                plane_off = np.zeros(n + 1, dtype=np.int64)
-                np.cumsum(lens_all, out=plane_off[1:])
-                self.d_tok = torch.cat(parts) if done[0] else torch.zeros(1, dtype=torch.int16, device=dev)
-                self.d_off = torch.from_numpy(plane_off).to(dev)
-                self.n, self.n_tokens = int(n), int(done[0])
-                main.synchronize()
+                self._finish()
         finally:
             wp.close()
+        return self
+
+    @classmethod
+    def from_device(cls, text, tokenizer, max_length: int, *, rows=None, max_chars: int = MAX_CHARS,
+                    max_bytes: Optional[int] = None, row_offset: int = 0, chunk_docs: int = CHUNK_DOCS) -> "RerankText":
+        """From a products.DeviceProductText (agg_text where rr_products_concat_dev wrote it): the plane `from_texts` builds
+        from ``text.agg_text()``, with no host copy of the text.  ``rows``: the product rows the plane holds, in order
+        (int array, e.g. the ``kept`` of embed.build_product_embeddings_device; None = all).  ``chunk_docs`` documents at a
+        time: rr_textprep_head_measure_dev / rr_textprep_head_write_dev cut the raw heads (``str[:max_chars]``, read
+        through ``rows`` without a copy of the text) into a block buffer, and the block goes through the step `from_texts`
+        runs.  What the tokenizer hands back is read back from that buffer; a document whose head holds malformed UTF-8 has
+        no head on the device, and its bytes are fetched from the text."""
+        import torch
+        from . import textprep as T
+        from .embed import DeviceWordPiece
+        cls._check_build(tokenizer, max_length, chunk_docs)
+        self = cls(text.device, row_offset)
+        n_src = int(text.n)
+        rows = np.arange(n_src, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        n = len(rows)
+        if n and (rows.min() < 0 or rows.max() >= n_src):
+            raise ValueError(f"rows outside the {n_src} products of the text")
+        self._begin(tokenizer, max_length, n, max_bytes)
+        dev = torch.device("cuda", self.device)
+        wp = DeviceWordPiece(tokenizer, self.device, unicode=True)
+        tp = T.TextPrep(self.device)
+        try:
+            with torch.cuda.device(dev):
+                main = torch.cuda.current_stream(dev)
+                st = main.cuda_stream
+                p_text = text.d_text.data_ptr() if text.text_bytes else None
+                d_rows = torch.from_numpy(rows if n else np.zeros(1, dtype=np.int32)).to(dev)
+                src_off = None
+                for c0 in range(0, n, int(chunk_docs)):
+                    nd = min(n, c0 + int(chunk_docs)) - c0
+                    d_len = torch.empty(nd, dtype=torch.int32, device=dev)
+                    d_st = torch.empty(nd, dtype=torch.int32, device=dev)
+                    d_off = torch.empty(nd + 1, dtype=torch.int64, device=dev)
+                    args = (p_text, text.text_bytes, text.d_off.data_ptr(), n_src, d_rows.data_ptr() + 4 * c0, nd, int(max_chars),
+                            False, 0, d_len.data_ptr(), d_st.data_ptr())
+                    tp.head_measure(*args, st)
+                    tp.head_offsets(d_len.data_ptr(), d_st.data_ptr(), nd, d_off.data_ptr(), st)
+                    nbytes = int(d_off[nd].item())             # sizes the block buffer
+                    if nbytes >= 2 ** 31:
+                        raise ValueError(f"{nbytes} bytes of heads in one block: lower chunk_docs")
+                    d_heads = torch.empty(nbytes + 16, dtype=torch.uint8, device=dev)
+                    tp.head_write(*args, d_heads.data_ptr(), nbytes, d_off.data_ptr(), st)
+                    left = np.flatnonzero(d_st.cpu().numpy()).tolist()
+                    tp.check()
+                    off_h = d_off.cpu().numpy()
+
+                    def host_head(i):                              # (called inside this block's step only)
+                        nonlocal src_off
+                        if i in left:                          # malformed inside the head: no head on the device
+                            if src_off is None:
+                                src_off = text.d_off.cpu().numpy()
+                            r = int(rows[c0 + i])
+                            raw = text.d_text[int(src_off[r]):int(src_off[r + 1])].cpu().numpy().tobytes()
+                            return raw.decode("utf-8", "surrogatepass")[:max_chars]
+                        return d_heads[int(off_h[i]):int(off_h[i + 1])].cpu().numpy().tobytes().decode("utf-8", "surrogatepass")
+
+                    self._block(wp, tokenizer, d_heads.data_ptr(), nbytes, d_off, c0, host_head, left)
+                wp.check()
+                self._finish()
+        finally:
+            wp.close()
+            tp.close()
         return self
 
     @classmethod

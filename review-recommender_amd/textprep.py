@@ -4,6 +4,11 @@ Stands in for nlp/11_build_product_embeddings.py:110-118: `normalize_text`, the 
 `drop_duplicates(subset=["sku", "__txt"])`, in front of the device tokenizer.  `TextPrep` is a thin ctypes wrapper of the three
 stages (clean, dedup, compact); `model_clean` states in plain Python, without `re`, exactly what the clean kernel computes,
 needs_host included -- what wp_unicode.model_tokenize is for the tokenizer.
+
+The head calls (`head_measure`, `head_offsets`, `head_write`) serve product text that is already on the device
+(products.DeviceProductText): the first max_chars code points of a document of ANY length, normalised as nlp/11's
+normalize_text does (for embed.build_product_embeddings_device) or verbatim (str[:k], for RerankText.from_device).
+`model_head` is their statement in Python.
 """
 from __future__ import annotations
 
@@ -59,6 +64,61 @@ def model_clean_bytes(raw: bytes, spam: bool = True, max_chars: int = MAX_CHARS)
     if spam and _spammy(txt, out):
         status |= SPAM
     return txt.encode("utf-8"), status
+
+
+def _decode_one(raw: bytes, i: int) -> Tuple[int, int]:
+    """The code point that starts at raw[i], strictly: (code point, bytes), or (-1, 0) for a byte that starts nothing, too
+    few or wrong continuation bytes, an overlong form, a surrogate or a value above U+10FFFF."""
+    b = raw[i]
+    if b < 0x80:
+        return b, 1
+    if 0xC2 <= b <= 0xDF:
+        n, c, lowest = 2, b & 0x1F, 0x80
+    elif b & 0xF0 == 0xE0:
+        n, c, lowest = 3, b & 0x0F, 0x800
+    elif 0xF0 <= b <= 0xF4:
+        n, c, lowest = 4, b & 0x07, 0x10000
+    else:
+        return -1, 0
+    if i + n > len(raw):
+        return -1, 0
+    for k in range(1, n):
+        t = raw[i + k]
+        if t & 0xC0 != 0x80:
+            return -1, 0
+        c = (c << 6) | (t & 0x3F)
+    if c < lowest or c > 0x10FFFF or 0xD800 <= c <= 0xDFFF:
+        return -1, 0
+    return c, n
+
+
+def model_head(raw: bytes, max_chars: int, normalize: bool, min_chars: int = 0) -> Tuple[bytes, int]:
+    """What rr_textprep_head_measure_dev / rr_textprep_head_write_dev answer for one document of ANY length: (the UTF-8
+    bytes of its head, status word).  A walk over code points, decoded strictly one at a time WHILE fewer than max_chars
+    have been emitted; a malformed one met during that walk gives (b"", NEEDS_HOST), bytes behind the point where the walk
+    stops are never examined.  normalize=True: a whitespace code point (WHITESPACE) sets a pending flag and emits nothing;
+    any other first emits one U+0020 if the flag is set and something was emitted before -- the space counts, and when it
+    is the max_chars-th emission the walk stops there -- then itself: embed.normalize_text (strip, \\s+ -> " ",
+    [:max_chars]) as a prefix computation.  normalize=False: every code point is emitted verbatim: s[:max_chars].
+    Status: SHORT when min_chars > 0 and fewer than min_chars code points were emitted, else 0."""
+    out = bytearray()
+    emitted, pending, i = 0, False, 0
+    while emitted < max_chars and i < len(raw):
+        c, n = _decode_one(raw, i)
+        if n == 0:
+            return b"", NEEDS_HOST
+        if normalize and c in WHITESPACE:
+            pending = True
+        else:
+            if pending and emitted:
+                out.append(0x20)
+                emitted += 1
+            pending = False
+            if emitted < max_chars:
+                out += raw[i:i + n]
+                emitted += 1
+        i += n
+    return bytes(out), (SHORT if min_chars > 0 and emitted < min_chars else 0)
 
 
 def _spammy(txt: str, chars: List[str]) -> bool:
@@ -126,6 +186,31 @@ class TextPrep:
                                                        int(out_bytes), C.c_void_p(out_offsets), C.c_void_p(src_row),
                                                        C.c_void_p(count), C.c_void_p(stream)), "rr_textprep_compact_dev")
 
+    def head_measure(self, text: int, text_bytes: int, offsets: int, n_src_docs: int, doc_rows: Optional[int], n_docs: int,
+                     max_chars: int, normalize: bool, min_chars: int, out_len: int, status: int,
+                     stream: Optional[int] = None) -> None:
+        """Pass 1 of the heads (`model_head`): lengths and status words of n_docs documents; doc_rows: address of the int32
+        source row of every output document, None = identity."""
+        _lib.check(_lib.load().rr_textprep_head_measure_dev(self._h, C.c_void_p(text), int(text_bytes), C.c_void_p(offsets),
+                                                            int(n_src_docs), C.c_void_p(doc_rows), int(n_docs), int(max_chars),
+                                                            1 if normalize else 0, int(min_chars), C.c_void_p(out_len),
+                                                            C.c_void_p(status), C.c_void_p(stream)), "rr_textprep_head_measure_dev")
+
+    def head_offsets(self, out_len: int, status: int, n_docs: int, out_off: int, stream: Optional[int] = None) -> None:
+        """out_off int64 [n_docs + 1]: where pass 2 writes the surviving heads, back to back."""
+        _lib.check(_lib.load().rr_textprep_head_offsets_dev(self._h, C.c_void_p(out_len), C.c_void_p(status), int(n_docs),
+                                                            C.c_void_p(out_off), C.c_void_p(stream)), "rr_textprep_head_offsets_dev")
+
+    def head_write(self, text: int, text_bytes: int, offsets: int, n_src_docs: int, doc_rows: Optional[int], n_docs: int,
+                   max_chars: int, normalize: bool, min_chars: int, out_len: int, status: int, out_text: int, out_bytes: int,
+                   out_off: int, stream: Optional[int] = None) -> None:
+        """Pass 2: the heads of the documents whose status word is 0, at out_text + out_off[j]."""
+        _lib.check(_lib.load().rr_textprep_head_write_dev(self._h, C.c_void_p(text), int(text_bytes), C.c_void_p(offsets),
+                                                          int(n_src_docs), C.c_void_p(doc_rows), int(n_docs), int(max_chars),
+                                                          1 if normalize else 0, int(min_chars), C.c_void_p(out_len),
+                                                          C.c_void_p(status), C.c_void_p(out_text), int(out_bytes),
+                                                          C.c_void_p(out_off), C.c_void_p(stream)), "rr_textprep_head_write_dev")
+
     def check(self) -> None:
         """Raises ValueError when a call since the last check met offsets that decrease or leave the text (waits for the device)."""
         bad = C.c_int32()
@@ -155,6 +240,42 @@ class TextPrep:
             torch.cuda.current_stream(dev).synchronize()
             out, lens, st = d_out.cpu().numpy(), d_len.cpu().numpy()[:n], d_st.cpu().numpy()[:n]
         return out, lens, st
+
+    def head_docs(self, docs: Sequence[bytes], max_chars: int, normalize: bool, min_chars: int = 0,
+                  doc_rows: Optional[Sequence[int]] = None, offsets: Optional[np.ndarray] = None, capacity: Optional[int] = None):
+        """(output buffer, out_off, lengths, status words) of measure + offsets + write for `docs`; `doc_rows` picks the
+        source document of every output document, `offsets` replaces the running sum of the lengths and `capacity` the size
+        the write call is told (tests: broken arguments; the buffer itself always has room).  The buffer is filled with 0xEE
+        first.  Does not call check()."""
+        import torch
+        blob = b"".join(docs)
+        off = np.zeros(len(docs) + 1, dtype=np.int64)
+        np.cumsum([len(d) for d in docs], out=off[1:])
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n_src = len(off) - 1
+        rows = None if doc_rows is None else np.ascontiguousarray(doc_rows, dtype=np.int32)
+        n = n_src if rows is None else len(rows)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev)
+            d_text = torch.from_numpy(np.frombuffer(blob + b"\0", dtype=np.uint8).copy()).to(dev)
+            d_off = torch.from_numpy(off).to(dev)
+            d_rows = None if rows is None else torch.from_numpy(rows if n else np.zeros(1, np.int32)).to(dev)
+            p_rows = None if d_rows is None else d_rows.data_ptr()
+            d_len = torch.full((max(n, 1),), -7, dtype=torch.int32, device=dev)
+            d_st = torch.full((max(n, 1),), -7, dtype=torch.int32, device=dev)
+            d_out_off = torch.full((n + 1,), -7, dtype=torch.int64, device=dev)
+            args = (d_text.data_ptr(), len(blob), d_off.data_ptr(), n_src, p_rows, n, max_chars, normalize, min_chars,
+                    d_len.data_ptr(), d_st.data_ptr())
+            self.head_measure(*args, st.cuda_stream)
+            self.head_offsets(d_len.data_ptr(), d_st.data_ptr(), n, d_out_off.data_ptr(), st.cuda_stream)
+            out_off = d_out_off.cpu().numpy()
+            room = max(int(out_off[-1]), 0)
+            d_out = torch.full((room + 16,), 0xEE, dtype=torch.uint8, device=dev)
+            self.head_write(*args, d_out.data_ptr(), room if capacity is None else capacity, d_out_off.data_ptr(), st.cuda_stream)
+            st.synchronize()
+            return d_out.cpu().numpy(), out_off, d_len.cpu().numpy()[:n], d_st.cpu().numpy()[:n]
 
     def close(self) -> None:
         if getattr(self, "_h", None):

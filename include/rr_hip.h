@@ -435,36 +435,34 @@ int rr_ce_set_wide_range(rr_ce* ce, int32_t on);
 /* ------------------------------------------------------------ WordPiece tokenisation on the device */
 
 /* What SentenceTransformer.encode does to its texts before the model runs (nlp/11_build_product_embeddings.py:46-47: the
- * model's BertTokenizer, lower-casing), for documents whose bytes are all below 0x80 (csrc/rr_wordpiece.hip).
+ * model's BertTokenizer, lower-casing), for UTF-8 documents (csrc/rr_wordpiece.hip: rr_wp_tokenize_utf8): the host
+ * tokenizer's ids, all-ASCII documents included.
  * Pieces: piece i (bytes h_piece_off[i] .. h_piece_off[i+1]) has token id i; an empty piece stands for "no such id";
- * pieces with a byte >= 0x80 or longer than max_chars_per_word (<= 255) can never match ASCII text and are left out of the
- * device table.  unk / cls / sep are ids in [0, n_pieces). */
+ * pieces of more than max_chars_per_word (<= 255) code points after their ## can never match and are left out of the
+ * device table.  unk / cls / sep are ids in [0, n_pieces).
+ * The three arrays are the per-code-point table of review-recommender_amd/wp_unicode.py (unicode_tables(): built from the
+ * interpreter's unicodedata so that it agrees with the host tokenizer): h_stage1 [n_stage1 = 8704] maps each block of 128
+ * code points to a block of h_stage2 [n_stage2, whole blocks]; an entry = class (bits 0-2: 0 deleted, 1 blank, 2 CJK,
+ * 3 other, 4 hard) | mapped code points n (bits 3-4, 0..3) | identity (bit 5) | punctuation flag of mapped code point j
+ * (bit 6 + j) | first mapped code point in h_pool [n_pool] (bits 9-31).  The tables are checked here (RR_E_INVALID): nothing
+ * the kernel indexes can leave them.  needs_host = 1 only for a document that, in the bytes the kernel reads (the whole
+ * document, or its first 4 096 bytes cut back to a character boundary): is malformed UTF-8 (overlong forms, surrogates,
+ * values above U+10FFFF, truncated sequences); holds a hard code point; has a mapped text of more than 4 096 bytes; or is
+ * longer than the window without max_length - 2 pieces in it. */
 typedef struct rr_wp rr_wp;
-int rr_wp_create(int32_t device, const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces,
-                 int32_t unk_id, int32_t cls_id, int32_t sep_id, int32_t max_chars_per_word, rr_wp** out);
-int rr_wp_destroy(rr_wp* wp);
-/* The UTF-8 handle: rr_wp_encode_dev on it tokenises Unicode text (csrc/rr_wordpiece.hip: rr_wp_tokenize_utf8) and gives the
- * host tokenizer's ids for it, all-ASCII documents included.  The three arrays are the per-code-point table of
- * review-recommender_amd/wp_unicode.py (unicode_tables(): built from the interpreter's unicodedata so that it agrees with
- * the host tokenizer): h_stage1 [n_stage1 = 8704] maps each block of 128 code points to a block of h_stage2 [n_stage2, whole
- * blocks]; an entry = class (bits 0-2: 0 deleted, 1 blank, 2 CJK, 3 other, 4 hard) | mapped code points n (bits 3-4, 0..3) |
- * identity (bit 5) | punctuation flag of mapped code point j (bit 6 + j) | first mapped code point in h_pool [n_pool]
- * (bits 9-31).  The tables are checked here (RR_E_INVALID): nothing the kernel indexes can leave them.  The piece table
- * keeps pieces with bytes >= 0x80, and max_chars_per_word counts code points.  needs_host = 1 on this handle only for a
- * document that, in the bytes the kernel reads (the whole document, or its first 4 096 bytes cut back to a character
- * boundary): is malformed UTF-8 (overlong forms, surrogates, values above U+10FFFF, truncated sequences); holds a hard code
- * point; has a mapped text of more than 4 096 bytes; or is longer than the window without max_length - 2 pieces in it. */
 int rr_wp_create_utf8(int32_t device, const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces,
                       int32_t unk_id, int32_t cls_id, int32_t sep_id, int32_t max_chars_per_word,
                       const uint16_t* h_stage1, int32_t n_stage1, const uint32_t* h_stage2, int32_t n_stage2,
                       const uint32_t* h_pool, int32_t n_pool, rr_wp** out);
+int rr_wp_destroy(rr_wp* wp);
 /* n_docs UTF-8 documents (document s = bytes d_text_off[s] .. d_text_off[s+1] of d_text; text_bytes = size of d_text,
  * below 2^31) -> exactly what rr_ce_forward_dev takes: sequence s = [CLS], the first max_length - 2 pieces, [SEP]; type ids
  * 0; position = index inside the sequence; d_cu_seqlens [n_docs + 1] the running sum; *d_max_len the longest sequence.
- * For an all-ASCII document the ids equal the host tokenizer's, id for id.  On a handle of rr_wp_create a document with
- * any byte >= 0x80 is not tokenised (a handle of rr_wp_create_utf8 tokenises it, with the exceptions listed there): d_needs_host[s] = 1 and its sequence is the placeholder [CLS] [SEP] (the packing stays dense; the caller
- * tokenises it on the host).  The kernel keeps the first 4 096 bytes of a document on chip: a longer document is
- * answered from them when they already hold max_length - 2 pieces in words that end inside them, else needs_host = 1.
+ * The ids equal the host tokenizer's, id for id.  A document the kernel hands back (the exceptions listed at
+ * rr_wp_create_utf8) is not tokenised: d_needs_host[s] = 1 and its sequence is the placeholder [CLS] [SEP] (the packing
+ * stays dense; the caller tokenises it on the host).  The kernel keeps the first 4 096 bytes of a document on chip: a longer
+ * document is answered from them when they already hold max_length - 2 pieces in words that end inside them, else
+ * needs_host = 1.
  * token_capacity (elements of the three id arrays; n_docs * max_length always suffices, 2 * n_docs is required) bounds
  * the writes: ids beyond it are dropped and d_cu_seqlens[n_docs] tells what was needed.
  * Asynchronous on `stream`, all d_ pointers device pointers; no host wait, except that the first call of a larger
@@ -479,15 +477,12 @@ int rr_wp_encode_dev(rr_wp* wp, const uint8_t* d_text, int64_t text_bytes, const
                      int32_t max_length, int64_t token_capacity, int32_t* d_token_ids, int32_t* d_type_ids, int32_t* d_pos_ids,
                      int32_t* d_cu_seqlens, int32_t* d_needs_host, int32_t* d_max_len, void* stream);
 int rr_wp_status(rr_wp* wp, int32_t* out_bad_docs);
-/* The piece table rr_wp_create puts on the device, built on the host (no device needed; tests walk it): n_slots =
+/* The piece table rr_wp_create_utf8 puts on the device, built on the host (no device needed; tests walk it): n_slots =
  * rr_wp_table_slots(n_pieces) (a power of two, at least twice the pieces); h_slots [n_slots][4] int32 = polynomial hash
- * (base 0x01000193 mod 2^32) of the piece's bytes without its ##, first byte in h_piece_bytes, length | (## form) << 16,
- * id (-1 = empty); open addressing, linear probing from murmur3's finaliser of hash ^ (length word * 0x9E3779B1). */
+ * (base 0x01000193 mod 2^32) of the piece's bytes without its ##, first byte in h_piece_bytes, length in BYTES |
+ * (## form) << 16, id (-1 = empty); open addressing, linear probing from murmur3's finaliser of hash ^ (length word *
+ * 0x9E3779B1).  max_chars_per_word counts code points (the bytes that are not 10xxxxxx). */
 int rr_wp_table_slots(int32_t n_pieces, int32_t* out_slots);
-int rr_wp_build_table(const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces, int32_t max_chars_per_word,
-                      int32_t n_slots, int32_t* h_slots, int32_t* out_kept);
-/* The same for a UTF-8 handle: pieces with bytes >= 0x80 are kept, and max_chars_per_word counts code points (the bytes that
- * are not 10xxxxxx); the length word of a slot stays the piece's length in BYTES. */
 int rr_wp_build_table_utf8(const uint8_t* h_piece_bytes, const int64_t* h_piece_off, int32_t n_pieces, int32_t max_chars_per_word,
                            int32_t n_slots, int32_t* h_slots, int32_t* out_kept);
 

@@ -103,14 +103,12 @@ PROTOTYPES = {
     "rr_ce_last_forward_ms": (C.c_int, [c_vp, P(c_f32)]),
     "rr_ce_range_status": (C.c_int, [c_vp, P(C.c_int32)]),
     "rr_ce_set_wide_range": (C.c_int, [c_vp, C.c_int32]),
-    "rr_wp_create": (C.c_int, [c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, P(c_vp)]),
     "rr_wp_create_utf8": (C.c_int, [c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32,
                                     P(c_vp)]),
     "rr_wp_destroy": (C.c_int, [c_vp]),
     "rr_wp_encode_dev": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rr_wp_status": (C.c_int, [c_vp, P(c_i32)]),
     "rr_wp_table_slots": (C.c_int, [c_i32, P(c_i32)]),
-    "rr_wp_build_table": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, P(c_i32)]),
     "rr_wp_build_table_utf8": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, P(c_i32)]),
     "rr_textprep_create": (C.c_int, [c_i32, P(c_vp)]),
     "rr_textprep_destroy": (C.c_int, [c_vp]),

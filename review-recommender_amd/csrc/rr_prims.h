@@ -1,6 +1,6 @@
 // rr_prims.h -- what the index builders share (rr_wordpiece.hip, rr_textprep.hip, rr_doctok.hip, rr_bm25_build.hip,
-// rr_products.hip): the workgroup scan, the device-wide scan, the stable radix sort, and the small helpers every builder
-// needs once.
+// rr_products.hip) and the query front (rr_query.hip): the workgroup scan, the device-wide scan, the stable radix sort, the
+// vocabulary table, and the small helpers every builder needs once.
 #pragma once
 
 #include "rr_common.h"
@@ -288,6 +288,83 @@ static int rr_radix_sort(hipStream_t st, int64_t n, int passes, const uint32_t* 
         RR_HIP_TRY(hipGetLastError());
     }
     return RR_OK;
+}
+
+// ---------------------------------------------------------------- the vocabulary table
+// An open-addressing table over a list of strings (bytes + int64 offsets; string p has id p), built on the host and probed
+// on the device: the WordPiece pieces (rr_wordpiece.hip) and the BM25 vocabulary of the query front (rr_query.hip).  A
+// string is found by the polynomial hash of its bytes and a KEY word, its length in bytes plus whatever else tells two
+// strings of the same bytes apart (WordPiece: the ## form << 16).  The slots are what the Python side and the tests read
+// as [n_slots][4] int32.
+#define RR_TAB_BASE 0x01000193u                        // odd: the polynomial hash is taken mod 2^32
+
+struct rr_tab_entry {    // one slot, 16 bytes; id < 0 = empty
+    uint32_t hash;       // polynomial hash of the bytes compared
+    int32_t off;         // their first byte in the list's bytes
+    int32_t key;
+    int32_t id;
+};
+
+__host__ __device__ static inline uint32_t rr_tab_slot_of(uint32_t hash, int32_t key) {
+    uint32_t h = hash ^ ((uint32_t)key * 0x9E3779B1u);
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;     // murmur3's finaliser
+    return h;
+}
+
+static inline int32_t rr_tab_slots_for(int32_t n) {    // a power of two, at least 64 and at least 2 n (n <= 2^28)
+    int32_t slots = 64;
+    while (slots < 2 * (int64_t)n) slots <<= 1;
+    return slots;
+}
+
+// Fills `slots` from the n strings.  filter(a, b, &first, &key) says of the string at bytes [a, b) whether it is kept, and
+// if so which bytes are compared, [first, b), and under which key.  A string listed twice keeps its LAST id (what a dict
+// built from the list holds).  Returns the strings kept, or -1 when n_slots is too small.
+template <class Filter>
+static int64_t rr_tab_fill(const uint8_t* bytes, const int64_t* off, int32_t n, int32_t n_slots, rr_tab_entry* slots,
+                           Filter filter) {
+    for (int32_t s = 0; s < n_slots; ++s) slots[s] = rr_tab_entry{0u, 0, 0, -1};
+    int64_t kept = 0;
+    for (int32_t p = 0; p < n; ++p) {
+        int64_t a = 0;
+        const int64_t b = off[p + 1];
+        int32_t key = 0;
+        if (!filter(off[p], b, &a, &key)) continue;
+        uint32_t h = 0;
+        for (int64_t i = a; i < b; ++i) h = h * RR_TAB_BASE + bytes[i];
+        if (2 * (kept + 1) > n_slots) return -1;
+        uint32_t s = rr_tab_slot_of(h, key) & (uint32_t)(n_slots - 1);
+        bool dup = false;
+        while (slots[s].id >= 0) {
+            if (slots[s].hash == h && slots[s].key == key && memcmp(bytes + slots[s].off, bytes + a, (size_t)(b - a)) == 0) {
+                dup = true;
+                break;
+            }
+            s = (s + 1) & (uint32_t)(n_slots - 1);
+        }
+        slots[s] = rr_tab_entry{h, (int32_t)a, key, p};
+        if (!dup) ++kept;
+    }
+    return kept;
+}
+
+// The id of the string of `len` bytes at `word` with this hash and key, or -1.  One 16-byte load per slot; hash and key are
+// compared before the bytes.  (The table is at most half full: an empty slot ends the walk.)
+__device__ __forceinline__ int rr_tab_lookup(const rr_tab_entry* __restrict__ table, uint32_t mask, const uint8_t* __restrict__ bytes,
+                                             uint32_t hash, int32_t key, int len, const uint8_t* word) {
+    uint32_t s = rr_tab_slot_of(hash, key) & mask;
+    for (uint32_t probes = 0; probes <= mask; ++probes) {
+        const int4 raw = *reinterpret_cast<const int4*>(table + s);
+        if (raw.w < 0) return -1;
+        if ((uint32_t)raw.x == hash && raw.z == key) {
+            const uint8_t* p = bytes + raw.y;
+            int k = 0;
+            while (k < len && p[k] == word[k]) ++k;
+            if (k == len) return raw.w;
+        }
+        s = (s + 1) & mask;
+    }
+    return -1;
 }
 
 #endif  // __HIPCC__

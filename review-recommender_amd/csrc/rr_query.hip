@@ -47,7 +47,6 @@
 #define QF_GATE_TERMS 64                           // rr_gate_limits: terms and term bytes per query
 #define QF_GATE_BYTES 1024
 #define QF_MAX_STATIC 64                           // static groups (colours + synonyms), colours at most 32
-#define QF_BASE 0x01000193u                        // odd: the polynomial hash is taken mod 2^32
 
 #define QF_FLAG_QUERY 1                            // needs_host bits: the query is longer than QF_MAX_QUERY bytes,
 #define QF_FLAG_TOKEN 2                            // a token is longer than QF_MAX_TOKEN bytes,
@@ -55,15 +54,8 @@
 #define QF_FLAG_WP 8                               // the WordPiece kernel handed the query back,
 #define QF_FLAG_SPAN 16                            // the offsets decrease or leave the text (counted by rr_query_status)
 
-struct qf_entry {        // one slot of the vocabulary table; id < 0 = empty
-    uint32_t hash;       // polynomial hash of the entry's bytes
-    int32_t off;         // first byte in the vocabulary's bytes
-    int32_t len;
-    int32_t id;
-};
-
 struct qf_tables {       // the per-index tables on the device
-    const qf_entry* table;
+    const rr_tab_entry* table;  // the BM25 vocabulary (rr_prims.h: the vocabulary table), key = length in bytes
     uint32_t mask;       // slots - 1
     const uint8_t* vbytes;
     const uint64_t* stop;       // stop words, packed little endian
@@ -85,49 +77,19 @@ struct rr_query {
     std::mutex mu;
 };
 
-__host__ __device__ static inline uint32_t qf_slot_of(uint32_t hash, int32_t len) {
-    uint32_t h = hash ^ ((uint32_t)len * 0x9E3779B1u);
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;     // murmur3's finaliser
-    return h;
-}
-
 static inline bool qf_token_byte(uint8_t c) { return (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') || c == '\''; }
-
-static int32_t qf_slots_for(int32_t n_entries) {
-    int32_t n = 64;
-    while (n < 2 * (int64_t)n_entries) n <<= 1;
-    return n;
-}
 
 // The table on the host: every entry a device-tokenised query token can equal (1 .. QF_MAX_TOKEN bytes of [a-z0-9']).
 // Returns the entries kept, or -1 when n_slots is too small.
-static int64_t qf_fill_table(const uint8_t* bytes, const int64_t* off, int32_t n_entries, int32_t n_slots, qf_entry* slots) {
-    for (int32_t s = 0; s < n_slots; ++s) slots[s] = qf_entry{0u, 0, 0, -1};
-    int64_t kept = 0;
-    for (int32_t p = 0; p < n_entries; ++p) {
-        const int64_t a = off[p], b = off[p + 1];
-        if (b - a < 1 || b - a > QF_MAX_TOKEN) continue;
-        bool ok = true;
-        uint32_t h = 0;
-        for (int64_t i = a; i < b; ++i) {
-            ok = ok && qf_token_byte(bytes[i]);
-            h = h * QF_BASE + bytes[i];
-        }
-        if (!ok) continue;
-        if (2 * (kept + 1) > n_slots) return -1;
-        uint32_t s = qf_slot_of(h, (int32_t)(b - a)) & (uint32_t)(n_slots - 1);
-        bool dup = false;
-        while (slots[s].id >= 0) {         // an entry listed twice keeps its LAST id (what a dict holds)
-            if (slots[s].hash == h && slots[s].len == b - a && memcmp(bytes + slots[s].off, bytes + a, (size_t)(b - a)) == 0) {
-                dup = true;
-                break;
-            }
-            s = (s + 1) & (uint32_t)(n_slots - 1);
-        }
-        slots[s] = qf_entry{h, (int32_t)a, (int32_t)(b - a), p};
-        if (!dup) ++kept;
-    }
-    return kept;
+static int64_t qf_fill_table(const uint8_t* bytes, const int64_t* off, int32_t n_entries, int32_t n_slots, rr_tab_entry* slots) {
+    return rr_tab_fill(bytes, off, n_entries, n_slots, slots, [=](int64_t a, int64_t b, int64_t* first, int32_t* key) {
+        if (b - a < 1 || b - a > QF_MAX_TOKEN) return false;
+        for (int64_t i = a; i < b; ++i)
+            if (!qf_token_byte(bytes[i])) return false;
+        *first = a;
+        *key = (int32_t)(b - a);
+        return true;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ device helpers
@@ -139,15 +101,8 @@ __device__ __forceinline__ bool qf_same(const uint8_t* a, const uint8_t* b, int 
 
 __device__ static int32_t qf_lookup(const qf_tables& tb, const uint8_t* p, int m) {
     uint32_t h = 0;
-    for (int j = 0; j < m; ++j) h = h * QF_BASE + p[j];
-    uint32_t s = qf_slot_of(h, m) & tb.mask;
-    for (uint32_t probes = 0; probes <= tb.mask; ++probes) {       // (the table is at most half full: an empty slot ends the walk)
-        const qf_entry e = tb.table[s];
-        if (e.id < 0) return -1;
-        if (e.hash == h && e.len == m && qf_same(tb.vbytes + e.off, p, m)) return e.id;
-        s = (s + 1) & tb.mask;
-    }
-    return -1;
+    for (int j = 0; j < m; ++j) h = h * RR_TAB_BASE + p[j];
+    return rr_tab_lookup(tb.table, tb.mask, tb.vbytes, h, m, m, p);
 }
 
 // The synonym group whose key the token is, or -1.
@@ -587,7 +542,7 @@ extern "C" int rr_query_limits(int32_t* out_max_query, int32_t* out_max_token, i
 
 extern "C" int rr_query_table_slots(int32_t n_entries, int32_t* out_slots) {
     RR_REQUIRE(out_slots && n_entries >= 0 && n_entries <= (1 << 28), "rr_query_table_slots: %d entries outside [0, 2^28]", n_entries);
-    *out_slots = qf_slots_for(n_entries);
+    *out_slots = rr_tab_slots_for(n_entries);
     return RR_OK;
 }
 
@@ -606,9 +561,9 @@ extern "C" int rr_query_build_table(const uint8_t* h_bytes, const int64_t* h_off
     int rc = qf_check_vocab("rr_query_build_table", h_bytes, h_off, n_entries);
     if (rc) return rc;
     RR_REQUIRE(h_slots && out_kept, "rr_query_build_table: NULL output");
-    RR_REQUIRE(n_slots == qf_slots_for(n_entries), "rr_query_build_table: n_slots %d, rr_query_table_slots says %d", n_slots,
-               qf_slots_for(n_entries));
-    const int64_t kept = qf_fill_table(h_bytes, h_off, n_entries, n_slots, reinterpret_cast<qf_entry*>(h_slots));
+    RR_REQUIRE(n_slots == rr_tab_slots_for(n_entries), "rr_query_build_table: n_slots %d, rr_query_table_slots says %d", n_slots,
+               rr_tab_slots_for(n_entries));
+    const int64_t kept = qf_fill_table(h_bytes, h_off, n_entries, n_slots, reinterpret_cast<rr_tab_entry*>(h_slots));
     RR_REQUIRE(kept >= 0, "rr_query_build_table: table overflow");
     *out_kept = (int32_t)kept;
     return RR_OK;
@@ -680,8 +635,8 @@ extern "C" int rr_query_create(int32_t device, const uint8_t* h_vocab_bytes, con
     }
     RR_REQUIRE(max_groups * QF_MAX_TOKEN <= QF_GATE_BYTES, "rr_query_create: %d keyword groups exceed the gate's term bytes", max_groups);
 
-    const int32_t n_slots = qf_slots_for(n_vocab);
-    std::vector<qf_entry> slot_mem((size_t)n_slots);
+    const int32_t n_slots = rr_tab_slots_for(n_vocab);
+    std::vector<rr_tab_entry> slot_mem((size_t)n_slots);
     const int64_t kept = qf_fill_table(h_vocab_bytes, h_vocab_off, n_vocab, n_slots, slot_mem.data());
     RR_REQUIRE(kept >= 0, "rr_query_create: table overflow");
     std::vector<uint64_t> stop_mem((size_t)n_stop + 1);
@@ -705,7 +660,7 @@ extern "C" int rr_query_create(int32_t device, const uint8_t* h_vocab_bytes, con
         return d;
     };
     qf_tables& t = h->t;
-    t.table = (const qf_entry*)up(slot_mem.data(), slot_mem.size() * sizeof(qf_entry));
+    t.table = (const rr_tab_entry*)up(slot_mem.data(), slot_mem.size() * sizeof(rr_tab_entry));
     t.mask = (uint32_t)(n_slots - 1);
     t.vbytes = (const uint8_t*)up(h_vocab_bytes, (size_t)h_vocab_off[n_vocab]);
     t.stop = (const uint64_t*)up(stop_mem.data(), (size_t)n_stop * 8);

@@ -9,10 +9,10 @@ over `normalize_text(agg_text)`), the builder of product_emb.npy / product_emb_m
     rr_index_store_rows_dev   x / max(||x||, 1e-12) into the index's rows
 
 with no host hop between the three: the host reads back two integers per chunk (tokens, longest sequence: what the forward
-call takes as arguments) and the needs_host flags, and prepares chunk i + 1 while chunk i runs.  The tokenizer is the UTF-8
-kernel (Unicode text through the table of wp_unicode.py); the few documents it flags (a hard code point, a mapped text beyond
+call takes as arguments) and the needs_host flags, and prepares chunk i + 1 while chunk i runs.  The tokenizer takes UTF-8
+(Unicode text through the table of wp_unicode.py); the few documents it flags (a hard code point, a mapped text beyond
 its buffers: wp_unicode.model_tokenize) are tokenised by wordpiece.py and encoded in one small pass at the end, scattered into
-their rows.  RR_WP_ASCII=1 in the environment restores the ASCII kernel, which flags every document with a byte >= 0x80.
+their rows.
 
 Review embeddings (nlp/11...:95-169, the builder of reviews_with_embeddings.parquet) take the same chain behind three more
 device stages (csrc/rr_textprep.hip, textprep.py), because the reference cleans review text before the model sees it:
@@ -33,7 +33,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import os
 import re
 import sys
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -101,7 +100,7 @@ def filter_products(products, text_col: str = "agg_text"):
 
 # ---------------------------------------------------------------------------------- the piece table
 def piece_arrays(vocab: Dict[str, int]) -> Tuple[np.ndarray, np.ndarray]:
-    """(bytes, offsets) of rr_wp_create: piece i = the vocabulary string with id i, empty where no string has that id."""
+    """(bytes, offsets) of rr_wp_create_utf8: piece i = the vocabulary string with id i, empty where no string has that id."""
     n = max(vocab.values()) + 1
     pieces: List[bytes] = [b""] * n
     for s, i in vocab.items():
@@ -114,49 +113,41 @@ def piece_arrays(vocab: Dict[str, int]) -> Tuple[np.ndarray, np.ndarray]:
     return blob, off
 
 
-def build_piece_table(vocab: Dict[str, int], max_chars_per_word: int = 100, unicode: bool = False):
-    """The open-addressing table the device matches against, built by the library ON THE HOST (rr_wp_build_table; no GPU
+def build_piece_table(vocab: Dict[str, int], max_chars_per_word: int = 100):
+    """The open-addressing table the device matches against, built by the library ON THE HOST (rr_wp_build_table_utf8; no GPU
     needed): (slots [n_slots][4] int32 = hash, first byte, length in bytes | ## form << 16, id or -1; piece bytes; pieces
-    kept).  unicode=True: the table of a UTF-8 handle (rr_wp_build_table_utf8), which keeps pieces with bytes >= 0x80 and
-    counts max_chars_per_word in code points."""
+    kept).  max_chars_per_word counts code points."""
     lib = _lib.load()
     blob, off = piece_arrays(vocab)
     n_slots, kept = C.c_int32(), C.c_int32()
     _lib.check(lib.rr_wp_table_slots(len(off) - 1, C.byref(n_slots)), "rr_wp_table_slots")
     slots = np.empty((n_slots.value, 4), dtype=np.int32)
-    fn, name = (lib.rr_wp_build_table_utf8, "rr_wp_build_table_utf8") if unicode else (lib.rr_wp_build_table, "rr_wp_build_table")
-    _lib.check(fn(_lib.ptr(blob), _lib.ptr(off), len(off) - 1, max_chars_per_word, n_slots.value, _lib.ptr(slots), C.byref(kept)),
-               name)
+    _lib.check(lib.rr_wp_build_table_utf8(_lib.ptr(blob), _lib.ptr(off), len(off) - 1, max_chars_per_word, n_slots.value,
+                                          _lib.ptr(slots), C.byref(kept)), "rr_wp_build_table_utf8")
     return slots, blob, kept.value
 
 
 class DeviceWordPiece:
-    """`WordPieceTokenizer` for single texts on one GPU (csrc/rr_wordpiece.hip).  unicode=False: the ASCII kernel, which leaves
-    every document with a byte >= 0x80 to the host.  unicode=True: the UTF-8 kernel over the per-code-point table of
+    """`WordPieceTokenizer` for single texts on one GPU (csrc/rr_wordpiece.hip): UTF-8 text over the per-code-point table of
     wp_unicode.unicode_tables(); it leaves to the host only what wp_unicode.model_tokenize flags."""
 
-    def __init__(self, tokenizer: WordPieceTokenizer, device: int = 0, unicode: bool = False):
+    def __init__(self, tokenizer: WordPieceTokenizer, device: int = 0):
         if not tokenizer.do_lower_case:
             raise ValueError("the device tokenizer lower-cases (uncased vocabularies); this tokenizer does not")
         import torch
         if not torch.cuda.is_available():
             raise _lib.HipLibraryError("no GPU visible: the device tokenizer runs on the device only")
-        self._torch, self.tokenizer, self.device, self.unicode = torch, tokenizer, device, bool(unicode)
+        from .wp_unicode import unicode_tables
+        self._torch, self.tokenizer, self.device = torch, tokenizer, device
         self._dev = torch.device("cuda", device)
         blob, off = piece_arrays(tokenizer.vocab)
+        t = unicode_tables()
+        st1, st2, pool = t["stage1"], t["stage2"], t["pool"]
         h = C.c_void_p()
-        if unicode:
-            from .wp_unicode import unicode_tables
-            t = unicode_tables()
-            st1, st2, pool = t["stage1"], t["stage2"], t["pool"]
-            _lib.check(_lib.load().rr_wp_create_utf8(device, _lib.ptr(blob), _lib.ptr(off), len(off) - 1, tokenizer.unk_id,
-                                                     tokenizer.cls_id, tokenizer.sep_id, tokenizer.max_chars_per_word,
-                                                     _lib.ptr(st1), len(st1), _lib.ptr(st2), len(st2), _lib.ptr(pool), len(pool),
-                                                     C.byref(h)), "rr_wp_create_utf8")
-        else:
-            _lib.check(_lib.load().rr_wp_create(device, _lib.ptr(blob), _lib.ptr(off), len(off) - 1, tokenizer.unk_id,
-                                                tokenizer.cls_id, tokenizer.sep_id, tokenizer.max_chars_per_word, C.byref(h)),
-                       "rr_wp_create")
+        _lib.check(_lib.load().rr_wp_create_utf8(device, _lib.ptr(blob), _lib.ptr(off), len(off) - 1, tokenizer.unk_id,
+                                                 tokenizer.cls_id, tokenizer.sep_id, tokenizer.max_chars_per_word,
+                                                 _lib.ptr(st1), len(st1), _lib.ptr(st2), len(st2), _lib.ptr(pool), len(pool),
+                                                 C.byref(h)), "rr_wp_create_utf8")
         self._h = h
 
     @property
@@ -173,22 +164,14 @@ class DeviceWordPiece:
         off = np.zeros(n + 1, dtype=np.int64)
         np.cumsum([len(d) for d in docs], out=off[1:])
         nbytes = int(off[-1])
-        cap = int(capacity) if capacity else n * int(max_length)
         stage = torch.empty(8 * (n + 1) + nbytes + 8, dtype=torch.uint8, pin_memory=True)
         host = stage.numpy()
         host[:8 * (n + 1)] = off.view(np.uint8)
         host[8 * (n + 1):8 * (n + 1) + nbytes] = np.frombuffer(b"".join(docs), dtype=np.uint8)
         with torch.cuda.device(self._dev):
-            d_in = stage.to(self._dev, non_blocking=True)
-            packed = torch.empty(3 * cap + 2 * n + 2, dtype=torch.int32, device=self._dev)
-            base, st = packed.data_ptr(), torch.cuda.current_stream(self._dev).cuda_stream
-            _lib.check(_lib.load().rr_wp_encode_dev(
-                self._h, C.c_void_p(d_in.data_ptr() + 8 * (n + 1)), nbytes, C.c_void_p(d_in.data_ptr()), n, int(max_length), cap,
-                C.c_void_p(base), C.c_void_p(base + 4 * cap), C.c_void_p(base + 8 * cap), C.c_void_p(base + 12 * cap),
-                C.c_void_p(base + 4 * (3 * cap + n + 1)), C.c_void_p(base + 4 * (3 * cap + 2 * n + 1)), C.c_void_p(st)),
-                "rr_wp_encode_dev")
-            info = torch.empty(n + 2, dtype=torch.int32, pin_memory=True)
-            info.copy_(packed[3 * cap + n:], non_blocking=True)
+            d_in = stage.to(self._dev, non_blocking=True)       # [offsets int64 (n + 1)] [text]
+        packed, info, n, cap, _ = self.queue_dev(d_in.data_ptr() + 8 * (n + 1), nbytes, d_in[:8 * (n + 1)].view(torch.int64),
+                                                 max_length, capacity)
         return packed, info, n, cap, (stage, d_in)
 
     def queue_dev(self, d_text: int, text_bytes: int, d_off, max_length: int, capacity: Optional[int] = None):
@@ -218,8 +201,9 @@ class DeviceWordPiece:
     def encode_dev(self, texts: Sequence[str], max_length: int):
         """The packed device tensors of `texts` (what `forward_packed_dev` takes) and the documents left to the host:
         (tok, typ, pos, cu_seqlens, max_len, needs_host) -- int32 device tensors, the longest sequence, and the indices of
-        the documents that were NOT tokenised (ASCII handle: a byte >= 0x80; UTF-8 handle: malformed UTF-8, a hard code point
-        or a mapped text beyond the buffers; both: longer than the kernel's window and not answerable from it): their sequences are the placeholder [CLS] [SEP].  Waits for the result (the sizes are host integers)."""
+        the documents that were NOT tokenised (malformed UTF-8, a hard code point, a mapped text beyond the buffers, or
+        longer than the kernel's window and not answerable from it): their sequences are the placeholder [CLS] [SEP].
+        Waits for the result (the sizes are host integers)."""
         torch = self._torch
         packed, info, n, cap, _keep = self.queue([t.encode("utf-8") for t in texts], max_length)
         torch.cuda.current_stream(self._dev).synchronize()
@@ -293,8 +277,7 @@ def _embed_into(index: ProductIndex, lens: Sequence[int], queue_docs, host_text,
     dev = torch.device("cuda", model.device)
     wp = getattr(encoder, "_device_wp", None)
     if wp is None:
-        wp = encoder._device_wp = DeviceWordPiece(encoder.tokenizer, model.device,
-                                                  unicode=os.environ.get("RR_WP_ASCII") != "1")
+        wp = encoder._device_wp = DeviceWordPiece(encoder.tokenizer, model.device)
     lib = _lib.load()
     kept = np.empty((n, HIDDEN), dtype=np.float32) if keep_rows else None
     fp32 = model.precision == "fp32"
@@ -379,8 +362,8 @@ def _embed_into(index: ProductIndex, lens: Sequence[int], queue_docs, host_text,
             settle(*prev)
         wp.check()
 
-        # the documents the device left to the host (wp_unicode.model_tokenize's reasons; with RR_WP_ASCII=1 every byte
-        # >= 0x80): one small pass, scattered into their rows
+        # the documents the device left to the host (wp_unicode.model_tokenize's reasons): one small pass, scattered into
+        # their rows
         at = 0
         while at < len(host_docs):
             part, tot = [], 0

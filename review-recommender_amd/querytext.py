@@ -32,13 +32,13 @@ import numpy as np
 
 from . import _lib, text
 from .gate import MAX_GROUPS, MAX_TERM_BYTES, MAX_TERMS, QUERY_TERM_BYTES, _utf8, factor_table, model_gate_plane
+from .vocabtable import model_hash, model_slot, table_lookup  # noqa: F401  (the walk of build_vocab_table's table)
 
 MAX_QUERY_BYTES = 1024      # rr_query_limits (QueryText checks these against the library): bytes of a query,
 MAX_TOKEN_BYTES = 64        # of a token,
 MAX_STOP_BYTES = 8          # of a stop word the kernels hold
 FLAG_QUERY, FLAG_TOKEN, FLAG_RERANK, FLAG_WP, FLAG_SPAN = 1, 2, 4, 8, 16     # needs_host bits (include/rr_hip.h)
 FLAG_ENCODER = 32           # needs_host bit: the QUERY ENCODER's WordPiece kernel handed the query back (rr_query_flag_dev)
-HASH_BASE = 0x01000193
 
 # alnums and the apostrophe stay, everything else (NUL and every byte >= 0x80 included) is a separator
 _MAP = bytes(c if (48 <= c <= 57 or 97 <= c <= 122 or c == 39) else 32 for c in range(256))
@@ -74,27 +74,10 @@ def vocab_arrays(vocab: Dict[str, int]) -> Tuple[np.ndarray, np.ndarray]:
     return _strings(entries, np.int64)
 
 
-def model_hash(token: bytes) -> int:
-    h = 0
-    for b in token:
-        h = (h * HASH_BASE + b) & 0xFFFFFFFF
-    return h
-
-
-def model_slot(token: bytes, n_slots: int) -> int:
-    """The slot a token's walk through the table starts at."""
-    h = model_hash(token) ^ ((len(token) * 0x9E3779B1) & 0xFFFFFFFF)
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-    h ^= h >> 16
-    return h & (n_slots - 1)
-
-
 def build_vocab_table(vocab: Dict[str, int]):
     """The open-addressing table the device looks tokens up in, built by the library ON THE HOST (rr_query_build_table; no
-    GPU needed): (slots [n_slots][4] int32 = hash, first byte, length, id or -1; vocabulary bytes; entries kept)."""
+    GPU needed): (slots [n_slots][4] int32 = hash, first byte, length, id or -1; vocabulary bytes; entries kept).
+    `table_lookup` (vocabtable.py) is the kernel's walk through it."""
     lib = _lib.load()
     blob, off = vocab_arrays(vocab)
     n_slots, kept = C.c_int32(), C.c_int32()
@@ -103,20 +86,6 @@ def build_vocab_table(vocab: Dict[str, int]):
     _lib.check(lib.rr_query_build_table(_lib.ptr(blob), _lib.ptr(off), len(off) - 1, n_slots.value, _lib.ptr(slots),
                                         C.byref(kept)), "rr_query_build_table")
     return slots, blob, kept.value
-
-
-def table_lookup(slots: np.ndarray, blob: np.ndarray, token: bytes) -> int:
-    """The kernel's walk: from the token's slot to the first empty one, the hash compared first, then the bytes."""
-    n_slots, h = len(slots), model_hash(token)
-    s = model_slot(token, n_slots)
-    for _ in range(n_slots):
-        hash_, first, length, id_ = (int(v) for v in slots[s])
-        if id_ < 0:
-            return -1
-        if (hash_ & 0xFFFFFFFF) == h and length == len(token) and blob[first:first + length].tobytes() == token:
-            return id_
-        s = (s + 1) & (n_slots - 1)
-    return -1
 
 
 # ---------------------------------------------------------------------------------- the model
@@ -358,7 +327,7 @@ class QueryText:
             if self.max_length < 3:
                 raise ValueError(f"max_length {self.max_length} leaves no room for [CLS] [SEP] [SEP]")
             from .embed import DeviceWordPiece
-            self.wp = DeviceWordPiece(rerank_tokenizer, self.device, unicode=True)
+            self.wp = DeviceWordPiece(rerank_tokenizer, self.device)
         self.encoder, self.enc_wp = None, None
         if encoder is not None:
             from .cross_encoder import QueryEncoder
@@ -371,7 +340,7 @@ class QueryText:
                 raise ValueError(f"encoder.max_length {encoder.max_length} leaves no room for [CLS] [SEP]")
             if max(encoder.tokenizer.vocab.values()) >= encoder.model.vocab:
                 raise ValueError("the tokenizer's vocabulary has ids beyond the encoder's embedding table")
-            self.enc_wp = DeviceWordPiece(encoder.tokenizer, self.device, unicode=True)
+            self.enc_wp = DeviceWordPiece(encoder.tokenizer, self.device)
             self.encoder = encoder
 
     def front(self, queries: Sequence, penalty=0.5, vectors: bool = True) -> QueryFront:

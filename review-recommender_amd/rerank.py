@@ -249,7 +249,7 @@ class RerankText:
         n, total = len(off) - 1, int(off[-1])
         self._begin(tokenizer, max_length, n, max_bytes)
         dev = torch.device("cuda", self.device)
-        wp = DeviceWordPiece(tokenizer, self.device, unicode=True)
+        wp = DeviceWordPiece(tokenizer, self.device)
         try:
             with torch.cuda.device(dev):
                 main = torch.cuda.current_stream(dev)
@@ -291,7 +291,7 @@ class RerankText:
             raise ValueError(f"rows outside the {n_src} products of the text")
         self._begin(tokenizer, max_length, n, max_bytes)
         dev = torch.device("cuda", self.device)
-        wp = DeviceWordPiece(tokenizer, self.device, unicode=True)
+        wp = DeviceWordPiece(tokenizer, self.device)
         tp = T.TextPrep(self.device)
         try:
             with torch.cuda.device(dev):

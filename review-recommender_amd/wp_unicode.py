@@ -1,4 +1,4 @@
-"""Unicode tables and the CPU model of the UTF-8 device tokenizer (csrc/rr_wordpiece.hip: rr_wp_tokenize_utf8).
+"""Unicode tables and the CPU model of the device tokenizer (csrc/rr_wordpiece.hip: rr_wp_tokenize_utf8).
 
 Everything `wordpiece.basic_tokenize` does to a text for an uncased vocabulary reduces to a rule per code point, so the device
 needs a table lookup per code point and no normaliser:
@@ -210,7 +210,7 @@ def model_words(text: str) -> Optional[List[str]]:
 
 def model_tokenize(text: Union[str, bytes], tokenizer: WordPieceTokenizer, max_length: Optional[int] = None,
                    window: int = WINDOW, want_ids: bool = True) -> Tuple[Optional[List[int]], int, Optional[str]]:
-    """(ids, needs_host, reason) as rr_wp_encode_dev answers one document on a UTF-8 handle.  needs_host = 1 comes with the
+    """(ids, needs_host, reason) as rr_wp_encode_dev answers one document.  needs_host = 1 comes with the
     placeholder [CLS] [SEP] and one of REASONS, tested in the kernel's order over the bytes it reads (the whole document,
     or its first `window` bytes):
         "malformed"  the bytes read are not well-formed UTF-8

@@ -40,21 +40,6 @@ def assert_equals_host(got, want_ids, what=""):
     assert max_len == int(lens.max()), what
 
 
-def test_k5_tokenizer_fixture_ascii_on_the_device_and_the_rest_flagged():
-    fx = json.loads((GOLDEN / "k5_tokenizer.json").read_text())
-    tok = WordPieceTokenizer({w: i for i, w in enumerate(fx["vocab"])})
-    ascii_ix = [i for i, t in enumerate(fx["texts"]) if t.isascii()]
-    assert ascii_ix == [0, 2, 3, 5, 6, 7, 8, 9]
-    wp = device_tokenizer(tok)
-    got = run(wp, fx["texts"], 32)
-    want = [fx["single_max32"][i] if i in ascii_ix else [tok.cls_id, tok.sep_id] for i in range(len(fx["texts"]))]
-    assert got[5] == [1, 4]                                       # café, 中文: left to the host
-    assert_equals_host(got, want, "k5_tokenizer.json")
-    # ... where the builder's second pass (wordpiece.py) reproduces the fixture
-    for i in (1, 4):
-        assert tok.encode_pair(fx["texts"][i], None, 32)[0].tolist() == fx["single_max32"][i]
-
-
 def test_wp_ascii_fixture_exactly():
     fx = json.loads((GOLDEN / "wp_ascii.json").read_text())
     tok = WordPieceTokenizer({w: i for i, w in enumerate(fx["vocab"])})
@@ -227,14 +212,18 @@ def test_input_checks_return_invalid_and_leave_the_outputs_alone(hip):
     torch.cuda.synchronize()
     assert bool((out == -7).all())
     # special ids out of range, decreasing piece offsets: refused at creation
+    from review_recommender_amd.wp_unicode import unicode_tables
+    t = unicode_tables()
+    uni = tuple(x for a in (t["stage1"], t["stage2"], t["pool"]) for x in (_lib.ptr(a), len(a)))
     blob = np.frombuffer(b"abc", dtype=np.uint8).copy()
     h = C.c_void_p()
     good = np.array([0, 1, 2, 3], dtype=np.int64)
-    assert hip.rr_wp_create(0, _lib.ptr(blob), _lib.ptr(good), 3, 3, 0, 1, 100, C.byref(h)) == -1
+    assert hip.rr_wp_create_utf8(0, _lib.ptr(blob), _lib.ptr(good), 3, 3, 0, 1, 100, *uni, C.byref(h)) == -1
     assert "special ids" in hip.rr_last_error().decode()
-    assert hip.rr_wp_create(0, _lib.ptr(blob), _lib.ptr(np.array([0, 2, 1, 3], dtype=np.int64)), 3, 0, 1, 2, 100, C.byref(h)) == -1
+    assert hip.rr_wp_create_utf8(0, _lib.ptr(blob), _lib.ptr(np.array([0, 2, 1, 3], dtype=np.int64)), 3, 0, 1, 2, 100, *uni,
+                                 C.byref(h)) == -1
     assert "decrease" in hip.rr_last_error().decode()
-    assert hip.rr_wp_create(0, _lib.ptr(blob), _lib.ptr(good), 3, 0, 1, 2, 256, C.byref(h)) == -1
+    assert hip.rr_wp_create_utf8(0, _lib.ptr(blob), _lib.ptr(good), 3, 0, 1, 2, 256, *uni, C.byref(h)) == -1
     # a valid call; then text offsets that decrease (they live on the device: the kernel refuses the document, reads
     # nothing, and rr_wp_status reports it)
     assert call() == 0

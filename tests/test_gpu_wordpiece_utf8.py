@@ -1,27 +1,19 @@
-"""The UTF-8 device tokenizer (csrc/rr_wordpiece.hip: rr_wp_tokenize_utf8, embed.DeviceWordPiece(unicode=True)) against the
+"""The device tokenizer (csrc/rr_wordpiece.hip: rr_wp_tokenize_utf8, embed.DeviceWordPiece) on non-ASCII text against the
 `transformers` fixtures, the host tokenizer and the CPU model of its flags (wp_unicode.model_tokenize): ids exactly, and
 needs_host for the model's reasons only."""
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 from review_recommender_amd import synth, wp_unicode as U
 from review_recommender_amd.wordpiece import WordPieceTokenizer
 
 import wp_utf8_texts as X
-from test_gpu_wordpiece import assert_equals_host, cut, host_ids, run
+from test_gpu_wordpiece import assert_equals_host, cut, device_tokenizer, host_ids, run
 
 pytestmark = pytest.mark.gpu
-
-
-def unicode_tokenizer(tok):
-    from review_recommender_amd.embed import DeviceWordPiece
-    return DeviceWordPiece(tok, 0, unicode=True)
 
 
 def run_bytes(wp, docs, L):
@@ -37,18 +29,17 @@ def run_bytes(wp, docs, L):
 
 
 def test_the_existing_fixtures_on_a_utf8_handle():
-    """k5_tokenizer.json (all ten texts: the ASCII handle flags "café" and "中文") and wp_ascii.json: the fixture ids, nothing
-    flagged."""
+    """k5_tokenizer.json (all ten texts, "café" and "中文" among them) and wp_ascii.json: the fixture ids, nothing flagged."""
     fx = json.loads((GOLDEN / "k5_tokenizer.json").read_text())
     tok = WordPieceTokenizer({w: i for i, w in enumerate(fx["vocab"])})
-    wp = unicode_tokenizer(tok)
+    wp = device_tokenizer(tok)
     assert sum(not t.isascii() for t in fx["texts"]) == 2 and len(fx["texts"]) == 10
     got = run(wp, fx["texts"], 32)
     assert got[5] == []
     assert_equals_host(got, fx["single_max32"], "k5_tokenizer.json on a UTF-8 handle")
     fx = json.loads((GOLDEN / "wp_ascii.json").read_text())
     tok = WordPieceTokenizer({w: i for i, w in enumerate(fx["vocab"])})
-    wp = unicode_tokenizer(tok)
+    wp = device_tokenizer(tok)
     for L in sorted({c["max_length"] for c in fx["cases"]}):
         cases = [c for c in fx["cases"] if c["max_length"] == L]
         got = run(wp, [c["text"] for c in cases], L)
@@ -60,7 +51,7 @@ def test_wp_utf8_fixture_exactly():
     fx = json.loads((GOLDEN / "wp_utf8.json").read_text())
     print("wp_utf8.json ids written by:", fx["ids_from"])
     tok = WordPieceTokenizer({w: i for i, w in enumerate(fx["vocab"])})
-    wp = unicode_tokenizer(tok)
+    wp = device_tokenizer(tok)
     assert len(fx["texts"]) >= 24 and sum(not t.isascii() for t in fx["texts"]) >= 24
     for L in (32, 512):
         got = run(wp, fx["texts"], L)
@@ -84,7 +75,7 @@ def clean_documents(tok, n, seed):
 
 def test_random_utf8_documents_equal_the_host_tokenizer():
     tok = WordPieceTokenizer({w: i for i, w in enumerate(X.vocabulary())})
-    wp = unicode_tokenizer(tok)
+    wp = device_tokenizer(tok)
     texts = clean_documents(tok, 20_000, 13)
     flags = [U.model_tokenize(t, tok, L, want_ids=False)[1] for t in texts for L in (8, 512)]
     assert sum(flags) == 0                                       # on the CPU: the model flags none of them
@@ -102,7 +93,7 @@ def test_random_utf8_documents_equal_the_host_tokenizer():
 
 def test_planted_reasons_are_flagged_as_the_model_says():
     tok = WordPieceTokenizer({w: i for i, w in enumerate(X.vocabulary())})
-    wp = unicode_tokenizer(tok)
+    wp = device_tokenizer(tok)
     rng = np.random.default_rng(3)
     docs, why = [], []
 
@@ -150,59 +141,50 @@ def test_planted_reasons_are_flagged_as_the_model_says():
     assert {"hard", "malformed", "window", "bound", None} == set(why)
 
 
-CHILD = """
-import sys
-sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
-import numpy as np
-import test_gpu_wordpiece_utf8 as T
-rows, stats = T.embed_rows()
-assert len(stats["host_docs"]) == {n_nonascii}, (len(stats["host_docs"]), {n_nonascii})
-np.save({out!r}, rows)
-"""
-
-
-def embed_world():
+def embed_world(n_layers=12, n_texts=1500, seed=21):
     from review_recommender_amd.cross_encoder import QueryEncoder
     words = X.vocabulary() + [w for w in synth.WORDS if w not in set(X.vocabulary())] + ["caf", "##e", "中", "文"]
     tok = WordPieceTokenizer({w: i for i, w in enumerate(words)})
-    enc = QueryEncoder(synth.bert_state_dict(78, n_layers=12, n_labels=0, prefix="", vocab=len(words)), tok)
-    return enc, X.mixed_product_texts(1500, 21, 0.3)
+    enc = QueryEncoder(synth.bert_state_dict(78, n_layers=n_layers, n_labels=0, prefix="", vocab=len(words)), tok)
+    return enc, X.mixed_product_texts(n_texts, seed, 0.3)
 
 
-def embed_rows():
-    from review_recommender_amd.embed import embed_texts_into, normalize_text
+def embed_rows(enc, texts, chunk_tokens):
+    from review_recommender_amd.embed import embed_texts_into
     from review_recommender_amd.index import ProductIndex
-    enc, texts = embed_world()
-    texts = [normalize_text(t) for t in texts]
     ix = ProductIndex(None, n_rows=len(texts), dim=384)
     stats = {}
-    embed_texts_into(ix, texts, enc, chunk_tokens=16_384, stats=stats)
+    embed_texts_into(ix, texts, enc, chunk_tokens=chunk_tokens, stats=stats)
     rows = ix.download_rows()
     ix.close()
     return rows, stats
 
 
-def test_embed_path_leaves_only_what_the_model_flags_to_the_host(tmp_path):
+def test_embed_path_leaves_only_what_the_model_flags_to_the_host():
     from review_recommender_amd.embed import normalize_text
     from review_recommender_amd.index import ProductIndex
-    assert os.environ.get("RR_WP_ASCII") != "1"
     enc, texts = embed_world()
     texts = [normalize_text(t) for t in texts]
     nonascii = [i for i, t in enumerate(texts) if not t.isascii()]
     assert 0.25 * len(texts) < len(nonascii) < 0.4 * len(texts)
     model = [i for i, t in enumerate(texts) if U.model_tokenize(t, enc.tokenizer, enc.max_length)[1]]
     assert 1 <= len(model) <= 8                                  # the planted hard code points, and nothing else
-    rows, stats = embed_rows()
+    rows, stats = embed_rows(enc, texts, 16_384)
     print(f"{len(nonascii)} of {len(texts)} texts hold non-ASCII text; left to the host: {stats['host_docs']}")
     assert sorted(stats["host_docs"]) == model
     want = ProductIndex.from_rows(enc.encode(texts), normalize=True).download_rows()
     bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
     diff = np.flatnonzero((bits(want) != bits(rows)).any(axis=1))
     assert len(diff) == 0, diff[:10]
-    # the ASCII handle (RR_WP_ASCII=1, a fresh process): every non-ASCII text through the host pass, the same bits
-    out = tmp_path / "ascii_rows.npy"
-    code = CHILD.format(root=str(ROOT), tests=str(ROOT / "tests"), n_nonascii=len(nonascii), out=str(out))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RR_WP_ASCII="1"), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert np.array_equal(bits(np.load(out)), bits(rows))
+    # the host pass over many documents, in several parts: a hard code point in every fifth of 200 texts, and
+    # chunk_tokens = 2048 = 4 documents of max_length 512 per part of the pass
+    enc, texts = embed_world(n_layers=2, n_texts=200, seed=22)
+    for i in range(0, len(texts), 5):
+        texts[i] += " " + X.HARD_SAMPLES[(i // 5) % len(X.HARD_SAMPLES)]
+    texts = [normalize_text(t) for t in texts]
+    model = [i for i, t in enumerate(texts) if U.model_tokenize(t, enc.tokenizer, enc.max_length)[1]]
+    assert len(model) >= 40 and set(range(0, len(texts), 5)) <= set(model) and enc.max_length == 512
+    rows, stats = embed_rows(enc, texts, 2048)
+    assert sorted(stats["host_docs"]) == model
+    want = ProductIndex.from_rows(enc.encode(texts), normalize=True).download_rows()
+    assert np.array_equal(bits(want), bits(rows))

@@ -11,8 +11,6 @@ from review_recommender_amd.wordpiece import WordPieceTokenizer, basic_tokenize
 
 import wp_utf8_texts as X
 
-BASE = 0x01000193
-
 
 def tokenizer():
     return WordPieceTokenizer({w: i for i, w in enumerate(X.vocabulary())})
@@ -155,40 +153,20 @@ def test_malformed_utf8_is_reason_b():
 
 def test_utf8_piece_table_on_the_host():
     """rr_wp_build_table_utf8 keeps what can match mapped text (non-ASCII pieces, up to max_chars_per_word CHARACTERS), and
-    a lookup as the kernel does it finds every kept piece and nothing else (the ASCII builder's test, in UTF-8)."""
-    from review_recommender_amd.embed import build_piece_table, piece_arrays
+    a lookup as the kernel does it finds every kept piece and nothing else."""
+    from review_recommender_amd.embed import build_piece_table
+    from review_recommender_amd.vocabtable import table_lookup
     long_piece = "##" + "中文字語" * 25                      # 100 characters of 3 bytes
     too_long = "é" * 101                                               # 101 characters
     words = X.vocabulary() + ["café", "中", long_piece, too_long, "x" * 100, "y" * 101]
     vocab = {w: i for i, w in enumerate(words)}
-    slots, blob, kept = build_piece_table(vocab, 100, unicode=True)
-    a_slots, _, a_kept = build_piece_table(vocab, 100)
-    assert a_kept < kept
-    _, off = piece_arrays(vocab)
+    slots, blob, kept = build_piece_table(vocab, 100)
     n = slots.shape[0]
     assert n & (n - 1) == 0 and n >= 2 * kept
 
     def find(s, form):
         raw = s.encode("utf-8")
-        h = 0
-        for b in raw:
-            h = (h * BASE + b) & 0xFFFFFFFF
-        lf = len(raw) | form << 16
-        x = (h ^ (lf * 0x9E3779B1)) & 0xFFFFFFFF
-        x ^= x >> 16
-        x = (x * 0x85EBCA6B) & 0xFFFFFFFF
-        x ^= x >> 13
-        x = (x * 0xC2B2AE35) & 0xFFFFFFFF
-        x ^= x >> 16
-        s_ = x & (n - 1)
-        for _ in range(n):
-            hh, o, l, i = (int(v) for v in slots[s_])
-            if i < 0:
-                return -1
-            if (hh & 0xFFFFFFFF) == h and l == lf and blob[o:o + len(raw)].tobytes() == raw:
-                return i
-            s_ = (s_ + 1) & (n - 1)
-        return -1
+        return table_lookup(slots, blob, raw, len(raw) | form << 16)
 
     want_kept = 0
     for w, i in vocab.items():
@@ -206,5 +184,3 @@ def test_utf8_piece_table_on_the_host():
     for absent in ("caf", "é", "中文字語", "zzzz", "丁"):
         if absent not in vocab:
             assert find(absent, 0) == -1, absent
-    # the ASCII builder still drops every non-ASCII piece
-    assert a_kept == sum(1 for w in vocab if w.isascii() and 1 <= len(w[2:] if w.startswith("##") and len(w) > 2 else w) <= 100)

@@ -3,8 +3,7 @@
     python tools/embed_build_time.py 100000 --precision fp32 --out profiles/embed_build_100k_fp32.json
     python tools/embed_build_time.py 100000 --precision bf16 --out profiles/embed_build_100k_bf16.json
     python tools/embed_build_time.py 100000 --precision bf16 --nonascii 0.3 --no-host-path        (30 % of the texts carry
-        accents, curly quotes, emoji or CJK; RR_WP_ASCII=1 in the environment times the ASCII-only kernel on them;
-        profiles/embed_build_100k_bf16_utf8.json)
+        accents, curly quotes, emoji or CJK; profiles/embed_build_100k_bf16_utf8.json)
 
 Prints one JSON line: (a) documents/s of the device tokenizer alone (HIP events around rr_wp_encode_dev, texts resident) beside
 the host tokenizer on a sample of the same texts on one core; (b) documents/s of the whole build_product_embeddings beside
@@ -79,7 +78,6 @@ def main():
     res = {"docs": a.docs, "precision": a.precision, "mean_chars": float(np.mean([len(t) for t in texts[:2000]])), "pieces": len(words),
            "nonascii": a.nonascii, "nonascii_docs": sum(not t.isascii() for t in texts)}
     embed.build_product_embeddings(products.iloc[:2048], enc)[0].close()             # warm-up: scratch, allocator, clocks
-    res["tokenizer"] = "utf8" if getattr(enc._device_wp, "unicode", False) else "ascii"      # RR_WP_ASCII=1: the ASCII kernel
     if a.build_only:
         t0 = time.perf_counter()
         meta, texts_f = embed.filter_products(products)

@@ -1491,13 +1491,72 @@ static int ce_reserve_seqs_f32(rr_ce* ce, int64_t seqs) {
 // The three forward passes: embeddings -> per layer QKV, attention, output projection + residual + LayerNorm, FFN (GELU) +
 // residual + LayerNorm -> head.  rr_ce_forward_dev has validated the call and reserved the scratch they use.
 
+// The launches of the bf16 path, one helper each: grid, block, dynamic LDS and arguments live HERE only.  ce_forward_bf16
+// calls them on the handle's scratch, the kernel-test harness (rr_debug_ce_bf16_*, rr_debug_ce_embed_ln) on caller buffers.
+static void ce_launch_embed_ln(const rr_ce* ce, const int32_t* d_tok, const int32_t* d_typ, const int32_t* d_pos, int T, float* h32,
+                               unsigned short* hb, hipStream_t st) {
+    hipLaunchKernelGGL(ce_embed_ln, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, d_tok, d_typ, d_pos, T, ce->cfg.vocab,
+                       ce->cfg.max_pos, ce->cfg.type_vocab, ce->word, ce->pos, ce->type, ce->eln_g, ce->eln_b, ce->cfg.ln_eps, h32, hb);
+}
+
+// qkv [T][1152] = bf16(hb [T][384] . wqkv^T + bqkv); `exp`: the debug library's timing ablations of ce_proj_ts (garbage results)
+static void ce_launch_proj(const rr_ce_layer& L, const unsigned short* hb, int T, unsigned short* qkv, hipStream_t st, int exp = 0) {
+    const dim3 pg((unsigned)((T + CE_QKV_TOK - 1) / CE_QKV_TOK));
+#define CE_PROJ(EXP) \
+    hipLaunchKernelGGL((ce_proj_ts<EXP>), pg, dim3(512), CE_QKV_LDS(3 * CE_H), st, hb, T, L.wqkv, L.bqkv, 3 * CE_H, qkv)
+#ifdef RR_DEBUG_HARNESS
+    if (exp == 1) CE_PROJ(1);
+    else if (exp == 2) CE_PROJ(2);
+    else if (exp == 3) CE_PROJ(3);
+    else if (exp == 7) CE_PROJ(7);
+    else if (exp == 8) CE_PROJ(8);
+    else if (exp == 16) CE_PROJ(16);
+    else if (exp == 32) CE_PROJ(32);
+    else
+#endif
+    CE_PROJ(0);
+#undef CE_PROJ
+    (void)exp;
+}
+
+// ctx_cls == null: ctx [T][384] of every token; else only query row 0 of every sequence, into ctx_cls [n_seqs][384].
+// `max_len` (at least every sequence's length) sizes the LDS.
+static void ce_launch_attention(const unsigned short* qkv, const int32_t* d_cu, int n_seqs, int max_len, unsigned short* ctx,
+                                unsigned short* ctx_cls, hipStream_t st) {
+    const int smax_pad = (max_len + 31) & ~31;
+    hipLaunchKernelGGL(ce_attention, dim3((unsigned)n_seqs, CE_HEADS), dim3(CE_ATT_THREADS), ce_attention_lds(smax_pad), st, qkv, d_cu,
+                       ctx, 0.17677669529663687f /* 1 / sqrt(32) */, smax_pad, ctx_cls);
+}
+
+// attention output projection + residual + LayerNorm + FFN + residual + LayerNorm on M rows: h32 in place, hb written
+// (`nostore`: the debug library's timing ablation, garbage results)
+static void ce_launch_ffn(const rr_ce* ce, const rr_ce_layer& L, const unsigned short* ctx, float* h32, unsigned short* hb, int M,
+                          hipStream_t st, bool nostore = false) {
+    const dim3 fg((unsigned)((M + CE_FFN_TOK - 1) / CE_FFN_TOK));
+#define CE_FFN_LAUNCH(NOSTORE) \
+    hipLaunchKernelGGL((ce_ffn_fused<NOSTORE>), fg, dim3(256), CE_FFN_LDS, st, hb, h32, M, L.w1, L.b1, L.w2p, L.b2, L.ln2_g, L.ln2_b, \
+                       ce->cfg.ln_eps, ce->gelu_tab, ctx, L.wo, L.bo, L.ln1_g, L.ln1_b)
+#ifdef RR_DEBUG_HARNESS
+    if (nostore) CE_FFN_LAUNCH(true);
+    else
+#endif
+    CE_FFN_LAUNCH(false);
+#undef CE_FFN_LAUNCH
+    (void)nostore;
+}
+
 // RR_CE_PRECISION_BF16: three launches per layer
 static int ce_forward_bf16(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d_type_ids, const int32_t* d_pos_ids,
                            const int32_t* d_cu_seqlens, int n_seqs, int T, int max_len, int mode, float* d_out, hipStream_t st) {
-    const int smax_pad = (max_len + 31) & ~31;
-    hipLaunchKernelGGL(ce_embed_ln, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, d_token_ids, d_type_ids, d_pos_ids, T,
-                       ce->cfg.vocab, ce->cfg.max_pos, ce->cfg.type_vocab, ce->word, ce->pos, ce->type, ce->eln_g, ce->eln_b,
-                       ce->cfg.ln_eps, ce->h32, ce->hb);
+    int proj_exp = 0;
+    bool ffn_nostore = false;
+#ifdef RR_DEBUG_HARNESS
+    static const int pe = getenv("RR_CE_PROJ_EXP") ? atoi(getenv("RR_CE_PROJ_EXP")) : 0;      // (tools/k5_proj_ablate.py)
+    static const bool nostore = getenv("RR_CE_FFN_NOSTORE") != nullptr;                       // (tools/k5_stamps.py)
+    proj_exp = pe;
+    ffn_nostore = nostore;
+#endif
+    ce_launch_embed_ln(ce, d_token_ids, d_type_ids, d_pos_ids, T, ce->h32, ce->hb, st);
     for (int l = 0; l < ce->cfg.n_layers; ++l) {
         const rr_ce_layer& L = ce->layers[l];
         // The last layer of a [CLS]-pooled output (logits, CLS embedding) needs keys and values of every token but
@@ -1508,38 +1567,11 @@ static int ce_forward_bf16(rr_ce* ce, const int32_t* d_token_ids, const int32_t*
         float* r32 = cls_tail ? ce->h32c : ce->h32;
         unsigned short* rb = cls_tail ? ce->hbc : ce->hb;
         const unsigned short* rctx = cls_tail ? ce->ctxc : ce->ctx;
-        const dim3 pg((unsigned)((T + CE_QKV_TOK - 1) / CE_QKV_TOK));
-#define CE_PROJ(EXP) \
-    hipLaunchKernelGGL((ce_proj_ts<EXP>), pg, dim3(512), CE_QKV_LDS(3 * CE_H), st, ce->hb, T, L.wqkv, L.bqkv, 3 * CE_H, ce->qkv)
-#ifdef RR_DEBUG_HARNESS
-        static const int pe = getenv("RR_CE_PROJ_EXP") ? atoi(getenv("RR_CE_PROJ_EXP")) : 0;      // (tools/k5_proj_ablate.py)
-        if (pe == 1) CE_PROJ(1);
-        else if (pe == 2) CE_PROJ(2);
-        else if (pe == 3) CE_PROJ(3);
-        else if (pe == 7) CE_PROJ(7);
-        else if (pe == 8) CE_PROJ(8);
-        else if (pe == 16) CE_PROJ(16);
-        else if (pe == 32) CE_PROJ(32);
-        else
-#endif
-        CE_PROJ(0);
-#undef CE_PROJ
-        hipLaunchKernelGGL(ce_attention, dim3((unsigned)n_seqs, CE_HEADS), dim3(CE_ATT_THREADS), ce_attention_lds(smax_pad), st,
-                           ce->qkv, d_cu_seqlens, ce->ctx, 0.17677669529663687f /* 1 / sqrt(32) */, smax_pad,
-                           cls_tail ? ce->ctxc : (unsigned short*)nullptr);
+        ce_launch_proj(L, ce->hb, T, ce->qkv, st, proj_exp);
+        ce_launch_attention(ce->qkv, d_cu_seqlens, n_seqs, max_len, ce->ctx, cls_tail ? ce->ctxc : (unsigned short*)nullptr, st);
         if (cls_tail) hipLaunchKernelGGL(ce_gather_cls, dim3((unsigned)n_seqs), dim3(128), 0, st, ce->h32, d_cu_seqlens, ce->h32c);
         // attention output projection + residual + LayerNorm + FFN + residual + LayerNorm: one launch
-        const dim3 fg((unsigned)((Mr + CE_FFN_TOK - 1) / CE_FFN_TOK));
-#define CE_FFN_LAUNCH(NOSTORE) \
-    hipLaunchKernelGGL((ce_ffn_fused<NOSTORE>), fg, dim3(256), CE_FFN_LDS, st, rb, r32, Mr, L.w1, L.b1, L.w2p, L.b2, L.ln2_g, L.ln2_b, \
-                       ce->cfg.ln_eps, ce->gelu_tab, rctx, L.wo, L.bo, L.ln1_g, L.ln1_b)
-#ifdef RR_DEBUG_HARNESS
-        static const bool nostore = getenv("RR_CE_FFN_NOSTORE") != nullptr;      // (tools/k5_stamps.py)
-        if (nostore) CE_FFN_LAUNCH(true);
-        else
-#endif
-        CE_FFN_LAUNCH(false);
-#undef CE_FFN_LAUNCH
+        ce_launch_ffn(ce, L, rctx, r32, rb, Mr, st, ffn_nostore);
     }
     if (mode == RR_CE_OUT_HIDDEN)
         RR_HIP_TRY(hipMemcpyAsync(d_out, ce->h32, sizeof(float) * (size_t)T * CE_H, hipMemcpyDeviceToDevice, st));
@@ -1590,9 +1622,7 @@ static int ce_forward_h2(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d
 // RR_CE_PRECISION_F32 after rr_ce_set_wide_range: three bf16 terms per operand, six products -- any fp32 range
 static int ce_forward_x3(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d_type_ids, const int32_t* d_pos_ids,
                          const int32_t* d_cu_seqlens, int n_seqs, int T, int mode, float* d_out, hipStream_t st) {
-    hipLaunchKernelGGL(ce_embed_ln, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, d_token_ids, d_type_ids, d_pos_ids, T,
-                       ce->cfg.vocab, ce->cfg.max_pos, ce->cfg.type_vocab, ce->word, ce->pos, ce->type, ce->eln_g, ce->eln_b,
-                       ce->cfg.ln_eps, ce->h32, ce->hb);
+    ce_launch_embed_ln(ce, d_token_ids, d_type_ids, d_pos_ids, T, ce->h32, ce->hb, st);
     const unsigned mt = (unsigned)((T + 127) / 128), ln_blocks = (unsigned)((T + 3) / 4);
     for (int l = 0; l < ce->cfg.n_layers; ++l) {
         const rr_ce_layer& L = ce->layers[l];
@@ -1733,4 +1763,78 @@ extern "C" int rr_debug_ce_x3_add_ln(const float* d_y, float* d_h, int32_t T, co
     RR_HIP_TRY(hipDeviceSynchronize());
     return RR_OK;
 }
+
+// tests/test_gpu_k5_bf16_kernels.py: the bf16 path's kernels (ce_embed_ln, ce_proj_ts, ce_attention, ce_ffn_fused) ONE launch at
+// a time on caller buffers (device pointers; bf16 rows as bit patterns), through the launch helpers ce_forward_bf16 itself
+// calls and with the weights of a handle created in RR_CE_PRECISION_BF16.  Every argument is checked before anything is
+// launched; every entry waits for its launch.
+#define CE_DBG_HANDLE(name)                                                                                              \
+    RR_REQUIRE(ce, name ": NULL handle");                                                                                \
+    RR_REQUIRE(ce->cfg.precision == RR_CE_PRECISION_BF16, name ": the handle was not created in RR_CE_PRECISION_BF16"); \
+    std::lock_guard<std::mutex> lk(ce->mu);                                                                              \
+    RR_HIP_TRY(hipSetDevice(ce->device));                                                                                \
+    if (int rc_ = ce_set_attributes(ce->device)) return rc_
+
+// h32 [T][384] fp32 and hb [T][384] bf16 = LayerNorm(word[tok] + type[typ] + pos[pos]) of T tokens (ids int32 on the device; the
+// kernel clamps them into the tables)
+extern "C" int rr_debug_ce_embed_ln(rr_ce* ce, const int32_t* d_tok, const int32_t* d_typ, const int32_t* d_pos, int32_t T, float* d_h32,
+                                    unsigned short* d_hb) {
+    RR_REQUIRE(d_tok && d_typ && d_pos && d_h32 && d_hb, "rr_debug_ce_embed_ln: NULL argument");
+    RR_REQUIRE(T >= 1, "rr_debug_ce_embed_ln: %d tokens", T);
+    CE_DBG_HANDLE("rr_debug_ce_embed_ln");
+    ce_launch_embed_ln(ce, d_tok, d_typ, d_pos, T, d_h32, d_hb, nullptr);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipDeviceSynchronize());
+    return RR_OK;
+}
+
+// qkv [T][1152] = bf16(hb [T][384] . wqkv^T + bqkv) of layer `layer`
+extern "C" int rr_debug_ce_bf16_proj(rr_ce* ce, int32_t layer, const unsigned short* d_hb, int32_t T, unsigned short* d_qkv) {
+    RR_REQUIRE(d_hb && d_qkv, "rr_debug_ce_bf16_proj: NULL argument");
+    RR_REQUIRE(T >= 1, "rr_debug_ce_bf16_proj: %d tokens", T);
+    CE_DBG_HANDLE("rr_debug_ce_bf16_proj");
+    RR_REQUIRE(layer >= 0 && layer < ce->cfg.n_layers, "rr_debug_ce_bf16_proj: layer %d outside [0, %d)", layer, ce->cfg.n_layers);
+    ce_launch_proj(ce->layers[layer], d_hb, T, d_qkv, nullptr);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipDeviceSynchronize());
+    return RR_OK;
+}
+
+// qkv [T][1152] bf16 (Q unscaled), cu_seqlens [n_seqs + 1] on the device with cu[0] = 0, cu[n_seqs] = T and every length in
+// [1, max_len], max_len <= 512 (checked here on a host copy: the kernel trusts them -- a sequence of no tokens would read in
+// front of the buffer, a longer one than max_len write past its LDS).  d_ctx_cls == NULL: ctx [T][384]; else ctx_cls [n_seqs][384]
+// = query row 0 of every sequence, and ctx is not written.
+extern "C" int rr_debug_ce_bf16_attention(const unsigned short* d_qkv, int32_t T, const int32_t* d_cu, int32_t n_seqs, int32_t max_len,
+                                          unsigned short* d_ctx, unsigned short* d_ctx_cls) {
+    RR_REQUIRE(d_qkv && d_cu && d_ctx, "rr_debug_ce_bf16_attention: NULL argument");
+    RR_REQUIRE(T >= 1 && n_seqs >= 1 && n_seqs <= T, "rr_debug_ce_bf16_attention: %d sequences / %d tokens", n_seqs, T);
+    RR_REQUIRE(max_len >= 1 && max_len <= 512, "rr_debug_ce_bf16_attention: max_len %d outside [1, 512]", max_len);
+    int dev = 0;
+    RR_HIP_TRY(hipGetDevice(&dev));
+    if (int rc = ce_set_attributes(dev)) return rc;
+    std::vector<int32_t> cu((size_t)n_seqs + 1);
+    RR_HIP_TRY(hipMemcpy(cu.data(), d_cu, sizeof(int32_t) * cu.size(), hipMemcpyDeviceToHost));
+    RR_REQUIRE(cu[0] == 0 && cu[n_seqs] == T, "rr_debug_ce_bf16_attention: cu_seqlens run from %d to %d, not from 0 to %d", cu[0], cu[n_seqs], T);
+    for (int i = 0; i < n_seqs; ++i)
+        RR_REQUIRE(cu[i + 1] - cu[i] >= 1 && cu[i + 1] - cu[i] <= max_len, "rr_debug_ce_bf16_attention: sequence %d has %d tokens, outside [1, %d]",
+                   i, cu[i + 1] - cu[i], max_len);
+    ce_launch_attention(d_qkv, d_cu, n_seqs, max_len, d_ctx, d_ctx_cls, nullptr);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipDeviceSynchronize());
+    return RR_OK;
+}
+
+// h32 [M][384] <- LayerNorm2(x + W2 gelu(W1 x + b1) + b2), x = LayerNorm1(h32 + ctx [M][384] . wo^T + bo), in place; hb [M][384] =
+// bf16(h32): layer `layer`'s weights (W2 as the handle holds it, columns permuted), the handle's Phi table and ln_eps
+extern "C" int rr_debug_ce_bf16_ffn(rr_ce* ce, int32_t layer, const unsigned short* d_ctx, float* d_h32, unsigned short* d_hb, int32_t M) {
+    RR_REQUIRE(d_ctx && d_h32 && d_hb, "rr_debug_ce_bf16_ffn: NULL argument");
+    RR_REQUIRE(M >= 1, "rr_debug_ce_bf16_ffn: %d rows", M);
+    CE_DBG_HANDLE("rr_debug_ce_bf16_ffn");
+    RR_REQUIRE(layer >= 0 && layer < ce->cfg.n_layers, "rr_debug_ce_bf16_ffn: layer %d outside [0, %d)", layer, ce->cfg.n_layers);
+    ce_launch_ffn(ce, ce->layers[layer], d_ctx, d_h32, d_hb, M, nullptr);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipDeviceSynchronize());
+    return RR_OK;
+}
+#undef CE_DBG_HANDLE
 #endif

@@ -40,5 +40,16 @@ int rr_debug_ce_h2_add_ln(const float* d_y, const float* d_h, int32_t T, const f
 int rr_debug_ce_x3_gemm(int32_t gelu, int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_bias, float* d_out);
 int rr_debug_ce_x3_attention(const float* d_qkv, int32_t T, const int32_t* d_cu, int32_t n_seqs, float* d_ctx);
 int rr_debug_ce_x3_add_ln(const float* d_y, float* d_h, int32_t T, const float* d_g, const float* d_b, float eps);
+// tests/test_gpu_k5_bf16_kernels.py: the bf16 path's kernels of rr_ce.hip (ce_embed_ln, ce_proj_ts, ce_attention, ce_ffn_fused) one
+// launch at a time on caller data, through the launch helpers of ce_forward_bf16 and with the weights of a handle created in
+// RR_CE_PRECISION_BF16 (`layer` picks the layer).  bf16 rows are bit patterns: hb / ctx [T][384], qkv [T][1152] (Q unscaled).
+// The attention writes ctx [T][384], or -- d_ctx_cls non-NULL -- only ctx_cls [n_seqs][384]; the FFN updates d_h32 in place and
+// writes d_hb.  See the definitions.
+int rr_debug_ce_embed_ln(rr_ce* ce, const int32_t* d_tok, const int32_t* d_typ, const int32_t* d_pos, int32_t T, float* d_h32,
+                         unsigned short* d_hb);
+int rr_debug_ce_bf16_proj(rr_ce* ce, int32_t layer, const unsigned short* d_hb, int32_t T, unsigned short* d_qkv);
+int rr_debug_ce_bf16_attention(const unsigned short* d_qkv, int32_t T, const int32_t* d_cu, int32_t n_seqs, int32_t max_len,
+                               unsigned short* d_ctx, unsigned short* d_ctx_cls);
+int rr_debug_ce_bf16_ffn(rr_ce* ce, int32_t layer, const unsigned short* d_ctx, float* d_h32, unsigned short* d_hb, int32_t M);
 }
 #endif

@@ -21,6 +21,15 @@ int rr_debug_flt_words(rr_index* ix, const float* d_queries, int32_t nq_a, int32
 int rr_debug_flt_select(rr_index* ix, int32_t pool, uint32_t* mtiles, int64_t cap, int32_t* count, uint32_t* tau, uint32_t* open,
                         int32_t* fb);
 int rr_debug_select_traces(rr_index* ix, int32_t nq, int32_t* out);
+// tests/test_gpu_rescore_kernels.py: ONE rr_rescore_chain / ONE rr_select_rescored launch (the product's launch helpers) on
+// caller lists placed in the selection scratch, into outputs filled with sentinels.  mtiles [nq][cap], count / fb / tau (keys) /
+// eps [nq]; sc [nq][cap][8] out of the rescoring, [nq][cap][rows_per_mtile] into the selection; rows / scores [nq][pool],
+// fb_out / n_cand [nq].  Every argument is checked before anything is launched.  See the definitions.
+int rr_debug_rescore_chain(rr_index* ix, const float* d_queries, int32_t nq, int32_t grid_x, int32_t use_plane, const uint32_t* mtiles,
+                           int64_t cap, const int32_t* count, const int32_t* fb, const uint32_t* tau, const float* eps, float* sc);
+int rr_debug_select_rescored(rr_index* ix, int32_t nq, int32_t pool, int32_t rows_per_mtile, int32_t floor_mode, const uint32_t* mtiles,
+                             int64_t cap, const int32_t* count, const int32_t* fb, const uint32_t* tau, const float* sc, int64_t* rows,
+                             float* scores, int32_t* fb_out, int32_t* n_cand);
 // tools/k5_stamps.py: in-kernel phase clocks of the last ce_ffn_fused launch (rr_ce.hip)
 int rr_debug_ce_ffn_stamps(unsigned long long* out20);
 // tools/k5_h2_stamps.py: phase clocks of one workgroup of the last FFN1 ce_gemm_h2 launch (rr_ce_h2.hip)

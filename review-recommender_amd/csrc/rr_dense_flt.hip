@@ -1374,6 +1374,22 @@ static int rr_flt_scan_set(rr_index* ix, int set, const rr_scan_geom& G, const v
     return RR_OK;
 }
 
+// The rr_rescore_chain launch of rr_flt_finish (the kernel-test harness launches through it as well): grid, block, template
+// instance and the plane argument.  The lists, cuts and bounds are the ones in the index's selection scratch.
+// (the plane pre-scoring of the rescored rows: fp32 storage with a valid plane.  Under a corpus-wide floor the row cut is
+//  the floor: rows below it come back as -inf and only fill the shard's list up -- the merge never takes them)
+// (grid_x = 16: 16 M-tiles per workgroup and pass, ~500-650 listed per query: up to 3 passes; 4 under a corpus-wide floor, where
+//  a shard opens ~pool / 8 M-tiles per query: a quarter of the workgroups.  Workgroups with nothing to do return before their barrier.)
+template <bool ROWS_BF16>
+static void rr_launch_rescore_chain(rr_index* ix, int64_t n_rows, const float* d_q, int nq, int grid_x, bool allow_plane,
+                                    hipStream_t st) {
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    const u32x4* plane_rows = (!ROWS_BF16 && ix->shadow_valid && ix->d_shadow && allow_plane)
+                                  ? reinterpret_cast<const u32x4*>(ix->d_shadow) : nullptr;
+    hipLaunchKernelGGL((rr_rescore_chain<ROWS_BF16>), dim3(grid_x, nq), dim3(256), 0, st, ix->d_matrix, n_rows, d_q,
+                       X.mtiles, X.count, X.fb, X.sc, plane_rows, X.tau, X.eps);
+}
+
 // selection + rescoring + ordering + per-64 fallback over nq_a (+ nq_b) queries of one (two) scan launches
 template <bool ROWS_BF16>
 static int rr_flt_finish(rr_index* ix, const rr_scan_geom& G, const float* d_q, int nq_a, int nq_b, int pool,
@@ -1383,16 +1399,8 @@ static int rr_flt_finish(rr_index* ix, const rr_scan_geom& G, const float* d_q, 
     const int nq = nq_a + nq_b;
     if (parts & 1)
         rr_launch_select_mtiles(ix, G, nq_a, pool, st, X.eps, sigma, nq_b, rr_flt_mmax_set_stride(G), rr_flt_smax_set_stride(), floor);
-    // (the plane pre-scoring of the rescored rows: fp32 storage with a valid plane.  Under a corpus-wide floor the row cut is
-    //  the floor: rows below it come back as -inf and only fill the shard's list up -- the merge never takes them)
     static const bool no_pre = getenv("RR_NO_RESCORE_PLANE") != nullptr;
-    const u32x4* plane_rows = (!ROWS_BF16 && ix->shadow_valid && ix->d_shadow && !no_pre)
-                                  ? reinterpret_cast<const u32x4*>(ix->d_shadow) : nullptr;
-    // (16 M-tiles per workgroup and pass, ~500-650 listed per query: up to 3 passes; under a corpus-wide floor a shard opens
-    //  ~pool / 8 M-tiles per query: a quarter of the workgroups.  Workgroups with nothing to do return before their barrier.)
-    if (parts & 2)
-        hipLaunchKernelGGL((rr_rescore_chain<ROWS_BF16>), dim3(floor ? 4 : 16, nq), dim3(256), 0, st, ix->d_matrix, G.n_rows, d_q,
-                           X.mtiles, X.count, X.fb, X.sc, plane_rows, X.tau, X.eps);
+    if (parts & 2) rr_launch_rescore_chain<ROWS_BF16>(ix, G.n_rows, d_q, nq, floor ? 4 : 16, !no_pre, st);
     RR_HIP_TRY(hipGetLastError());
     if (!(parts & 4)) return RR_OK;
     rr_launch_select_rescored(ix, G, nq, pool, d_rows, d_scores, st, floor != nullptr);
@@ -1886,6 +1894,122 @@ extern "C" int rr_debug_select_traces(rr_index* ix, int32_t nq, int32_t* out) {
     RR_HIP_TRY(hipSetDevice(ix->device));
     RR_HIP_TRY(hipDeviceSynchronize());
     RR_HIP_TRY(hipMemcpy(out, ix->d_sel_trace, sizeof(int32_t) * 16 * nq, hipMemcpyDeviceToHost));
+    return RR_OK;
+}
+
+// ---- the batch tail's rescoring and final selection, one launch at a time on caller lists (tests/test_gpu_rescore_kernels.py)
+// Sentinels the outputs are filled with before the launch.  Score: a NaN with a payload -- rr_rescore_chain stores -inf for
+// a NaN score and rr_select_rescored stores rr_key2f of keys it took from such scores.  Row: no row + row_offset is negative.
+// n_cand (trace word 3): a count is not negative.
+#define RR_DEBUG_SC_SENTINEL 0x7FC5A5A5u
+#define RR_DEBUG_ROW_SENTINEL (-0x5A5A5A5A5A5A5A5All)
+#define RR_DEBUG_NCAND_SENTINEL (-0x5A5A5A5A)
+
+// what both entries refuse about the lists (nothing has been launched or copied yet)
+static int rr_debug_check_lists(const rr_index* ix, const char* who, int32_t nq, int64_t cap, int rows_per_mtile, const uint32_t* mtiles,
+                                const int32_t* count) {
+    RR_REQUIRE(ix->dim_pad == 384 && ix->d_matrix, "%s: index of dim 384 expected", who);
+    RR_REQUIRE(nq >= 1 && nq <= RR_SEL_MAXQ, "%s: nq %d outside 1..%d", who, nq, RR_SEL_MAXQ);
+    RR_REQUIRE(cap >= 1 && cap <= RR_X3_MCAP, "%s: cap %lld outside 1..%d", who, (long long)cap, RR_X3_MCAP);
+    const int64_t n_mtiles = (ix->n_rows + rows_per_mtile - 1) / rows_per_mtile;
+    for (int q = 0; q < nq; ++q) {
+        RR_REQUIRE(count[q] >= 0 && count[q] <= cap, "%s: count[%d] = %d outside 0..cap = %lld", who, q, count[q], (long long)cap);
+        for (int i = 0; i < count[q]; ++i)
+            RR_REQUIRE((int64_t)mtiles[(int64_t)q * cap + i] < n_mtiles, "%s: mtiles[%d][%d] = %u is not one of the %lld M-tiles of %d rows",
+                       who, q, i, mtiles[(int64_t)q * cap + i], (long long)n_mtiles, rows_per_mtile);
+    }
+    return RR_OK;
+}
+
+// host lists -> the index's selection scratch, where rr_flt_finish's launches read them
+static int rr_debug_place_lists(const rr_x3_scratch& X, int32_t nq, int64_t cap, const uint32_t* mtiles, const int32_t* count,
+                                const int32_t* fb, const uint32_t* tau) {
+    RR_HIP_TRY(hipMemcpy2D(X.mtiles, sizeof(uint32_t) * RR_X3_MCAP, mtiles, sizeof(uint32_t) * cap, sizeof(uint32_t) * cap, (size_t)nq,
+                           hipMemcpyHostToDevice));
+    RR_HIP_TRY(hipMemcpy(X.count, count, sizeof(int32_t) * nq, hipMemcpyHostToDevice));
+    RR_HIP_TRY(hipMemcpy(X.fb, fb, sizeof(int32_t) * nq, hipMemcpyHostToDevice));
+    RR_HIP_TRY(hipMemcpy(X.tau, tau, sizeof(uint32_t) * nq, hipMemcpyHostToDevice));
+    return RR_OK;
+}
+
+// ONE rr_rescore_chain launch (through rr_launch_rescore_chain, as rr_flt_finish launches it) on caller lists: mtiles[nq][cap]
+// (the first count[q] of a row are listed; repeats are fine), fb, tau (keys) and eps go to the selection scratch, the first
+// cap * 8 scores of every query are set to RR_DEBUG_SC_SENTINEL, and sc[nq][cap][8] comes back.  d_queries: device, [nq][384]
+// fp32.  grid_x: 16, or 4 (the launch under a corpus-wide floor).  use_plane 0: the storage rows alone (rr_rescore_chain<true> on
+// a bf16 index, the no-plane form on an fp32 one); 1: an fp32 index with its bf16 plane (built here if need be).  Every argument
+// is checked before anything is copied or launched.
+extern "C" int rr_debug_rescore_chain(rr_index* ix, const float* d_queries, int32_t nq, int32_t grid_x, int32_t use_plane,
+                                      const uint32_t* mtiles, int64_t cap, const int32_t* count, const int32_t* fb, const uint32_t* tau,
+                                      const float* eps, float* sc) {
+    RR_REQUIRE(ix && d_queries && mtiles && count && fb && tau && eps && sc, "rr_debug_rescore_chain: NULL argument");
+    RR_REQUIRE(grid_x == 16 || grid_x == 4, "rr_debug_rescore_chain: grid_x %d (the product launches 16, or 4 under a floor)", grid_x);
+    RR_REQUIRE(use_plane == 0 || (use_plane == 1 && ix->dtype == RR_DTYPE_F32), "rr_debug_rescore_chain: use_plane %d on a %s index",
+               use_plane, ix->dtype == RR_DTYPE_F32 ? "fp32" : "bf16");
+    int rc = rr_debug_check_lists(ix, "rr_debug_rescore_chain", nq, cap, 8, mtiles, count);
+    if (rc != RR_OK) return rc;
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = nullptr;
+    if (use_plane) {
+        ix->use_shadow = 1;
+        rc = rr_flt_ensure_shadow(ix, st);
+        if (rc != RR_OK) return rc;
+        RR_REQUIRE(ix->shadow_valid, "rr_debug_rescore_chain: no room for the bf16 filter plane");
+    }
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    rc = rr_debug_place_lists(X, nq, cap, mtiles, count, fb, tau);
+    if (rc != RR_OK) return rc;
+    RR_HIP_TRY(hipMemcpy(X.eps, eps, sizeof(float) * nq, hipMemcpyHostToDevice));
+    for (int q = 0; q < nq; ++q)
+        RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(X.sc + (int64_t)q * RR_X3_MCAP * 8), (int)RR_DEBUG_SC_SENTINEL, (size_t)cap * 8, st));
+    if (ix->dtype == RR_DTYPE_BF16) rr_launch_rescore_chain<true>(ix, ix->n_rows, d_queries, nq, grid_x, false, st);
+    else rr_launch_rescore_chain<false>(ix, ix->n_rows, d_queries, nq, grid_x, use_plane != 0, st);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    RR_HIP_TRY(hipMemcpy2D(sc, sizeof(float) * cap * 8, X.sc, sizeof(float) * RR_X3_MCAP * 8, sizeof(float) * cap * 8, (size_t)nq,
+                           hipMemcpyDeviceToHost));
+    return RR_OK;
+}
+
+// ONE rr_select_rescored launch (through rr_launch_select_rescored, with the index's n_rows and row_offset) on caller lists and
+// caller scores sc[nq][cap][rows_per_mtile]; rows_per_mtile 8 (the filter scan's M-tiles, G.mm_pairs = 3) or 16 (the
+// split-operand scans', G.mm_pairs = 1).  rows[nq][pool], scores[nq][pool] and n_cand[nq] (trace word 3) start from
+// RR_DEBUG_ROW_SENTINEL / RR_DEBUG_SC_SENTINEL / RR_DEBUG_NCAND_SENTINEL; fb_out is the flag array after the launch.  Every
+// argument is checked before anything is copied or launched.
+extern "C" int rr_debug_select_rescored(rr_index* ix, int32_t nq, int32_t pool, int32_t rows_per_mtile, int32_t floor_mode,
+                                        const uint32_t* mtiles, int64_t cap, const int32_t* count, const int32_t* fb, const uint32_t* tau,
+                                        const float* sc, int64_t* rows, float* scores, int32_t* fb_out, int32_t* n_cand) {
+    RR_REQUIRE(ix && mtiles && count && fb && tau && sc && rows && scores && fb_out && n_cand, "rr_debug_select_rescored: NULL argument");
+    RR_REQUIRE(rows_per_mtile == 8 || rows_per_mtile == 16, "rr_debug_select_rescored: rows_per_mtile %d (8 or 16)", rows_per_mtile);
+    RR_REQUIRE(floor_mode == 0 || floor_mode == 1, "rr_debug_select_rescored: floor_mode %d (0 or 1)", floor_mode);
+    RR_REQUIRE(pool >= 1 && pool <= RR_MAX_POOL && pool <= ix->n_rows, "rr_debug_select_rescored: pool %d out of [1,min(%d,n_rows=%lld)]", pool,
+               RR_MAX_POOL, (long long)ix->n_rows);
+    int rc = rr_debug_check_lists(ix, "rr_debug_select_rescored", nq, cap, rows_per_mtile, mtiles, count);
+    if (rc != RR_OK) return rc;
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = nullptr;
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    rc = rr_debug_place_lists(X, nq, cap, mtiles, count, fb, tau);
+    if (rc != RR_OK) return rc;
+    const size_t row_bytes = sizeof(float) * cap * rows_per_mtile;
+    RR_HIP_TRY(hipMemcpy2D(X.sc, sizeof(float) * RR_X3_MCAP * rows_per_mtile, sc, row_bytes, row_bytes, (size_t)nq, hipMemcpyHostToDevice));
+    std::vector<int64_t> row_fill((size_t)nq * pool, (int64_t)RR_DEBUG_ROW_SENTINEL);
+    std::vector<int32_t> trace((size_t)16 * nq, (int32_t)RR_DEBUG_NCAND_SENTINEL);
+    RR_HIP_TRY(hipMemcpy(ix->d_rows_out, row_fill.data(), sizeof(int64_t) * row_fill.size(), hipMemcpyHostToDevice));
+    RR_HIP_TRY(hipMemcpy(ix->d_sel_trace, trace.data(), sizeof(int32_t) * trace.size(), hipMemcpyHostToDevice));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_scores_out, (int)RR_DEBUG_SC_SENTINEL, (size_t)nq * pool, st));
+    rr_scan_geom G = {};
+    G.n_rows = ix->n_rows;
+    G.mm_pairs = rows_per_mtile == 8 ? 3 : 1;
+    rr_launch_select_rescored(ix, G, nq, pool, ix->d_rows_out, ix->d_scores_out, st, floor_mode != 0);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    RR_HIP_TRY(hipMemcpy(rows, ix->d_rows_out, sizeof(int64_t) * nq * pool, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(scores, ix->d_scores_out, sizeof(float) * nq * pool, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(fb_out, X.fb, sizeof(int32_t) * nq, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(trace.data(), ix->d_sel_trace, sizeof(int32_t) * trace.size(), hipMemcpyDeviceToHost));
+    for (int q = 0; q < nq; ++q) n_cand[q] = trace[(size_t)16 * q + 3];
     return RR_OK;
 }
 

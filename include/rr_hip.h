@@ -866,6 +866,44 @@ int rr_query_vectors_dev(const float* d_rows, int32_t n_queries, int32_t dim, fl
  * zeros).  Queue it after the front call on the same stream.  Asynchronous on `stream`. */
 int rr_query_flag_dev(const int32_t* d_src, int32_t n_queries, int32_t bit, int32_t* d_needs_host, void* stream);
 
+/* ------------------------------------------------------------ IR metrics of a batch's answer (csrc/rr_evals.hip) */
+
+/* What evals/performance_metrics.py:162-205 (IRMetrics.evaluate_query) computes from a ranked sku list, for a whole batch
+ * from K3's outputs where they lie: retrieved row j of query b is d_out_rows[b][d_order[b][j]] (d_out_rows int64
+ * [nq x pool], d_order int32 [nq x k] pool positions, best first -- what rr_fuse_topk_dev wrote; K3 returns distinct rows,
+ * so the reference's set intersection is a count).  evals.model_ir_metrics states the same in numpy.
+ * THE LABELS, a CSR over the queries: d_lab_off int64 [nq + 1]; d_lab_row int64 [n_labels] global rows, ascending inside a
+ * query (only labelled skus the index holds have an entry); d_lab_grade float64 = the sku's relevance_scores value (1.0 for
+ * binary labels); d_lab_rel uint8 = 1 when the sku is in relevant_items (the two differ when a caller passes both).
+ * n_labels = d_lab_off[nq] as the host knows it: a segment is cut to [0, n_labels), so no label array is read outside it;
+ * with n_labels = 0 the three label arrays may be NULL.  An empty segment is legal.
+ * PER-QUERY TABLES, the labels' alone (made once per query set on the host): d_n_rel int32 [nq] = len(relevant_items),
+ * skus absent from the index included (the reference's recall counts them); d_idcg float64 [nq x 2] = IDCG@5 and IDCG@10 of
+ * the sorted relevance_scores values, absent skus included.  d_log2 float64 [10] = numpy's log2(arange(1, 11) + 1), uploaded
+ * (the device's log2 is not numpy's bit for bit).
+ * d_metrics float64 [nq x 8]: ndcg@5, ndcg@10, mrr, recall@10, recall@20, precision@5, precision@10, first_hit -- to the bit
+ * what the reference computes:
+ *   DCG@c       L = min(c, k) terms t_i = grade_i / d_log2[i] (unlabelled rows: grade 0.0), one IEEE division each, added in
+ *               numpy's order for a contiguous float64 sum: L < 8 left to right from 0.0; 8 <= L <= 10
+ *               ((t0 + t1) + (t2 + t3)) + ((t4 + t5) + (t6 + t7)), then + t8, then + t9;
+ *   nDCG@c      dcg / idcg, 0.0 when idcg == 0.0;
+ *   first_hit   the 1-based rank of the first retrieved row whose d_lab_rel is 1 among ALL k, 0.0 when there is none;
+ *               mrr = 1.0 / first_hit, 0.0 with no hit;
+ *   recall@c    hits(min(c, k)) / n_rel, 0.0 when n_rel == 0; precision@c = hits(min(c, k)) / min(c, k); hits count
+ *               d_lab_rel, not grades.
+ * d_mean float64 [8] or NULL: the column means over the nq queries, from a second launch behind the first: fixed-order
+ * float64 sums without floating-point atomics (two runs give the same bits), within nq * 2^-52 relative of any other order.
+ * nq >= 1, 1 <= k <= pool <= RR_MAX_POOL; outside that or with a NULL argument RR_E_INVALID and nothing is launched.  A
+ * d_order entry outside [0, pool) names no row (it counts as unlabelled).  A wave per query; the pointers belong to the
+ * CURRENT device.  Asynchronous on `stream`; no scratch memory, nothing read back. */
+int rr_ir_metrics_dev(const int64_t* d_out_rows, const int32_t* d_order, int32_t nq, int32_t pool, int32_t k,
+                      const int64_t* d_lab_off, const int64_t* d_lab_row, const double* d_lab_grade, const uint8_t* d_lab_rel,
+                      int64_t n_labels, const int32_t* d_n_rel, const double* d_idcg, const double* d_log2,
+                      double* d_metrics, double* d_mean, void* stream);
+/* The column means alone: d_mean float64 [8] of a d_metrics table of nq >= 1 rows (a query set that went through
+ * rr_ir_metrics_dev in several batches, each into its rows of one table).  The launch rr_ir_metrics_dev makes for a d_mean. */
+int rr_ir_mean_dev(const double* d_metrics, int32_t nq, double* d_mean, void* stream);
+
 /* Two-phase K1 for ROW SHARDS (sharded.py: one process per GPU, this shard's rows in `ix`).  A shard's
  * own top-`top_k` threshold sits far below the corpus-wide one (rank 150 of 1.25M rows ~ rank 1 200 of 10M), so a shard
  * that selects on its own rescoring ~8x the candidates the merged answer needs.  Instead:

@@ -163,6 +163,9 @@ PROTOTYPES = {
     "rr_query_status": (C.c_int, [c_vp, P(c_i32)]),
     "rr_query_vectors_dev": (C.c_int, [c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
     "rr_query_flag_dev": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "rr_ir_metrics_dev": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp]),
+    "rr_ir_mean_dev": (C.c_int, [c_vp, c_i32, c_vp, c_vp]),
     "rr_index_stream": (C.c_int, [c_vp, P(c_vp)]),
     "rr_index_synchronize": (C.c_int, [c_vp]),
 }

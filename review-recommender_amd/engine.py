@@ -74,6 +74,34 @@ class BatchResult:
         return np.take_along_axis(c, self.order.astype(np.int64), axis=1)
 
 
+@dataclass
+class DeviceBatch:
+    """One query batch's answer where the kernels left it (HybridSearcher.search_batch_dev): BatchResult's fields as tensors
+    on the searcher's device.  Nothing has been waited for."""
+    device: object
+    pool_rows: object          # (B, pool) int64
+    columns: object            # (B, 8, pool) float64
+    order: object              # (B, k) int32
+    dense_raw: object          # (B, pool) float32
+    bm25_raw: object           # (B, pool) float32
+    pool: int
+    k: int
+    best_ids: object = None    # (B, pool) int32, with reviews
+    best_raw: object = None    # (B, pool) float32, with reviews
+    needs_host: object = None  # (B,) int32, with a query front
+
+    def download(self) -> BatchResult:
+        """The copy to the host `search_batch` ends with."""
+        with _torch().cuda.device(self.device):
+            res = BatchResult(self.pool_rows.cpu().numpy(), self.columns.cpu().numpy(), self.order.cpu().numpy(),
+                              self.dense_raw.cpu().numpy(), self.bm25_raw.cpu().numpy(), self.pool, self.k)
+            if self.best_ids is not None:
+                res.best_ids, res.best_raw = self.best_ids.cpu().numpy(), self.best_raw.cpu().numpy()
+            if self.needs_host is not None:
+                res.needs_host = self.needs_host.cpu().numpy()
+        return res
+
+
 def _torch():
     import torch
     return torch
@@ -449,8 +477,26 @@ class HybridSearcher:
         the rows of a flagged query were computed from an EMPTY query text and are the caller's to replace.
         ``on_queued``: called once when every kernel of the batch is queued, before the answer is waited for.
         ``bm25_f64``: the CLI flavour without a BM25 artefact (float64 zeros column, app/test.py:252)."""
+        dev = self.search_batch_dev(qvecs, term_id_lists, k, rerank_k, weights, pool_floor, gate_fn, rerank_fn, bm25_mode,
+                                    reviews, max_scan, bm25_f64, gate_groups, gate_host, rerank_pairs, query_front, on_queued)
+        return dev.download()
+
+    def search_batch_dev(self, qvecs, term_id_lists, k: int, rerank_k: int = 0, weights: Optional[FusionWeights] = None,
+                         pool_floor: int = APP_POOL_FLOOR, gate_fn=None, rerank_fn=None, bm25_mode: str = "forward",
+                         reviews=None, max_scan: int = 0, bm25_f64: bool = False, gate_groups=None, gate_host=None,
+                         rerank_pairs: Optional[Tuple] = None, query_front=None, on_queued=None,
+                         shared: Optional[dict] = None) -> DeviceBatch:
+        """`search_batch` up to the download: every kernel of the batch queued, the answer left in device tensors
+        (`DeviceBatch`; ``download()`` makes the BatchResult `search_batch` returns).
+        ``shared``: a dict that lives as long as ONE batch of queries is searched under several configurations
+        (SearchEngine.evaluate).  A stage whose inputs the dict has seen is not run again but read from it: K1 and K2 per
+        pool, the best-review column per (pool, max_scan), the gate factors per (pool, gate_penalty), the reranker's scores per
+        (pool, rerank_k).  The keys hold everything of THIS call's arguments the stage reads, on the understanding that the
+        caller passes the same queries, ``bm25_mode``, ``reviews`` and the same gate / rerank functions with every call that
+        shares the dict; K3 always runs.  With None nothing is kept."""
         torch = _torch()
         w = weights or FusionWeights()
+        memo = shared if shared is not None else {}
         q = q_dev = None
         if qvecs is None:
             q_dev = getattr(query_front, "qvecs", None)
@@ -477,66 +523,81 @@ class HybridSearcher:
             raise ValueError("pass either query_front or term_id_lists")
         packed = check_columns(B, w, self.gate_text, self.rerank_text, gate_fn, gate_groups, gate_host, rerank_fn, rerank_pairs,
                                query_front)
+
+        def once(key, make):
+            if key not in memo:
+                memo[key] = make()
+            return memo[key]
+
         with torch.cuda.device(self.device):
             if q_dev is None:
-                q_dev = torch.from_numpy(q).to(self.device)
-            if packed is query_front:
-                staged_groups = query_front.gate_staged if packed is not None else None
-            else:
-                staged_groups = self.gate_text.upload(packed) if packed is not None else None    # (ahead of the kernels)
-            rows, dense = self.dense_pool(q_dev, pool)
-            tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
-            if query_front is not None and self.bm25 is not None:
-                tl = query_front.terms
-            bm = self.bm25_at(tl, rows, bm25_mode)
+                q_dev = once(("q",), lambda: torch.from_numpy(q).to(self.device))
+            staged_groups = None
+            if ("gate", pool, w.gate_penalty) not in memo:
+                if packed is query_front:
+                    staged_groups = query_front.gate_staged if packed is not None else None
+                else:
+                    staged_groups = self.gate_text.upload(packed) if packed is not None else None    # (ahead of the kernels)
+
+            def k1_k2():
+                rows, dense = self.dense_pool(q_dev, pool)
+                tl = term_id_lists if term_id_lists is not None else [[] for _ in range(B)]
+                if query_front is not None and self.bm25 is not None:
+                    tl = query_front.terms
+                return rows, dense, self.bm25_at(tl, rows, bm25_mode)
+
+            rows, dense, bm = once(("pool", pool), k1_k2)
             gate = rerank = best = None
             best_ids = None
-            rows_h = None
+            rows_host = lambda: once(("rows_h", pool), lambda: rows.cpu().numpy())
             if reviews is not None:
                 # best review per candidate (csrc/rr_reviews.hip), the whole batch in one call; the
                 # reference's iloc[:max_rows] cut is evaluated per query on the device
-                best = torch.empty((B, pool), dtype=torch.float32, device=self.device)
-                best_ids = torch.empty((B, pool), dtype=torch.int32, device=self.device)
-                _lib.check(self.lib.rr_reviews_best_cut_dev(
-                    reviews.handle, C.c_void_p(q_dev.data_ptr()), B, C.c_void_p(rows.data_ptr()), pool,
-                    self.index.row_offset, int(max_scan), C.c_void_p(best.data_ptr()),
-                    C.c_void_p(best_ids.data_ptr()), self._stream()), "rr_reviews_best_cut_dev")
+                def best_review():
+                    best = torch.empty((B, pool), dtype=torch.float32, device=self.device)
+                    best_ids = torch.empty((B, pool), dtype=torch.int32, device=self.device)
+                    _lib.check(self.lib.rr_reviews_best_cut_dev(
+                        reviews.handle, C.c_void_p(q_dev.data_ptr()), B, C.c_void_p(rows.data_ptr()), pool,
+                        self.index.row_offset, int(max_scan), C.c_void_p(best.data_ptr()),
+                        C.c_void_p(best_ids.data_ptr()), self._stream()), "rr_reviews_best_cut_dev")
+                    return best, best_ids
+                best, best_ids = once(("best", pool, int(max_scan)), best_review)
             if packed is not None:
-                gate = self.gate_text.gate(rows, packed, gate_host, staged_groups)
-            if gate_fn is not None or (rerank_fn is not None and rr_k > 0):
-                rows_h = rows.cpu().numpy() if rows_h is None else rows_h
-                if gate_fn is not None:
-                    g = np.ascontiguousarray(gate_fn(rows_h), dtype=np.float32)
-                    gate = torch.from_numpy(g).to(self.device)
-                if rerank_fn is not None and rr_k > 0:
+                gate = once(("gate", pool, w.gate_penalty), lambda: self.gate_text.gate(rows, packed, gate_host, staged_groups))
+            if gate_fn is not None:
+                def host_gate():
+                    g = np.ascontiguousarray(gate_fn(rows_host()), dtype=np.float32)
+                    return torch.from_numpy(g).to(self.device)
+                gate = once(("gate", pool, w.gate_penalty), host_gate)
+            if rerank_fn is not None and rr_k > 0:
+                def host_rerank():
                     r = np.zeros((B, pool), dtype=np.float32)
-                    r[:, :rr_k] = np.asarray(rerank_fn(rows_h[:, :rr_k]), dtype=np.float32)
-                    rerank = torch.from_numpy(r).to(self.device)
+                    r[:, :rr_k] = np.asarray(rerank_fn(rows_host()[:, :rr_k]), dtype=np.float32)
+                    return torch.from_numpy(r).to(self.device)
+                rerank = once(("rerank", pool, rr_k), host_rerank)
             if rerank_pairs is not None and rr_k > 0:
-                rr_ce, rr_queries, rerank_host = rerank_pairs
-                rerank = torch.zeros((B, pool), dtype=torch.float32, device=self.device)
-                if rr_queries is None:
-                    rr_queries = query_front
-                    rerank[:, :rr_k] = self.rerank_text.scores(rr_ce, rows, rr_k, rr_queries, staged=query_front.rerank_staged)
-                else:
-                    rerank[:, :rr_k] = self.rerank_text.scores(rr_ce, rows, rr_k, rr_queries)
-                if rr_queries.host_queries:
-                    rows_h = rows.cpu().numpy() if rows_h is None else rows_h
-                    for b in rr_queries.host_queries:
-                        r = np.ascontiguousarray(rerank_host(b, rows_h[b, :rr_k]), dtype=np.float32).reshape(rr_k)
-                        rerank[b, :rr_k].copy_(torch.from_numpy(r))
+                def device_rerank():
+                    rr_ce, rr_queries, rerank_host = rerank_pairs
+                    rerank = torch.zeros((B, pool), dtype=torch.float32, device=self.device)
+                    if rr_queries is None:
+                        rr_queries = query_front
+                        rerank[:, :rr_k] = self.rerank_text.scores(rr_ce, rows, rr_k, rr_queries, staged=query_front.rerank_staged)
+                    else:
+                        rerank[:, :rr_k] = self.rerank_text.scores(rr_ce, rows, rr_k, rr_queries)
+                    if rr_queries.host_queries:
+                        rows_h = rows_host()
+                        for b in rr_queries.host_queries:
+                            r = np.ascontiguousarray(rerank_host(b, rows_h[b, :rr_k]), dtype=np.float32).reshape(rr_k)
+                            rerank[b, :rr_k].copy_(torch.from_numpy(r))
+                    return rerank
+                rerank = once(("rerank", pool, rr_k), device_rerank)
             params = self.make_params(w, k_eff, pool, pool, rr_k, bm25_f64=bm25_f64 and self.bm25 is None)
             out_rows, cols, order = self.fuse(params, B, rows, dense, None if params.bm25_f64 else bm, None,
                                               rerank, best, gate)
             if on_queued is not None:
                 on_queued()
-            res = BatchResult(out_rows.cpu().numpy(), cols.cpu().numpy(), order.cpu().numpy(),
-                              dense.cpu().numpy(), bm.cpu().numpy(), pool, k_eff)
-            if best_ids is not None:
-                res.best_ids, res.best_raw = best_ids.cpu().numpy(), best.cpu().numpy()
-            if query_front is not None:
-                res.needs_host = query_front.needs_host.cpu().numpy()
-        return res
+        return DeviceBatch(self.device, out_rows, cols, order, dense, bm, pool, k_eff, best_ids, best if best_ids is not None else None,
+                           query_front.needs_host if query_front is not None else None)
 
 
 class SearchEngine:
@@ -872,6 +933,25 @@ class SearchEngine:
                    "groups": [list(g) for g in groups[b]], "pool": max(k, rerank_k, floor)}
             out.append((frame, snips, dbg))
         return out
+
+    def evaluate(self, test_queries, method_configs: Dict[str, Dict], *, qvecs: Optional[np.ndarray] = None,
+                 batch: int = 1024):
+        """The reference's ``evaluate_ranking_methods(run_search, test_queries, method_configs)`` as a device operation
+        (evals.py, csrc/rr_evals.hip).  ``test_queries``: the evals dicts (``id``, ``query``, ``relevant_items``, optional
+        ``relevance_scores``), the app tab's JSONL entries (``query``, ``relevant``), or a ready `evals.LabelSet`;
+        ``method_configs``: method -> `run_search` keyword arguments, as in BENCHMARK_CONFIGS; ``qvecs`` (Q, dim): the query
+        embeddings when no encoder is loaded.  Returns an `evals.EvalReport`: ``summary`` (methods x the seven metrics),
+        ``detailed(method)`` (per query, downloaded on demand), ``metrics_dev[method]`` ((Q, 8) float64 on the device).
+
+        The queries go through in batches of at most ``batch`` (<= RR_MAX_BATCH).  Per batch every configuration ranks
+        exactly as `run_search_batch` does with its arguments, but the stages the fusion weights do not touch run once for
+        all configurations that read the same thing -- the query front per gate penalty (the query vectors once), K1 and K2
+        per pool, the best-review column per (pool, max_scan), the gate match per (pool, gate_penalty), the reranker per
+        (pool, rerank_k) -- and only K3 and rr_ir_metrics_dev run per configuration.  Pool rows, columns and orders stay on
+        the device and no frame is built; what is read back is the front's flags (the queries it hands back are searched
+        again through the host functions, as in `run_search_batch`) and, when asked for, the metrics."""
+        from .evals import evaluate_engine
+        return evaluate_engine(self, test_queries, method_configs, qvecs=qvecs, batch=batch)
 
     def _search_device_text(self, queries, qv, k, rerank_k, w, gate_penalty, common, host_text, search_host):
         """One batch with query_text="device": the bytes are staged once and the front end is queued ahead of K1; the

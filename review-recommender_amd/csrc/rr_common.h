@@ -77,6 +77,7 @@ struct rr_index {
     float* d_q = nullptr;        // staged queries [RR_MAX_BATCH][dim_pad]
     float norm_bound = -1.f;     // upper bound of the largest row norm; < 0: not computed (any write to the matrix resets it)
     float delta_bound = 0.f;     // ... and of the largest ||row - bf16(row)||
+    int32_t norm_kinds = -1;     // RR_NORM_KIND_* of a matrix without a finite bound; < 0: not computed (reset with norm_bound)
     int32_t last_scan[5] = {0, 0, 0, 0, 0};   // kernel id, template variant, queries in the launch, bf16 MFMA terms per dim, bytes per scanned element
     // bf16 filter plane of an fp32 matrix (rr_dense_flt.hip): every element rounded once to nearest even.  The batched
     // filter scan reads it instead of the fp32 rows (half the bytes per launch, the same approximate scores: the scan

@@ -5,6 +5,13 @@
 #pragma once
 #ifdef RR_DEBUG_HARNESS
 #include "rr_common.h"
+#include "rr_dense.h"
+// The two sentinels rr_dense_x3w.hip shares with rr_dense_flt.hip, where they are defined (the same tokens) and explained.
+#define RR_DEBUG_KEY_SENTINEL 0xFFC00001u
+#define RR_DEBUG_SC_SENTINEL 0x7FC5A5A5u
+// rr_dense_x3.hip: the 16-slot launches of rr_debug_x3_scan / rr_debug_x3_rescore (rr_dense_x3w.hip)
+void rr_debug_x3_scan16(rr_index* ix, const float* d_q, int mode, rr_scan_geom* G, hipStream_t st);
+void rr_debug_x3_rescore16(rr_index* ix, const float* d_q, int nq, hipStream_t st);
 extern "C" {
 // tools/x3w_ablate.py: variants of the 64-query fp32 split-operand scan (bit 0: no operand split, bit 1: no B-fragment
 // reads, bit 2: no MFMA, bit 3: no lane swap)
@@ -30,6 +37,15 @@ int rr_debug_rescore_chain(rr_index* ix, const float* d_queries, int32_t nq, int
 int rr_debug_select_rescored(rr_index* ix, int32_t nq, int32_t pool, int32_t rows_per_mtile, int32_t floor_mode, const uint32_t* mtiles,
                              int64_t cap, const int32_t* count, const int32_t* fb, const uint32_t* tau, const float* sc, int64_t* rows,
                              float* scores, int32_t* fb_out, int32_t* n_cand);
+// tests/test_gpu_x3_scan_kernels.py: ONE split-operand scan launch (rr_scan_mfma_x3 / rr_scan_x3w, routed by nq as the product
+// routes; mode 0 normal scan, 1 stored pass, 2 stored pass as the fallback launches it: flags + in-kernel query split) into
+// scratch filled with sentinels, and its raw words on the host; ONE rescoring launch (rr_rescore_x3 / rr_rescore_x3w) on
+// caller lists of 16-row M-tiles.  Both go through the launch helpers the product calls.  See the definitions (rr_dense_x3w.hip).
+int rr_debug_x3_scan(rr_index* ix, const float* d_queries, int32_t nq, int32_t mode, const int32_t* flags, int64_t* geom,
+                     uint32_t* sims, int64_t sims_cap, uint32_t* gmax, int64_t gmax_cap, uint32_t* smax, int64_t smax_cap,
+                     unsigned short* planes);
+int rr_debug_x3_rescore(rr_index* ix, const float* d_queries, int32_t nq, const uint32_t* mtiles, int64_t cap, const int32_t* count,
+                        const int32_t* fb, float* sc);
 // tools/k5_stamps.py: in-kernel phase clocks of the last ce_ffn_fused launch (rr_ce.hip)
 int rr_debug_ce_ffn_stamps(unsigned long long* out20);
 // tools/k5_h2_stamps.py: phase clocks of one workgroup of the last FFN1 ce_gemm_h2 launch (rr_ce_h2.hip)

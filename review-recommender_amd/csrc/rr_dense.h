@@ -41,6 +41,7 @@ static inline void rr_scan_note(rr_index* ix, int kernel, int variant, int nq, i
 // any write to the matrix: the cached row-norm bound and the bf16 filter plane no longer describe it
 static inline void rr_matrix_written(rr_index* ix) {
     ix->norm_bound = -1.f;
+    ix->norm_kinds = -1;
     ix->shadow_valid = false;
 }
 // scan slots (rr_common.h: rr_scan_slot): which of the two sets of per-batch scan state the index fields describe
@@ -103,6 +104,11 @@ int rr_dense_chunk_x3(rr_index* ix, const float* d_q, int nq, int pool, int64_t*
 int rr_dense_chunk_flt(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                        float* d_scores, hipStream_t st, int phase = 0, int kth = 0, float* d_bound = nullptr,
                        const float* d_floor = nullptr, int parts = 7);
+// Which non-finite squared row norms the matrix holds (one pass, cached; asked only when there is no finite bound): a NaN one
+// = a row with a NaN element, a +inf one = a row with an inf element or whose squares overflow (and no NaN).  Both are reported.
+#define RR_NORM_KIND_NAN 1
+#define RR_NORM_KIND_INF 2
+int rr_flt_norm_kinds(rr_index* ix, hipStream_t st, int* kinds);
 // any other search on the index makes a parked phase-1 scan void
 void rr_flt_drop_pending(rr_index* ix);
 // fp32 rows (device, n x dim) -> the index's bf16 matrix rows [first, first + n), optional l2 normalise

@@ -1332,7 +1332,8 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
         if (mfma_ok && left > valu_max && !exact_scan && ix->scan_mode == RR_SCAN_MODE_DEFAULT &&
             (ix->n_rows + 63) / 64 < 8 * (int64_t)pool)
             small = true;
-        if (mfma_ok && left > valu_max && !small) {
+        bool valu = !(mfma_ok && left > valu_max) || small;
+        if (!valu) {
             // 5..128 queries share one read of the matrix: bf16 filter scan + exact rescoring of the
             // candidates (rr_dense_flt.hip); without a finite row-norm bound, or with RR_SCAN_EXACT=1 /
             // RR_SCAN_MODE_STORED, the exact split-operand scans, 64 queries per read
@@ -1345,15 +1346,26 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
                 int nf = left < RR_FLT_MAXQ ? left : RR_FLT_MAXQ;
                 if (!no_pair && left > RR_FLT_MAXQ + RR_MFMA_MAXQ) nf = left < RR_SEL_MAXQ ? left : RR_SEL_MAXQ;
                 rc = rr_dense_chunk_flt(ix, q, nf, pool, rows, scores, st);
-                if (rc != RR_FLT_NO_BOUND && rc != RR_FLT_SMALL) {
+                if (rc == RR_FLT_NO_BOUND) {
+                    // No finite bound.  NaN rows alone stay on the split-operand scans (a NaN score ranks last there as in
+                    // every scan).  A +inf norm -- an inf element, or squares that overflow -- does not: the split of +-inf is
+                    // (+-inf, NaN, NaN) and inf * 0 is NaN, so such a row scores NaN = -inf there and +-inf in the per-row
+                    // chain; a query's answer must not depend on its batch, so these matrices take the VALU scans (the
+                    // single-query arithmetic, eight queries per read).  RR_SCAN_EXACT / RR_SCAN_MODE_STORED stay diagnostics.
+                    int kinds = 0;
+                    const int rk = rr_flt_norm_kinds(ix, st, &kinds);
+                    if (rk != RR_OK) return rk;
+                    if (kinds & RR_NORM_KIND_INF) valu = true;
+                } else if (rc != RR_FLT_SMALL) {
                     done = true;
                     n = nf;
                 }
             }
-            if (!done) rc = rr_dense_chunk_x3(ix, q, n, pool, rows, scores, st);
-        } else {
+            if (!done && !valu) rc = rr_dense_chunk_x3(ix, q, n, pool, rows, scores, st);
+        }
+        if (valu) {
             // the VALU scan kernels read NB = 1/2/4/8 query slots; slots past n hold zeros
-            const int vmax = small ? 8 : valu_max;
+            const int vmax = (mfma_ok && left > valu_max) ? 8 : valu_max;
             n = left < vmax ? left : vmax;
             rc = bf16 ? rr_dense_chunk_bf16(ix, q, n, pool, rows, scores, st)
                       : rr_dense_chunk(ix, q, n, pool, rows, scores, st, q0 == 0);

@@ -152,6 +152,43 @@ __global__ __launch_bounds__(256) void rr_row_norm_max(const void* __restrict__ 
     }
 }
 
+// The kinds of non-finite squared row norms (RR_NORM_KIND_*), OR-ed into out[0]: the sums of rr_row_norm_max, row by row.  A
+// sum of squares is NaN only through a NaN element (squares are not negative: no inf - inf), +inf through an inf element or
+// an overflow.  Runs once per matrix, and only on one rr_row_norm_max found no finite bound for.
+template <bool A_BF16>
+__global__ __launch_bounds__(256) void rr_row_norm_kinds(const void* __restrict__ mat, int64_t n_rows, int dim_pad,
+                                                         unsigned int* __restrict__ out) {
+    const int lane = threadIdx.x & 63, sub = lane & 15, grp = lane >> 4;
+    const int64_t row0 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 64;
+    const int units = dim_pad / (A_BF16 ? 8 : 4);            // 16-byte units per row
+    unsigned int kinds = 0u;
+    for (int it = 0; it < 16; ++it) {
+        const int64_t row = row0 + 4 * it + grp;
+        float ss = 0.f;
+        if (row < n_rows) {
+            const u32x4* p = static_cast<const u32x4*>(mat) + row * units;
+            for (int u = sub; u < units; u += 16) {
+                const u32x4 w = p[u];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (A_BF16) {
+                        const float x0 = __uint_as_float(w[e] << 16), x1 = __uint_as_float(w[e] & 0xFFFF0000u);
+                        ss = __builtin_fmaf(x0, x0, ss);
+                        ss = __builtin_fmaf(x1, x1, ss);
+                    } else {
+                        const float x = __uint_as_float(w[e]);
+                        ss = __builtin_fmaf(x, x, ss);
+                    }
+                }
+            }
+        }
+        ss = rr_row16_sum(ss);
+        kinds |= (ss != ss) ? (unsigned)RR_NORM_KIND_NAN : (ss == INFINITY) ? (unsigned)RR_NORM_KIND_INF : 0u;
+    }
+    if (__any(kinds & RR_NORM_KIND_NAN) && lane == 0) atomicOr(out, (unsigned)RR_NORM_KIND_NAN);
+    if (__any(kinds & RR_NORM_KIND_INF) && lane == 0) atomicOr(out, (unsigned)RR_NORM_KIND_INF);
+}
+
 // ------------------------------------------------------------------ the filter scan
 // v_max_f32 / v_max3_f32 spelled out: fmaxf() brings a canonicalising v_max x, x, x per operand with it
 // (three instructions per maximum); like fmaxf they return the other operand for a NaN.
@@ -1247,6 +1284,24 @@ static int rr_flt_get_bounds(rr_index* ix, hipStream_t st, rr_flt_bounds* out) {
     return RR_OK;
 }
 
+int rr_flt_norm_kinds(rr_index* ix, hipStream_t st, int* kinds) {
+    if (ix->norm_kinds < 0) {
+        unsigned int* d = reinterpret_cast<unsigned int*>(rr_x3_scratch_of(ix).eps);   // borrowed for one word
+        RR_HIP_TRY(hipMemsetAsync(d, 0, sizeof(unsigned int), st));
+        const unsigned blocks = (unsigned)((ix->n_rows + 255) / 256);
+        if (ix->dtype == RR_DTYPE_BF16)
+            hipLaunchKernelGGL((rr_row_norm_kinds<true>), dim3(blocks), dim3(256), 0, st, ix->d_matrix, ix->n_rows, ix->dim_pad, d);
+        else
+            hipLaunchKernelGGL((rr_row_norm_kinds<false>), dim3(blocks), dim3(256), 0, st, ix->d_matrix, ix->n_rows, ix->dim_pad, d);
+        unsigned int bits = 0u;
+        RR_HIP_TRY(hipMemcpyAsync(&bits, d, sizeof(bits), hipMemcpyDeviceToHost, st));
+        RR_HIP_TRY(hipStreamSynchronize(st));
+        ix->norm_kinds = (int32_t)bits;
+    }
+    *kinds = ix->norm_kinds;
+    return RR_OK;
+}
+
 // geometry of rr_scan_flt / rr_scan_flt16: one run per resident wave, quarter runs as selection groups
 template <int NQ2, bool A_BF16>
 static rr_scan_geom rr_flt_geom(rr_index* ix) {
@@ -1906,7 +1961,7 @@ extern "C" int rr_debug_select_traces(rr_index* ix, int32_t nq, int32_t* out) {
 #define RR_DEBUG_NCAND_SENTINEL (-0x5A5A5A5A)
 
 // what both entries refuse about the lists (nothing has been launched or copied yet)
-static int rr_debug_check_lists(const rr_index* ix, const char* who, int32_t nq, int64_t cap, int rows_per_mtile, const uint32_t* mtiles,
+int rr_debug_check_lists(const rr_index* ix, const char* who, int32_t nq, int64_t cap, int rows_per_mtile, const uint32_t* mtiles,
                                 const int32_t* count) {
     RR_REQUIRE(ix->dim_pad == 384 && ix->d_matrix, "%s: index of dim 384 expected", who);
     RR_REQUIRE(nq >= 1 && nq <= RR_SEL_MAXQ, "%s: nq %d outside 1..%d", who, nq, RR_SEL_MAXQ);
@@ -1922,7 +1977,7 @@ static int rr_debug_check_lists(const rr_index* ix, const char* who, int32_t nq,
 }
 
 // host lists -> the index's selection scratch, where rr_flt_finish's launches read them
-static int rr_debug_place_lists(const rr_x3_scratch& X, int32_t nq, int64_t cap, const uint32_t* mtiles, const int32_t* count,
+int rr_debug_place_lists(const rr_x3_scratch& X, int32_t nq, int64_t cap, const uint32_t* mtiles, const int32_t* count,
                                 const int32_t* fb, const uint32_t* tau) {
     RR_HIP_TRY(hipMemcpy2D(X.mtiles, sizeof(uint32_t) * RR_X3_MCAP, mtiles, sizeof(uint32_t) * cap, sizeof(uint32_t) * cap, (size_t)nq,
                            hipMemcpyHostToDevice));

@@ -4,6 +4,8 @@
 // exact sum of three bf16 numbers (8 + 8 + 8 significant bits: x1 = top 16 bits of x,
 // x2 = top 16 bits of x - x1, x3 = x - x1 - x2, every subtraction exact), and a product of two
 // bf16 numbers is exact in fp32.  So  a*q = sum_{i,j} a_i*q_j  with every partial product exact;
+// ("exact sum": for |x| >= 2^-110 and 0 -- below, x3 is an fp32 subnormal whose low 16 bits the bf16 operand cuts; +-inf
+// splits into (+-inf, NaN, NaN): rr_x3.h, DESIGN.md "Domain of exact".)
 // the three smallest of the nine terms (a2*q3, a3*q2, a3*q3 <= 2^-24 |a*q|, below fp32's own
 // rounding of the product) are dropped:
 //   fp32 matrix  : a1q1 + a1q2 + a2q1 + a2q2 + a1q3 + a3q1   6 MFMAs per 32 dims ( 96 cycles; f32 MFMA: 256)
@@ -287,27 +289,49 @@ __global__ __launch_bounds__(256) void rr_rescore_x3(
     }
 }
 
+// ---- the pieces of one launch sequence, shared by the product (rr_dense_chunk_x3_t) and the kernel-test harness
+// geometry of a rr_scan_mfma_x3 launch: one run of 64-row tiles per resident wave, 16 query slots
 template <bool A_BF16>
-static int rr_dense_chunk_x3_t(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
-                               float* d_scores, hipStream_t st) {
+static rr_scan_geom rr_x3_geom(rr_index* ix) {
     constexpr int THREADS = 256;
-    constexpr int QN = 16;
     static int waves = 0;
     if (!waves) waves = rr_resident_waves((const void*)rr_scan_mfma_x3<A_BF16, false>, THREADS, ix->device);
     rr_scan_geom G = rr_make_geom(ix, waves / 4);
-    G.qs = QN;
-    // the split query planes live behind the staged queries in the index's query buffer
-    unsigned short* planes = reinterpret_cast<unsigned short*>(ix->d_qplanes);
-    const u32x4* mat = reinterpret_cast<const u32x4*>(ix->d_matrix);
-    const u32x4* pl4 = reinterpret_cast<const u32x4*>(planes);
+    G.qs = 16;
+    return G;
+}
+// the 16 query slots at d_q -> the split planes behind the staged queries in the index's query buffer, in the scan's k order
+template <bool A_BF16>
+static void rr_x3_split_launch(rr_index* ix, const float* d_q, hipStream_t st) {
+    rr_launch_split_queries(d_q, reinterpret_cast<unsigned short*>(ix->d_qplanes), 16,
+                            A_BF16 ? RR_X3_ORDER_NATURAL : RR_X3_ORDER_PAIR64, st);
+}
+// one rr_scan_mfma_x3 launch on those planes into the index's scan scratch (`flags`: the STORE pass's gate, may be null)
+template <bool A_BF16, bool STORE>
+static void rr_x3_scan_launch(rr_index* ix, const rr_scan_geom& G, const int32_t* flags, int n_flags, hipStream_t st) {
+    constexpr int THREADS = 256;
     const dim3 grid((G.n_waves + THREADS / 64 - 1) / (THREADS / 64)), block(THREADS);
+    hipLaunchKernelGGL((rr_scan_mfma_x3<A_BF16, STORE>), grid, block, 0, st, reinterpret_cast<const u32x4*>(ix->d_matrix), G,
+                       reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_sims, ix->d_gmax, ix->d_smax, flags, n_flags);
+}
+// one rr_rescore_x3 launch on the lists of the selection scratch
+template <bool A_BF16>
+static void rr_x3_rescore_launch(rr_index* ix, const rr_scan_geom& G, int nq, hipStream_t st) {
     const rr_x3_scratch X = rr_x3_scratch_of(ix);
-    rr_launch_split_queries(d_q, planes, QN, A_BF16 ? RR_X3_ORDER_NATURAL : RR_X3_ORDER_PAIR64, st);
+    hipLaunchKernelGGL((rr_rescore_x3<A_BF16>), dim3(64, nq), dim3(256), 0, st, reinterpret_cast<const u32x4*>(ix->d_matrix),
+                       G.n_rows, reinterpret_cast<const u32x4*>(ix->d_qplanes), 16, X.mtiles, X.count, X.fb, X.sc);
+}
+
+template <bool A_BF16>
+static int rr_dense_chunk_x3_t(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
+                               float* d_scores, hipStream_t st) {
+    const rr_scan_geom G = rr_x3_geom<A_BF16>(ix);
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    rr_x3_split_launch<A_BF16>(ix, d_q, st);
     if (rr_x3_stored_path(ix)) {
         const int slot = rr_scan_events_begin(ix, st);
         rr_scan_note(ix, 3, 1, nq, A_BF16 ? 3 : 6);
-        hipLaunchKernelGGL((rr_scan_mfma_x3<A_BF16, true>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
-                           ix->d_gmax, ix->d_smax, (const int32_t*)nullptr, 0);
+        rr_x3_scan_launch<A_BF16, true>(ix, G, nullptr, 0, st);
         rr_scan_events_end(ix, slot, st);
         rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st);
         RR_HIP_TRY(hipGetLastError());
@@ -315,16 +339,13 @@ static int rr_dense_chunk_x3_t(rr_index* ix, const float* d_q, int nq, int pool,
     }
     const int slot = rr_scan_events_begin(ix, st);
     rr_scan_note(ix, 3, 1, nq, A_BF16 ? 3 : 6);
-    hipLaunchKernelGGL((rr_scan_mfma_x3<A_BF16, false>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
-                       ix->d_gmax, ix->d_smax, (const int32_t*)nullptr, 0);
+    rr_x3_scan_launch<A_BF16, false>(ix, G, nullptr, 0, st);
     rr_scan_events_end(ix, slot, st);
     rr_launch_select_mtiles(ix, G, nq, pool, st);
-    hipLaunchKernelGGL((rr_rescore_x3<A_BF16>), dim3(64, nq), dim3(256), 0, st, mat, G.n_rows, pl4, QN,
-                       X.mtiles, X.count, X.fb, X.sc);
+    rr_x3_rescore_launch<A_BF16>(ix, G, nq, st);
     rr_launch_select_rescored(ix, G, nq, pool, d_rows, d_scores, st);
     // Fallback for the queries that raised their flag: both launches return at once otherwise.
-    hipLaunchKernelGGL((rr_scan_mfma_x3<A_BF16, true>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
-                       ix->d_gmax, ix->d_smax, (const int32_t*)X.fb, nq);
+    rr_x3_scan_launch<A_BF16, true>(ix, G, X.fb, nq, st);
     rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st, X.fb);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
@@ -337,3 +358,29 @@ int rr_dense_chunk_x3(rr_index* ix, const float* d_q, int nq, int pool, int64_t*
     return ix->dtype == RR_DTYPE_BF16 ? rr_dense_chunk_x3_t<true>(ix, d_q, nq, pool, d_rows, d_scores, st)
                                       : rr_dense_chunk_x3_t<false>(ix, d_q, nq, pool, d_rows, d_scores, st);
 }
+
+#ifdef RR_DEBUG_HARNESS
+#include "rr_debug.h"
+// rr_debug_x3_scan / rr_debug_x3_rescore (rr_dense_x3w.hip), 5..16 queries: the launch sequence pieces above, one at a time.
+// mode 0: split + the normal scan; 1: split + the stored pass.
+template <bool A_BF16>
+static void rr_debug_x3_scan16_t(rr_index* ix, const float* d_q, int mode, rr_scan_geom* G, hipStream_t st) {
+    *G = rr_x3_geom<A_BF16>(ix);
+    rr_x3_split_launch<A_BF16>(ix, d_q, st);
+    if (mode == 0) rr_x3_scan_launch<A_BF16, false>(ix, *G, nullptr, 0, st);
+    else rr_x3_scan_launch<A_BF16, true>(ix, *G, nullptr, 0, st);
+}
+void rr_debug_x3_scan16(rr_index* ix, const float* d_q, int mode, rr_scan_geom* G, hipStream_t st) {
+    if (ix->dtype == RR_DTYPE_BF16) rr_debug_x3_scan16_t<true>(ix, d_q, mode, G, st);
+    else rr_debug_x3_scan16_t<false>(ix, d_q, mode, G, st);
+}
+void rr_debug_x3_rescore16(rr_index* ix, const float* d_q, int nq, hipStream_t st) {
+    if (ix->dtype == RR_DTYPE_BF16) {
+        rr_x3_split_launch<true>(ix, d_q, st);
+        rr_x3_rescore_launch<true>(ix, rr_x3_geom<true>(ix), nq, st);
+    } else {
+        rr_x3_split_launch<false>(ix, d_q, st);
+        rr_x3_rescore_launch<false>(ix, rr_x3_geom<false>(ix), nq, st);
+    }
+}
+#endif  // RR_DEBUG_HARNESS

@@ -449,27 +449,54 @@ __global__ __launch_bounds__(256, 4) void rr_rescore_x3w(
     }
 }
 
+// ---- the pieces of one launch sequence, shared by the product (rr_dense_chunk_x3w_t, rr_x3w_fallback_t) and the kernel-test
+// harness.  Geometry of a rr_scan_x3w<NQ2> launch: one run of 64-row tiles per resident wave of the STORE instance the
+// launch runs, 32 NQ2 query slots.
+template <int NQ2, bool A_BF16, bool STORE>
+static rr_scan_geom rr_x3w_geom(rr_index* ix) {
+    constexpr int THREADS = NQ2 == 2 ? 512 : 256;
+    static int waves = 0;
+    if (!waves) waves = rr_resident_waves((const void*)rr_scan_x3w<NQ2, A_BF16, STORE>, THREADS, ix->device);
+    rr_scan_geom G = rr_make_geom(ix, waves / 4);
+    G.qs = 32 * NQ2;
+    if (!STORE) G.mm_pairs = 1;
+    return G;
+}
+// the 32 NQ2 query slots at d_q -> the split planes in the index's query buffer, in the scan's k order
+template <int NQ2, bool A_BF16>
+static void rr_x3w_split_launch(rr_index* ix, const float* d_q, hipStream_t st) {
+    rr_launch_split_queries(d_q, reinterpret_cast<unsigned short*>(ix->d_qplanes), 32 * NQ2,
+                            A_BF16 ? RR_X3_ORDER_WIDE_BF16 : RR_X3_ORDER_NATURAL, st);
+}
+// one rr_scan_x3w launch into the index's scan scratch.  `flags`: the STORE pass's gate (may be null); `raw_q` non-null: the
+// kernel splits these fp32 queries itself and does not read the planes (the fallback launches)
+template <int NQ2, bool A_BF16, bool STORE>
+static void rr_x3w_scan_launch(rr_index* ix, const rr_scan_geom& G, const int32_t* flags, int n_flags, const float* raw_q,
+                               hipStream_t st) {
+    constexpr int THREADS = NQ2 == 2 ? 512 : 256;
+    const dim3 grid((G.n_waves + THREADS / 64 - 1) / (THREADS / 64)), block(THREADS);
+    hipLaunchKernelGGL((rr_scan_x3w<NQ2, A_BF16, STORE>), grid, block, 0, st, reinterpret_cast<const u32x4*>(ix->d_matrix), G,
+                       reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_sims, ix->d_gmax, ix->d_smax, flags, n_flags, raw_q);
+}
+// one rr_rescore_x3w launch on the lists of the selection scratch (QN: query slots of the planes)
+template <bool A_BF16>
+static void rr_x3w_rescore_launch(rr_index* ix, const rr_scan_geom& G, int QN, int nq, hipStream_t st) {
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    hipLaunchKernelGGL((rr_rescore_x3w<A_BF16>), dim3(64, nq), dim3(256), 0, st, reinterpret_cast<const u32x4*>(ix->d_matrix),
+                       G.n_rows, reinterpret_cast<const u32x4*>(ix->d_qplanes), QN, X.mtiles, X.count, X.fb, X.sc);
+}
+
 template <int NQ2, bool A_BF16>
 static int rr_dense_chunk_x3w_t(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                                 float* d_scores, hipStream_t st) {
-    constexpr int THREADS = NQ2 == 2 ? 512 : 256;
     constexpr int QN = 32 * NQ2;
-    static int waves = 0;
-    if (!waves) waves = rr_resident_waves((const void*)rr_scan_x3w<NQ2, A_BF16, false>, THREADS, ix->device);
-    rr_scan_geom G = rr_make_geom(ix, waves / 4);
-    G.qs = QN;
-    G.mm_pairs = 1;
-    unsigned short* planes = reinterpret_cast<unsigned short*>(ix->d_qplanes);
-    const u32x4* mat = reinterpret_cast<const u32x4*>(ix->d_matrix);
-    const u32x4* pl4 = reinterpret_cast<const u32x4*>(planes);
-    const dim3 grid((G.n_waves + THREADS / 64 - 1) / (THREADS / 64)), block(THREADS);
+    const rr_scan_geom G = rr_x3w_geom<NQ2, A_BF16, false>(ix);
     const rr_x3_scratch X = rr_x3_scratch_of(ix);
-    rr_launch_split_queries(d_q, planes, QN, A_BF16 ? RR_X3_ORDER_WIDE_BF16 : RR_X3_ORDER_NATURAL, st);
+    rr_x3w_split_launch<NQ2, A_BF16>(ix, d_q, st);
     if (rr_x3_stored_path(ix)) {
         const int slot = rr_scan_events_begin(ix, st);
         rr_scan_note(ix, 4, NQ2, nq, A_BF16 ? 3 : 6);
-        hipLaunchKernelGGL((rr_scan_x3w<NQ2, A_BF16, true>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
-                           ix->d_gmax, ix->d_smax, (const int32_t*)nullptr, 0);
+        rr_x3w_scan_launch<NQ2, A_BF16, true>(ix, G, nullptr, 0, nullptr, st);
         rr_scan_events_end(ix, slot, st);
         rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st);
         RR_HIP_TRY(hipGetLastError());
@@ -477,16 +504,13 @@ static int rr_dense_chunk_x3w_t(rr_index* ix, const float* d_q, int nq, int pool
     }
     const int slot = rr_scan_events_begin(ix, st);
     rr_scan_note(ix, 4, NQ2, nq, A_BF16 ? 3 : 6);
-    hipLaunchKernelGGL((rr_scan_x3w<NQ2, A_BF16, false>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
-                       ix->d_gmax, ix->d_smax, (const int32_t*)nullptr, 0);
+    rr_x3w_scan_launch<NQ2, A_BF16, false>(ix, G, nullptr, 0, nullptr, st);
     rr_scan_events_end(ix, slot, st);
     rr_launch_select_mtiles(ix, G, nq, pool, st);
-    hipLaunchKernelGGL((rr_rescore_x3w<A_BF16>), dim3(64, nq), dim3(256), 0, st, mat, G.n_rows, pl4, QN,
-                       X.mtiles, X.count, X.fb, X.sc);
+    rr_x3w_rescore_launch<A_BF16>(ix, G, QN, nq, st);
     rr_launch_select_rescored(ix, G, nq, pool, d_rows, d_scores, st);
     // Fallback for the queries that raised their flag: both launches return at once otherwise.
-    hipLaunchKernelGGL((rr_scan_x3w<NQ2, A_BF16, true>), grid, block, 0, st, mat, G, pl4, ix->d_sims,
-                       ix->d_gmax, ix->d_smax, (const int32_t*)X.fb, nq);
+    rr_x3w_scan_launch<NQ2, A_BF16, true>(ix, G, X.fb, nq, nullptr, st);
     rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st, X.fb);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
@@ -495,16 +519,8 @@ static int rr_dense_chunk_x3w_t(rr_index* ix, const float* d_q, int nq, int pool
 template <int NQ2, bool A_BF16>
 static int rr_x3w_fallback_t(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                              float* d_scores, const int32_t* flags, hipStream_t st) {
-    constexpr int THREADS = NQ2 == 2 ? 512 : 256;
-    constexpr int QN = 32 * NQ2;
-    static int waves = 0;
-    if (!waves) waves = rr_resident_waves((const void*)rr_scan_x3w<NQ2, A_BF16, true>, THREADS, ix->device);
-    rr_scan_geom G = rr_make_geom(ix, waves / 4);
-    G.qs = QN;
-    unsigned short* planes = reinterpret_cast<unsigned short*>(ix->d_qplanes);
-    const dim3 grid((G.n_waves + THREADS / 64 - 1) / (THREADS / 64)), block(THREADS);
-    hipLaunchKernelGGL((rr_scan_x3w<NQ2, A_BF16, true>), grid, block, 0, st, reinterpret_cast<const u32x4*>(ix->d_matrix), G,
-                       reinterpret_cast<const u32x4*>(planes), ix->d_sims, ix->d_gmax, ix->d_smax, flags, nq, d_q);
+    const rr_scan_geom G = rr_x3w_geom<NQ2, A_BF16, true>(ix);
+    rr_x3w_scan_launch<NQ2, A_BF16, true>(ix, G, flags, nq, d_q, st);
     rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st, flags);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
@@ -639,6 +655,132 @@ extern "C" int rr_debug_scan_x3w(rr_index* ix, int32_t dbg, int32_t reps, float*
         default: RR_REQUIRE(false, "unknown ablation %d", dbg);
     }
     RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
+// ---- one split-operand scan launch / one rescoring launch by itself (tests/test_gpu_x3_scan_kernels.py)
+// (rr_dense_flt.hip: what the list-taking entries refuse about caller lists, and the lists into the selection scratch)
+int rr_debug_check_lists(const rr_index* ix, const char* who, int32_t nq, int64_t cap, int rows_per_mtile, const uint32_t* mtiles,
+                         const int32_t* count);
+int rr_debug_place_lists(const rr_x3_scratch& X, int32_t nq, int64_t cap, const uint32_t* mtiles, const int32_t* count,
+                         const int32_t* fb, const uint32_t* tau);
+// mode 0: split + normal scan; 1: split + stored pass; 2: the stored pass as rr_x3w_fallback_t launches it (flags + raw queries)
+template <int NQ2, bool A_BF16>
+static void rr_debug_x3w_scan_t(rr_index* ix, const float* d_q, int nq, int mode, const int32_t* d_flags, rr_scan_geom* G,
+                                hipStream_t st) {
+    if (mode == 2) {
+        *G = rr_x3w_geom<NQ2, A_BF16, true>(ix);
+        rr_x3w_scan_launch<NQ2, A_BF16, true>(ix, *G, d_flags, nq, d_q, st);
+        return;
+    }
+    *G = rr_x3w_geom<NQ2, A_BF16, false>(ix);
+    rr_x3w_split_launch<NQ2, A_BF16>(ix, d_q, st);
+    if (mode == 0) rr_x3w_scan_launch<NQ2, A_BF16, false>(ix, *G, nullptr, 0, nullptr, st);
+    else rr_x3w_scan_launch<NQ2, A_BF16, true>(ix, *G, nullptr, 0, nullptr, st);
+}
+
+// query slots of the launch that serves nq queries in `mode`: the product's routing (rr_dense_chunk_x3, rr_dense_chunk_x3w,
+// rr_dense_chunk_x3w_fallback -- the fallback launches are rr_scan_x3w at any count)
+static int rr_debug_x3_slots(int nq, int mode) { return (mode != 2 && nq <= 16) ? 16 : nq <= 32 ? 32 : 64; }
+
+// what both entries need of the index, and the caller's queries (device, [nq][384]) as the QN zero-padded slots the split reads
+static int rr_debug_x3_stage(rr_index* ix, const char* who, const float* d_queries, int nq, int QN, hipStream_t st) {
+    RR_HIP_TRY(hipMemsetAsync(ix->d_q, 0, sizeof(float) * (size_t)QN * 384, st));
+    RR_HIP_TRY(hipMemcpyAsync(ix->d_q, d_queries, sizeof(float) * (size_t)nq * 384, hipMemcpyDeviceToDevice, st));
+    (void)who;
+    return RR_OK;
+}
+#define RR_DEBUG_X3_INDEX_OK(ix, who)                                                                                              \
+    RR_REQUIRE((ix)->dim_pad == 384 && (ix)->dim == 384 && (ix)->d_matrix && (ix)->n_rows >= 64, who ": index of dim 384 and 64 rows or more expected"); \
+    RR_REQUIRE((ix)->scratch_q >= 64 && (ix)->maxima_q >= RR_FLT_MAXQ && (ix)->cur_slot == 0 && (ix)->d_sims && (ix)->d_gmax && (ix)->d_smax, \
+               who ": run a batched search of 64 queries first (allocates the scratch)")
+
+// ONE scan launch on caller queries (device, [nq][384], 5 <= nq <= 64) through the product's launch helpers, routed as the product
+// routes (<= 16 rr_scan_mfma_x3, <= 32 rr_scan_x3w<1>, else <2>; mode 2 is rr_scan_x3w at any count).  flags: host, [nq], mode 2 only.
+// Before the launch the whole score scratch and both maxima buffers are filled with RR_DEBUG_SC_SENTINEL / RR_DEBUG_KEY_SENTINEL
+// and the plane buffer with 0x5A5A; afterwards the first sims_cap / gmax_cap / smax_cap words of each come back as they are
+// (no more than the buffers hold: geom[6..8]), and planes[3][QN][384] (mode 2 leaves the planes alone: the kernel splits).
+// geom[10]: n_rows, n_tiles, tiles_per_wave, n_waves, qs, mm_pairs, words of the score scratch, of the tile-maxima buffer, of
+// the key buffer, query slots QN.  Every argument is checked before anything is copied or launched.
+extern "C" int rr_debug_x3_scan(rr_index* ix, const float* d_queries, int32_t nq, int32_t mode, const int32_t* flags, int64_t* geom,
+                                uint32_t* sims, int64_t sims_cap, uint32_t* gmax, int64_t gmax_cap, uint32_t* smax, int64_t smax_cap,
+                                unsigned short* planes) {
+    RR_REQUIRE(ix && d_queries && geom && sims && gmax && smax && planes, "rr_debug_x3_scan: NULL argument");
+    RR_REQUIRE(nq >= 5 && nq <= RR_MFMA_MAXQ, "rr_debug_x3_scan: nq %d outside 5..%d", nq, RR_MFMA_MAXQ);
+    RR_REQUIRE(mode >= 0 && mode <= 2 && (mode == 2) == (flags != nullptr), "rr_debug_x3_scan: mode %d (0, 1, or 2 with flags)", mode);
+    RR_DEBUG_X3_INDEX_OK(ix, "rr_debug_x3_scan");
+    const int64_t n_tiles = (ix->n_rows + 63) / 64;
+    const int64_t sims_words = (int64_t)ix->scratch_q * n_tiles * 64;
+    const int64_t gmax_words = (int64_t)ix->maxima_q * n_tiles * 4 + (int64_t)RR_MAX_SCAN_WAVES * RR_FLT_MAXQ;   // (rr_ensure_maxima)
+    const int64_t smax_words = (int64_t)2 * ix->maxima_q * RR_MAX_SCAN_WAVES;
+    RR_REQUIRE(sims_cap >= 0 && sims_cap <= sims_words && gmax_cap >= 0 && gmax_cap <= gmax_words && smax_cap >= 0 && smax_cap <= smax_words,
+               "rr_debug_x3_scan: caps %lld / %lld / %lld beyond the buffers (%lld / %lld / %lld words)", (long long)sims_cap,
+               (long long)gmax_cap, (long long)smax_cap, (long long)sims_words, (long long)gmax_words, (long long)smax_words);
+    const int QN = rr_debug_x3_slots(nq, mode);
+    const bool b = ix->dtype == RR_DTYPE_BF16;
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = nullptr;
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_sims, (int)RR_DEBUG_SC_SENTINEL, (size_t)sims_words, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_gmax, (int)RR_DEBUG_SC_SENTINEL, (size_t)gmax_words, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_smax, (int)RR_DEBUG_KEY_SENTINEL, (size_t)smax_words, st));
+    RR_HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)ix->d_qplanes, (unsigned short)0x5A5A, (size_t)3 * 64 * 384, st));
+    if (flags) RR_HIP_TRY(hipMemcpyAsync(X.fb, flags, sizeof(int32_t) * nq, hipMemcpyHostToDevice, st));
+    int rc = rr_debug_x3_stage(ix, "rr_debug_x3_scan", d_queries, nq, QN, st);
+    if (rc != RR_OK) return rc;
+    rr_scan_geom G;
+    if (QN == 16) rr_debug_x3_scan16(ix, ix->d_q, mode, &G, st);
+    else if (QN == 32) b ? rr_debug_x3w_scan_t<1, true>(ix, ix->d_q, nq, mode, X.fb, &G, st) : rr_debug_x3w_scan_t<1, false>(ix, ix->d_q, nq, mode, X.fb, &G, st);
+    else b ? rr_debug_x3w_scan_t<2, true>(ix, ix->d_q, nq, mode, X.fb, &G, st) : rr_debug_x3w_scan_t<2, false>(ix, ix->d_q, nq, mode, X.fb, &G, st);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    const int64_t g[10] = {G.n_rows, G.n_tiles, G.tiles_per_wave, G.n_waves, G.qs, G.mm_pairs, sims_words, gmax_words, smax_words, QN};
+    memcpy(geom, g, sizeof(g));
+    RR_HIP_TRY(hipMemcpy(sims, ix->d_sims, sizeof(uint32_t) * sims_cap, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(gmax, ix->d_gmax, sizeof(uint32_t) * gmax_cap, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(smax, ix->d_smax, sizeof(uint32_t) * smax_cap, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(planes, ix->d_qplanes, sizeof(unsigned short) * 3 * QN * 384, hipMemcpyDeviceToHost));
+    return RR_OK;
+}
+
+// ONE rescoring launch (rr_rescore_x3 for nq <= 16, else rr_rescore_x3w, on the planes rr_split_queries makes of the caller's
+// queries) on caller lists of 16-row M-tiles: mtiles[nq][cap] (the first count[q] are listed; repeats are fine), count, fb go to
+// the selection scratch through rr_debug_place_lists, the first cap * 16 scores of every query are set to RR_DEBUG_SC_SENTINEL,
+// and sc[nq][cap][16] comes back.  Every argument is checked before anything is copied or launched.
+extern "C" int rr_debug_x3_rescore(rr_index* ix, const float* d_queries, int32_t nq, const uint32_t* mtiles, int64_t cap,
+                                   const int32_t* count, const int32_t* fb, float* sc) {
+    RR_REQUIRE(ix && d_queries && mtiles && count && fb && sc, "rr_debug_x3_rescore: NULL argument");
+    RR_REQUIRE(nq >= 5 && nq <= RR_MFMA_MAXQ, "rr_debug_x3_rescore: nq %d outside 5..%d", nq, RR_MFMA_MAXQ);
+    RR_DEBUG_X3_INDEX_OK(ix, "rr_debug_x3_rescore");
+    int rc = rr_debug_check_lists(ix, "rr_debug_x3_rescore", nq, cap, 16, mtiles, count);
+    if (rc != RR_OK) return rc;
+    const int QN = rr_debug_x3_slots(nq, 0);
+    const bool b = ix->dtype == RR_DTYPE_BF16;
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = nullptr;
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    std::vector<uint32_t> tau((size_t)nq, 0u);              // (the rescoring does not read the thresholds)
+    rc = rr_debug_place_lists(X, nq, cap, mtiles, count, fb, tau.data());
+    if (rc != RR_OK) return rc;
+    for (int q = 0; q < nq; ++q)
+        RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(X.sc + (int64_t)q * RR_X3_MCAP * 16), (int)RR_DEBUG_SC_SENTINEL, (size_t)cap * 16, st));
+    rc = rr_debug_x3_stage(ix, "rr_debug_x3_rescore", d_queries, nq, QN, st);
+    if (rc != RR_OK) return rc;
+    if (QN == 16) {
+        rr_debug_x3_rescore16(ix, ix->d_q, nq, st);
+    } else if (QN == 32) {
+        if (b) { rr_x3w_split_launch<1, true>(ix, ix->d_q, st); rr_x3w_rescore_launch<true>(ix, rr_x3w_geom<1, true, false>(ix), QN, nq, st); }
+        else { rr_x3w_split_launch<1, false>(ix, ix->d_q, st); rr_x3w_rescore_launch<false>(ix, rr_x3w_geom<1, false, false>(ix), QN, nq, st); }
+    } else {
+        if (b) { rr_x3w_split_launch<2, true>(ix, ix->d_q, st); rr_x3w_rescore_launch<true>(ix, rr_x3w_geom<2, true, false>(ix), QN, nq, st); }
+        else { rr_x3w_split_launch<2, false>(ix, ix->d_q, st); rr_x3w_rescore_launch<false>(ix, rr_x3w_geom<2, false, false>(ix), QN, nq, st); }
+    }
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    RR_HIP_TRY(hipMemcpy2D(sc, sizeof(float) * cap * 16, X.sc, sizeof(float) * RR_X3_MCAP * 16, sizeof(float) * cap * 16, (size_t)nq,
+                           hipMemcpyDeviceToHost));
     return RR_OK;
 }
 #endif  // RR_DEBUG_HARNESS

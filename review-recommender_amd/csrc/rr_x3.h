@@ -52,6 +52,10 @@ __device__ __forceinline__ rr_x3_afrag rr_x3_split(u32x4 lo_unit, u32x4 hi_unit)
     return f;
 }
 
+// "Exact sum": x1 + x2 + x3 == x for |x| >= 2^-110 (and 0).  Below that x3 is an fp32 subnormal and its low 16 bits are cut
+// where the term becomes a bf16 operand (rr_pack_hi here, `>> 16` in rr_split_queries): the sum misses < 2^-133.  +-inf
+// splits into (+-inf, NaN, NaN) -- x - x1 is inf - inf -- so a row with an inf element scores NaN (-inf after rr_x3_canon) in
+// the split-operand scans; matrices with an infinite row norm are routed to the VALU scans instead (rr_dense_topk_impl).
 // Query planes for a scan launch: planes[3][slots][384] bf16 (truncating split, exact sum), with the
 // k order inside every 32-dim group that the scan's A-fragment loads imply (RR_X3_ORDER_*).
 #define RR_X3_ORDER_NATURAL 0    // rr_scan_mfma_x3 on a bf16 matrix; rr_scan_x3w on an fp32 matrix

@@ -181,6 +181,11 @@ DEBUG_PROTOTYPES = {
     "rr_debug_rescore_chain": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rr_debug_select_rescored": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp, c_vp]),
+    "rr_debug_select": (C.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp]),
+    "rr_debug_group_kth": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "rr_debug_select_mtiles": (C.c_int, [c_vp, c_i64, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp]),
     "rr_debug_x3_scan": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "rr_debug_x3_rescore": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "rr_debug_ce_ffn_stamps":(C.c_int, [P(C.c_uint64)]),

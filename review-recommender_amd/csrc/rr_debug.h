@@ -37,6 +37,37 @@ int rr_debug_rescore_chain(rr_index* ix, const float* d_queries, int32_t nq, int
 int rr_debug_select_rescored(rr_index* ix, int32_t nq, int32_t pool, int32_t rows_per_mtile, int32_t floor_mode, const uint32_t* mtiles,
                              int64_t cap, const int32_t* count, const int32_t* fb, const uint32_t* tau, const float* sc, int64_t* rows,
                              float* scores, int32_t* fb_out, int32_t* n_cand);
+// tests/test_gpu_select_kernels.py: ONE rr_select / rr_group_kth / rr_select_mtiles launch (rr_dense.hip) on CALLER levels --
+// scores, tile or M-tile maxima, group keys made on the host for any geometry (tests/select_model.py) -- placed in the
+// index's scan scratch, through the launch helpers the product calls (rr_launch_select, rr_launch_select_listed,
+// rr_launch_group_kth, rr_launch_select_mtiles), into outputs filled with sentinels and copied back whole.  None of them
+// reads a matrix: an index created without one will do.  Every argument and every size is checked against the scratch
+// before anything is copied or launched.
+//   rr_debug_select: n_tiles = ceil(n_rows / 64), n_pad = 64 n_tiles, n_waves = ceil(n_tiles / tiles_per_wave) <=
+//     RR_MAX_SCAN_WAVES; qs 0 | 16 | 32 | 64 and the levels in the layout rr_scan_geom::qs documents, S slots of them (S = qs,
+//     or nq when qs = 0).  form 0: nq queries, no flags; 1: flags[nq] as `only_if`; 2: the sliced launch, qs = 64, `slices`
+//     2..4 blocks of levels (the entry puts block y at rr_select_slice_strides), nq = the call's queries (it ends inside the
+//     last slice), flags[nq]; 3: the listed launch, qlist[1 + RR_SEL_LISTED] = count + the listed queries of a call of nq,
+//     RR_SEL_LISTED slots of levels (qs = 0) or qs of them, flags[nq] the call's flags.  rows / score_bits [nq][pool],
+//     trace [nq][16], flags_out [nq] (forms 1..3: the flags after the launch).  Trace words 11..13 of a query that took
+//     rr_select_slow: tiles listed (n_tiles when it took all), n_cand before step 3b, whether step 3b ran; word 14 of a
+//     query the fast path served: 1 = the rank sort ordered its candidates, 2 = the bitonic sort.
+//   rr_debug_group_kth: keys [set][n_waves gpw][qs] (qs > 0: the only layout the kernel reads), eps [RR_SEL_MAXQ] with set
+//     1's entries at RR_FLT_MAXQ, the product's set stride (rr_flt_smax_set_stride); bound_bits [nq_a + nq_b].
+//   rr_debug_select_mtiles: ONE set, no sigma, mm_pairs 0 ([tile][qs][4]) or 1 ([32-row tile][qs][2]) with plain float
+//     maxima (mm_pairs 3, the filter scan's words, stays with rr_debug_flt_select), keys [n_waves gpw][qs]; eps [nq] and
+//     floor [nq] each NULL or given.  The threshold and floor code is shared by all three forms, which is why it is tested
+//     here, on plain maxima -- but `eps` with plain maxima is a combination the PRODUCT never launches (its split-operand
+//     scans pass no eps, its filter scan passes words).  mtiles [nq][RR_X3_MCAP], count / tau / fb [nq], trace [nq][16]
+//     (word 6 = `open`).
+int rr_debug_select(rr_index* ix, int64_t n_rows, int64_t tiles_per_wave, int32_t qs, int32_t nq, int32_t pool, int32_t form, int32_t slices,
+                    const float* sims, const float* gmax, const uint32_t* smax, const int32_t* flags, const int32_t* qlist, int64_t* rows,
+                    uint32_t* score_bits, int32_t* trace, int32_t* flags_out);
+int rr_debug_group_kth(rr_index* ix, int32_t n_waves, int32_t gpw, int32_t qs, int32_t kth, int32_t nq_a, int32_t nq_b, const uint32_t* keys,
+                       const float* eps, uint32_t* bound_bits);
+int rr_debug_select_mtiles(rr_index* ix, int64_t n_rows, int64_t tiles_per_wave, int32_t gpw, int64_t tiles_per_group, int32_t qs,
+                           int32_t mm_pairs, int32_t nq, int32_t pool, const float* mmax, const uint32_t* keys, const float* eps,
+                           const float* floor, uint32_t* mtiles, int32_t* count, uint32_t* tau, int32_t* fb, int32_t* trace);
 // tests/test_gpu_x3_scan_kernels.py: ONE split-operand scan launch (rr_scan_mfma_x3 / rr_scan_x3w, routed by nq as the product
 // routes; mode 0 normal scan, 1 stored pass, 2 stored pass as the fallback launches it: flags + in-kernel query split) into
 // scratch filled with sentinels, and its raw words on the host; ONE rescoring launch (rr_rescore_x3 / rr_rescore_x3w) on

@@ -57,6 +57,20 @@ int rr_dense_listed_fallback(rr_index* ix, const float* d_q, int nq, int pool, i
 void rr_launch_select(rr_index* ix, const rr_scan_geom& G, int nq, int pool, int64_t* d_rows,
                       float* d_scores, hipStream_t st, const int32_t* only_if = nullptr, int slices = 1,
                       int64_t sims_slice = 0, int64_t gmax_slice = 0, int64_t smax_slice = 0);
+// The sliced launches (rr_dense_x3w_fallback_all: gridDim.y = slices of RR_MFMA_MAXQ queries, qs = RR_MFMA_MAXQ): how far slice
+// y + 1's scores, tile maxima and group keys sit behind slice y's, in 4-byte words.  ONE definition for the scan that
+// writes the slices, the selection that reads them and the kernel test that places them (rr_debug_select).
+struct rr_select_slices { int64_t sims, gmax, smax; };
+static inline rr_select_slices rr_select_slice_strides(const rr_scan_geom& G) {
+    return rr_select_slices{(int64_t)RR_MFMA_MAXQ * G.n_pad, (int64_t)RR_MFMA_MAXQ * G.n_tiles, (int64_t)RR_MFMA_MAXQ * RR_MAX_SCAN_WAVES};
+}
+// The listed launch (rr_dense_listed_fallback): RR_SEL_LISTED workgroups; workgroup b serves query ix->d_flag_list[1 + b] of
+// the call from score slot b when b < ix->d_flag_list[0], writes its answer at that query's place and takes its flag down.
+#define RR_SEL_LISTED 8
+void rr_launch_select_listed(rr_index* ix, const rr_scan_geom& G, int pool, int64_t* d_rows, float* d_scores, int32_t* flags,
+                             hipStream_t st);
+// group keys of the second set of a two-set launch (rr_dense_flt.hip) sit this many words behind the first set's
+static inline int64_t rr_flt_smax_set_stride() { return (int64_t)RR_FLT_MAXQ * RR_MAX_SCAN_WAVES; }
 // Two-pass selection of the split-operand scan (see rr_select_mtiles in rr_dense.hip).
 #define RR_X3_MCAP 16384         // M-tiles (8 or 16 rows) one query may ask to have rescored
 struct rr_x3_scratch {           // (every array RR_FLT_MAXQ queries long)

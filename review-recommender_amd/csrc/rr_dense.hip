@@ -29,6 +29,10 @@
 #include "rr_common.h"
 #include "rr_dense.h"
 #include "rr_x3.h"
+#include "rr_debug.h"
+#ifdef RR_DEBUG_HARNESS
+#include <vector>
+#endif
 
 #define RR_SEL_THREADS 1024
 #define RR_SEL_GCAP 4096    // slow path: tiles kept in LDS
@@ -298,12 +302,12 @@ __device__ __forceinline__ void rr_bitonic_desc(uint64_t* keys, int n) {
 // Exact for any input, but slow on large N: 8-bit radix passes over every tile maximum with
 // an LDS histogram (heavily contended when the keys share their top bits).  Kept as the
 // fallback of rr_select for inputs whose candidate lists overflow the fast path's LDS.
-// Leaves the ordered top-pool keys in cand[0..pool).
+// Leaves the ordered top-pool keys in cand[0..pool).  `trace`: the query's 16 trace words (written under RR_DEBUG_HARNESS only).
 template <typename ScoreAt, typename TileMaxAt>
 __device__ void rr_select_slow(ScoreAt score_at, TileMaxAt tile_max_at,
                                int64_t n_rows, int64_t n_tiles, int pool, uint32_t* hist,
                                uint32_t* wsum, uint32_t* sel, uint32_t* counters, uint32_t* glist,
-                               uint64_t* cand) {
+                               uint64_t* cand, int32_t* trace) {
     const int tid = threadIdx.x;
 
     // ---- 1. tau = pool-th largest tile maximum (or "everything" if few tiles)
@@ -359,6 +363,13 @@ __device__ void rr_select_slow(ScoreAt score_at, TileMaxAt tile_max_at,
     }
     __syncthreads();
     uint32_t n_cand = counters[1];
+#ifdef RR_DEBUG_HARNESS
+    if (tid == 0) {   // rr_debug_select: which sub-branch ran -- tiles listed | candidates before step 3b | step 3b taken
+        trace[11] = (int32_t)n_list;
+        trace[12] = (int32_t)n_cand;
+        trace[13] = n_cand > RR_SEL_SORTCAP ? 1 : 0;
+    }
+#endif
 
     if (n_cand > RR_SEL_SORTCAP) {
         // ---- 3b. too many survivors: exact radix select of the pool-th largest
@@ -625,6 +636,7 @@ __global__ __launch_bounds__(RR_SEL_THREADS) void rr_select(
     RR_STAMP();
     const int ng = G.n_waves;
     bool fast = ng <= RR_SEL_RK * RR_SEL_THREADS;
+    int sort_taken = 0;                              // 1 rank sort, 2 bitonic sort (traced under RR_DEBUG_HARNESS only)
 
     if (tid < 4) counters[tid] = 0;
     __syncthreads();
@@ -670,10 +682,12 @@ __global__ __launch_bounds__(RR_SEL_THREADS) void rr_select(
             if (n_cand > RR_SEL_CCAP / 2 || n_cand < (uint32_t)pool) {
                 fast = false;                              // massive ties at the cut
             } else if (n_cand <= RR_SEL_THREADS) {
+                sort_taken = 1;
                 rr_rank_sort_desc(cand, (int)n_cand, cand + RR_SEL_CCAP / 2);
                 for (int i = tid; i < pool; i += RR_SEL_THREADS) cand[i] = cand[RR_SEL_CCAP / 2 + i];
                 __syncthreads();
             } else {
+                sort_taken = 2;
                 int n_sort = 1;
                 while (n_sort < (int)n_cand) n_sort <<= 1;
                 for (int i = tid; i < n_sort; i += RR_SEL_THREADS)
@@ -689,10 +703,13 @@ __global__ __launch_bounds__(RR_SEL_THREADS) void rr_select(
         dbg[q * 16 + 2] = (int32_t)counters[1];
         dbg[q * 16 + 3] = (int32_t)counters[2];
         for (int i = 1; i < 8; ++i) dbg[q * 16 + 3 + i] = i < n_stamp ? (int32_t)(stamp[i] - stamp[i - 1]) : -1;
+#ifdef RR_DEBUG_HARNESS
+        if (fast) dbg[q * 16 + 14] = sort_taken;     // rr_debug_select: which sort ordered the fast path's candidates
+#endif
     }
     if (!fast) {
         __syncthreads();
-        rr_select_slow(score_at, tile_max_at, n_rows, n_tiles, pool, hist, wsum, sel, counters, list1, cand);
+        rr_select_slow(score_at, tile_max_at, n_rows, n_tiles, pool, hist, wsum, sel, counters, list1, cand, dbg + q * 16);
     }
     for (int i = tid; i < pool; i += RR_SEL_THREADS) {
         const uint64_t key = cand[i];
@@ -1206,6 +1223,12 @@ void rr_launch_select(rr_index* ix, const rr_scan_geom& G, int nq, int pool, int
                        ix->d_smax, pool, ix->row_offset, d_rows, d_scores, ix->d_sel_trace, only_if, nq, sims_slice,
                        gmax_slice, smax_slice, (const int32_t*)nullptr, (int32_t*)nullptr);
 }
+void rr_launch_select_listed(rr_index* ix, const rr_scan_geom& G, int pool, int64_t* d_rows, float* d_scores, int32_t* flags,
+                             hipStream_t st) {
+    hipLaunchKernelGGL(rr_select, dim3(RR_SEL_LISTED), dim3(RR_SEL_THREADS), 0, st, G, ix->d_sims, ix->d_gmax, ix->d_smax, pool,
+                       ix->row_offset, d_rows, d_scores, ix->d_sel_trace, (const int32_t*)nullptr, RR_SEL_LISTED, (int64_t)0, (int64_t)0,
+                       (int64_t)0, (const int32_t*)ix->d_flag_list, flags);
+}
 int rr_resident_waves(const void* kernel, int threads, int device) {
     int per_cu = 0, cus = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu < 1)
@@ -1250,9 +1273,7 @@ int rr_dense_listed_fallback(rr_index* ix, const float* d_q, int nq, int pool, i
     hipLaunchKernelGGL((rr_scan_f32<6, 8, true>), dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
                        reinterpret_cast<const f32x4*>(ix->d_matrix), G, d_q, ix->d_sims, ix->d_gmax, ix->d_smax,
                        (const int32_t*)flags, nq, ix->d_flag_list);
-    hipLaunchKernelGGL(rr_select, dim3(8), dim3(RR_SEL_THREADS), 0, st, G, ix->d_sims, ix->d_gmax, ix->d_smax, pool,
-                       ix->row_offset, d_rows, d_scores, ix->d_sel_trace, (const int32_t*)nullptr, 8, (int64_t)0, (int64_t)0,
-                       (int64_t)0, (const int32_t*)ix->d_flag_list, flags);
+    rr_launch_select_listed(ix, G, pool, d_rows, d_scores, flags, st);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }
@@ -1645,3 +1666,202 @@ extern "C" int rr_index_l2_normalize(rr_index* ix, float eps) {
     RR_HIP_TRY(hipStreamSynchronize(ix->stream));
     return RR_OK;
 }
+
+#ifdef RR_DEBUG_HARNESS
+// ------------------------------------------------------------------ kernel-test entries (rr_debug.h; tests/test_gpu_select_kernels.py)
+// Sentinels the outputs are filled with before the launch.  Row: no row + row_offset is negative.  Score: a NaN with a payload
+// (the selections store rr_key2f of keys of stored scores, and no scan stores a NaN).  Word (trace words, counts, thresholds,
+// flags of rr_select_mtiles, M-tile ids): a count is not negative, a flag is 0 or 1, and as a key the pattern is that of a NaN.
+#define RR_DEBUG_SEL_ROW_SENTINEL (-0x5A5A5A5A5A5A5A5All)
+#define RR_DEBUG_SEL_SCORE_SENTINEL 0x7FC5A5A5u
+#define RR_DEBUG_SEL_WORD_SENTINEL (-0x5A5A5A5A)
+
+// geometry of caller levels: what a scan of n_rows rows with runs of tiles_per_wave tiles leaves
+static int rr_debug_sel_geom(const char* who, const rr_index* ix, int64_t n_rows, int64_t tiles_per_wave, rr_scan_geom* G) {
+    RR_REQUIRE(n_rows >= 1 && n_rows <= ix->n_rows, "%s: n_rows %lld outside 1..%lld (the index's)", who, (long long)n_rows, (long long)ix->n_rows);
+    RR_REQUIRE(tiles_per_wave >= 1, "%s: tiles_per_wave %lld", who, (long long)tiles_per_wave);
+    *G = rr_scan_geom{};
+    G->n_rows = n_rows;
+    G->n_tiles = (n_rows + 63) / 64;
+    G->n_pad = G->n_tiles * 64;
+    G->tiles_per_wave = tiles_per_wave;
+    const int64_t n_waves = (G->n_tiles + tiles_per_wave - 1) / tiles_per_wave;
+    RR_REQUIRE(n_waves <= RR_MAX_SCAN_WAVES, "%s: %lld waves (runs of %lld tiles): no scan launches more than %d", who, (long long)n_waves,
+               (long long)tiles_per_wave, RR_MAX_SCAN_WAVES);
+    G->n_waves = (int32_t)n_waves;
+    G->gpw = 1;
+    G->tiles_per_group = tiles_per_wave;
+    return RR_OK;
+}
+
+// what the index's scan scratch holds, in 4-byte words (rr_ensure_scratch / rr_ensure_maxima)
+static int rr_debug_sel_room(const char* who, const rr_index* ix, int64_t sims_words, int64_t gmax_words, int64_t smax_words) {
+    const int64_t n_tiles = rr_round_up(ix->n_rows, 64) / 64;
+    const int64_t have_sims = (int64_t)ix->scratch_q * n_tiles * 64;
+    const int64_t have_gmax = (int64_t)ix->maxima_q * n_tiles * 4 + (int64_t)RR_MAX_SCAN_WAVES * RR_FLT_MAXQ;
+    const int64_t have_smax = (int64_t)2 * ix->maxima_q * RR_MAX_SCAN_WAVES;
+    RR_REQUIRE(sims_words <= have_sims && gmax_words <= have_gmax && smax_words <= have_smax,
+               "%s: the levels want %lld / %lld / %lld words of scores / tile maxima / group keys, the scratch holds %lld / %lld / %lld", who,
+               (long long)sims_words, (long long)gmax_words, (long long)smax_words, (long long)have_sims, (long long)have_gmax, (long long)have_smax);
+    return RR_OK;
+}
+
+extern "C" int rr_debug_select(rr_index* ix, int64_t n_rows, int64_t tiles_per_wave, int32_t qs, int32_t nq, int32_t pool, int32_t form,
+                               int32_t slices, const float* sims, const float* gmax, const uint32_t* smax, const int32_t* flags,
+                               const int32_t* qlist, int64_t* rows, uint32_t* score_bits, int32_t* trace, int32_t* flags_out) {
+    const char* who = "rr_debug_select";
+    RR_REQUIRE(ix && sims && gmax && smax && rows && score_bits && trace, "%s: NULL argument", who);
+    RR_REQUIRE(qs == 0 || qs == 16 || qs == 32 || qs == 64, "%s: qs %d (0, 16, 32 or 64)", who, qs);
+    RR_REQUIRE(form >= 0 && form <= 3, "%s: form %d (0 plain, 1 only_if, 2 sliced, 3 listed)", who, form);
+    RR_REQUIRE(form == 2 || slices == 1, "%s: %d slices in form %d", who, slices, form);
+    RR_REQUIRE((form == 0) == (flags == nullptr) && (form == 0) == (flags_out == nullptr), "%s: form %d %s flags and flags_out", who, form,
+               form == 0 ? "takes no" : "wants");
+    RR_REQUIRE((form == 3) == (qlist != nullptr), "%s: form %d %s qlist", who, form, form == 3 ? "wants" : "takes no");
+    rr_scan_geom G;
+    int rc = rr_debug_sel_geom(who, ix, n_rows, tiles_per_wave, &G);
+    if (rc != RR_OK) return rc;
+    G.qs = qs;
+    RR_REQUIRE(pool >= 1 && pool <= RR_MAX_POOL && pool <= n_rows, "%s: pool %d out of [1,min(%d,n_rows=%lld)]", who, pool, RR_MAX_POOL,
+               (long long)n_rows);
+    int slots = qs ? qs : nq, blocks = 1;
+    if (form <= 1) {
+        RR_REQUIRE(nq >= 1 && nq <= (qs ? qs : RR_MFMA_MAXQ), "%s: nq %d outside 1..%d", who, nq, qs ? qs : RR_MFMA_MAXQ);
+    } else if (form == 2) {
+        RR_REQUIRE(qs == RR_MFMA_MAXQ, "%s: the sliced launch reads qs = %d", who, RR_MFMA_MAXQ);
+        RR_REQUIRE(slices >= 2 && slices <= 4 && nq > RR_MFMA_MAXQ * (slices - 1) && nq <= RR_MFMA_MAXQ * slices,
+                   "%s: %d queries do not end inside the last of %d slices (2..4)", who, nq, slices);
+        blocks = slices;
+    } else {
+        RR_REQUIRE(nq >= 1 && nq <= RR_SEL_MAXQ, "%s: nq %d outside 1..%d", who, nq, RR_SEL_MAXQ);
+        RR_REQUIRE(qlist[0] >= 0 && qlist[0] <= RR_SEL_LISTED, "%s: %d listed queries (0..%d)", who, qlist[0], RR_SEL_LISTED);
+        for (int b = 0; b < qlist[0]; ++b) {
+            RR_REQUIRE(qlist[1 + b] >= 0 && qlist[1 + b] < nq, "%s: listed query %d outside the call's %d", who, qlist[1 + b], nq);
+            for (int c = 0; c < b; ++c) RR_REQUIRE(qlist[1 + c] != qlist[1 + b], "%s: query %d is listed twice", who, qlist[1 + b]);
+        }
+        slots = qs ? qs : RR_SEL_LISTED;
+    }
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    RR_REQUIRE(ix->cur_slot == 0, "%s: scan slot %d is active", who, ix->cur_slot);
+    hipStream_t st = nullptr;
+    rc = rr_ensure_scratch(ix, blocks * slots);
+    if (rc != RR_OK) return rc;
+    const rr_select_slices S = form == 2 ? rr_select_slice_strides(G) : rr_select_slices{0, 0, 0};
+    const int64_t sims_w = (int64_t)slots * G.n_pad, gmax_w = (int64_t)slots * G.n_tiles, smax_w = (int64_t)slots * G.n_waves;
+    rc = rr_debug_sel_room(who, ix, (blocks - 1) * S.sims + sims_w, (blocks - 1) * S.gmax + gmax_w, (blocks - 1) * S.smax + smax_w);
+    if (rc != RR_OK) return rc;
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    for (int y = 0; y < blocks; ++y) {
+        RR_HIP_TRY(hipMemcpy(ix->d_sims + y * S.sims, sims + y * sims_w, sizeof(float) * sims_w, hipMemcpyHostToDevice));
+        RR_HIP_TRY(hipMemcpy(ix->d_gmax + y * S.gmax, gmax + y * gmax_w, sizeof(float) * gmax_w, hipMemcpyHostToDevice));
+        RR_HIP_TRY(hipMemcpy(ix->d_smax + y * S.smax, smax + y * smax_w, sizeof(uint32_t) * smax_w, hipMemcpyHostToDevice));
+    }
+    if (flags) RR_HIP_TRY(hipMemcpy(X.fb, flags, sizeof(int32_t) * nq, hipMemcpyHostToDevice));
+    if (qlist) {
+        int32_t list[16] = {0};
+        memcpy(list, qlist, sizeof(int32_t) * (1 + RR_SEL_LISTED));
+        // (slots past the count repeat the last listed query, as rr_flagged_list leaves them; none is read)
+        for (int b = qlist[0]; b < RR_SEL_LISTED; ++b) list[1 + b] = qlist[0] > 0 ? qlist[qlist[0]] : 0;
+        RR_HIP_TRY(hipMemcpy(ix->d_flag_list, list, sizeof(list), hipMemcpyHostToDevice));
+    }
+    std::vector<int64_t> row_fill((size_t)nq * pool, (int64_t)RR_DEBUG_SEL_ROW_SENTINEL);
+    RR_HIP_TRY(hipMemcpy(ix->d_rows_out, row_fill.data(), sizeof(int64_t) * row_fill.size(), hipMemcpyHostToDevice));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_scores_out, (int)RR_DEBUG_SEL_SCORE_SENTINEL, (size_t)nq * pool, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_sel_trace, (int)RR_DEBUG_SEL_WORD_SENTINEL, (size_t)nq * 16, st));
+    if (form <= 1) rr_launch_select(ix, G, nq, pool, ix->d_rows_out, ix->d_scores_out, st, form == 1 ? X.fb : nullptr);
+    else if (form == 2) rr_launch_select(ix, G, nq, pool, ix->d_rows_out, ix->d_scores_out, st, X.fb, slices, S.sims, S.gmax, S.smax);
+    else rr_launch_select_listed(ix, G, pool, ix->d_rows_out, ix->d_scores_out, X.fb, st);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    RR_HIP_TRY(hipMemcpy(rows, ix->d_rows_out, sizeof(int64_t) * nq * pool, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(score_bits, ix->d_scores_out, sizeof(uint32_t) * nq * pool, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(trace, ix->d_sel_trace, sizeof(int32_t) * nq * 16, hipMemcpyDeviceToHost));
+    if (flags_out) RR_HIP_TRY(hipMemcpy(flags_out, X.fb, sizeof(int32_t) * nq, hipMemcpyDeviceToHost));
+    return RR_OK;
+}
+
+extern "C" int rr_debug_group_kth(rr_index* ix, int32_t n_waves, int32_t gpw, int32_t qs, int32_t kth, int32_t nq_a, int32_t nq_b,
+                                  const uint32_t* keys, const float* eps, uint32_t* bound_bits) {
+    const char* who = "rr_debug_group_kth";
+    RR_REQUIRE(ix && keys && eps && bound_bits, "%s: NULL argument", who);
+    RR_REQUIRE(qs == 16 || qs == 32 || qs == 64 || qs == 128, "%s: qs %d (16, 32, 64 or 128: the kernel reads keys [group][qs] only)", who, qs);
+    const int64_t per_set = (int64_t)n_waves * gpw * qs, stride = rr_flt_smax_set_stride();
+    RR_REQUIRE(n_waves >= 1 && n_waves <= RR_MAX_SCAN_WAVES && gpw >= 1 && gpw <= RR_MAX_SCAN_WAVES && per_set <= stride,
+               "%s: %d waves x %d groups x %d queries do not fit a set of %lld keys", who, n_waves, gpw, qs, (long long)stride);
+    RR_REQUIRE(nq_a >= 1 && nq_a <= qs && nq_a <= RR_FLT_MAXQ && nq_b >= 0 && nq_b <= qs && nq_b <= RR_FLT_MAXQ,
+               "%s: %d + %d queries of sets of %d", who, nq_a, nq_b, qs);
+    RR_REQUIRE(kth >= 1 && kth <= RR_MAX_POOL, "%s: kth %d outside 1..%d", who, kth, RR_MAX_POOL);
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    RR_REQUIRE(ix->cur_slot == 0, "%s: scan slot %d is active", who, ix->cur_slot);
+    hipStream_t st = nullptr;
+    int rc = rr_ensure_maxima(ix, RR_MFMA_MAXQ);
+    if (rc != RR_OK) return rc;
+    const int sets = nq_b > 0 ? 2 : 1, nq = nq_a + nq_b;
+    rc = rr_debug_sel_room(who, ix, 0, 0, (sets - 1) * stride + per_set);
+    if (rc != RR_OK) return rc;
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    for (int s = 0; s < sets; ++s)
+        RR_HIP_TRY(hipMemcpy(ix->d_smax + s * stride, keys + s * per_set, sizeof(uint32_t) * per_set, hipMemcpyHostToDevice));
+    RR_HIP_TRY(hipMemcpy(X.eps, eps, sizeof(float) * RR_SEL_MAXQ, hipMemcpyHostToDevice));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_scores_out, (int)RR_DEBUG_SEL_SCORE_SENTINEL, (size_t)nq, st));
+    rr_scan_geom G = {};
+    G.n_waves = n_waves;
+    G.gpw = gpw;
+    G.qs = qs;
+    rr_launch_group_kth(ix, G, nq_a, nq_b, kth, X.eps, ix->d_scores_out, stride, st);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    RR_HIP_TRY(hipMemcpy(bound_bits, ix->d_scores_out, sizeof(uint32_t) * nq, hipMemcpyDeviceToHost));
+    return RR_OK;
+}
+
+extern "C" int rr_debug_select_mtiles(rr_index* ix, int64_t n_rows, int64_t tiles_per_wave, int32_t gpw, int64_t tiles_per_group, int32_t qs,
+                                      int32_t mm_pairs, int32_t nq, int32_t pool, const float* mmax, const uint32_t* keys, const float* eps,
+                                      const float* floor, uint32_t* mtiles, int32_t* count, uint32_t* tau, int32_t* fb, int32_t* trace) {
+    const char* who = "rr_debug_select_mtiles";
+    RR_REQUIRE(ix && mmax && keys && mtiles && count && tau && fb && trace, "%s: NULL argument", who);
+    RR_REQUIRE(qs == 16 || qs == 32 || qs == 64 || qs == 128, "%s: qs %d (16, 32, 64 or 128)", who, qs);
+    RR_REQUIRE(mm_pairs == 0 || mm_pairs == 1, "%s: mm_pairs %d (0 or 1; the filter scan's words go through rr_debug_flt_select)", who, mm_pairs);
+    RR_REQUIRE(nq >= 1 && nq <= qs && nq <= RR_FLT_MAXQ, "%s: nq %d outside 1..%d", who, nq, qs < RR_FLT_MAXQ ? qs : RR_FLT_MAXQ);
+    RR_REQUIRE(pool >= 1 && pool <= RR_MAX_POOL, "%s: pool %d outside 1..%d", who, pool, RR_MAX_POOL);
+    rr_scan_geom G;
+    int rc = rr_debug_sel_geom(who, ix, n_rows, tiles_per_wave, &G);
+    if (rc != RR_OK) return rc;
+    RR_REQUIRE(gpw >= 1 && gpw <= 64 && tiles_per_group >= 1 && tiles_per_group <= tiles_per_wave && gpw * tiles_per_group >= tiles_per_wave,
+               "%s: %d groups of %lld tiles do not cover a run of %lld", who, gpw, (long long)tiles_per_group, (long long)tiles_per_wave);
+    G.qs = qs;
+    G.mm_pairs = mm_pairs;
+    G.gpw = gpw;
+    G.tiles_per_group = tiles_per_group;
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    RR_REQUIRE(ix->cur_slot == 0, "%s: scan slot %d is active", who, ix->cur_slot);
+    hipStream_t st = nullptr;
+    rc = rr_ensure_maxima(ix, qs);
+    if (rc != RR_OK) return rc;
+    const int64_t mmax_w = G.n_tiles * qs * 4, keys_w = (int64_t)G.n_waves * gpw * qs;
+    rc = rr_debug_sel_room(who, ix, 0, mmax_w, keys_w);
+    if (rc != RR_OK) return rc;
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    RR_HIP_TRY(hipMemcpy(ix->d_gmax, mmax, sizeof(float) * mmax_w, hipMemcpyHostToDevice));
+    RR_HIP_TRY(hipMemcpy(ix->d_smax, keys, sizeof(uint32_t) * keys_w, hipMemcpyHostToDevice));
+    if (eps) RR_HIP_TRY(hipMemcpy(X.eps, eps, sizeof(float) * nq, hipMemcpyHostToDevice));
+    if (floor) RR_HIP_TRY(hipMemcpy(ix->d_scores_out, floor, sizeof(float) * nq, hipMemcpyHostToDevice));
+    const int fill = (int)RR_DEBUG_SEL_WORD_SENTINEL;
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X.mtiles, fill, (size_t)nq * RR_X3_MCAP, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X.count, fill, (size_t)nq, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X.tau, fill, (size_t)nq, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)X.fb, fill, (size_t)nq, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_sel_trace, fill, (size_t)nq * 16, st));
+    rr_launch_select_mtiles(ix, G, nq, pool, st, eps ? X.eps : nullptr, nullptr, 0, 0, 0, floor ? ix->d_scores_out : nullptr);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    RR_HIP_TRY(hipMemcpy(mtiles, X.mtiles, sizeof(uint32_t) * nq * RR_X3_MCAP, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(count, X.count, sizeof(int32_t) * nq, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(tau, X.tau, sizeof(uint32_t) * nq, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(fb, X.fb, sizeof(int32_t) * nq, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(trace, ix->d_sel_trace, sizeof(int32_t) * nq * 16, hipMemcpyDeviceToHost));
+    return RR_OK;
+}
+#endif

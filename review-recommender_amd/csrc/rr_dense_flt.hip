@@ -1374,7 +1374,7 @@ static int rr_flt_ensure_shadow(rr_index* ix, hipStream_t st) {
 // scan launches can be followed by ONE selection + rescoring sequence over up to RR_SEL_MAXQ queries: the selection
 // kernels are latency-bound, one workgroup per query -- 128 of them fill half the CUs.
 static int64_t rr_flt_mmax_set_stride(const rr_scan_geom& G) { return (int64_t)2 * G.n_tiles * RR_FLT_MAXQ; }   // 4-byte words
-static int64_t rr_flt_smax_set_stride() { return (int64_t)RR_FLT_MAXQ * RR_MAX_SCAN_WAVES; }
+// (the group keys': rr_flt_smax_set_stride, rr_dense.h)
 
 template <int NQ2, bool SCAN_BF16>
 static int rr_flt_scan_set(rr_index* ix, int set, const rr_scan_geom& G, const void* scan_mat, const float* d_q, int nq,

@@ -549,7 +549,8 @@ int rr_dense_x3w_fallback_all(rr_index* ix, const float* d_q, int nq, int pool, 
                                 : rr_resident_waves((const void*)rr_scan_x3w<2, false, true>, 512, ix->device);
     rr_scan_geom G = rr_make_geom(ix, waves[b] / 4);
     G.qs = 64;
-    const int64_t sims_slice = (int64_t)64 * G.n_pad, gmax_slice = (int64_t)64 * G.n_tiles, smax_slice = (int64_t)64 * RR_MAX_SCAN_WAVES;
+    const rr_select_slices S = rr_select_slice_strides(G);
+    const int64_t sims_slice = S.sims, gmax_slice = S.gmax, smax_slice = S.smax;
     const dim3 grid((G.n_waves + 7) / 8, slices), block(512);
     const u32x4* planes = reinterpret_cast<const u32x4*>(ix->d_qplanes);          // (unused: the queries are split in the kernel)
     if (b)

@@ -120,7 +120,8 @@ int rr_index_scan_stats(rr_index* ix, double* out_total_ms, int64_t* out_launche
 /* Which scan kernel the last scan launch on this handle ran: out8[0] = 1 rr_scan_f32, 2 rr_scan_bf16,
  * 3 rr_scan_mfma_x3, 4 rr_scan_x3w, 5 the filter scans (rr_scan_flt over fp32 rows; over a bf16 stream rr_scan_flt16
  * and, for two query sets in one launch, rr_scan_fltq); 6 and 7 are retired (the removed f32-input MFMA scans); [1] = its template
- * variant (query tiles / query slots; filter scans: 9 = rr_scan_fltq; 8 was the two-set rr_scan_flt16, no longer reported);
+ * variant (query tiles / query slots; filter scans: 9 = rr_scan_fltq; 16 = rr_scan_fltw, the runtime-width scan of an fp32 index whose
+ * padded width is 64 .. 1024 and not 384 (csrc/rr_dense_fltw.hip); 8 was the two-set rr_scan_flt16, no longer reported);
  * [2] = queries in that launch; [3] = bf16 MFMA terms per dimension
  * (0: not a bf16 matrix-core kernel); [4] = bytes per matrix element the scan streamed (2 = bf16 rows or the bf16
  * filter plane, 4 = fp32 rows).  bench.py names the roofline kernel and its algorithmic bytes from this. */

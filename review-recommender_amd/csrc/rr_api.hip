@@ -404,6 +404,7 @@ extern "C" int rr_index_destroy(rr_index* ix) {
         hipFree(s.d_flt_samp); hipFree(s.d_flt_sigma); free(s.flt_pending);
     }
     hipFree(ix->d_sims); hipFree(ix->d_sel_trace); hipFree(ix->d_flag_list); hipFree(ix->d_x3);
+    hipFree(ix->d_wplanes); hipFree(ix->d_flag_done);
     hipFree(ix->d_rows_out); hipFree(ix->d_scores_out); hipFree(ix->d_shadow);
     for (int i = 0; i < RR_SCAN_SLOTS; ++i) if (ix->slot_ev[i]) hipEventDestroy(ix->slot_ev[i]);
     if (ix->ev0) hipEventDestroy(ix->ev0);

@@ -93,6 +93,11 @@ struct rr_index {
     int32_t scan_mode = 0;       // RR_SCAN_MODE_* (rr_index_set_scan_mode)
     void* d_x3 = nullptr;        // two-pass selection scratch of the split-operand scan (rr_x3_scratch)
     void* d_qplanes = nullptr;   // [3][64][384] bf16: one launch's queries split in three bf16 terms
+    // the filter path at other widths (rr_dense_fltw.hip), allocated at its first launch: [RR_FLTW_MAXQ][dim_pad] bf16 query
+    // planes of one launch (d_qplanes is sized for 384), and [RR_SEL_MAXQ] words the listed passes' selections write their
+    // "served" marks to (the launch's own flags stay up until the last pass has ranked them)
+    void* d_wplanes = nullptr;
+    int32_t* d_flag_done = nullptr;
     int64_t* d_rows_out = nullptr;  // host-API staging [RR_MAX_BATCH][RR_MAX_POOL]
     float* d_scores_out = nullptr;
     hipStream_t stream = nullptr;

@@ -12,7 +12,16 @@
 // rr_dense_x3.hip: the 16-slot launches of rr_debug_x3_scan / rr_debug_x3_rescore (rr_dense_x3w.hip)
 void rr_debug_x3_scan16(rr_index* ix, const float* d_q, int mode, rr_scan_geom* G, hipStream_t st);
 void rr_debug_x3_rescore16(rr_index* ix, const float* d_q, int nq, hipStream_t st);
+// rr_dense_flt.hip: the one-set launch rr_debug_fltw_words (rr_dense_fltw.hip) leaves for rr_debug_flt_select
+void rr_debug_flt_note_state(rr_index* ix, const rr_scan_geom& G, int nq);
 extern "C" {
+// tests/test_gpu_fltw_kernels.py: rr_debug_flt_words / rr_debug_rescore_chain at a runtime width (fp32 storage, dim_pad 64 .. 1024
+// other than 384): ONE rr_scan_fltw launch for one set of up to 64 queries -- geometry, eps, every word and key -- which
+// rr_debug_flt_select and rr_debug_select_traces then work on; ONE rr_rescore_chain_w launch on caller lists.  See the definitions.
+int rr_debug_fltw_words(rr_index* ix, const float* d_queries, int32_t nq, int32_t pool, int64_t* geom, float* eps, uint32_t* words,
+                        int64_t words_cap, uint32_t* keys, int64_t keys_cap);
+int rr_debug_fltw_rescore(rr_index* ix, const float* d_queries, int32_t nq, const uint32_t* mtiles, int64_t cap, const int32_t* count,
+                          const int32_t* fb, float* sc);
 // tools/x3w_ablate.py: variants of the 64-query fp32 split-operand scan (bit 0: no operand split, bit 1: no B-fragment
 // reads, bit 2: no MFMA, bit 3: no lane swap)
 int rr_debug_scan_x3w(rr_index* ix, int32_t variant, int32_t reps, float* out_ms);

@@ -137,3 +137,29 @@ int rr_device_visible(const void* p, const void** out, const char* what);
 // fp32 queries into ix->d_q plus their bf16 planes and error bounds.  Returns RR_FLT_NO_BOUND (nothing launched) when the
 // matrix has no finite row-norm bound: the caller pads the plain way.
 int rr_flt_pad_prep(rr_index* ix, const float* d_queries, int nq, int slots, hipStream_t st);
+
+// rr_dense_flt.hip: what the error bound of a filter scan takes from the matrix (cached in the index; one pass over the rows)
+struct rr_flt_bounds {
+    float row_norm;      // >= max over rows ||a||
+    float row_delta;     // >= max over rows ||a - bf16(a)||   (0 for a bf16 matrix)
+};
+int rr_flt_get_bounds(rr_index* ix, hipStream_t st, rr_flt_bounds* out);
+// the bf16 filter plane of an fp32 index (any width), built on first use; no room for it: ix->use_shadow = 0, RR_OK
+int rr_flt_ensure_shadow(rr_index* ix, hipStream_t st);
+
+// rr_dense_fltw.hip: the filter path at a runtime width -- fp32 storage, dim_pad in {64, 128, .. 1024} other than 384, up to
+// RR_FLTW_MAXQ queries per launch over the bf16 plane + exact rescoring on the fp32 rows + the listed VALU passes for flagged
+// queries.  RR_FLT_SMALL / RR_FLT_NO_BOUND as rr_dense_chunk_flt; RR_FLT_SMALL also when there is no plane (RR_NO_SHADOW, no room).
+#define RR_FLTW_MAXQ 64
+#define RR_FLTW_MAX_DIM 1024
+// Smallest batch the wide path takes: more than W = RR_FLTW_MIN_Q - 1 = 1 queries.  Measured crossover (1M rows, pool 150,
+// profiles/wide_dim_scan.json): with the routing started at W = 8 (one VALU read serves eight queries) the
+// path won from its first batch, 9; taken from 2 on it needs 0.39 / 0.53 ms per call at width 768 / 1024 for ANY batch up
+// to 64, against 0.68 / 0.87 ms of the VALU scan at 2 queries, 0.94 / 1.22 ms at 3 - 4 and 1.77 / 2.32 ms at 5 - 8.  A single
+// query stays on the VALU scan, whose per-row chain defines the answer (0.55 / 0.73 ms).
+#define RR_FLTW_MIN_Q 2
+int rr_dense_chunk_fltw(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores, hipStream_t st);
+// rr_dense.hip: ceil(nq / 8) pairs of (listed generic VALU scan, listed selection) behind a wide filter launch: pair p serves
+// the flagged queries ranked [8 p, 8 p + 8) of the launch with the single-query chain; a pair whose slice is empty returns at once
+int rr_dense_listed_fallback_wide(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores,
+                                  const int32_t* flags, hipStream_t st);

@@ -245,6 +245,94 @@ __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_f32_generic(
     }
 }
 
+// rr_flagged_list with a skip count: the queries whose flag is up, ranked by query number, ranks [skip, skip + NB).  Returns
+// how many of them there are (0: the slice is empty); slots past the count repeat the last one.  (A sibling, not a new
+// argument of rr_flagged_list: that one is compiled into rr_scan_f32<6, 8, true>, which every 384-wide batch launches.)
+template <int NB>
+__device__ __forceinline__ int rr_flagged_slice(const int32_t* __restrict__ flags, int nq, int lane, int skip, int (&list)[NB]) {
+    int n = 0, seen = 0;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) list[b] = 0;
+    for (int i = 0; i < (nq + 63) / 64; ++i) {
+        const int q = 64 * i + lane;
+        unsigned long long m = __ballot(q < nq && flags[q] != 0);
+        while (m && n < NB) {
+            const int b = __builtin_ctzll(m);
+            m &= m - 1;
+            if (seen++ < skip) continue;
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+                if (j == n) list[j] = 64 * i + b;
+            ++n;
+        }
+    }
+#pragma unroll
+    for (int j = 1; j < NB; ++j)
+        if (j >= n && n > 0) list[j] = list[j - 1];
+    return n;
+}
+
+// The LISTED form of rr_scan_f32_generic: the NB queries are the flagged ones ranked [skip, skip + NB) of a wide filter launch
+// (rr_dense_fltw.hip), read in place from the launch's padded queries.  The per-row chain is the one above, so a flagged
+// query's answer is bit for bit the single-query answer.  An empty slice: every workgroup returns at once.
+template <int NB>
+__global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_f32_generic_listed(
+    const f32x4* __restrict__ mat, rr_scan_geom G, int nf, const float* __restrict__ queries,
+    float* __restrict__ sims, float* __restrict__ gmax, uint32_t* __restrict__ smax,
+    const int32_t* __restrict__ flags, int nq_total, int skip, int32_t* __restrict__ list_out) {
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    int list[NB];
+    const int n = rr_flagged_slice<NB>(flags, nq_total, lane, skip, list);
+    if (blockIdx.x == 0 && tid == 0) {
+        list_out[0] = n;                              // (also when it is 0: the selection behind this launch reads it)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) list_out[1 + b] = list[b];
+    }
+    if (n == 0) return;
+    const int sub = lane & 15;
+    const int grp = lane >> 4;
+    const int64_t wave = (int64_t)blockIdx.x * (RR_SCAN_THREADS / 64) + (tid >> 6);
+    if (wave >= G.n_waves) return;
+    const int64_t t0 = wave * G.tiles_per_wave;
+    const int64_t t1 = t0 + G.tiles_per_wave < G.n_tiles ? t0 + G.tiles_per_wave : G.n_tiles;
+    const f32x4* q4 = reinterpret_cast<const f32x4*>(queries);
+    float gm[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) gm[b] = -INFINITY;
+    for (int64_t tile = t0; tile < t1; ++tile) {
+        const int64_t row0 = tile * 64;
+        float mine[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) mine[b] = 0.f;
+        for (int it = 0; it < 16; ++it) {
+            int64_t row = row0 + 4 * it + grp;
+            row = row < G.n_rows ? row : G.n_rows - 1;
+            const f32x4* p = mat + row * (int64_t)(nf * 16) + sub;
+            float acc[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[b] = 0.f;
+            for (int i = 0; i < nf; ++i) {
+                const f32x4 x = p[16 * i];
+#pragma unroll
+                for (int b = 0; b < NB; ++b) {
+                    const f32x4 q = q4[(int64_t)list[b] * nf * 16 + 16 * i + sub];
+                    acc[b] = __builtin_fmaf(x.x, q.x, acc[b]);
+                    acc[b] = __builtin_fmaf(x.y, q.y, acc[b]);
+                    acc[b] = __builtin_fmaf(x.z, q.z, acc[b]);
+                    acc[b] = __builtin_fmaf(x.w, q.w, acc[b]);
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const float sacc = rr_row16_sum(acc[b]);
+                mine[b] = (sub == it) ? sacc : mine[b];
+            }
+        }
+        rr_finish_tile<NB>(G, tile, wave, t0, t1, lane, sub, grp, mine, gm, sims, gmax, smax);
+    }
+}
+
 // ------------------------------------------------------------------ select
 // Suffix scan over a 256-bin histogram: finds the bin holding the k-th largest
 // element (counting from the top bin) and the count strictly above it.
@@ -1278,6 +1366,26 @@ int rr_dense_listed_fallback(rr_index* ix, const float* d_q, int nq, int pool, i
     return RR_OK;
 }
 
+// The flagged queries of a wide filter launch (rr_dense_fltw.hip; fp32 storage, any width): ceil(nq / 8) pairs of the listed
+// generic scan and the listed selection, pair p for the flagged queries ranked [8 p, 8 p + 8).  The ranking of every pair is
+// taken from the launch's flags as the filter tail left them, so the selections write their "served" marks elsewhere
+// (ix->d_flag_done); nothing reads the flags after the last pair.  No host read: an empty slice costs two launches that return.
+int rr_dense_listed_fallback_wide(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores,
+                                  const int32_t* flags, hipStream_t st) {
+    RR_REQUIRE(ix->dtype == RR_DTYPE_F32 && ix->d_flag_list && ix->d_flag_done, "rr_dense_listed_fallback_wide: fp32 index expected");
+    static int cap = 0;
+    if (!cap) cap = rr_resident_grid(rr_scan_f32_generic_listed<RR_SEL_LISTED>, ix->device);
+    rr_scan_geom G = rr_make_geom(ix, cap);
+    for (int p = 0; p < (nq + RR_SEL_LISTED - 1) / RR_SEL_LISTED; ++p) {
+        hipLaunchKernelGGL((rr_scan_f32_generic_listed<RR_SEL_LISTED>), dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
+                           reinterpret_cast<const f32x4*>(ix->d_matrix), G, ix->dim_pad / 64, d_q, ix->d_sims, ix->d_gmax, ix->d_smax,
+                           flags, nq, RR_SEL_LISTED * p, ix->d_flag_list);
+        rr_launch_select_listed(ix, G, pool, d_rows, d_scores, ix->d_flag_done, st);
+    }
+    RR_HIP_TRY(hipGetLastError());
+    return RR_OK;
+}
+
 // Scan + select for up to 8 queries already on the device (padded to dim_pad).
 static int rr_dense_chunk(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                           float* d_scores, hipStream_t st, bool time_it) {
@@ -1342,6 +1450,21 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
     const int scratch_slots = (int)rr_round_up(nq < RR_SEL_MAXQ ? nq : RR_SEL_MAXQ, RR_MFMA_MAXQ);
     int rc = rr_ensure_scratch(ix, (mfma_ok && nq > valu_max) ? scratch_slots : 8);
     if (rc) return rc;
+    // Other widths (fp32 storage, dim_pad 64 .. 1024): batches above the crossover take the runtime-width filter path
+    // (rr_dense_fltw.hip) under the rules of the 384 one -- default scan mode, no RR_SCAN_EXACT, >= 8 pool tiles of 64 rows --
+    // RR_FLTW_MAXQ queries per read of the bf16 plane; what is left at the end of a call, and every matrix the path declines
+    // (no finite row-norm bound, no plane), stays on the VALU scans.  RR_NO_WIDE_FLT=1: the VALU scans for everything (A/B).
+    static const bool no_wide = getenv("RR_NO_WIDE_FLT") != nullptr;
+    const bool wide_ok = !bf16 && ix->dim_pad != 384 && ix->dim_pad <= RR_FLTW_MAX_DIM && ix->n_rows >= 64 && !no_wide && !exact_scan &&
+                   ix->scan_mode == RR_SCAN_MODE_DEFAULT && (ix->n_rows + 63) / 64 >= 8 * (int64_t)pool;
+    // A call of B >= RR_FLTW_MIN_Q queries goes in ceil(B / RR_FLTW_MAXQ) launches of equal size (65 queries: 33 + 32), so no
+    // remainder is left for a VALU read of its own: ceil(B / 64) reads of the plane serve the whole call.
+    int wide_left = (wide_ok && nq >= RR_FLTW_MIN_Q) ? (nq + RR_FLTW_MAXQ - 1) / RR_FLTW_MAXQ : 0;
+    if (wide_left > 0) {
+        // (tile words and group keys of a filter launch; the listed passes of its flagged queries use 8 score slots)
+        rc = rr_ensure_maxima(ix, RR_MFMA_MAXQ);
+        if (rc) return rc;
+    }
     int q0 = 0;
     while (q0 < nq) {
         const int left = nq - q0;
@@ -1354,6 +1477,19 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
             (ix->n_rows + 63) / 64 < 8 * (int64_t)pool)
             small = true;
         bool valu = !(mfma_ok && left > valu_max) || small;
+        if (wide_left > 0) {
+            n = (left + wide_left - 1) / wide_left;
+            rc = rr_dense_chunk_fltw(ix, q, n, pool, rows, scores, st);
+            if (rc == RR_FLT_NO_BOUND || rc == RR_FLT_SMALL) {
+                wide_left = 0;                        // declined for the matrix, not for the chunk: the whole call
+                rc = RR_OK;
+            } else {
+                if (rc) return rc;
+                --wide_left;
+                q0 += n;
+                continue;
+            }
+        }
         if (!valu) {
             // 5..128 queries share one read of the matrix: bf16 filter scan + exact rescoring of the
             // candidates (rr_dense_flt.hip); without a finite row-norm bound, or with RR_SCAN_EXACT=1 /

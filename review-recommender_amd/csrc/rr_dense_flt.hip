@@ -38,10 +38,7 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // One workgroup (64 lanes) per query slot: the bf16 plane (round to nearest even, memory order: both filter scans take
 // their A operands as they sit in the rows) and the slot's error bound (see rr_flt_bounds).
-struct rr_flt_bounds {
-    float row_norm;      // >= max over rows ||a||
-    float row_delta;     // >= max over rows ||a - bf16(a)||   (0 for a bf16 matrix)
-};
+// (struct rr_flt_bounds: rr_dense.h)
 __global__ __launch_bounds__(64) void rr_flt_prep_queries(const float* __restrict__ q, unsigned short* __restrict__ plane,
                                                           float* __restrict__ eps, rr_flt_bounds B) {
     const int slot = blockIdx.x, lane = threadIdx.x;
@@ -1262,7 +1259,7 @@ __global__ __launch_bounds__(256, 3) void rr_rescore_chain(
 }
 
 // ------------------------------------------------------------------ host side
-static int rr_flt_get_bounds(rr_index* ix, hipStream_t st, rr_flt_bounds* out) {
+int rr_flt_get_bounds(rr_index* ix, hipStream_t st, rr_flt_bounds* out) {
     if (ix->norm_bound < 0.f) {
         unsigned int* d = reinterpret_cast<unsigned int*>(rr_x3_scratch_of(ix).eps);   // borrowed for two words
         RR_HIP_TRY(hipMemsetAsync(d, 0, 2 * sizeof(unsigned int), st));
@@ -1347,9 +1344,9 @@ __global__ __launch_bounds__(256) void rr_shadow_from_f32(const f32x4* __restric
     dst[i] = u32x2{__builtin_bit_cast(unsigned int, lo), __builtin_bit_cast(unsigned int, hi)};
 }
 
-static int rr_flt_ensure_shadow(rr_index* ix, hipStream_t st) {
+int rr_flt_ensure_shadow(rr_index* ix, hipStream_t st) {
     if (ix->shadow_valid) return RR_OK;
-    const size_t bytes = (size_t)ix->n_rows * 384 * 2;
+    const size_t bytes = (size_t)ix->n_rows * ix->dim_pad * 2;        // (any width: rr_dense_fltw.hip streams the same plane)
     if (!ix->d_shadow) {
         const hipError_t e = hipMalloc((void**)&ix->d_shadow, bytes);
         if (e != hipSuccess) {          // no room for the plane: scan the fp32 rows (correct, twice the bytes)
@@ -1358,7 +1355,7 @@ static int rr_flt_ensure_shadow(rr_index* ix, hipStream_t st) {
             return RR_OK;
         }
     }
-    const int64_t n4 = ix->n_rows * 96;
+    const int64_t n4 = ix->n_rows * (ix->dim_pad / 4);
     hipLaunchKernelGGL(rr_shadow_from_f32, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
                        reinterpret_cast<const f32x4*>(ix->d_matrix), reinterpret_cast<u32x2*>(ix->d_shadow), n4);
     RR_HIP_TRY(hipGetLastError());
@@ -1816,6 +1813,8 @@ struct rr_debug_flt_state {          // what rr_debug_flt_words left for rr_debu
     const float* sigma;
 };
 static rr_debug_flt_state g_debug_flt = {nullptr, {}, 0, 0, nullptr};
+// rr_debug_fltw_words (rr_dense_fltw.hip) leaves its one-set launch here: rr_debug_flt_select reads scratch, not width
+void rr_debug_flt_note_state(rr_index* ix, const rr_scan_geom& G, int nq) { g_debug_flt = rr_debug_flt_state{ix, G, nq, 0, nullptr}; }
 
 template <int NQ2, bool SCAN_BF16>
 static int rr_debug_flt_single(rr_index* ix, const void* scan_mat, int nq, int pool, bool prefilter, rr_flt_bounds nb, bool launch,

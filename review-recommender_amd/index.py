@@ -155,7 +155,8 @@ class ProductIndex:
 
     def last_scan_info(self):
         """(kernel family, variant, queries per launch, MFMA terms, stream element bytes) of the last batched scan launch
-        (rr_index_last_scan_info; family 5 = filter scan, variant 9 = the 256-query query-stationary rr_scan_fltq)."""
+        (rr_index_last_scan_info; family 5 = filter scan, variant 9 = the 256-query query-stationary rr_scan_fltq, variant 16 =
+        rr_scan_fltw, the runtime-width scan of an fp32 index whose padded width is 64 .. 1024 and not 384)."""
         out = (C.c_int32 * 8)()
         _lib.check(_lib.load().rr_index_last_scan_info(self._h, out), "rr_index_last_scan_info")
         return tuple(out[:5])

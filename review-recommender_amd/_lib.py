@@ -178,6 +178,9 @@ DEBUG_PROTOTYPES = {
     "rr_debug_flt_words": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64]),
     "rr_debug_flt_select": (C.c_int, [c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rr_debug_select_traces": (C.c_int, [c_vp, c_i32, c_vp]),
+    "rr_debug_fltq_prefiltered": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, C.c_uint32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                            c_i64, c_vp, c_i64]),
+    "rr_debug_select_mlcap": (C.c_int, [c_i32]),
     "rr_debug_fltw_words": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64]),
     "rr_debug_fltw_rescore": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "rr_debug_rescore_chain": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -13,10 +13,17 @@ Here every instruction of four M-tile bodies (ring of four LDS images x two accu
   matrix return zeros), the epilogue of the PREVIOUS M-tile (35 vector instructions per 32-query fragment pair, the
   arithmetic of `piece()` in rr_scan_fltq, bit for bit) spread over the MFMA shadows at <= CAPS[n] instructions behind
   the MFMA of fragment n, 2 tile-word stores (buffer_store_dword: the upper lane half carries an out-of-range offset and
-  is dropped by the bounds check).
+  is dropped by the bounds check).  The store prefilter (sigma per query, rr_scan_fltq) rides on the same mechanism: a
+  v_cmp of the tile maximum against the lane's sigma, "any lane" on the scalar unit, and a v_cndmask that hands the store
+  the out-of-range offset in EVERY lane when no query of the 32-query line reaches its sigma -- the store is always
+  issued (the counted vmcnt waits stand), it just writes nothing.  The same scalar sequence ORs the running M-tile bit
+  into the line's 64-bit mask of stored M-tiles (mask0 / mask1; the bit moves up once per body).
 
 Hazards kept by construction (wait states = instructions in between):
-  VALU write -> v_permlane16/32_swap of that register: 2;  v_cmp (VALU) write of an SGPR pair -> VALU read of it: 2;
+  VALU write -> v_permlane16/32_swap of that register: 2;  v_cmp (VALU) write of an SGPR pair -> VALU read of it: 2,
+  and the same distance is kept from the v_cmp to the scalar instructions that read the pair and from their write of it
+  to the v_cndmask that takes it as its mask (the ISA asks for wait states only where a VALU-written SGPR feeds a VMEM
+  address, v_readlane's lane select or v_div_fmas -- none of them here; the distance costs nothing);
   s_add m0 -> LDS-DMA: 1;  MFMA write of an accumulator -> VALU read: the previous body's last MFMAs are > 60 cycles back.
 
 Usage: python gen_fltq_loop.py > rr_fltq_loop.inc   (build.py checks that the committed .inc is up to date)
@@ -62,15 +69,17 @@ def acc_reg(P, f, i):
 
 class Instr:
     def __init__(self, text, reads=(), writes=(), kind="valu", cond_w=None, cond_r=None):
+        # text: one instruction, or a list of scalar instructions that stay together (they hand SCC to one another)
         self.text, self.reads, self.writes, self.kind = text, set(reads), set(writes), kind
-        self.cond_w, self.cond_r = cond_w, cond_r      # SGPR pair written by a v_cmp / read as a condition
+        self.cond_w, self.cond_r = cond_w, cond_r      # SGPR pair written by a v_cmp (or a scalar group) / read as a condition
 
 
 def epilogue_program(P, t):
     """The epilogue of fragment t of accumulator set P: list of Instr.  Temps x0..x9 of the fragment, three condition
     pairs c0..c2 and a junk carry pair cj (named operands)."""
     x = [f"%[x{t}_{i}]" for i in range(10)]
-    c = [f"%[c{t}_0]"]
+    c = [f"%[c{t}_0]", f"%[c{t}_1]"]
+    sg, mask, voff = f"%[sg{t}]", f"%[mask{t}]", x[4]
     gm = f"%[gm{t}]"
     R = [acc_reg(P, t, i) for i in range(16)]
     e0, e1, e2, e3, eu, ew, gu, gw, cu, cw = x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], x[9]
@@ -92,6 +101,8 @@ def epilogue_program(P, t):
     V(f"v_permlane32_swap_b32 {mh}, {t1}", [mh, t1], [mh, t1], kind="swap")
     V(f"v_max_f32 {em}, {mh}, {t1}", [mh, t1], [em])                           # the tile maximum, in both halves
     V(f"v_max_f32 {gm}, {gm}, {em}", [gm, em], [gm])
+    # store prefilter: lanes whose query's tile maximum is not below its sigma (a NaN maximum keeps the line)
+    V(f"v_cmp_nlt_f32_e64 {c[1]}, {em}, {sg}", [em], [], cond_w=c[1])
     # bf16 of the tile maximum, rounded up: (b >> 31) ? (b >> 16) : ((b + 0xFFFF) >> 16)
     V(f"v_cmp_gt_i32_e64 {c[0]}, 0, {em}", [em], [], cond_w=c[0])
     V(f"v_add_u32 {w0}, 0xffff, {em}", [em], [w0])
@@ -100,6 +111,9 @@ def epilogue_program(P, t):
     V(f"v_lshrrev_b32 {w0}, 16, {w0}", [w0], [w0])
     # the two gap codes of this lane (rr_flt_gap_code, rr_x3.h): bits 20..23 of min(8 + gap / step, 31.99)
     V(f"v_fma_f32 {gu}, {gu}, %[inv], %[k8]", [gu], [gu])
+    # any lane -> the pair becomes all ones / zero (wave-uniform); the running M-tile bit goes into the line's mask
+    V([f"s_cmp_lg_u64 {c[1]}, 0", f"s_cselect_b64 {c[1]}, -1, 0", f"s_and_b64 %[stmp], {c[1]}, %[mbit]",
+       f"s_or_b64 {mask}, {mask}, %[stmp]"], [], [], kind="salu", cond_r=c[1], cond_w=c[1])
     V(f"v_sub_f32 {gw}, {em}, {ew}", [em, ew], [gw])
     V(f"v_fma_f32 {gw}, {gw}, %[inv], %[k8]", [gw], [gw])
     V(f"v_min_f32 {gu}, 0x41ffeb85, {gu}", [gu], [gu])
@@ -107,12 +121,13 @@ def epilogue_program(P, t):
     V(f"v_bfe_u32 {cu}, {gu}, 20, 4", [gu], [cu])
     V(f"v_bfe_u32 {cw}, {gw}, 20, 4", [gw], [cw])
     V(f"v_lshl_or_b32 {mine}, {cw}, 8, {cu}", [cw, cu], [mine])
+    V(f"v_cndmask_b32_e64 {voff}, %[oob], %[stvoff], {c[1]}", [], [voff], cond_r=c[1])    # (eu is dead: its register is the offset)
     V(f"v_lshlrev_b32 {mine}, %[cshift], {mine}", [mine], [mine])
     V(f"v_mov_b32 {t1}, {mine}", [mine], [t1])
     V(f"v_permlane32_swap_b32 {mine}, {t1}", [mine, t1], [mine, t1], kind="swap")
     V(f"v_or3_b32 {w0}, {mine}, {t1}, {w0}", [mine, t1, w0], [w0])
     off = " offset:128" if t else ""
-    V(f"buffer_store_dword {w0}, %[stvoff], s[{ST_RSRC}:{ST_RSRC + 3}], %[stsoff] offen{off}", [w0], [], kind="vmem")
+    V(f"buffer_store_dword {w0}, {voff}, s[{ST_RSRC}:{ST_RSRC + 3}], %[stsoff] offen{off}", [w0, voff], [], kind="vmem")
     return p
 
 
@@ -137,7 +152,7 @@ class Stream:
                     return False
         if ins.cond_r is not None and self.pos - self.cond_w.get(ins.cond_r, -99) < 3:
             return False
-        if ins.cond_w is not None and self.cond_busy.get(ins.cond_w):
+        if ins.cond_w is not None and ins.cond_w != ins.cond_r and self.cond_busy.get(ins.cond_w):
             return False
         return True
 
@@ -146,13 +161,15 @@ class Stream:
         if ins.kind in ("valu", "swap"):
             for r in ins.writes:
                 self.valu_w[r] = self.pos
-        if ins.cond_w is not None:
-            self.cond_w[ins.cond_w] = self.pos
-            self.cond_busy[ins.cond_w] = True
         if ins.cond_r is not None:
             # the last reader of a condition frees it: a pair is read exactly once per write
             self.cond_busy[ins.cond_r] = False
-        self.raw(ins.text)
+        lines = ins.text if isinstance(ins.text, list) else [ins.text]
+        for ln in lines:
+            self.raw(ln)
+        if ins.cond_w is not None:
+            self.cond_w[ins.cond_w] = self.pos - 1      # (a group: its last instruction, at the latest)
+            self.cond_busy[ins.cond_w] = True
 
 
 def gen_body(S, k):
@@ -236,6 +253,8 @@ def gen_body(S, k):
             S.emit(ins)
             nxt[t] += 1
             S.raw("; (epilogue instruction behind the last MFMA)", 0)
+    if not (ABL & 2):
+        S.raw("s_lshl_b64 %[mbit], %[mbit], 1")        # the next body's epilogue: the next M-tile of the group
 
 
 def emit_loop(abl=0):
@@ -266,7 +285,7 @@ def emit_loop(abl=0):
     out.append("{")
     out.append("    u32x4 " + ", ".join(f"tA{i}" for i in range(AD + 1)) + ";")
     out.append("    uint32_t " + ", ".join(f"tx{t}_{i}" for t in (0, 1) for i in range(10)) + ";")
-    out.append("    uint64_t tc0_0, tc1_0;")
+    out.append("    uint64_t tc0_0, tc1_0, tc0_1, tc1_1, tstmp;")
     out.append("    uint32_t tm0;")
     out.append("    asm volatile(")
     for ln in S.lines:
@@ -278,9 +297,11 @@ def emit_loop(abl=0):
     outs += [f'"+{{s[{LD_RSRC}:{LD_RSRC + 3}]}}"(ld_rsrc)', '[stsoff] "+s"(st_soff)', '[loops] "+s"(loops)']
     outs += [f'[A{i}] "=&v"(tA{i})' for i in range(AD + 1)]
     outs += [f'[x{t}_{i}] "=&v"(tx{t}_{i})' for t in (0, 1) for i in range(10)]
-    outs += [f'[c{t}_0] "=&s"(tc{t}_0)' for t in (0, 1)]
+    outs += [f'[c{t}_{i}] "=&s"(tc{t}_{i})' for t in (0, 1) for i in (0, 1)]
+    outs += ['[stmp] "=&s"(tstmp)', '[mbit] "+s"(mask_bit)'] + [f'[mask{t}] "+s"(mask[{t}])' for t in (0, 1)]
     outs += ['[m0s] "=&s"(tm0)']
     ins = [f'[b{ks}_{n}] "a"(bq[{ks}][{n}])' for ks in range(12) for n in range(4)]
+    ins += [f'[sg{t}] "v"(sg[{t}])' for t in (0, 1)] + ['[oob] "v"(0xFFFFF000u)']
     ins += [f'[al{m}] "v"(al[{m}])' for m in range(2)] + [f'[ah{m}] "v"(ah[{m}])' for m in range(2)]
     ins += ['[dvoff] "v"(dma_voff)', '[stvoff] "v"(st_voff)', '[cshift] "v"(code_shift)', '[inv] "s"(inv_step_s)',
             '[ldsw] "s"(lds_w)', f'"{{s[{ST_RSRC}:{ST_RSRC + 3}]}}"(st_rsrc)', '[k8] "v"(8.0f)']
@@ -299,7 +320,9 @@ def emit_loop(abl=0):
 HEADER = """// GENERATED by gen_fltq_loop.py -- do not edit.  The steady-state loop of rr_scan_fltq: four M-tile bodies per
 // iteration, every instruction placed by hand (see the generator's header).  Expects in scope: acc[2][2] (f32x16),
 // gm[2], bq[12][4], al[2], ah[2] (A-read addresses of images 0/1 and 2/3), dma_voff, st_voff, code_shift (VGPR),
-// inv_step_s, lds_w, st_soff, loops (SGPR), ld_rsrc, st_rsrc (u32x4 SGPR).
+// inv_step_s, lds_w, st_soff, loops (SGPR), ld_rsrc, st_rsrc (u32x4 SGPR), sg[2] (VGPR: the lane's sigma per 32-query
+// block), mask[2], mask_bit (uint64_t SGPR: stored M-tiles of the open group per block, the bit of the M-tile whose
+// epilogue the first body runs).
 """
 
 

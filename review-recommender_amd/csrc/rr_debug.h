@@ -37,6 +37,14 @@ int rr_debug_flt_words(rr_index* ix, const float* d_queries, int32_t nq_a, int32
 int rr_debug_flt_select(rr_index* ix, int32_t pool, uint32_t* mtiles, int64_t cap, int32_t* count, uint32_t* tau, uint32_t* open,
                         int32_t* fb);
 int rr_debug_select_traces(rr_index* ix, int32_t nq, int32_t* out);
+// tests/test_gpu_fltq_prefilter.py: the two-set scan's prefiltered pair (launch A over the first groups, rr_fltq_sigma, launch B
+// with thresholds and masks) through the product's launch code into sentinel-filled scratch -- geometry, eps, sigma, every
+// word, key and mask; rr_debug_flt_select then runs the product's selection on what the pair left.  mlcap > 0: the LDS
+// list of rr_select_mtiles' mask path holds only that many M-tiles from then on (0: the product's).  See the definitions.
+int rr_debug_fltq_prefiltered(rr_index* ix, const float* d_queries, int32_t nq_a, int32_t nq_b, int32_t pool, int32_t flags,
+                              uint32_t fill_word, int64_t* geom, float* eps, float* sigma, uint32_t* words, int64_t words_cap,
+                              uint32_t* keys, int64_t keys_cap, uint64_t* masks, int64_t masks_cap);
+int rr_debug_select_mlcap(int32_t mlcap);
 // tests/test_gpu_rescore_kernels.py: ONE rr_rescore_chain / ONE rr_select_rescored launch (the product's launch helpers) on
 // caller lists placed in the selection scratch, into outputs filled with sentinels.  mtiles [nq][cap], count / fb / tau (keys) /
 // eps [nq]; sc [nq][cap][8] out of the rescoring, [nq][cap][rows_per_mtile] into the selection; rows / scores [nq][pool],

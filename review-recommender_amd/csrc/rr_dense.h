@@ -90,9 +90,11 @@ size_t rr_x3_scratch_bytes();
 // nq + nq_b) from set 1, whose tile / group maxima sit `set_stride_words` 4-byte words behind set 0's and whose eps /
 // sigma entries start at index RR_FLT_MAXQ.
 // `floor` (device, per query of the launch, may be null): row shards -- a lower bound of the corpus-wide pool-th best score.
+// `masks` (device, may be null): filter words of a prefiltered two-set scan -- only the marked words of an opened group are read.
 void rr_launch_select_mtiles(rr_index* ix, const rr_scan_geom& G, int nq, int pool, hipStream_t st,
                              const float* eps = nullptr, const float* sigma = nullptr, int nq_b = 0,
-                             int64_t mmax_set_stride = 0, int64_t smax_set_stride = 0, const float* floor = nullptr);
+                             int64_t mmax_set_stride = 0, int64_t smax_set_stride = 0, const float* floor = nullptr,
+                             const uint64_t* masks = nullptr);     // rr_scan_fltq's stored-M-tile masks (prefiltered pair), or null
 void rr_launch_select_rescored(rr_index* ix, const rr_scan_geom& G, int nq, int pool, int64_t* d_rows,
                                float* d_scores, hipStream_t st, bool floor_mode = false);
 void rr_launch_group_kth(rr_index* ix, const rr_scan_geom& G, int nq_a, int nq_b, int kth, const float* eps, float* d_bound,

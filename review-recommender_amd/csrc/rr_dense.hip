@@ -41,6 +41,7 @@
 #define RR_SEL_RCAP 8192    // rr_select_rescored's key area for pools up to 512 (64 KB: two of its workgroups share a CU; rows are collected
                             // into the first half); larger pools take RR_SEL_CCAP
 #define RR_SEL_LCAP 4096    // groups opened by the fast path
+#define RR_SEL_MLCAP 6144   // rr_select_mtiles with masks: marked 32-row M-tiles of the opened groups (24 KB of LDS)
 
 // ------------------------------------------------------------------ scan
 template <int NF>
@@ -822,10 +823,14 @@ __global__ __launch_bounds__(RR_SEL_THREADS) void rr_select_mtiles(
     uint32_t* __restrict__ out_mtiles, int32_t* __restrict__ out_count, uint32_t* __restrict__ out_tau,
     int32_t* __restrict__ fb, int32_t* __restrict__ dbg, const float* __restrict__ eps,
     const float* __restrict__ sigma, int nq_a, int nq_b, int64_t mmax_set_stride, int64_t smax_set_stride,
-    const float* __restrict__ floor) {      // [nq_a + nq_b] or null: a lower bound of the corpus-wide pool-th best SCORE
+    const float* __restrict__ floor,        // [nq_a + nq_b] or null: a lower bound of the corpus-wide pool-th best SCORE
+    const unsigned long long* __restrict__ masks, int mlcap) {   // filter words (mm_pairs == 3) of a prefiltered rr_scan_fltq pair, or null:
+                                            // [set][RR_MAX_SCAN_WAVES groups][4 lines of 32 queries], bit j = M-tile j of the group was stored;
+                                            // mlcap <= RR_SEL_MLCAP: M-tiles the LDS list of the mask path may hold
     __shared__ uint32_t cnt[2][3][16];
     __shared__ uint32_t counters[4];
     __shared__ uint32_t list2[RR_SEL_LCAP];
+    __shared__ uint32_t mlist[RR_SEL_MLCAP];
     const int tid = threadIdx.x;
     // Query Q of the launch belongs to scan launch (set) 0 or 1; inside its set it is slot q.  Per-query OUTPUT arrays
     // (mtiles, count, tau, fb, dbg) are indexed by Q; the set's maxima by slot q; eps / sigma by set * RR_FLT_MAXQ + q.
@@ -914,6 +919,64 @@ __global__ __launch_bounds__(RR_SEL_THREADS) void rr_select_mtiles(
             // skipped tiles are stale: they can only open extra M-tiles, which the rescoring then discards.)
             if (sigma && !(sigma[q] <= openf)) ok = false;
             const int n2i = (int)n2;                                       // (<= 4096 groups x tiles per group)
+            // A prefiltered two-set scan stored only the word lines some query of the line can use and marked them per group:
+            // first the masks of the opened groups (8 bytes each), the marked 32-row M-tiles of this query's line compacted
+            // into LDS, then only their words -- one in ten of a group's, and never a stale one.  Group 0 of a run was
+            // scanned without thresholds: fully marked.  A list that outgrows its LDS area: the loop over all words below.
+            bool from_masks = false;
+            if (masks) {
+                const unsigned long long* mk = masks + (size_t)set * RR_MAX_SCAN_WAVES * 4 + (q >> 5);
+                const int n_open = (int)counters[0];
+                for (int i = tid; i < n_open; i += RR_SEL_THREADS) {
+                    const int g = (int)list2[i], k = g % gpw;
+                    const int64_t first = (int64_t)(g / gpw) * G.tiles_per_wave + (int64_t)k * C;   // the group's first 64-row tile
+                    int64_t nt = G.tiles_per_wave - (int64_t)k * C;                               // ... and how many it has
+                    nt = nt < C ? nt : C;
+                    nt = nt < G.n_tiles - first ? nt : G.n_tiles - first;
+                    const int nm = nt > 0 ? (int)(2 * nt) : 0;
+                    unsigned long long m = k == 0 ? ~0ull : mk[(size_t)g * 4];
+                    m &= nm >= 64 ? ~0ull : (1ull << nm) - 1ull;
+                    if (m) {
+                        uint32_t slot = atomicAdd(&counters[3], (uint32_t)__popcll(m));
+                        while (m) {
+                            const int j = __ffsll(m) - 1;
+                            m &= m - 1ull;
+                            if (slot < (uint32_t)mlcap) mlist[slot] = (uint32_t)(2 * first + j);
+                            ++slot;
+                        }
+                    }
+                }
+                __syncthreads();
+                from_masks = counters[3] <= (uint32_t)mlcap;
+            }
+            if (from_masks) {
+                const int n3 = (int)counters[3];
+                for (int i0 = tid; i0 < n3; i0 += U * RR_SEL_THREADS) {
+                    uint32_t mt[U], wd[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int i = i0 + u * RR_SEL_THREADS;
+                        mt[u] = i < n3 ? mlist[i] : 0xFFFFFFFFu;
+                        wd[u] = reinterpret_cast<const uint32_t*>(mmax)[(int64_t)(i < n3 ? mt[u] : 0u) * QS + q];
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        if (mt[u] == 0xFFFFFFFFu) continue;
+                        const uint32_t w = wd[u];
+                        const float mx = __uint_as_float(w << 16);
+                        if (!(mx >= openf)) continue;                              // the whole 32-row tile is below the threshold
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            const uint32_t code = (w >> (16 + 4 * g)) & 15u;
+                            const float bound = mx - rr_flt_gap_steps(code) * step;
+                            if (bound >= openf) {
+                                const uint32_t slot = atomicAdd(&counters[1], 1u);
+                                if (slot < RR_X3_MCAP) out_mtiles[(int64_t)q * RR_X3_MCAP + slot] = mt[u] * 4u + (uint32_t)g;
+                            }
+                        }
+                    }
+                }
+            } else
             for (int i0 = tid; i0 < n2i; i0 += U * RR_SEL_THREADS) {
                 int64_t tt[U];
                 uint32_t w0[U], w1[U];
@@ -1092,13 +1155,24 @@ size_t rr_x3_scratch_bytes() {
     return sizeof(uint32_t) * RR_SEL_MAXQ * RR_X3_MCAP + 4 * sizeof(int32_t) * RR_SEL_MAXQ +
            sizeof(float) * (size_t)RR_SEL_MAXQ * RR_X3_MCAP * 16;
 }
+#ifdef RR_DEBUG_HARNESS
+static int g_debug_sel_mlcap = 0;      // tests: a smaller LDS list for the mask path (the fallback to the loop over all words)
+extern "C" int rr_debug_select_mlcap(int32_t mlcap) {
+    g_debug_sel_mlcap = mlcap > 0 && mlcap < RR_SEL_MLCAP ? mlcap : 0;
+    return RR_OK;
+}
+#endif
 void rr_launch_select_mtiles(rr_index* ix, const rr_scan_geom& G, int nq, int pool, hipStream_t st, const float* eps,
                              const float* sigma, int nq_b, int64_t mmax_set_stride, int64_t smax_set_stride,
-                             const float* floor) {
+                             const float* floor, const uint64_t* masks) {
     const rr_x3_scratch s = rr_x3_scratch_of(ix);
+    int mlcap = RR_SEL_MLCAP;
+#ifdef RR_DEBUG_HARNESS
+    if (g_debug_sel_mlcap) mlcap = g_debug_sel_mlcap;
+#endif
     hipLaunchKernelGGL(rr_select_mtiles, dim3(nq + nq_b), dim3(RR_SEL_THREADS), 0, st, G, ix->d_gmax, ix->d_smax, pool,
                        s.mtiles, s.count, s.tau, s.fb, ix->d_sel_trace, eps, sigma, nq, nq_b, mmax_set_stride,
-                       smax_set_stride, floor);
+                       smax_set_stride, floor, reinterpret_cast<const unsigned long long*>(masks), mlcap);
 }
 void rr_launch_select_rescored(rr_index* ix, const rr_scan_geom& G, int nq, int pool, int64_t* d_rows,
                                float* d_scores, hipStream_t st, bool floor_mode) {

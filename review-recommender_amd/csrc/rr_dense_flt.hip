@@ -721,11 +721,24 @@ __global__ __launch_bounds__(512, 2) void rr_scan_flt16(
 // of the C++ bodies -- which stay for the first five M-tiles of a run, the last few and the matrix's short last M-tile
 // (RR_FLTQ_NOASM=1 runs them everywhere: A/B).
 // ABL (debug harness only): timing ablation of the hand-scheduled loop (gen_fltq_loop.py --abl), wrong results
+template <int... I, class Fn>
+__device__ __forceinline__ void rr_static_for(std::integer_sequence<int, I...>, Fn&& f) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
 template <bool ASM = false, int ABL = 0>
 __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
     const u32x4* __restrict__ mat, rr_scan_geom G, const u32x4* __restrict__ plane,   // [256][48] units: set 0, then set 1
     float* __restrict__ gmax, uint32_t* __restrict__ smax, const float* __restrict__ eps, int nq_a, int nq_b,
-    int64_t gmax_set_stride, unsigned long long* __restrict__ stamps = nullptr) {      // stamps (ABL != 0): [run][wave][4]
+    int64_t gmax_set_stride, unsigned long long* __restrict__ stamps,                  // stamps (ABL != 0): [run][wave][4]
+    int g0, int g1, const float* __restrict__ sigma, unsigned long long* __restrict__ masks) {
+    // [g0, g1): the selection groups of EVERY run this launch scans (0, G.gpw: all of them).  Group numbers, key indices
+    // and finish_tile keep their meaning in the whole run.
+    // sigma (null: every word is stored): [set][RR_FLT_MAXQ] store thresholds.  A word line -- one M-tile x the 32 queries of
+    // a block -- is stored only if some query of the line has its tile maximum >= its sigma; the decision is wave-uniform.
+    // A NaN maximum keeps its line (the compare is "not less than"); the matrix's short last M-tile is compared on its
+    // canonicalised maximum, i.e. on its real rows only, like any other.
+    // masks (null: none): [set][RR_MAX_SCAN_WAVES groups][4 lines] 64-bit words, bit j = M-tile j of the group was stored
+    // for that line; written at the group's end (host: only while a group has <= 64 M-tiles).
     constexpr int NB = 4;                             // ring of M-tile images
     constexpr int F = 2;                              // 32-query blocks (pairs of 16-query fragments) per wave
     constexpr int PW = 6;                             // LDS-DMA pieces per wave and M-tile
@@ -740,9 +753,14 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
     float* const gm_out = gmax + set * gmax_set_stride;
     uint32_t* const sm_out = smax + (size_t)set * RR_FLT_MAXQ * RR_MAX_SCAN_WAVES;
     const float* const eps_set = eps + set * RR_FLT_MAXQ;
-    const int64_t t0 = (int64_t)run * G.tiles_per_wave;
-    const int64_t t1 = t0 + G.tiles_per_wave < G.n_tiles ? t0 + G.tiles_per_wave : G.n_tiles;
-    const int64_t m0 = t0 * 2, m1 = t1 * 2;           // 32-row M-tiles of this run
+    const int64_t tr0 = (int64_t)run * G.tiles_per_wave;                                  // the run's 64-row tiles [tr0, tr1)
+    const int64_t tr1 = tr0 + G.tiles_per_wave < G.n_tiles ? tr0 + G.tiles_per_wave : G.n_tiles;
+    int64_t t0 = tr0 + (int64_t)g0 * G.tiles_per_group, t1 = tr0 + (int64_t)g1 * G.tiles_per_group;   // this launch's share of them
+    t0 = t0 < tr1 ? t0 : tr1;
+    t1 = t1 < tr1 ? t1 : tr1;
+    if (t0 >= t1) return;                             // (whole workgroup; a run has its group 0: the keys of absent groups are launch [0, ..)'s)
+    const int64_t m0 = t0 * 2, m1 = t1 * 2;           // 32-row M-tiles of this launch in this run
+    const int64_t cg2 = 2 * G.tiles_per_group;        // M-tiles per selection group
 
     // ---- B fragments (v_mfma_f32_16x16x32_bf16: 16 queries x 32 dims): query 16 n + (l & 15) of this wave, dims 32 ks +
     // 8 (l >> 4) .. + 7  ->  bq[ks][n], accumulation registers (12 x 4 x 4 = 192)
@@ -799,6 +817,25 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
     float gm[F];
 #pragma unroll
     for (int t = 0; t < F; ++t) gm[t] = -INFINITY;
+    float sg[F];                                      // this lane's query's store threshold, per block
+    uint64_t mask[F];                                 // stored M-tiles of the open group, per block (wave-uniform)
+#pragma unroll
+    for (int t = 0; t < F; ++t) {
+        sg[t] = sigma ? sigma[set * RR_FLT_MAXQ + qoff + 32 * t + c] : -INFINITY;
+        mask[t] = 0ull;
+    }
+    uint64_t mbit = 1ull;                             // bit of the M-tile whose epilogue runs next, in its group's masks
+    // the tile words of this wave's set as a buffer: a store whose offset is out of range writes nothing
+    const uint32_t st_voff = h == 0 ? (uint32_t)(qoff + c) * 4u : 0xFFFFF000u;      // (upper half: out of range, dropped)
+    u32x4 st_rsrc;
+    {
+        const uint64_t st_base = (uint64_t)(uintptr_t)gm_out;
+        const uint64_t st_bytes = (uint64_t)(2 * G.n_tiles) * (RR_FLT_MAXQ * 4);     // (every M-tile of every 64-row tile has its words)
+        st_rsrc.x = __builtin_amdgcn_readfirstlane((uint32_t)st_base);
+        st_rsrc.y = __builtin_amdgcn_readfirstlane((uint32_t)(st_base >> 32) & 0xFFFFu);
+        st_rsrc.z = __builtin_amdgcn_readfirstlane((uint32_t)(st_bytes < 0xFFFFE000ull ? st_bytes : 0xFFFFE000ull));
+        st_rsrc.w = 0x00020000u;
+    }
     // accumulators: [set P = M-tile parity][32-query block t]: sixteen registers = (row half r, fragment 2 t + nn) at
     // 8 r + 4 nn .. + 3.  C layout of one MFMA (lane l, register i): row 16 r + 4 (l >> 4) + i, query 16 n + (l & 15).
     f32x16 acc[2][F];
@@ -848,19 +885,50 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
         } else if (k == 14) {
             eword[t] |= ecu[t] | ecw[t];
         } else if (k == 15) {
-            if (h == 0 && live) reinterpret_cast<uint32_t*>(gm_out)[tile * RR_FLT_MAXQ + qoff + 32 * t + c] = eword[t];   // ONE store
+            if (live) {
+                // ONE store, always issued (the ring's vmcnt waits count it), through the set's buffer: the upper lane half
+                // carries an out-of-range offset and writes nothing -- and so does every lane of a line no query of which
+                // reaches its sigma (store prefilter; sigma = -inf without one).  mbit: this M-tile's bit in its group.
+                // The generated loop's sequence, as ONE statement (the unrolled bodies are at the size limit of the unroller):
+                // lanes not below their sigma (a NaN maximum keeps its line) -> any lane -> the pair all ones / zero -> the
+                // group's mask, the offset select, the store.
+                uint64_t cc, tmp;
+                uint32_t vo;
+                const uint32_t soff = (uint32_t)tile * (uint32_t)(RR_FLT_MAXQ * 4) + 128u * (uint32_t)t;    // (a set's words fit 4 GB)
+                asm volatile("v_cmp_nlt_f32_e64 %[cc], %[em], %[sg]\n\t"
+                             "s_nop 1\n\t"
+                             "s_cmp_lg_u64 %[cc], 0\n\t"
+                             "s_cselect_b64 %[cc], -1, 0\n\t"
+                             "s_and_b64 %[tmp], %[cc], %[bit]\n\t"
+                             "s_or_b64 %[mask], %[mask], %[tmp]\n\t"
+                             "s_nop 1\n\t"
+                             "v_cndmask_b32_e64 %[vo], %[oob], %[voff], %[cc]\n\t"
+                             "buffer_store_dword %[w], %[vo], %[rsrc], %[soff] offen"
+                             : [cc] "=&s"(cc), [tmp] "=&s"(tmp), [mask] "+s"(mask[t]), [vo] "=&v"(vo)
+                             : [em] "v"(em32[t]), [sg] "v"(sg[t]), [bit] "s"(mbit), [oob] "v"(0xFFFFF000u), [voff] "v"(st_voff),
+                               [w] "v"(eword[t]), [rsrc] "s"(st_rsrc), [soff] "s"(soff)
+                             : "scc", "memory");
+            }
         }
     };
+    auto uniform64 = [](uint64_t x) -> uint64_t {    // (wave-uniform by construction; tells the compiler, which keeps it in SGPRs then)
+        return (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)x) | ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(x >> 32)) << 32);
+    };
     auto finish_tile = [&](int64_t pm) {              // group bookkeeping of the M-tile whose epilogue has just finished
-        const int in_run = (int)((pm >> 1) - t0), cg = (int)G.tiles_per_group;
+        const int in_run = (int)((pm >> 1) - tr0), cg = (int)G.tiles_per_group;
+        mbit <<= 1;
         if ((pm & 1) == 1 && ((in_run + 1) % cg == 0 || pm == m1 - 1)) {
+            mbit = 1ull;
             const int64_t group = (int64_t)run * G.gpw + in_run / cg;
 #pragma unroll
             for (int t = 0; t < F; ++t) {
                 if (h == 0) sm_out[group * RR_FLT_MAXQ + qoff + 32 * t + c] = rr_f2key(gm[t]);
                 gm[t] = -INFINITY;
+                if (masks && lane == 0) masks[((size_t)set * RR_MAX_SCAN_WAVES + group) * 4 + (qoff >> 5) + t] = mask[t];
+                mask[t] = 0ull;
             }
         }
+        mbit = uniform64(mbit);
     };
     auto canon_set = [&](int P, int64_t tile) {       // rows past the end (and NaNs) of the matrix's last, short M-tile -> -inf
         const int64_t rbase = tile * 32 + 4 * (lane >> 4);
@@ -899,8 +967,10 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
         f32x4 c4[2][4];                               // [row half][fragment] of this M-tile
 #pragma unroll
         for (int i = 0; i < AD; ++i) RR_FLTQ_READ_A(a[i], toff, i);
-#pragma unroll
-        for (int u = 0; u < 24; ++u) {                // operand u = 2 ks + r: rows 16 r .. + 15, dims 32 ks .. + 31; four MFMAs
+        // (a fold over constants, not `#pragma unroll`: the 24 operands with their pieces outgrow the unroller's size limit,
+        //  and the offsets below must be constants)
+        rr_static_for(std::make_integer_sequence<int, 24>{}, [&](auto UC) {
+            constexpr int u = decltype(UC)::value;      // operand u = 2 ks + r: rows 16 r .. + 15, dims 32 ks .. + 31; four MFMAs
             if (u + AD < 24) RR_FLTQ_READ_A(a[(u + AD) % (AD + 1)], toff, u + AD);
             // reads return in order: with the (up to AD) younger ones outstanding, this operand's is in
             if (u + AD < 24) asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(AD) : "memory");
@@ -921,7 +991,7 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
                 if (idx % PB >= 16 && idx % PB < 19) dma_tile(mt + 3, (it + 3) & (NB - 1), 3 * (idx / PB) + idx % PB - 16, 3 * (idx / PB) + idx % PB - 15);
                 __builtin_amdgcn_sched_barrier(0);
             }
-        }
+        });
         // the last MFMAs' results are copied by vector instructions below: the wait states the compiler would count for its own
         asm volatile("s_nop 15\n\ts_nop 3" : "+v"(c4[0][0]), "+v"(c4[0][1]), "+v"(c4[0][2]), "+v"(c4[0][3]), "+v"(c4[1][0]), "+v"(c4[1][1]),
                      "+v"(c4[1][2]), "+v"(c4[1][3]) :: "memory");
@@ -938,7 +1008,6 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
         const int wu = __builtin_amdgcn_readfirstlane(w);
         const uint32_t lds_w = __builtin_amdgcn_readfirstlane(ring_lds) + (uint32_t)wu * (PW * 1024);
         const uint32_t dma_voff = (uint32_t)d_r8 * 768u + 16u * (uint32_t)(d_slot ^ (d_r8 >> 1) ^ ((wu & 1) << 2));
-        const uint32_t st_voff = h == 0 ? (uint32_t)(qoff + c) * 4u : 0xFFFFF000u;      // (upper half: out of range, dropped)
         const uint32_t inv_step_s = __builtin_amdgcn_readfirstlane(__float_as_uint(inv_step));
         uint32_t al[2], ah[2];
 #pragma unroll
@@ -946,16 +1015,9 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
             al[m] = a_addr[m];
             ah[m] = a_addr[m] + 2u * (TILE_UNITS * 16);
         }
-        const uint64_t st_base = (uint64_t)(uintptr_t)gm_out;
-        const uint64_t st_bytes = (uint64_t)((G.n_rows + 31) / 32) * (RR_FLT_MAXQ * 4);
-        u32x4 st_rsrc;
-        st_rsrc.x = __builtin_amdgcn_readfirstlane((uint32_t)st_base);
-        st_rsrc.y = __builtin_amdgcn_readfirstlane((uint32_t)(st_base >> 32) & 0xFFFFu);
-        st_rsrc.z = (uint32_t)(st_bytes < 0xFFFFE000ull ? st_bytes : 0xFFFFE000ull);
-        st_rsrc.w = 0x00020000u;
-        const int64_t T = m1 - m0;                                      // M-tiles of this run
+        const int64_t T = m1 - m0;                                      // M-tiles of this launch in this run
         const int64_t full = G.n_rows / 32 - m0 < T ? G.n_rows / 32 - m0 : T;   // M-tiles [0, full) are whole
-        const int64_t cg2 = 2 * G.tiles_per_group;                     // M-tiles per selection group (a multiple of 4: rr_fltq_geom)
+        // (cg2, M-tiles per selection group: a multiple of 4, rr_fltq_geom; m0 sits on a group's first M-tile)
         int64_t it = 0;
         while (it < T) {
             int64_t n_it = 0;
@@ -978,6 +1040,7 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
                 ld_rsrc.w = 0x00020000u;
                 uint32_t st_soff = __builtin_amdgcn_readfirstlane((uint32_t)((m0 + it - 2) * (RR_FLT_MAXQ * 4)));
                 uint32_t loops = __builtin_amdgcn_readfirstlane((uint32_t)n_it);
+                uint64_t mask_bit = mbit;                                // (the first body's epilogue is M-tile it - 1's)
                 // (the compiler moves the accumulators into / out of the loop's pinned registers with plain copies and does not
                 //  know that MFMAs -- inline asm to it -- wrote them: the matrix pipe must have drained on both sides; the
                 //  loop ends with its own s_nops, in front of the copies out)
@@ -988,6 +1051,9 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
 #endif
 #include "rr_fltq_loop.inc"
                 it += 4 * n_it;
+                mbit = uniform64(mask_bit) >> 1;                        // every body moved it up: back to M-tile it - 2's
+                mask[0] = uniform64(mask[0]);
+                mask[1] = uniform64(mask[1]);
                 finish_tile(m0 + it - 2);                               // (flushes only where that M-tile closes a group)
             } else {
                 if (it & 1) body(std::integral_constant<int, 1>{}, m0 + it);
@@ -1014,9 +1080,9 @@ __global__ __launch_bounds__(256, 1) void rr_scan_fltq(
         unsigned long long* o = stamps + ((size_t)run * 4 + w) * 4;
         o[0] = 0; o[1] = 0; o[2] = 0; o[3] = __builtin_amdgcn_s_memtime() - dbg_t0;
     }
-    if (h == 0) {
+    if (h == 0 && g0 == 0) {                          // keys of the groups this (short) run does not have
         const int cg = (int)G.tiles_per_group;
-        for (int k = (int)((t1 - t0 + cg - 1) / cg); k < G.gpw; ++k)
+        for (int k = (int)((tr1 - tr0 + cg - 1) / cg); k < G.gpw; ++k)
 #pragma unroll
             for (int t = 0; t < F; ++t) sm_out[((int64_t)run * G.gpw + k) * RR_FLT_MAXQ + qoff + 32 * t + c] = 0u;
     }
@@ -1098,6 +1164,36 @@ __global__ __launch_bounds__(256) void rr_flt_sigma(const float* __restrict__ sa
         geq += o >= mine ? 1 : 0;
     }
     if (greater < m && m <= geq) sigma[q] = rr_key2f(mine) - 2.05f * e;      // (threads with equal keys write the same value)
+}
+
+// The two-set scan's own thresholds (rr_scan_fltq in two launches): the first group of each of the n_runs runs is
+// 1 / gpw of the matrix, spread evenly over it, and its keys are written by the launch over group 0.
+// sigma[set][q] = key2f(the m-th largest of those keys of query q) - 2.05 eps[q], the rule of rr_flt_sigma with the
+// sample stride = gpw.  Key 0 (a run without rows) is left out; fewer than m real keys, no finite bound or more runs
+// than threads: -inf (everything is stored); slots past the set's queries: +inf (they keep no line).
+// One 256-thread workgroup per query slot, the m-th largest by counting.
+__global__ __launch_bounds__(256) void rr_fltq_sigma(const uint32_t* __restrict__ smax, int n_runs, int gpw, int nq_a, int nq_b,
+                                                     int m, const float* __restrict__ eps, float* __restrict__ sigma) {
+    __shared__ uint32_t keys[256];
+    __shared__ float res;
+    const int tid = threadIdx.x, set = blockIdx.x / RR_FLT_MAXQ, q = blockIdx.x % RR_FLT_MAXQ;
+    float* out = sigma + set * RR_FLT_MAXQ + q;
+    if (q >= (set ? nq_b : nq_a)) { if (tid == 0) *out = INFINITY; return; }
+    const float e = eps[set * RR_FLT_MAXQ + q];
+    if (n_runs > 256 || !(e >= 0.f && e < 3.0e38f)) { if (tid == 0) *out = -INFINITY; return; }
+    if (tid == 0) res = -INFINITY;
+    const uint32_t mine = tid < n_runs ? smax[(size_t)set * RR_FLT_MAXQ * RR_MAX_SCAN_WAVES + ((size_t)tid * gpw) * RR_FLT_MAXQ + q] : 0u;
+    keys[tid] = mine;
+    __syncthreads();
+    int greater = 0, geq = 0;
+    for (int i = 0; i < 256; ++i) {
+        const uint32_t o = keys[i];
+        greater += o > mine ? 1 : 0;
+        geq += o >= mine ? 1 : 0;
+    }
+    if (mine != 0u && greater < m && m <= geq) res = rr_key2f(mine) - 2.05f * e;    // (threads with equal keys write the same value)
+    __syncthreads();
+    if (tid == 0) *out = res;
 }
 
 // ------------------------------------------------------------------ exact rescoring
@@ -1399,10 +1495,8 @@ static int rr_flt_scan_set(rr_index* ix, int set, const rr_scan_geom& G, const v
         int64_t n_samp = (n_tiles32 - 1) / stride;
         if (n_samp > RR_FLT_SAMP_CAP) n_samp = RR_FLT_SAMP_CAP;
         const int m = 16 + (4 * pool + stride - 1) / stride;
-        if (!ix->d_flt_samp) {
-            RR_HIP_TRY(hipMalloc((void**)&ix->d_flt_samp, sizeof(float) * (size_t)RR_FLT_SAMP_CAP * RR_FLT_MAXQ));
-            RR_HIP_TRY(hipMalloc((void**)&ix->d_flt_sigma, sizeof(float) * 2 * RR_FLT_MAXQ));
-        }
+        if (!ix->d_flt_samp) RR_HIP_TRY(hipMalloc((void**)&ix->d_flt_samp, sizeof(float) * (size_t)RR_FLT_SAMP_CAP * RR_FLT_MAXQ));
+        if (!ix->d_flt_sigma) RR_HIP_TRY(hipMalloc((void**)&ix->d_flt_sigma, sizeof(float) * 2 * RR_FLT_MAXQ));
         float* sg = ix->d_flt_sigma + set * RR_FLT_MAXQ;
         hipLaunchKernelGGL((rr_flt_sample<NQ2>), dim3(256), dim3(512), 0, st, reinterpret_cast<const u32x4*>(scan_mat),
                            reinterpret_cast<const u32x4*>(plane), stride, (int)n_samp, ix->d_flt_samp);
@@ -1446,11 +1540,11 @@ static void rr_launch_rescore_chain(rr_index* ix, int64_t n_rows, const float* d
 template <bool ROWS_BF16>
 static int rr_flt_finish(rr_index* ix, const rr_scan_geom& G, const float* d_q, int nq_a, int nq_b, int pool,
                          int64_t* d_rows, float* d_scores, const float* sigma, hipStream_t st, const float* floor = nullptr,
-                         int parts = 7) {
+                         int parts = 7, const uint64_t* masks = nullptr) {     // masks: rr_scan_fltq's, of a prefiltered pair
     const rr_x3_scratch X = rr_x3_scratch_of(ix);
     const int nq = nq_a + nq_b;
     if (parts & 1)
-        rr_launch_select_mtiles(ix, G, nq_a, pool, st, X.eps, sigma, nq_b, rr_flt_mmax_set_stride(G), rr_flt_smax_set_stride(), floor);
+        rr_launch_select_mtiles(ix, G, nq_a, pool, st, X.eps, sigma, nq_b, rr_flt_mmax_set_stride(G), rr_flt_smax_set_stride(), floor, masks);
     static const bool no_pre = getenv("RR_NO_RESCORE_PLANE") != nullptr;
     if (parts & 2) rr_launch_rescore_chain<ROWS_BF16>(ix, G.n_rows, d_q, nq, floor ? 4 : 16, !no_pre, st);
     RR_HIP_TRY(hipGetLastError());
@@ -1475,6 +1569,7 @@ struct rr_flt_pending {
     int nq_a, nq_b, pool;
     const float* sigma;
     bool rows_bf16;
+    const uint64_t* masks;       // rr_scan_fltq's stored-M-tile masks (a prefiltered pair), or null
 };
 struct rr_flt_phase {            // how a chunk function was called
     int phase = 0;               // 0 both, 1 scan only (+ bound), 2 selection only
@@ -1492,11 +1587,12 @@ void rr_flt_drop_pending(rr_index* ix) {
 // the tail of every scan path: straight on to the selection, or park the state for phase 2
 template <bool ROWS_BF16>
 static int rr_flt_after_scan(rr_index* ix, const rr_scan_geom& G, const float* d_q, int nq_a, int nq_b, int pool,
-                             int64_t* d_rows, float* d_scores, const float* sigma, hipStream_t st, const rr_flt_phase& ph) {
-    if (ph.phase != 1) return rr_flt_finish<ROWS_BF16>(ix, G, d_q, nq_a, nq_b, pool, d_rows, d_scores, sigma, st);
+                             int64_t* d_rows, float* d_scores, const float* sigma, hipStream_t st, const rr_flt_phase& ph,
+                             const uint64_t* masks = nullptr) {
+    if (ph.phase != 1) return rr_flt_finish<ROWS_BF16>(ix, G, d_q, nq_a, nq_b, pool, d_rows, d_scores, sigma, st, nullptr, 7, masks);
     rr_flt_pending* p = rr_flt_pending_of(ix);
     if (!p) return RR_E_HIP;
-    *p = rr_flt_pending{true, G, d_q, nq_a, nq_b, pool, sigma, ROWS_BF16};
+    *p = rr_flt_pending{true, G, d_q, nq_a, nq_b, pool, sigma, ROWS_BF16, masks};
     if (ph.kth > 0 && ph.d_bound)     // (kth = 0: the pipelined single-GPU K1 wants the split, not a bound)
         rr_launch_group_kth(ix, G, nq_a, nq_b, ph.kth, rr_x3_scratch_of(ix).eps, ph.d_bound, rr_flt_smax_set_stride(), st);
     RR_HIP_TRY(hipGetLastError());
@@ -1513,33 +1609,86 @@ static int rr_dense_chunk_flt_t(rr_index* ix, const void* scan_mat, const float*
     return rr_flt_after_scan<ROWS_BF16>(ix, G, d_q, nq, 0, pool, d_rows, d_scores, sigma, st, ph);
 }
 
-// The two-set launch of rr_dense_pair_flt_t (the debug harness launches it through this as well): planes and bounds of
-// both sets are in place.
-static int rr_flt_launch_fltq(rr_index* ix, const rr_scan_geom& G, const void* scan_mat, int nq_a, int nq_b, bool noasm, hipStream_t st) {
+// One launch of rr_scan_fltq over groups [g0, g1) of every run (sigma / masks: see the kernel)
+static void rr_fltq_launch_range(rr_index* ix, const rr_scan_geom& G, const void* scan_mat, int nq_a, int nq_b, bool noasm, int g0,
+                                 int g1, const float* sigma, uint64_t* masks, hipStream_t st) {
     const rr_x3_scratch X = rr_x3_scratch_of(ix);
-    const int slot = rr_scan_events_begin(ix, st);
-    rr_scan_note(ix, 5, 9, nq_a + nq_b, 1, 2);
     if (noasm)
         hipLaunchKernelGGL((rr_scan_fltq<false>), dim3(G.n_waves), dim3(256), 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
                            reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, X.eps, nq_a, nq_b,
-                           rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr);
+                           rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr, g0, g1, sigma, (unsigned long long*)masks);
     else
         hipLaunchKernelGGL((rr_scan_fltq<true>), dim3(G.n_waves), dim3(256), 0, st, reinterpret_cast<const u32x4*>(scan_mat), G,
                            reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, X.eps, nq_a, nq_b,
-                           rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr);
+                           rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr, g0, g1, sigma, (unsigned long long*)masks);
+}
+
+// The two-set launch of rr_dense_pair_flt_t (the debug harness launches it through this as well): planes and bounds of
+// both sets are in place.  Unfiltered: every word of every M-tile is stored.
+static int rr_flt_launch_fltq(rr_index* ix, const rr_scan_geom& G, const void* scan_mat, int nq_a, int nq_b, bool noasm, hipStream_t st) {
+    const int slot = rr_scan_events_begin(ix, st);
+    rr_scan_note(ix, 5, 9, nq_a + nq_b, 1, 2);
+    rr_fltq_launch_range(ix, G, scan_mat, nq_a, nq_b, noasm, 0, G.gpw, nullptr, nullptr, st);
     rr_scan_events_end(ix, slot, st);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }
+
+// The stored-M-tile masks of a prefiltered pair: [set][RR_MAX_SCAN_WAVES groups][4 lines] 64-bit words in the line-per-
+// scan-wave area behind the two sets of tile words (rr_ensure_maxima: RR_MAX_SCAN_WAVES x RR_FLT_MAXQ words; the masks
+// take a quarter of it and the two-set scan has no other use for it).
+static uint64_t* rr_fltq_masks_of(rr_index* ix, const rr_scan_geom& G) {
+    static_assert(2 * 4 * 2 <= RR_FLT_MAXQ, "the masks fit the area behind the tile words");
+    return reinterpret_cast<uint64_t*>(reinterpret_cast<uint32_t*>(ix->d_gmax) + (size_t)4 * G.n_tiles * RR_FLT_MAXQ);
+}
+
+// The same pass over the plane as rr_flt_launch_fltq, with the store prefilter from the scan's own first groups:
+//   launch A   group 0 of every run (1 / gpw of the matrix, spread evenly over it), every word stored;
+//   rr_fltq_sigma   sigma[q] = (m-th largest of q's first-group keys) - 2.05 eps[q], m = 16 + ceil(4 pool / gpw);
+//   launch B   groups 1 .. gpw - 1: a word line is stored only where some query of it reaches its sigma, and the lines
+//              stored are marked in the group's mask (use_masks).
+// Stream order carries the dependencies.  ONE event pair and one note span the three launches: a "scan launch" of the
+// timing rows stays one pass over the plane for the call's queries, the new overhead inside it.
+static int rr_flt_launch_fltq_prefiltered(rr_index* ix, const rr_scan_geom& G, const void* scan_mat, int nq_a, int nq_b, int pool,
+                                          bool noasm, bool use_masks, hipStream_t st, const float** sigma_out,
+                                          const uint64_t** masks_out) {
+    if (!ix->d_flt_sigma) RR_HIP_TRY(hipMalloc((void**)&ix->d_flt_sigma, sizeof(float) * 2 * RR_FLT_MAXQ));
+    uint64_t* masks = use_masks ? rr_fltq_masks_of(ix, G) : nullptr;
+    const int m = 16 + (4 * pool + G.gpw - 1) / G.gpw;
+    const int slot = rr_scan_events_begin(ix, st);
+    rr_scan_note(ix, 5, 9, nq_a + nq_b, 1, 2);
+    rr_fltq_launch_range(ix, G, scan_mat, nq_a, nq_b, noasm, 0, 1, nullptr, nullptr, st);
+    hipLaunchKernelGGL(rr_fltq_sigma, dim3(2 * RR_FLT_MAXQ), dim3(256), 0, st, ix->d_smax, G.n_waves, G.gpw, nq_a, nq_b, m,
+                       rr_x3_scratch_of(ix).eps, ix->d_flt_sigma);
+    rr_fltq_launch_range(ix, G, scan_mat, nq_a, nq_b, noasm, 1, G.gpw, ix->d_flt_sigma, masks, st);
+    rr_scan_events_end(ix, slot, st);
+    RR_HIP_TRY(hipGetLastError());
+    *sigma_out = ix->d_flt_sigma;
+    *masks_out = masks;
+    return RR_OK;
+}
+// where the product takes the prefiltered pair (RR_NO_FLTQ_PREFILTER=1: the single launch, A/B); `force`: the debug harness
+static bool rr_fltq_prefilter_wanted(const rr_scan_geom& G, const rr_flt_phase& ph, bool force) {
+    static const bool off = getenv("RR_NO_FLTQ_PREFILTER") != nullptr;
+    if (G.gpw < 2) return false;
+    if ((uint64_t)((G.n_rows + 31) / 32) * (RR_FLT_MAXQ * 4) >= 0xFFFFE000ull) return false;   // (the kernel's 32-bit word offsets)
+    if (force) return true;
+    // phase 1 of a shard exchange with a floor to come: the floor may open M-tiles below this shard's own sigma
+    return !off && G.n_rows >= 2000000 && !(ph.phase == 1 && ph.kth > 0);
+}
+// masks serve while a group's M-tiles fit one 64-bit word (up to ~16.8M rows per GPU); beyond, the selection reads every
+// word of an opened group, stale ones included, as the one-set path does
+static bool rr_fltq_masks_fit(const rr_scan_geom& G) { return 2 * G.tiles_per_group <= 64; }
 
 // 129 .. 256 queries whose second part still fills a 128-slot launch (> 64 queries): two scan launches, one selection
 template <bool SCAN_BF16, bool ROWS_BF16>
 static int rr_dense_pair_flt_t(rr_index* ix, const void* scan_mat, const float* d_q, int nq_a, int nq_b, int pool,
                                int64_t* d_rows, float* d_scores, rr_flt_bounds bounds, hipStream_t st,
                                const rr_flt_phase& ph = rr_flt_phase()) {
-    // bf16 stream: both sets in ONE launch of the query-stationary rr_scan_fltq, the matrix leaves HBM once for the 256
-    // queries.  It runs without the store prefilter: the launch is paced by the matrix side, where the skipped stores
-    // saved 0.08 ms and the two samples cost 0.125 (r02).  RR_NO_DUAL=1: two launches back to back (A/B).  An fp32
+    // bf16 stream: both sets in ONE pass of the query-stationary rr_scan_fltq, the matrix leaves HBM once for the 256
+    // queries.  The sampled store prefilter of the one-set scans does not pay here (the skipped stores saved 0.08 ms,
+    // the two sample + sigma launch pairs cost 0.125: r02); from 2M rows on the pass takes its thresholds from its own
+    // first groups instead (rr_flt_launch_fltq_prefiltered).  RR_NO_DUAL=1: two launches back to back (A/B).  An fp32
     // stream (no plane) has no two-set kernel and takes the two launches as well.
     // (nq_a = RR_FLT_MAXQ at every caller: the two sets' query slots, planes and bounds are contiguous)
     RR_REQUIRE(nq_a == RR_FLT_MAXQ && nq_b >= 1 && nq_b <= RR_FLT_MAXQ, "a pair is %d + nq_b queries", RR_FLT_MAXQ);
@@ -1550,9 +1699,13 @@ static int rr_dense_pair_flt_t(rr_index* ix, const void* scan_mat, const float* 
             hipLaunchKernelGGL(rr_flt_prep_queries, dim3(2 * RR_FLT_MAXQ), dim3(64), 0, st, d_q,
                                reinterpret_cast<unsigned short*>(ix->d_qplanes), rr_x3_scratch_of(ix).eps, bounds);
         static const bool noasm = getenv("RR_FLTQ_NOASM") != nullptr;    // the C++ bodies everywhere (A/B)
-        const int rc = rr_flt_launch_fltq(ix, G, scan_mat, nq_a, nq_b, noasm, st);
+        const float* sigma = nullptr;
+        const uint64_t* masks = nullptr;
+        const int rc = rr_fltq_prefilter_wanted(G, ph, false)
+                           ? rr_flt_launch_fltq_prefiltered(ix, G, scan_mat, nq_a, nq_b, pool, noasm, rr_fltq_masks_fit(G), st, &sigma, &masks)
+                           : rr_flt_launch_fltq(ix, G, scan_mat, nq_a, nq_b, noasm, st);
         if (rc != RR_OK) return rc;
-        return rr_flt_after_scan<ROWS_BF16>(ix, G, d_q, nq_a, nq_b, pool, d_rows, d_scores, nullptr, st, ph);
+        return rr_flt_after_scan<ROWS_BF16>(ix, G, d_q, nq_a, nq_b, pool, d_rows, d_scores, sigma, st, ph, masks);
     }
     const rr_scan_geom G = rr_flt_geom<4, SCAN_BF16>(ix);
     const float *sg0 = nullptr, *sg1 = nullptr;
@@ -1592,8 +1745,8 @@ int rr_dense_chunk_flt(rr_index* ix, const float* d_q, int nq, int pool, int64_t
         rr_flt_pending* p = rr_flt_pending_of(ix);
         if (!p || !p->valid || p->nq_a + p->nq_b != nq || p->pool != pool || p->d_q != d_q) return RR_FLT_SMALL;   // (caller: plain call)
         if (parts & 4) p->valid = false;
-        return p->rows_bf16 ? rr_flt_finish<true>(ix, p->G, d_q, p->nq_a, p->nq_b, pool, d_rows, d_scores, p->sigma, st, d_floor, parts)
-                            : rr_flt_finish<false>(ix, p->G, d_q, p->nq_a, p->nq_b, pool, d_rows, d_scores, p->sigma, st, d_floor, parts);
+        return p->rows_bf16 ? rr_flt_finish<true>(ix, p->G, d_q, p->nq_a, p->nq_b, pool, d_rows, d_scores, p->sigma, st, d_floor, parts, p->masks)
+                            : rr_flt_finish<false>(ix, p->G, d_q, p->nq_a, p->nq_b, pool, d_rows, d_scores, p->sigma, st, d_floor, parts, p->masks);
     }
     rr_flt_phase ph;
     ph.phase = phase;
@@ -1714,7 +1867,8 @@ static float rr_debug_time_fltq_asm(rr_index* ix, hipStream_t st, int reps) {
         hipEventRecord(e0, st);
         hipLaunchKernelGGL((rr_scan_fltq<true, ABL>), dim3(G.n_waves), dim3(256), 0, st, reinterpret_cast<const u32x4*>(ix->d_shadow), G,
                            reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, rr_x3_scratch_of(ix).eps, 128, 128,
-                           rr_flt_mmax_set_stride(G), ABL ? d_st : (unsigned long long*)nullptr);
+                           rr_flt_mmax_set_stride(G), ABL ? d_st : (unsigned long long*)nullptr, 0, (int)G.gpw, (const float*)nullptr,
+                           (unsigned long long*)nullptr);
         hipEventRecord(e1, st);
         hipEventSynchronize(e1);
         float ms = 0.f;
@@ -1754,11 +1908,13 @@ extern "C" int rr_debug_fltq_compare(rr_index* ix, int64_t* out) {
         if (v == 0)
             hipLaunchKernelGGL((rr_scan_fltq<false>), dim3(G.n_waves), dim3(256), 0, st, reinterpret_cast<const u32x4*>(ix->d_shadow), G,
                                reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, rr_x3_scratch_of(ix).eps, 128, 128,
-                               rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr);
+                               rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr, 0, (int)G.gpw, (const float*)nullptr,
+                               (unsigned long long*)nullptr);
         else
             hipLaunchKernelGGL((rr_scan_fltq<true>), dim3(G.n_waves), dim3(256), 0, st, reinterpret_cast<const u32x4*>(ix->d_shadow), G,
                                reinterpret_cast<const u32x4*>(ix->d_qplanes), ix->d_gmax, ix->d_smax, rr_x3_scratch_of(ix).eps, 128, 128,
-                               rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr);
+                               rr_flt_mmax_set_stride(G), (unsigned long long*)nullptr, 0, (int)G.gpw, (const float*)nullptr,
+                               (unsigned long long*)nullptr);
         RR_HIP_TRY(hipGetLastError());
         w[v].resize(words);
         g[v].resize(groups);
@@ -1811,8 +1967,9 @@ struct rr_debug_flt_state {          // what rr_debug_flt_words left for rr_debu
     rr_scan_geom G;
     int nq_a, nq_b;
     const float* sigma;
+    const uint64_t* masks;           // rr_debug_fltq_prefiltered: the stored-M-tile masks of the pair, or null
 };
-static rr_debug_flt_state g_debug_flt = {nullptr, {}, 0, 0, nullptr};
+static rr_debug_flt_state g_debug_flt = {nullptr, {}, 0, 0, nullptr, nullptr};
 // rr_debug_fltw_words (rr_dense_fltw.hip) leaves its one-set launch here: rr_debug_flt_select reads scratch, not width
 void rr_debug_flt_note_state(rr_index* ix, const rr_scan_geom& G, int nq) { g_debug_flt = rr_debug_flt_state{ix, G, nq, 0, nullptr}; }
 
@@ -1912,6 +2069,77 @@ extern "C" int rr_debug_flt_words(rr_index* ix, const float* d_queries, int32_t 
     return RR_OK;
 }
 
+// ---- the two-set scan with the store prefilter from its own first groups (tests/test_gpu_fltq_prefilter.py)
+// The product's prefiltered pair (rr_flt_launch_fltq_prefiltered: launch A, rr_fltq_sigma, launch B) on 128 + nq_b queries,
+// into a word scratch filled with `fill_word` (0: the word sentinel), key and mask scratch filled with their sentinels.
+// flags: 1 = take the pair below the product's 2M rows as well; 2 = no masks (launch B only skips stores); 4 = the C++
+// bodies everywhere.  Where the pair does not apply (one group per run), the single launch runs, as in the product.
+// geom[16] as rr_debug_flt_words, [10] = 1 the pair ran + 2 with masks.  masks: [set][n_waves gpw groups][4 lines] 64-bit
+// words (the sentinel 0xA5A5.. where none was written).  rr_debug_flt_select then runs the product's selection on what
+// the pair left, masks included.
+#define RR_DEBUG_MASK_SENTINEL 0xA5A5A5A5A5A5A5A5ull
+extern "C" int rr_debug_fltq_prefiltered(rr_index* ix, const float* d_queries, int32_t nq_a, int32_t nq_b, int32_t pool, int32_t flags,
+                                         uint32_t fill_word, int64_t* geom, float* eps, float* sigma, uint32_t* words, int64_t words_cap,
+                                         uint32_t* keys, int64_t keys_cap, uint64_t* masks, int64_t masks_cap) {
+    RR_REQUIRE(ix && geom && d_queries && eps && sigma && words && keys && masks && ix->dim_pad == 384 && ix->d_matrix, "NULL argument / index of dim 384 expected");
+    RR_REQUIRE(nq_a == RR_FLT_MAXQ && nq_b >= 1 && nq_b <= RR_FLT_MAXQ && pool >= 1, "a pair is %d + nq_b queries", RR_FLT_MAXQ);
+    RR_REQUIRE(ix->scratch_q >= 64 && ix->maxima_q >= RR_FLT_MAXQ && ix->cur_slot == 0,
+               "run a batched search of 64 queries or more first (allocates the scratch)");
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = nullptr;
+    g_debug_flt.ix = nullptr;
+    const void* scan_mat = ix->d_matrix;
+    if (ix->dtype != RR_DTYPE_BF16) {
+        ix->use_shadow = 1;
+        const int rc = rr_flt_ensure_shadow(ix, st);
+        if (rc != RR_OK) return rc;
+        RR_REQUIRE(ix->shadow_valid, "no room for the bf16 filter plane");
+        scan_mat = ix->d_shadow;
+    }
+    rr_flt_bounds nb = {0.f, 0.f};
+    int rc = rr_flt_get_bounds(ix, st, &nb);
+    if (rc != RR_OK) return rc;
+    const rr_scan_geom G = rr_fltq_geom(ix);
+    const int nq = nq_a + nq_b;
+    const size_t n_words = (size_t)4 * ((ix->n_rows + 63) / 64) * RR_FLT_MAXQ;       // both sets (rr_ensure_maxima)
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_gmax, (int)(fill_word ? fill_word : RR_DEBUG_WORD_SENTINEL), n_words, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_smax, (int)RR_DEBUG_KEY_SENTINEL, (size_t)2 * rr_flt_smax_set_stride(), st));
+    RR_HIP_TRY(hipMemsetAsync(rr_fltq_masks_of(ix, G), 0xA5, sizeof(uint64_t) * 2 * RR_MAX_SCAN_WAVES * 4, st));
+    rc = rr_flt_pad_prep(ix, d_queries, nq, (int)rr_round_up(nq, RR_MFMA_MAXQ), st);
+    RR_REQUIRE(rc == RR_OK, "no finite row-norm bound: the filter scans do not run on this matrix");
+    rr_flt_fresh_guard fresh_guard{ix};
+    const float* sg = nullptr;
+    const uint64_t* mk = nullptr;
+    const bool pair = rr_fltq_prefilter_wanted(G, rr_flt_phase(), (flags & 1) != 0);
+    rc = pair ? rr_flt_launch_fltq_prefiltered(ix, G, scan_mat, nq_a, nq_b, pool, (flags & 4) != 0, rr_fltq_masks_fit(G) && !(flags & 2),
+                                               st, &sg, &mk)
+              : rr_flt_launch_fltq(ix, G, scan_mat, nq_a, nq_b, (flags & 4) != 0, st);
+    if (rc != RR_OK) return rc;
+    const int64_t per_set_w = 2 * G.n_tiles * G.qs, n_groups = (int64_t)G.n_waves * G.gpw, per_set_k = n_groups * G.qs;
+    const int64_t g[16] = {G.n_rows, G.n_tiles, G.tiles_per_wave, G.n_waves, G.gpw, G.tiles_per_group, G.qs, per_set_w, per_set_k, 2,
+                           (pair ? 1 : 0) + (mk ? 2 : 0), 4, (int64_t)RR_DEBUG_WORD_SENTINEL, (int64_t)RR_DEBUG_KEY_SENTINEL,
+                           rr_flt_mmax_set_stride(G), rr_flt_smax_set_stride()};
+    memcpy(geom, g, sizeof(g));
+    RR_REQUIRE(words_cap >= 2 * per_set_w && keys_cap >= 2 * per_set_k && masks_cap >= 2 * n_groups * 4,
+               "output arrays too small: %lld words, %lld keys, %lld masks wanted", (long long)(2 * per_set_w), (long long)(2 * per_set_k),
+               (long long)(2 * n_groups * 4));
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    for (int s = 0; s < 2; ++s) {
+        RR_HIP_TRY(hipMemcpy(words + s * per_set_w, reinterpret_cast<const uint32_t*>(ix->d_gmax) + s * rr_flt_mmax_set_stride(G),
+                             sizeof(uint32_t) * per_set_w, hipMemcpyDeviceToHost));
+        RR_HIP_TRY(hipMemcpy(keys + s * per_set_k, ix->d_smax + s * rr_flt_smax_set_stride(), sizeof(uint32_t) * per_set_k,
+                             hipMemcpyDeviceToHost));
+        RR_HIP_TRY(hipMemcpy(masks + s * n_groups * 4, rr_fltq_masks_of(ix, G) + (size_t)s * RR_MAX_SCAN_WAVES * 4,
+                             sizeof(uint64_t) * n_groups * 4, hipMemcpyDeviceToHost));
+    }
+    RR_HIP_TRY(hipMemcpy(eps, rr_x3_scratch_of(ix).eps, sizeof(float) * RR_SEL_MAXQ, hipMemcpyDeviceToHost));
+    for (int i = 0; i < RR_SEL_MAXQ; ++i) sigma[i] = -INFINITY;
+    if (sg) RR_HIP_TRY(hipMemcpy(sigma, sg, sizeof(float) * 2 * RR_FLT_MAXQ, hipMemcpyDeviceToHost));
+    g_debug_flt = rr_debug_flt_state{ix, G, nq_a, nq_b, sg, mk};
+    return RR_OK;
+}
+
 // The product's selection (rr_select_mtiles, through rr_launch_select_mtiles as rr_flt_finish calls it) on the words and
 // keys the last rr_debug_flt_words of this index left in the scratch.  Per query Q of the launch: mtiles[Q][cap] (the first
 // min(count, cap) listed 8-row M-tiles), count, tau (key of the row cut), open (key the M-tiles were opened down to), fb.
@@ -1925,7 +2153,8 @@ extern "C" int rr_debug_flt_select(rr_index* ix, int32_t pool, uint32_t* mtiles,
     const rr_debug_flt_state& S = g_debug_flt;
     const rr_x3_scratch X = rr_x3_scratch_of(ix);
     const int nq = S.nq_a + S.nq_b;
-    rr_launch_select_mtiles(ix, S.G, S.nq_a, pool, st, X.eps, S.sigma, S.nq_b, rr_flt_mmax_set_stride(S.G), rr_flt_smax_set_stride());
+    rr_launch_select_mtiles(ix, S.G, S.nq_a, pool, st, X.eps, S.sigma, S.nq_b, rr_flt_mmax_set_stride(S.G), rr_flt_smax_set_stride(),
+                            nullptr, S.masks);
     RR_HIP_TRY(hipGetLastError());
     RR_HIP_TRY(hipStreamSynchronize(st));
     RR_HIP_TRY(hipMemcpy(count, X.count, sizeof(int32_t) * nq, hipMemcpyDeviceToHost));

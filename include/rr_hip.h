@@ -38,7 +38,7 @@ extern "C" {
 #define RR_E_STATE      -4   /* handle not ready for this call (e.g. meta not set) */
 
 #define RR_DTYPE_F32     0
-#define RR_DTYPE_BF16    1   /* storage only (dim 384): queries, products and accumulation stay fp32 */
+#define RR_DTYPE_BF16    1   /* storage only (dim 1 .. 1024): queries, products and accumulation stay fp32 */
 
 #define RR_MAX_POOL   2048   /* upper bound for pool / k */
 #define RR_MAX_BATCH  1024
@@ -56,7 +56,12 @@ int rr_device_count(int* out);
 /* Device-resident copy of product_emb.npy (nlp/11_build_product_embeddings.py:82-85):
  * n_rows x dim, row-major.  h_matrix may be NULL (fill later with
  * rr_index_upload_rows / rr_index_adopt_device).  row_offset is added to every
- * row this shard reports.  dim is padded internally to a multiple of 64. */
+ * row this shard reports.  dim is padded internally to a multiple of 64.
+ * Widths: RR_DTYPE_F32 takes dim 1 .. 8192, RR_DTYPE_BF16 dim 1 .. 1024 (2 bytes per element and no filter plane beside the
+ * rows: a third of what an fp32 index of the same rows takes once it has searched a batch).  A padded width of 384 is served
+ * by the 384-wide kernels; every other padded width up to 1024 by the runtime-width ones (csrc/rr_dense_bf16w.hip,
+ * csrc/rr_dense_fltw.hip), with the same contract: a query's answer is the exact top-pool of its per-row-chain scores,
+ * bitwise the same alone, in any batch and on any shard.  An adopted bf16 matrix is n_rows x dim_padded() bf16. */
 int rr_index_create(const void* h_matrix, int64_t n_rows, int32_t dim, int32_t dtype,
                     int32_t device, int64_t row_offset, rr_index** out);
 int rr_index_upload_rows(rr_index* ix, int64_t first_row, int64_t n_rows, const void* h_rows);
@@ -120,7 +125,7 @@ int rr_index_scan_stats(rr_index* ix, double* out_total_ms, int64_t* out_launche
 /* Which scan kernel the last scan launch on this handle ran: out8[0] = 1 rr_scan_f32, 2 rr_scan_bf16,
  * 3 rr_scan_mfma_x3, 4 rr_scan_x3w, 5 the filter scans (rr_scan_flt over fp32 rows; over a bf16 stream rr_scan_flt16
  * and, for two query sets in one launch, rr_scan_fltq); 6 and 7 are retired (the removed f32-input MFMA scans); [1] = its template
- * variant (query tiles / query slots; filter scans: 9 = rr_scan_fltq; 16 = rr_scan_fltw, the runtime-width scan of an fp32 index whose
+ * variant (query tiles / query slots; filter scans: 9 = rr_scan_fltq; 16 = rr_scan_fltw, the runtime-width scan of an index of either dtype whose
  * padded width is 64 .. 1024 and not 384 (csrc/rr_dense_fltw.hip); 8 was the two-set rr_scan_flt16, no longer reported);
  * [2] = queries in that launch; [3] = bf16 MFMA terms per dimension
  * (0: not a bf16 matrix-core kernel); [4] = bytes per matrix element the scan streamed (2 = bf16 rows or the bf16
@@ -139,7 +144,8 @@ int rr_index_select_trace(rr_index* ix, int32_t* out16);
  * once-rounded bf16 copy of the matrix (n_rows x 384 x 2 bytes of extra HBM, built lazily at the first batched search
  * and dropped by any write to the matrix) instead of the fp32 rows -- half the bytes per launch for the same approximate
  * scores and the same error bound -- and candidates are rescored on the fp32 rows exactly as before: identical answers.
- * enable = 0 frees the plane and scans the fp32 rows.  Environment RR_NO_SHADOW=1 does the same process-wide. */
+ * enable = 0 frees the plane and scans the fp32 rows.  Environment RR_NO_SHADOW=1 does the same process-wide.
+ * A bf16 index never has a plane, at any width (its rows are one): neither switch applies to it. */
 int rr_index_set_shadow(rr_index* ix, int32_t enable);
 #define RR_SCAN_MODE_DEFAULT 0
 #define RR_SCAN_MODE_STORED 1

@@ -131,7 +131,8 @@ extern "C" int rr_index_create(const void* h_matrix, int64_t n_rows, int32_t dim
                (long long)n_rows);
     RR_REQUIRE(dim >= 1 && dim <= 8192, "rr_index_create: dim %d out of [1, 8192]", dim);
     RR_REQUIRE(dtype == RR_DTYPE_F32 || dtype == RR_DTYPE_BF16, "rr_index_create: unknown dtype %d", dtype);
-    RR_REQUIRE(dtype == RR_DTYPE_F32 || dim == 384, "rr_index_create: bf16 storage is built for dim 384 only");
+    RR_REQUIRE(dtype == RR_DTYPE_F32 || dim <= RR_FLTW_MAX_DIM, "rr_index_create: bf16 storage is built for dim 1 .. %d, not %d",
+               RR_FLTW_MAX_DIM, dim);
     RR_REQUIRE(row_offset >= 0 && row_offset + n_rows < (1ll << 32),
                "rr_index_create: global rows must stay below 2^32");
     int ndev = 0;

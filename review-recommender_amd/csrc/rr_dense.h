@@ -104,6 +104,9 @@ int rr_resident_waves(const void* kernel, int threads, int device);
 // bf16-storage VALU scan (rr_dense_bf16.hip): up to 8 queries.
 int rr_dense_chunk_bf16(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                         float* d_scores, hipStream_t st);
+// ... at a runtime width (rr_dense_bf16w.hip: dim_pad 64 .. RR_FLTW_MAX_DIM other than 384): up to 8 queries
+int rr_dense_chunk_bf16w(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
+                         float* d_scores, hipStream_t st);
 // l2_normalize of rows [first, first + n) of an fp32 index, in place
 int rr_l2norm_rows_f32(rr_index* ix, int64_t first_row, int64_t n, float eps, hipStream_t st);
 // ... of n padded rows anywhere on the device (a staging copy): the same kernel
@@ -165,3 +168,76 @@ int rr_dense_chunk_fltw(rr_index* ix, const float* d_q, int nq, int pool, int64_
 // the flagged queries ranked [8 p, 8 p + 8) of the launch with the single-query chain; a pair whose slice is empty returns at once
 int rr_dense_listed_fallback_wide(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores,
                                   const int32_t* flags, hipStream_t st);
+// rr_dense_bf16w.hip: the listed scan of such a pair over the rows of a bf16 index (rr_scan_bf16_generic_listed); returns the
+// geometry its selection reads
+rr_scan_geom rr_launch_scan_bf16w_listed(rr_index* ix, const float* d_q, const int32_t* flags, int nq, int skip, hipStream_t st);
+
+#ifdef __HIPCC__
+// ------------------------------------------------------------------ device pieces the VALU scan files share
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+// bf16 rows at a runtime width (rr_dense_bf16w.hip, rr_dense_fltw.hip): eight products of one 16-byte chunk onto acc, in memory order; q0 / q1: the eight query floats beside it
+__device__ __forceinline__ float rr_bf16w_chunk(const u32x4 x, const f32x4 q0, const f32x4 q1, float acc) {
+    acc = __builtin_fmaf(__uint_as_float(x.x << 16), q0.x, acc);
+    acc = __builtin_fmaf(__uint_as_float(x.x & 0xFFFF0000u), q0.y, acc);
+    acc = __builtin_fmaf(__uint_as_float(x.y << 16), q0.z, acc);
+    acc = __builtin_fmaf(__uint_as_float(x.y & 0xFFFF0000u), q0.w, acc);
+    acc = __builtin_fmaf(__uint_as_float(x.z << 16), q1.x, acc);
+    acc = __builtin_fmaf(__uint_as_float(x.z & 0xFFFF0000u), q1.y, acc);
+    acc = __builtin_fmaf(__uint_as_float(x.w << 16), q1.z, acc);
+    acc = __builtin_fmaf(__uint_as_float(x.w & 0xFFFF0000u), q1.w, acc);
+    return acc;
+}
+
+// End of a tile: lane (sub, grp) holds row row0 + 4*sub + grp for every query.
+template <int NB>
+__device__ __forceinline__ void rr_finish_tile(const rr_scan_geom& G, int64_t tile, int64_t wave,
+                                               int64_t t0, int64_t t1, int lane, int sub, int grp,
+                                               float (&mine)[NB], float (&gm)[NB],
+                                               float* __restrict__ sims, float* __restrict__ gmax,
+                                               uint32_t* __restrict__ smax) {
+    const int64_t my_row = tile * 64 + 4 * sub + grp;
+    const bool valid = my_row < G.n_rows;
+    const bool group_end = tile == t1 - 1;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        float v = mine[b];
+        v = (valid && v == v) ? v : -INFINITY;  // NaN scores and pad rows rank last
+        sims[(int64_t)b * G.n_pad + my_row] = v;
+        const float m = rr_wave_max(v);
+        gm[b] = fmaxf(gm[b], m);
+        if (lane == 0) {
+            gmax[(int64_t)b * G.n_tiles + tile] = m;
+            if (group_end)
+                smax[(int64_t)b * G.n_waves + wave] = rr_f2key(gm[b]);
+        }
+        if (group_end) gm[b] = -INFINITY;
+    }
+}
+
+// rr_flagged_list with a skip count: the queries whose flag is up, ranked by query number, ranks [skip, skip + NB).  Returns
+// how many of them there are (0: the slice is empty); slots past the count repeat the last one.  (A sibling, not a new
+// argument of rr_flagged_list: that one is compiled into rr_scan_f32<6, 8, true>, which every 384-wide batch launches.)
+template <int NB>
+__device__ __forceinline__ int rr_flagged_slice(const int32_t* __restrict__ flags, int nq, int lane, int skip, int (&list)[NB]) {
+    int n = 0, seen = 0;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) list[b] = 0;
+    for (int i = 0; i < (nq + 63) / 64; ++i) {
+        const int q = 64 * i + lane;
+        unsigned long long m = __ballot(q < nq && flags[q] != 0);
+        while (m && n < NB) {
+            const int b = __builtin_ctzll(m);
+            m &= m - 1;
+            if (seen++ < skip) continue;
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+                if (j == n) list[j] = 64 * i + b;
+            ++n;
+        }
+    }
+#pragma unroll
+    for (int j = 1; j < NB; ++j)
+        if (j >= n && n > 0) list[j] = list[j - 1];
+    return n;
+}
+#endif  // __HIPCC__

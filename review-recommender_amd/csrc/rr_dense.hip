@@ -74,31 +74,7 @@ __device__ __forceinline__ void rr_dot_rows(const f32x4 (&x)[NF], const f32x4 (&
     }
 }
 
-// End of a tile: lane (sub, grp) holds row row0 + 4*sub + grp for every query.
-template <int NB>
-__device__ __forceinline__ void rr_finish_tile(const rr_scan_geom& G, int64_t tile, int64_t wave,
-                                               int64_t t0, int64_t t1, int lane, int sub, int grp,
-                                               float (&mine)[NB], float (&gm)[NB],
-                                               float* __restrict__ sims, float* __restrict__ gmax,
-                                               uint32_t* __restrict__ smax) {
-    const int64_t my_row = tile * 64 + 4 * sub + grp;
-    const bool valid = my_row < G.n_rows;
-    const bool group_end = tile == t1 - 1;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        float v = mine[b];
-        v = (valid && v == v) ? v : -INFINITY;  // NaN scores and pad rows rank last
-        sims[(int64_t)b * G.n_pad + my_row] = v;
-        const float m = rr_wave_max(v);
-        gm[b] = fmaxf(gm[b], m);
-        if (lane == 0) {
-            gmax[(int64_t)b * G.n_tiles + tile] = m;
-            if (group_end)
-                smax[(int64_t)b * G.n_waves + wave] = rr_f2key(gm[b]);
-        }
-        if (group_end) gm[b] = -INFINITY;
-    }
-}
+// (rr_finish_tile, the end of a tile shared by every VALU scan, and rr_flagged_slice are in rr_dense.h)
 
 // The queries of a call whose flag is up, if there are at most NB of them: every wave works the list out for itself (four
 // coalesced loads + ballots), so that no launch stands between the flags and their readers.  Returns the count -- 0 when
@@ -244,33 +220,6 @@ __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_f32_generic(
         }
         rr_finish_tile<NB>(G, tile, wave, t0, t1, lane, sub, grp, mine, gm, sims, gmax, smax);
     }
-}
-
-// rr_flagged_list with a skip count: the queries whose flag is up, ranked by query number, ranks [skip, skip + NB).  Returns
-// how many of them there are (0: the slice is empty); slots past the count repeat the last one.  (A sibling, not a new
-// argument of rr_flagged_list: that one is compiled into rr_scan_f32<6, 8, true>, which every 384-wide batch launches.)
-template <int NB>
-__device__ __forceinline__ int rr_flagged_slice(const int32_t* __restrict__ flags, int nq, int lane, int skip, int (&list)[NB]) {
-    int n = 0, seen = 0;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) list[b] = 0;
-    for (int i = 0; i < (nq + 63) / 64; ++i) {
-        const int q = 64 * i + lane;
-        unsigned long long m = __ballot(q < nq && flags[q] != 0);
-        while (m && n < NB) {
-            const int b = __builtin_ctzll(m);
-            m &= m - 1;
-            if (seen++ < skip) continue;
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-                if (j == n) list[j] = 64 * i + b;
-            ++n;
-        }
-    }
-#pragma unroll
-    for (int j = 1; j < NB; ++j)
-        if (j >= n && n > 0) list[j] = list[j - 1];
-    return n;
 }
 
 // The LISTED form of rr_scan_f32_generic: the NB queries are the flagged ones ranked [skip, skip + NB) of a wide filter launch
@@ -1440,13 +1389,21 @@ int rr_dense_listed_fallback(rr_index* ix, const float* d_q, int nq, int pool, i
     return RR_OK;
 }
 
-// The flagged queries of a wide filter launch (rr_dense_fltw.hip; fp32 storage, any width): ceil(nq / 8) pairs of the listed
+// The flagged queries of a wide filter launch (rr_dense_fltw.hip; either storage dtype, any width): ceil(nq / 8) pairs of the listed
 // generic scan and the listed selection, pair p for the flagged queries ranked [8 p, 8 p + 8).  The ranking of every pair is
 // taken from the launch's flags as the filter tail left them, so the selections write their "served" marks elsewhere
 // (ix->d_flag_done); nothing reads the flags after the last pair.  No host read: an empty slice costs two launches that return.
 int rr_dense_listed_fallback_wide(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores,
                                   const int32_t* flags, hipStream_t st) {
-    RR_REQUIRE(ix->dtype == RR_DTYPE_F32 && ix->d_flag_list && ix->d_flag_done, "rr_dense_listed_fallback_wide: fp32 index expected");
+    RR_REQUIRE(ix->d_flag_list && ix->d_flag_done, "rr_dense_listed_fallback_wide: the listed scratch is missing");
+    if (ix->dtype == RR_DTYPE_BF16) {                 // bf16 rows: the listed form of rr_scan_bf16_generic (rr_dense_bf16w.hip)
+        for (int p = 0; p < (nq + RR_SEL_LISTED - 1) / RR_SEL_LISTED; ++p) {
+            const rr_scan_geom G = rr_launch_scan_bf16w_listed(ix, d_q, flags, nq, RR_SEL_LISTED * p, st);
+            rr_launch_select_listed(ix, G, pool, d_rows, d_scores, ix->d_flag_done, st);
+        }
+        RR_HIP_TRY(hipGetLastError());
+        return RR_OK;
+    }
     static int cap = 0;
     if (!cap) cap = rr_resident_grid(rr_scan_f32_generic_listed<RR_SEL_LISTED>, ix->device);
     rr_scan_geom G = rr_make_geom(ix, cap);
@@ -1524,12 +1481,13 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
     const int scratch_slots = (int)rr_round_up(nq < RR_SEL_MAXQ ? nq : RR_SEL_MAXQ, RR_MFMA_MAXQ);
     int rc = rr_ensure_scratch(ix, (mfma_ok && nq > valu_max) ? scratch_slots : 8);
     if (rc) return rc;
-    // Other widths (fp32 storage, dim_pad 64 .. 1024): batches above the crossover take the runtime-width filter path
+    // Other widths (either storage dtype, dim_pad 64 .. 1024): batches above the crossover take the runtime-width filter path
     // (rr_dense_fltw.hip) under the rules of the 384 one -- default scan mode, no RR_SCAN_EXACT, >= 8 pool tiles of 64 rows --
-    // RR_FLTW_MAXQ queries per read of the bf16 plane; what is left at the end of a call, and every matrix the path declines
-    // (no finite row-norm bound, no plane), stays on the VALU scans.  RR_NO_WIDE_FLT=1: the VALU scans for everything (A/B).
+    // RR_FLTW_MAXQ queries per read of the bf16 plane (of the rows themselves in a bf16 index); what is left at the end of a
+    // call, and every matrix the path declines (no finite row-norm bound, no plane), stays on the VALU scans.
+    // RR_NO_WIDE_FLT=1: the VALU scans for everything (A/B).
     static const bool no_wide = getenv("RR_NO_WIDE_FLT") != nullptr;
-    const bool wide_ok = !bf16 && ix->dim_pad != 384 && ix->dim_pad <= RR_FLTW_MAX_DIM && ix->n_rows >= 64 && !no_wide && !exact_scan &&
+    const bool wide_ok = ix->dim_pad != 384 && ix->dim_pad <= RR_FLTW_MAX_DIM && ix->n_rows >= 64 && !no_wide && !exact_scan &&
                    ix->scan_mode == RR_SCAN_MODE_DEFAULT && (ix->n_rows + 63) / 64 >= 8 * (int64_t)pool;
     // A call of B >= RR_FLTW_MIN_Q queries goes in ceil(B / RR_FLTW_MAXQ) launches of equal size (65 queries: 33 + 32), so no
     // remainder is left for a VALU read of its own: ceil(B / 64) reads of the plane serve the whole call.
@@ -1598,8 +1556,9 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
             // the VALU scan kernels read NB = 1/2/4/8 query slots; slots past n hold zeros
             const int vmax = (mfma_ok && left > valu_max) ? 8 : valu_max;
             n = left < vmax ? left : vmax;
-            rc = bf16 ? rr_dense_chunk_bf16(ix, q, n, pool, rows, scores, st)
-                      : rr_dense_chunk(ix, q, n, pool, rows, scores, st, q0 == 0);
+            rc = !bf16 ? rr_dense_chunk(ix, q, n, pool, rows, scores, st, q0 == 0)
+                 : ix->dim_pad == 384 ? rr_dense_chunk_bf16(ix, q, n, pool, rows, scores, st)
+                                      : rr_dense_chunk_bf16w(ix, q, n, pool, rows, scores, st);
         }
         if (rc) return rc;
         q0 += n;
@@ -1707,8 +1666,6 @@ extern "C" int rr_dense_topk_slot_dev(rr_index* ix, int32_t slot, const float* d
                "rr_dense_topk_dev: pool %d out of [1,min(%d,n_rows=%lld)]", pool, RR_MAX_POOL,
                (long long)ix->n_rows);
     RR_REQUIRE(ix->d_matrix, "rr_dense_topk_dev: index has no matrix");
-    RR_REQUIRE(ix->dtype == RR_DTYPE_F32 || ix->dim_pad == 384,
-               "rr_dense_topk_dev: bf16 storage is built for dim 384 only");
     std::lock_guard<std::mutex> lk(ix->mu);
     RR_HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = (hipStream_t)stream;  // NULL = the device's default stream
@@ -1757,8 +1714,6 @@ extern "C" int rr_dense_topk(rr_index* ix, const float* h_queries, int32_t n_que
     if (eff == 0) return RR_OK;  // top_k == 0 returns two empty arrays
     RR_REQUIRE(h_out_rows && h_out_scores, "rr_dense_topk: NULL output");
     RR_REQUIRE(ix->d_matrix, "rr_dense_topk: index has no matrix");
-    RR_REQUIRE(ix->dtype == RR_DTYPE_F32 || ix->dim_pad == 384,
-               "rr_dense_topk: bf16 storage is built for dim 384 only");
     std::lock_guard<std::mutex> lk(ix->mu);
     RR_HIP_TRY(hipSetDevice(ix->device));
     // The scan scratch of the handle is shared with rr_dense_topk_dev callers, who run on the

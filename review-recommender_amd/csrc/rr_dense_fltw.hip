@@ -1,17 +1,20 @@
-// rr_dense_fltw.hip -- K1 batched scan at a RUNTIME WIDTH: the filter path of rr_dense_flt.hip for fp32 indexes whose
-// dim_pad is 64, 128, .. 1024 and not 384 (another embedding model: 768 or 1024 floats).  Same contract, same tail:
+// rr_dense_fltw.hip -- K1 batched scan at a RUNTIME WIDTH: the filter path of rr_dense_flt.hip for indexes of either storage
+// dtype whose dim_pad is 64, 128, .. 1024 and not 384 (another embedding model: 768 or 1024 floats).  Same contract, same tail:
 //
 //   rr_fltw_prep_queries   pads the launch's queries, writes their bf16 planes and the error bound eps per slot
 //   rr_scan_fltw           streams the bf16 filter plane of the fp32 rows once for up to RR_FLTW_MAXQ = 64 queries and leaves
 //                          what rr_scan_flt16 leaves: one tile word per (32-row tile, query), one key per selection group
 //   rr_select_mtiles       (rr_dense.hip, unchanged) the 8-row M-tiles that can hold a top-pool row
 //   rr_rescore_chain_w     their rows with the per-row fmaf chain of rr_scan_f32_generic at nf = dim_pad / 64
+//   rr_rescore_chain_wb    ... of a bf16 index with the chain of rr_scan_bf16_generic (rr_dense_bf16w.hip)
 //   rr_select_rescored     (unchanged) exact top-pool, (score desc, row asc)
 //   listed VALU passes     (rr_dense.hip: rr_dense_listed_fallback_wide) flagged queries, eight per pass
 //
 // so a query's answer is the exact top-pool of its per-row-chain scores, bitwise the same alone, in any batch, on any shard.
 // The 384-wide kernels are not templated on the width: they keep every constant and every hand-placed wait they have.
 // This scan is plain C++: the compiler counts the waits of a three-stage register ring.
+//   A bf16 index has no plane: its rows ARE one (the scan streams ix->d_matrix), and the first term of the bound vanishes
+// because rr_row_norm_max<true> reports a row delta of 0 at every width (it never touches the delta sum).
 #include "rr_x3.h"
 
 // ------------------------------------------------------------------ the error bound at width D
@@ -287,6 +290,62 @@ __global__ __launch_bounds__(256) void rr_rescore_chain_w(
     }
 }
 
+// The same launch for the rows of a bf16 index: lane `sub` of a row takes the 16-byte chunks sub + 16 i, i < ceil(units / 16),
+// those with a number below units = dim_pad / 8, eight fmaf each in memory order (rr_bf16w_chunk) onto one accumulator, then
+// rr_row16_sum -- the chain of rr_scan_bf16_generic.  Same lists, same sc layout, same masking of the repeated last tile.
+__global__ __launch_bounds__(256) void rr_rescore_chain_wb(
+    const u32x4* __restrict__ mat, int64_t n_rows, int units, const float* __restrict__ queries,   // [nq][8 units] fp32, padded
+    const uint32_t* __restrict__ mtiles, const int32_t* __restrict__ count, const int32_t* __restrict__ fb, float* __restrict__ sc) {
+    __shared__ f32x4 qs[RR_FLTW_MAX_DIM / 4];
+    const int q = blockIdx.y;
+    if (fb[q]) return;
+    const int n = count[q];
+    constexpr int U = 2;
+    if ((int)blockIdx.x * 4 * U >= n) return;                      // (the whole workgroup: before the barrier)
+    for (int i = threadIdx.x; i < 2 * units; i += 256) qs[i] = reinterpret_cast<const f32x4*>(queries + (int64_t)q * units * 8)[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane & 15, grp = lane >> 4;
+    const int nr = (units + 15) >> 4;
+    mtiles += (int64_t)q * RR_X3_MCAP;
+    sc += (int64_t)q * RR_X3_MCAP * 8;
+    const int64_t last_row = n_rows - 1;
+    for (int s0 = ((int)blockIdx.x * 4 + wave) * U; s0 < n; s0 += (int)gridDim.x * 4 * U) {
+        uint32_t m8[U];
+        const u32x4* p[U][2];
+        float acc[U][2];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            m8[u] = mtiles[s0 + u < n ? s0 + u : n - 1];           // (a repeated last tile: its stores are masked)
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {                       // four rows per step: lane (sub, grp) -> row 4 it + grp
+                int64_t row = (int64_t)m8[u] * 8 + 4 * it + grp;
+                row = row < last_row ? row : last_row;
+                p[u][it] = mat + row * units;
+                acc[u][it] = 0.f;
+            }
+        }
+        for (int i = 0; i < nr; ++i) {
+            const int c = sub + 16 * i;
+            if (c < units) {                                       // (a chunk past the row does not exist: nothing is read)
+                const f32x4 q0 = qs[2 * c], q1 = qs[2 * c + 1];
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int it = 0; it < 2; ++it) acc[u][it] = rr_bf16w_chunk(p[u][it][c], q0, q1, acc[u][it]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const float a = rr_row16_sum(acc[u][it]);
+                const int64_t row = (int64_t)m8[u] * 8 + 4 * it + grp;
+                if (sub == 0 && s0 + u < n) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = (row < n_rows && a == a) ? a : -INFINITY;
+            }
+    }
+}
+
 // ------------------------------------------------------------------ host side
 static size_t rr_fltw_lds_bytes(const rr_index* ix, int nq2) { return (size_t)32 * nq2 * ix->dim_pad * 2; }
 
@@ -339,7 +398,8 @@ static int rr_fltw_scan(rr_index* ix, const float* src, int64_t src_stride, int 
     rr_scan_note(ix, 5, 16, nq, 1, 2);
     (void)hipEventRecord(ix->ev0, st);
     hipLaunchKernelGGL((rr_scan_fltw<NQ2>), dim3((G->n_waves + 7) / 8), dim3(512), rr_fltw_lds_bytes(ix, NQ2), st,
-                       reinterpret_cast<const u32x4*>(ix->d_shadow), *G, ix->dim_pad / 32, reinterpret_cast<const u32x4*>(plane),
+                       reinterpret_cast<const u32x4*>(ix->dtype == RR_DTYPE_BF16 ? ix->d_matrix : (void*)ix->d_shadow), *G, ix->dim_pad / 32,
+                       reinterpret_cast<const u32x4*>(plane),
                        reinterpret_cast<uint32_t*>(ix->d_gmax), ix->d_smax, X.eps, nq);
     (void)hipEventRecord(ix->ev1, st);
     ix->timing_valid = true;
@@ -351,27 +411,34 @@ static int rr_fltw_scan(rr_index* ix, const float* src, int64_t src_stride, int 
 // the rr_rescore_chain_w launch of the tail (the kernel-test harness launches through it as well)
 static void rr_launch_rescore_chain_w(rr_index* ix, const float* d_q, int nq, hipStream_t st) {
     const rr_x3_scratch X = rr_x3_scratch_of(ix);
-    hipLaunchKernelGGL(rr_rescore_chain_w, dim3(16, nq), dim3(256), 0, st, reinterpret_cast<const f32x4*>(ix->d_matrix), ix->n_rows,
-                       ix->dim_pad / 64, d_q, X.mtiles, X.count, X.fb, X.sc);
+    if (ix->dtype == RR_DTYPE_BF16)
+        hipLaunchKernelGGL(rr_rescore_chain_wb, dim3(16, nq), dim3(256), 0, st, reinterpret_cast<const u32x4*>(ix->d_matrix), ix->n_rows,
+                           ix->dim_pad / 8, d_q, X.mtiles, X.count, X.fb, X.sc);
+    else
+        hipLaunchKernelGGL(rr_rescore_chain_w, dim3(16, nq), dim3(256), 0, st, reinterpret_cast<const f32x4*>(ix->d_matrix), ix->n_rows,
+                           ix->dim_pad / 64, d_q, X.mtiles, X.count, X.fb, X.sc);
 }
 
 // what the path asks of the index before anything is launched (rr_dense_chunk_fltw and the debug door)
 static int rr_fltw_ready(rr_index* ix, int pool, hipStream_t st, rr_flt_bounds* nb) {
     if ((ix->n_rows + 63) / 64 < 8 * (int64_t)pool) return RR_FLT_SMALL;      // (the small-index rule of rr_dense_chunk_flt)
+    const bool bf16 = ix->dtype == RR_DTYPE_BF16;     // bf16 rows are the plane: none is allocated, the plane switches do not apply
     static const bool no_shadow = getenv("RR_NO_SHADOW") != nullptr;
-    if (!ix->use_shadow || no_shadow) return RR_FLT_SMALL;                    // no plane: the VALU scans (this path has no fp32 stream)
+    if (!bf16 && (!ix->use_shadow || no_shadow)) return RR_FLT_SMALL;         // no plane: the VALU scans (this path has no fp32 stream)
     int rc = rr_flt_get_bounds(ix, st, nb);
     if (rc != RR_OK) return rc;
     if (!(nb->row_norm < 3.0e18f)) return RR_FLT_NO_BOUND;
-    rc = rr_flt_ensure_shadow(ix, st);
-    if (rc != RR_OK) return rc;
-    if (!ix->shadow_valid) return RR_FLT_SMALL;                               // no room for the plane
+    if (!bf16) {
+        rc = rr_flt_ensure_shadow(ix, st);
+        if (rc != RR_OK) return rc;
+        if (!ix->shadow_valid) return RR_FLT_SMALL;                           // no room for the plane
+    }
     return rr_fltw_ensure_buffers(ix);
 }
 
 int rr_dense_chunk_fltw(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores, hipStream_t st) {
-    RR_REQUIRE(ix->dtype == RR_DTYPE_F32 && ix->dim_pad != 384 && ix->dim_pad <= RR_FLTW_MAX_DIM && ix->dim_pad % 64 == 0,
-               "rr_dense_chunk_fltw: fp32 index of width 64 .. %d other than 384 expected", RR_FLTW_MAX_DIM);
+    RR_REQUIRE(ix->dim_pad != 384 && ix->dim_pad <= RR_FLTW_MAX_DIM && ix->dim_pad % 64 == 0,
+               "rr_dense_chunk_fltw: index of width 64 .. %d other than 384 expected", RR_FLTW_MAX_DIM);
     RR_REQUIRE(nq >= 1 && nq <= RR_FLTW_MAXQ, "rr_dense_chunk_fltw: %d queries outside 1..%d", nq, RR_FLTW_MAXQ);
     rr_flt_bounds nb;
     int rc = rr_fltw_ready(ix, pool, st, &nb);
@@ -397,8 +464,8 @@ int rr_dense_chunk_fltw(rr_index* ix, const float* d_q, int nq, int pool, int64_
 // rr_debug_flt_select.
 extern "C" int rr_debug_fltw_words(rr_index* ix, const float* d_queries, int32_t nq, int32_t pool, int64_t* geom, float* eps,
                                    uint32_t* words, int64_t words_cap, uint32_t* keys, int64_t keys_cap) {
-    RR_REQUIRE(ix && geom && ix->d_matrix && ix->dtype == RR_DTYPE_F32 && ix->dim_pad != 384 && ix->dim_pad <= RR_FLTW_MAX_DIM,
-               "rr_debug_fltw_words: fp32 index of width 64 .. %d other than 384 expected", RR_FLTW_MAX_DIM);
+    RR_REQUIRE(ix && geom && ix->d_matrix && ix->dim_pad != 384 && ix->dim_pad <= RR_FLTW_MAX_DIM,
+               "rr_debug_fltw_words: index of width 64 .. %d other than 384 expected", RR_FLTW_MAX_DIM);
     RR_REQUIRE(nq >= 1 && nq <= RR_FLTW_MAXQ, "rr_debug_fltw_words: %d queries outside 1..%d", nq, RR_FLTW_MAXQ);
     RR_REQUIRE(ix->maxima_q >= RR_FLT_MAXQ && ix->cur_slot == 0, "rr_debug_fltw_words: run a batched search of 9 queries or more first (allocates the scratch)");
     const bool launch = words != nullptr;
@@ -410,7 +477,7 @@ extern "C" int rr_debug_fltw_words(rr_index* ix, const float* d_queries, int32_t
     int rc = nq <= 32 ? rr_fltw_geom<1>(ix, &G) : rr_fltw_geom<2>(ix, &G);
     if (rc != RR_OK) return rc;
     if (launch) {
-        ix->use_shadow = 1;
+        if (ix->dtype != RR_DTYPE_BF16) ix->use_shadow = 1;
         rr_flt_bounds nb;
         rc = rr_fltw_ready(ix, pool, st, &nb);
         RR_REQUIRE(rc == RR_OK, "rr_debug_fltw_words: the wide filter path does not run on this matrix (code %d)", rc);
@@ -442,8 +509,8 @@ extern "C" int rr_debug_fltw_words(rr_index* ix, const float* d_queries, int32_t
 extern "C" int rr_debug_fltw_rescore(rr_index* ix, const float* d_queries, int32_t nq, const uint32_t* mtiles, int64_t cap,
                                      const int32_t* count, const int32_t* fb, float* sc) {
     RR_REQUIRE(ix && d_queries && mtiles && count && fb && sc, "rr_debug_fltw_rescore: NULL argument");
-    RR_REQUIRE(ix->d_matrix && ix->dtype == RR_DTYPE_F32 && ix->dim_pad != 384 && ix->dim_pad <= RR_FLTW_MAX_DIM,
-               "rr_debug_fltw_rescore: fp32 index of width 64 .. %d other than 384 expected", RR_FLTW_MAX_DIM);
+    RR_REQUIRE(ix->d_matrix && ix->dim_pad != 384 && ix->dim_pad <= RR_FLTW_MAX_DIM,
+               "rr_debug_fltw_rescore: index of width 64 .. %d other than 384 expected", RR_FLTW_MAX_DIM);
     RR_REQUIRE(nq >= 1 && nq <= RR_SEL_MAXQ && cap >= 1 && cap <= RR_X3_MCAP, "rr_debug_fltw_rescore: nq %d / cap %lld out of range", nq, (long long)cap);
     const int64_t n_mtiles = (ix->n_rows + 7) / 8;
     for (int q = 0; q < nq; ++q) {

@@ -21,6 +21,11 @@ class ProductIndex:
     ``matrix`` may be a numpy array (copied to the device), or ``None`` with
     ``device_ptr`` naming caller-owned device memory that is already padded to
     ``dim_padded`` columns (used by bench.py, which generates 10M rows on the GPU).
+
+    ``dtype="bf16"`` stores the rows rounded once to bf16 (2 bytes per element, no filter plane beside them) at any
+    ``dim`` from 1 to 1024; queries and accumulation stay fp32.  fp32 rows enter through ``from_rows`` /
+    ``store_rows_dev`` (normalised in fp32 if asked, then rounded); adopted memory (``device_ptr=``) is
+    ``n_rows x dim_padded`` bf16.
     """
 
     def __init__(self, matrix: Optional[np.ndarray] = None, *, n_rows: Optional[int] = None,
@@ -156,7 +161,8 @@ class ProductIndex:
     def last_scan_info(self):
         """(kernel family, variant, queries per launch, MFMA terms, stream element bytes) of the last batched scan launch
         (rr_index_last_scan_info; family 5 = filter scan, variant 9 = the 256-query query-stationary rr_scan_fltq, variant 16 =
-        rr_scan_fltw, the runtime-width scan of an fp32 index whose padded width is 64 .. 1024 and not 384)."""
+        rr_scan_fltw, the runtime-width scan of an index of either dtype whose padded width is 64 .. 1024 and not 384;
+        family 2 = the bf16 VALU scans, rr_scan_bf16 at width 384 and rr_scan_bf16_generic at the others)."""
         out = (C.c_int32 * 8)()
         _lib.check(_lib.load().rr_index_last_scan_info(self._h, out), "rr_index_last_scan_info")
         return tuple(out[:5])

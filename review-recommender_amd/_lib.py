@@ -193,6 +193,7 @@ DEBUG_PROTOTYPES = {
                                          c_vp, c_vp, c_vp, c_vp]),
     "rr_debug_x3_scan": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "rr_debug_x3_rescore": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "rr_debug_valu_scan": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "rr_debug_ce_ffn_stamps":(C.c_int, [P(C.c_uint64)]),
     "rr_debug_ce_h2_stamps": (C.c_int, [P(C.c_uint64)]),
     "rr_debug_ce_h2_gemm": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, P(C.c_int32)]),

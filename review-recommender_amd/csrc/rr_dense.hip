@@ -1372,18 +1372,36 @@ static rr_scan_geom rr_launch_scan(rr_index* ix, const float* d_q, hipStream_t s
     return G;
 }
 
-// The filter path's flagged queries (candidate lists overflowed: massive ties, a crowded cut), when a call has at most eight:
-// the single-query scan's per-row chain over the whole matrix + the stored-score selection, bit for bit what a batch of
-// one returns; their flags come down.  More than eight: all of them go on to the split-operand pass.  fp32 storage, dim 384.
-int rr_dense_listed_fallback(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores,
-                             int32_t* flags, hipStream_t st) {
-    if (ix->dtype != RR_DTYPE_F32 || ix->dim_pad != 384 || !ix->d_flag_list) return RR_OK;
+// one listed launch of the 384-wide fp32 scan into the index's score scratch (rr_dense_listed_fallback): the flagged queries of
+// the call's `nq`, when there are at most eight; the geometry the listed selection reads
+static rr_scan_geom rr_launch_scan_listed(rr_index* ix, const float* d_q, const int32_t* flags, int nq, hipStream_t st) {
     static int cap = 0;
     if (!cap) cap = rr_resident_grid(rr_scan_f32<6, 8, true>, ix->device);
     rr_scan_geom G = rr_make_geom(ix, cap);
     hipLaunchKernelGGL((rr_scan_f32<6, 8, true>), dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
                        reinterpret_cast<const f32x4*>(ix->d_matrix), G, d_q, ix->d_sims, ix->d_gmax, ix->d_smax,
                        (const int32_t*)flags, nq, ix->d_flag_list);
+    return G;
+}
+
+// ... of the runtime-width fp32 scan (rr_dense_listed_fallback_wide): the flagged queries ranked [skip, skip + 8)
+static rr_scan_geom rr_launch_scan_generic_listed(rr_index* ix, const float* d_q, const int32_t* flags, int nq, int skip, hipStream_t st) {
+    static int cap = 0;
+    if (!cap) cap = rr_resident_grid(rr_scan_f32_generic_listed<RR_SEL_LISTED>, ix->device);
+    rr_scan_geom G = rr_make_geom(ix, cap);
+    hipLaunchKernelGGL((rr_scan_f32_generic_listed<RR_SEL_LISTED>), dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
+                       reinterpret_cast<const f32x4*>(ix->d_matrix), G, ix->dim_pad / 64, d_q, ix->d_sims, ix->d_gmax, ix->d_smax,
+                       flags, nq, skip, ix->d_flag_list);
+    return G;
+}
+
+// The filter path's flagged queries (candidate lists overflowed: massive ties, a crowded cut), when a call has at most eight:
+// the single-query scan's per-row chain over the whole matrix + the stored-score selection, bit for bit what a batch of
+// one returns; their flags come down.  More than eight: all of them go on to the split-operand pass.  fp32 storage, dim 384.
+int rr_dense_listed_fallback(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores,
+                             int32_t* flags, hipStream_t st) {
+    if (ix->dtype != RR_DTYPE_F32 || ix->dim_pad != 384 || !ix->d_flag_list) return RR_OK;
+    const rr_scan_geom G = rr_launch_scan_listed(ix, d_q, flags, nq, st);
     rr_launch_select_listed(ix, G, pool, d_rows, d_scores, flags, st);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
@@ -1404,13 +1422,8 @@ int rr_dense_listed_fallback_wide(rr_index* ix, const float* d_q, int nq, int po
         RR_HIP_TRY(hipGetLastError());
         return RR_OK;
     }
-    static int cap = 0;
-    if (!cap) cap = rr_resident_grid(rr_scan_f32_generic_listed<RR_SEL_LISTED>, ix->device);
-    rr_scan_geom G = rr_make_geom(ix, cap);
     for (int p = 0; p < (nq + RR_SEL_LISTED - 1) / RR_SEL_LISTED; ++p) {
-        hipLaunchKernelGGL((rr_scan_f32_generic_listed<RR_SEL_LISTED>), dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
-                           reinterpret_cast<const f32x4*>(ix->d_matrix), G, ix->dim_pad / 64, d_q, ix->d_sims, ix->d_gmax, ix->d_smax,
-                           flags, nq, RR_SEL_LISTED * p, ix->d_flag_list);
+        const rr_scan_geom G = rr_launch_scan_generic_listed(ix, d_q, flags, nq, RR_SEL_LISTED * p, st);
         rr_launch_select_listed(ix, G, pool, d_rows, d_scores, ix->d_flag_done, st);
     }
     RR_HIP_TRY(hipGetLastError());
@@ -2027,6 +2040,81 @@ extern "C" int rr_debug_select_mtiles(rr_index* ix, int64_t n_rows, int64_t tile
     RR_HIP_TRY(hipMemcpy(tau, X.tau, sizeof(uint32_t) * nq, hipMemcpyDeviceToHost));
     RR_HIP_TRY(hipMemcpy(fb, X.fb, sizeof(int32_t) * nq, hipMemcpyDeviceToHost));
     RR_HIP_TRY(hipMemcpy(trace, ix->d_sel_trace, sizeof(int32_t) * nq * 16, hipMemcpyDeviceToHost));
+    return RR_OK;
+}
+
+// ---- one VALU scan launch by itself (rr_debug.h; tests/test_gpu_valu_scan_kernels.py)
+extern "C" int rr_debug_valu_scan(rr_index* ix, const float* d_queries, int32_t nq, int32_t form, const int32_t* flags, int32_t skip,
+                                  int64_t* geom, uint32_t* sims, int64_t sims_cap, uint32_t* gmax, int64_t gmax_cap, uint32_t* smax,
+                                  int64_t smax_cap, int32_t* list_out) {
+    const char* who = "rr_debug_valu_scan";
+    RR_REQUIRE(ix && d_queries && geom && sims && gmax && smax, "%s: NULL argument", who);
+    RR_REQUIRE(form == 0 || form == 1, "%s: form %d (0 plain, 1 listed)", who, form);
+    RR_REQUIRE((form == 1) == (flags != nullptr) && (form == 0 || list_out != nullptr), "%s: form %d %s", who, form,
+               form == 1 ? "wants flags and list_out" : "takes no flags");
+    RR_REQUIRE(ix->d_matrix && ix->d_flag_list && ix->d_q, "%s: the index has no matrix", who);
+    const bool bf16 = ix->dtype == RR_DTYPE_BF16, wide = ix->dim_pad != 384;
+    RR_REQUIRE(ix->dim_pad >= 64 && ix->dim_pad % 64 == 0 && (!bf16 || ix->dim_pad <= RR_FLTW_MAX_DIM), "%s: no VALU scan takes width %d of this dtype",
+               who, ix->dim_pad);
+    if (form == 0) {
+        RR_REQUIRE(nq >= 1 && nq <= 8, "%s: nq %d outside 1..8", who, nq);
+        RR_REQUIRE(skip == 0, "%s: skip %d in the plain form", who, skip);
+    } else {
+        RR_REQUIRE(nq >= 1 && nq <= RR_SEL_MAXQ, "%s: nq %d outside 1..%d", who, nq, RR_SEL_MAXQ);
+        RR_REQUIRE(wide || !bf16, "%s: a bf16 index of width 384 has no listed scan", who);
+        RR_REQUIRE(skip >= 0 && skip <= RR_SEL_MAXQ && (wide || skip == 0), "%s: skip %d (0 at width 384, else 0..%d)", who, skip, RR_SEL_MAXQ);
+    }
+    RR_REQUIRE(sims_cap >= 0 && gmax_cap >= 0 && smax_cap >= 0, "%s: negative cap", who);
+    const int NB = form == 1 ? RR_SEL_LISTED : nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8;
+    const void* q_vis = nullptr;
+    int rc = rr_device_visible(d_queries, &q_vis, "rr_debug_valu_scan (queries)");
+    if (rc != RR_OK) return rc;
+    d_queries = static_cast<const float*>(q_vis);
+    std::lock_guard<std::mutex> lock(ix->mu);
+    RR_HIP_TRY(hipSetDevice(ix->device));
+    RR_REQUIRE(ix->cur_slot == 0, "%s: scan slot %d is active", who, ix->cur_slot);
+    hipStream_t st = nullptr;
+    rr_flt_drop_pending(ix);
+    rc = rr_ensure_scratch(ix, 8);
+    if (rc != RR_OK) return rc;
+    const int64_t n_tiles = rr_round_up(ix->n_rows, 64) / 64;
+    const int64_t sims_words = (int64_t)ix->scratch_q * n_tiles * 64;
+    const int64_t gmax_words = (int64_t)ix->maxima_q * n_tiles * 4 + (int64_t)RR_MAX_SCAN_WAVES * RR_FLT_MAXQ;   // (rr_ensure_maxima)
+    const int64_t smax_words = (int64_t)2 * ix->maxima_q * RR_MAX_SCAN_WAVES;
+    RR_REQUIRE(sims_cap <= sims_words && gmax_cap <= gmax_words && smax_cap <= smax_words,
+               "%s: caps %lld / %lld / %lld beyond the buffers (%lld / %lld / %lld words)", who, (long long)sims_cap, (long long)gmax_cap,
+               (long long)smax_cap, (long long)sims_words, (long long)gmax_words, (long long)smax_words);
+    RR_REQUIRE(ix->scratch_q >= NB && ix->maxima_q >= NB, "%s: the scratch holds %d / %d query slots, the launch writes %d", who, ix->scratch_q,
+               ix->maxima_q, NB);
+    const rr_x3_scratch X = rr_x3_scratch_of(ix);
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_sims, (int)RR_DEBUG_SC_SENTINEL, (size_t)sims_words, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_gmax, (int)RR_DEBUG_SC_SENTINEL, (size_t)gmax_words, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_smax, (int)RR_DEBUG_KEY_SENTINEL, (size_t)smax_words, st));
+    RR_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->d_flag_list, (int)RR_DEBUG_KEY_SENTINEL, 16, st));
+    if (flags) RR_HIP_TRY(hipMemcpyAsync(X.fb, flags, sizeof(int32_t) * nq, hipMemcpyHostToDevice, st));
+    const int slots = (int)rr_round_up(nq, RR_MFMA_MAXQ);             // (rr_dense_topk_slot_dev: kernels read whole query tiles)
+    const int64_t total = (int64_t)slots * ix->dim_pad;
+    hipLaunchKernelGGL(rr_pad_queries, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_queries, ix->d_q, nq, ix->dim, ix->dim_pad, slots);
+    ix->flt_prep_fresh = false;
+    rr_scan_geom G;
+    if (form == 1) {
+        G = bf16 ? rr_launch_scan_bf16w_listed(ix, ix->d_q, X.fb, nq, skip, st)
+            : wide ? rr_launch_scan_generic_listed(ix, ix->d_q, X.fb, nq, skip, st) : rr_launch_scan_listed(ix, ix->d_q, X.fb, nq, st);
+    } else if (bf16) {
+        G = wide ? rr_debug_launch_scan_bf16w(ix, ix->d_q, NB, st) : rr_debug_launch_scan_bf16(ix, ix->d_q, NB, st);
+    } else {
+        G = NB == 1 ? rr_launch_scan<1>(ix, ix->d_q, st) : NB == 2 ? rr_launch_scan<2>(ix, ix->d_q, st)
+          : NB == 4 ? rr_launch_scan<4>(ix, ix->d_q, st) : rr_launch_scan<8>(ix, ix->d_q, st);
+    }
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipStreamSynchronize(st));
+    const int64_t g[10] = {G.n_rows, G.n_tiles, G.n_pad, G.tiles_per_wave, G.n_waves, NB, (bf16 ? 2 : 1) + (wide ? 10 : 0) + (form == 1 ? 100 : 0),
+                           sims_words, gmax_words, smax_words};
+    memcpy(geom, g, sizeof(g));
+    RR_HIP_TRY(hipMemcpy(sims, ix->d_sims, sizeof(uint32_t) * sims_cap, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(gmax, ix->d_gmax, sizeof(uint32_t) * gmax_cap, hipMemcpyDeviceToHost));
+    RR_HIP_TRY(hipMemcpy(smax, ix->d_smax, sizeof(uint32_t) * smax_cap, hipMemcpyDeviceToHost));
+    if (list_out) RR_HIP_TRY(hipMemcpy(list_out, ix->d_flag_list, sizeof(int32_t) * (1 + RR_SEL_LISTED), hipMemcpyDeviceToHost));
     return RR_OK;
 }
 #endif

@@ -166,6 +166,14 @@ static rr_scan_geom rr_launch_scan_bf16(rr_index* ix, const float* d_q, hipStrea
     return G;
 }
 
+#ifdef RR_DEBUG_HARNESS
+// rr_debug_valu_scan (rr_dense.hip): the launch helper above for NB = 1, 2, 4 or 8
+rr_scan_geom rr_debug_launch_scan_bf16(rr_index* ix, const float* d_q, int nb, hipStream_t st) {
+    return nb == 1 ? rr_launch_scan_bf16<1>(ix, d_q, st) : nb == 2 ? rr_launch_scan_bf16<2>(ix, d_q, st)
+         : nb == 4 ? rr_launch_scan_bf16<4>(ix, d_q, st) : rr_launch_scan_bf16<8>(ix, d_q, st);
+}
+#endif
+
 int rr_dense_chunk_bf16(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                         float* d_scores, hipStream_t st) {
     const int slot = rr_scan_events_begin(ix, st);

@@ -22,6 +22,7 @@
 // stands once, behind the unrolled body.  The queries sit in LDS (fp32, memory order); the four rows of a wave read the same
 // 16 addresses per ds_read_b128 (broadcast).  Registers: 32 ring + 8 query + 3 NB sums + addressing: no spills at NB = 8.
 #define RR_BF16W_RING 8
+static_assert(16 % RR_BF16W_RING == 0, "16 nr stages per tile must be a multiple of the ring: rr_finish_tile stands once, behind the unrolled body");
 template <int NB>
 __device__ __forceinline__ void rr_bf16w_scan_rows(const u32x4* __restrict__ mat, const rr_scan_geom& G, int units,
                                                    const f32x4 (*qs)[RR_FLTW_MAX_DIM / 4], float* __restrict__ sims,
@@ -149,6 +150,14 @@ static rr_scan_geom rr_launch_scan_bf16w(rr_index* ix, const float* d_q, hipStre
                        reinterpret_cast<const u32x4*>(ix->d_matrix), G, ix->dim_pad / 8, d_q, ix->d_sims, ix->d_gmax, ix->d_smax);
     return G;
 }
+
+#ifdef RR_DEBUG_HARNESS
+// rr_debug_valu_scan (rr_dense.hip): the launch helper above for NB = 1, 2, 4 or 8
+rr_scan_geom rr_debug_launch_scan_bf16w(rr_index* ix, const float* d_q, int nb, hipStream_t st) {
+    return nb == 1 ? rr_launch_scan_bf16w<1>(ix, d_q, st) : nb == 2 ? rr_launch_scan_bf16w<2>(ix, d_q, st)
+         : nb == 4 ? rr_launch_scan_bf16w<4>(ix, d_q, st) : rr_launch_scan_bf16w<8>(ix, d_q, st);
+}
+#endif
 
 int rr_dense_chunk_bf16w(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores, hipStream_t st) {
     RR_REQUIRE(ix->dtype == RR_DTYPE_BF16 && ix->dim_pad <= RR_FLTW_MAX_DIM && ix->dim_pad % 64 == 0 && nq >= 1 && nq <= 8,

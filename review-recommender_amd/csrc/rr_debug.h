@@ -14,9 +14,6 @@ void rr_debug_x3_scan16(rr_index* ix, const float* d_q, int mode, rr_scan_geom* 
 void rr_debug_x3_rescore16(rr_index* ix, const float* d_q, int nq, hipStream_t st);
 // rr_dense_flt.hip: the one-set launch rr_debug_fltw_words (rr_dense_fltw.hip) leaves for rr_debug_flt_select
 void rr_debug_flt_note_state(rr_index* ix, const rr_scan_geom& G, int nq);
-// rr_dense_bf16.hip / rr_dense_bf16w.hip: rr_launch_scan_bf16<nb> / rr_launch_scan_bf16w<nb> for rr_debug_valu_scan (nb = 1, 2, 4, 8)
-rr_scan_geom rr_debug_launch_scan_bf16(rr_index* ix, const float* d_q, int nb, hipStream_t st);
-rr_scan_geom rr_debug_launch_scan_bf16w(rr_index* ix, const float* d_q, int nb, hipStream_t st);
 extern "C" {
 // tests/test_gpu_fltw_kernels.py: rr_debug_flt_words / rr_debug_rescore_chain at a runtime width (fp32 storage, dim_pad 64 .. 1024
 // other than 384): ONE rr_scan_fltw launch for one set of up to 64 queries -- geometry, eps, every word and key -- which
@@ -100,12 +97,12 @@ int rr_debug_x3_rescore(rr_index* ix, const float* d_queries, int32_t nq, const 
 // tests/test_gpu_valu_scan_kernels.py: ONE VALU scan launch -- the per-row fmaf chain every other dense path is held against --
 // on the index's own matrix, and its raw levels on the host.  The routing is the product's: fp32 rows at 384 rr_scan_f32<6, NB>,
 // at another width rr_scan_f32_generic<NB>; bf16 rows rr_scan_bf16<NB> / rr_scan_bf16_generic<NB>.  form 0 (plain): nq = 1..8
-// queries, NB = 1 / 2 / 4 / 8 as rr_dense_chunk, rr_dense_chunk_bf16 and rr_dense_chunk_bf16w choose it, flags NULL, skip 0.
+// queries, NB = 1 / 2 / 4 / 8 as rr_dense_chunk chooses it (rr_valu_nb), flags NULL, skip 0.
 // form 1 (listed): nq = the call's queries (1..RR_SEL_MAXQ), flags[nq] (host), the launch of rr_dense_listed_fallback (fp32 384,
 // skip 0) or of one pair of rr_dense_listed_fallback_wide (another width, either dtype: the flagged queries ranked [skip,
 // skip + 8)); a bf16 index of width 384 has no listed form.  d_queries: device, nq x dim, unpadded, as rr_dense_topk_dev takes
 // them: they go through rr_pad_queries into ix->d_q (slots past nq zero); the scratch comes from rr_ensure_scratch(ix, 8); the
-// launch goes through rr_launch_scan<NB>, rr_launch_scan_bf16<NB>, rr_launch_scan_bf16w<NB>, rr_launch_scan_listed,
+// launch goes through rr_launch_scan_f32, rr_launch_scan_bf16, rr_launch_scan_bf16w (the product's own), rr_launch_scan_listed,
 // rr_launch_scan_generic_listed or rr_launch_scan_bf16w_listed.  Before the launch the score scratch and the tile maxima are
 // filled whole with RR_DEBUG_SC_SENTINEL, the group keys and the 16 words of the flagged list with RR_DEBUG_KEY_SENTINEL;
 // afterwards the first sims_cap / gmax_cap / smax_cap words come back as they are (no more than the buffers hold: geom[7..9])

@@ -101,12 +101,16 @@ void rr_launch_group_kth(rr_index* ix, const rr_scan_geom& G, int nq_a, int nq_b
                          int64_t smax_set_stride, hipStream_t st);
 // Waves a kernel can keep resident on the device (occupancy x CUs x waves per workgroup).
 int rr_resident_waves(const void* kernel, int threads, int device);
-// bf16-storage VALU scan (rr_dense_bf16.hip): up to 8 queries.
-int rr_dense_chunk_bf16(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
-                        float* d_scores, hipStream_t st);
-// ... at a runtime width (rr_dense_bf16w.hip: dim_pad 64 .. RR_FLTW_MAX_DIM other than 384): up to 8 queries
-int rr_dense_chunk_bf16w(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
-                         float* d_scores, hipStream_t st);
+// Query slots NB = 1, 2, 4 or 8 of the VALU scan launch that serves nq = 1 .. 8 queries (slots past nq hold zeros).
+static inline int rr_valu_nb(int nq) { return nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8; }
+// ... and that NB's place in a launcher's table of its four kernel instances
+static inline int rr_nb_slot(int nb) { return nb == 1 ? 0 : nb == 2 ? 1 : nb == 4 ? 2 : 3; }
+// One VALU scan launch of nb = 1, 2, 4 or 8 query slots into the index's score scratch; *out: the geometry its selection reads.
+// fp32 rows of any width (rr_dense.hip), bf16 rows 384 wide (rr_dense_bf16.hip), bf16 rows at a runtime width (rr_dense_bf16w.hip:
+// dim_pad 64 .. RR_FLTW_MAX_DIM other than 384).  rr_dense_chunk (rr_dense.hip) picks one by (dtype, width).
+int rr_launch_scan_f32(rr_index* ix, const float* d_q, int nb, hipStream_t st, rr_scan_geom* out);
+int rr_launch_scan_bf16(rr_index* ix, const float* d_q, int nb, hipStream_t st, rr_scan_geom* out);
+int rr_launch_scan_bf16w(rr_index* ix, const float* d_q, int nb, hipStream_t st, rr_scan_geom* out);
 // l2_normalize of rows [first, first + n) of an fp32 index, in place
 int rr_l2norm_rows_f32(rr_index* ix, int64_t first_row, int64_t n, float eps, hipStream_t st);
 // ... of n padded rows anywhere on the device (a staging copy): the same kernel
@@ -175,8 +179,25 @@ rr_scan_geom rr_launch_scan_bf16w_listed(rr_index* ix, const float* d_q, const i
 #ifdef __HIPCC__
 // ------------------------------------------------------------------ device pieces the VALU scan files share
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-// bf16 rows at a runtime width (rr_dense_bf16w.hip, rr_dense_fltw.hip): eight products of one 16-byte chunk onto acc, in memory order; q0 / q1: the eight query floats beside it
-__device__ __forceinline__ float rr_bf16w_chunk(const u32x4 x, const f32x4 q0, const f32x4 q1, float acc) {
+// THE PER-ROW CHAIN.  A query's answer is the exact top-pool of these scores, whether the query is alone, in a batch, rescored
+// behind a filter scan or on a shard; every kernel below computes them through the two steps here, so they agree by construction.
+//   A row is dim_pad / 4 chunks of 16 bytes in fp32 storage (four floats), dim_pad / 8 in bf16 storage (eight bf16).  Lane j of
+//   the 16 lanes of a row takes chunks j, j + 16, j + 32, .. in ascending order; a chunk past the row's end does not exist and
+//   adds nothing (bf16 widths 64, 192, 320, ..: the last round is half full).  The lane's ONE accumulator starts at 0 and takes
+//   each chunk's products in memory order, one fmaf each (no contraction, no reassociation); rr_row16_sum adds the 16 lanes.
+//   A NaN score and a row past the end become -inf (rr_rank_last).
+// Callers.  rr_f32_chunk: rr_scan_f32 (rr_dot_rows), rr_scan_f32_generic and its listed form (rr_f32w_scan_rows), rr_rescore_chain
+// (both fp32 branches, rr_dense_flt.hip), rr_rescore_chain_w (rr_dense_fltw.hip).  rr_bf16_chunk: rr_scan_bf16, rr_scan_bf16_generic
+// and its listed form (rr_bf16w_scan_rows), rr_rescore_chain (plane pass = the chain of a bf16 index), rr_rescore_chain_wb.
+__device__ __forceinline__ float rr_f32_chunk(const f32x4 x, const f32x4 q, float acc) {
+    acc = __builtin_fmaf(x.x, q.x, acc);
+    acc = __builtin_fmaf(x.y, q.y, acc);
+    acc = __builtin_fmaf(x.z, q.z, acc);
+    acc = __builtin_fmaf(x.w, q.w, acc);
+    return acc;
+}
+// q0 / q1: the eight query floats beside the chunk's eight bf16
+__device__ __forceinline__ float rr_bf16_chunk(const u32x4 x, const f32x4 q0, const f32x4 q1, float acc) {
     acc = __builtin_fmaf(__uint_as_float(x.x << 16), q0.x, acc);
     acc = __builtin_fmaf(__uint_as_float(x.x & 0xFFFF0000u), q0.y, acc);
     acc = __builtin_fmaf(__uint_as_float(x.y << 16), q0.z, acc);
@@ -187,6 +208,8 @@ __device__ __forceinline__ float rr_bf16w_chunk(const u32x4 x, const f32x4 q0, c
     acc = __builtin_fmaf(__uint_as_float(x.w & 0xFFFF0000u), q1.w, acc);
     return acc;
 }
+// NaN scores and pad rows rank last
+__device__ __forceinline__ float rr_rank_last(float v, bool valid) { return (valid && v == v) ? v : -INFINITY; }
 
 // End of a tile: lane (sub, grp) holds row row0 + 4*sub + grp for every query.
 template <int NB>
@@ -201,7 +224,7 @@ __device__ __forceinline__ void rr_finish_tile(const rr_scan_geom& G, int64_t ti
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         float v = mine[b];
-        v = (valid && v == v) ? v : -INFINITY;  // NaN scores and pad rows rank last
+        v = rr_rank_last(v, valid);
         sims[(int64_t)b * G.n_pad + my_row] = v;
         const float m = rr_wave_max(v);
         gm[b] = fmaxf(gm[b], m);
@@ -211,6 +234,18 @@ __device__ __forceinline__ void rr_finish_tile(const rr_scan_geom& G, int64_t ti
                 smax[(int64_t)b * G.n_waves + wave] = rr_f2key(gm[b]);
         }
         if (group_end) gm[b] = -INFINITY;
+    }
+}
+
+// A listed scan tells the selection behind it which queries it served: list_out[0] = how many (also when that is 0: the
+// selection reads it), list_out[1 ..] = their numbers in the call.  One thread of the launch writes it.  (The runtime-width
+// listed scans; rr_scan_f32<6, 8, true> writes the same block in place, where it keeps that kernel's instructions as they are.)
+template <int NB>
+__device__ __forceinline__ void rr_publish_list(int32_t* __restrict__ list_out, int n, const int (&list)[NB]) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        list_out[0] = n;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) list_out[1 + b] = list[b];
     }
 }
 

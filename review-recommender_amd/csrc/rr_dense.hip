@@ -13,10 +13,9 @@
 //
 // rr_scan_f32: HBM-bound streaming kernel.  A 16-lane DPP row owns one matrix row:
 // lane j reads float4 j, j+16, ... of the row (NF = dim_pad/64 loads, each wave
-// instruction covers four rows x 256 contiguous bytes) and runs one fp32 fmaf
-// chain over its 4*NF elements; the 16 partials are added by rr_row16_sum.
-// Every row therefore has the same summation order wherever it sits, so a
-// score does not depend on sharding, batch size or launch geometry.
+// instruction covers four rows x 256 contiguous bytes) and runs the per-row chain
+// of rr_dense.h over them.  Every row therefore has the same summation order
+// wherever it sits, so a score does not depend on sharding, batch size or launch geometry.
 // A wave owns a contiguous run of `tiles_per_wave` 64-row tiles; it walks a tile in 16
 // steps of 4 rows, double-buffered in registers (2 x NF loads of 16 B per lane in
 // flight, prefetching across the tile seam), keeps row (4*it+grp) in lane
@@ -64,10 +63,7 @@ __device__ __forceinline__ void rr_dot_rows(const f32x4 (&x)[NF], const f32x4 (&
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
             const f32x4 q = FROM_LDS ? qs[b][16 * i + sub] : qreg[i];
-            acc = __builtin_fmaf(x[i].x, q.x, acc);
-            acc = __builtin_fmaf(x[i].y, q.y, acc);
-            acc = __builtin_fmaf(x[i].z, q.z, acc);
-            acc = __builtin_fmaf(x[i].w, q.w, acc);
+            acc = rr_f32_chunk(x[i], q, acc);
         }
         acc = rr_row16_sum(acc);
         mine[b] = (sub == it) ? acc : mine[b];
@@ -118,7 +114,7 @@ __global__ __launch_bounds__(RR_SCAN_THREADS, (NB <= 1 ? 4 : 2)) void rr_scan_f3
     if (LISTED) {
         int list[NB];
         const int n = rr_flagged_list<NB>(flags, nq_total, tid & 63, list);
-        if (blockIdx.x == 0 && tid == 0) {
+        if (blockIdx.x == 0 && tid == 0) {            // (rr_publish_list, written out: through the helper this kernel schedules otherwise)
             list_out[0] = n;                          // (also when it is 0: the selection behind this launch reads it)
 #pragma unroll
             for (int b = 0; b < NB; ++b) list_out[1 + b] = list[b];
@@ -172,11 +168,12 @@ __global__ __launch_bounds__(RR_SCAN_THREADS, (NB <= 1 ? 4 : 2)) void rr_scan_f3
     }
 }
 
-// Generic-dimension variant (runtime NF); same per-row summation order.
-template <int NB>
-__global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_f32_generic(
-    const f32x4* __restrict__ mat, rr_scan_geom G, int nf, const float* __restrict__ queries,
-    float* __restrict__ sims, float* __restrict__ gmax, uint32_t* __restrict__ smax) {
+// Runtime-width variant (nf = dim_pad / 64 float4 per lane and row); the per-row chain of rr_dense.h.  The NB queries are rows
+// 0 .. NB - 1 of `queries`, or (LISTED) its rows list[0 .. NB - 1].
+template <int NB, bool LISTED>
+__device__ __forceinline__ void rr_f32w_scan_rows(const f32x4* __restrict__ mat, const rr_scan_geom& G, int nf,
+                                                  const float* __restrict__ queries, const int (&list)[NB],
+                                                  float* __restrict__ sims, float* __restrict__ gmax, uint32_t* __restrict__ smax) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int sub = lane & 15;
@@ -204,13 +201,8 @@ __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_f32_generic(
             for (int i = 0; i < nf; ++i) {
                 const f32x4 x = p[16 * i];
 #pragma unroll
-                for (int b = 0; b < NB; ++b) {
-                    const f32x4 q = q4[(int64_t)b * nf * 16 + 16 * i + sub];
-                    acc[b] = __builtin_fmaf(x.x, q.x, acc[b]);
-                    acc[b] = __builtin_fmaf(x.y, q.y, acc[b]);
-                    acc[b] = __builtin_fmaf(x.z, q.z, acc[b]);
-                    acc[b] = __builtin_fmaf(x.w, q.w, acc[b]);
-                }
+                for (int b = 0; b < NB; ++b)
+                    acc[b] = rr_f32_chunk(x, q4[(int64_t)(LISTED ? list[b] : b) * nf * 16 + 16 * i + sub], acc[b]);
             }
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
@@ -222,65 +214,28 @@ __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_f32_generic(
     }
 }
 
-// The LISTED form of rr_scan_f32_generic: the NB queries are the flagged ones ranked [skip, skip + NB) of a wide filter launch
-// (rr_dense_fltw.hip), read in place from the launch's padded queries.  The per-row chain is the one above, so a flagged
-// query's answer is bit for bit the single-query answer.  An empty slice: every workgroup returns at once.
+// NB = 1, 2, 4, 8 queries per read of the matrix; queries: NB x dim_pad fp32, padded
+template <int NB>
+__global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_f32_generic(
+    const f32x4* __restrict__ mat, rr_scan_geom G, int nf, const float* __restrict__ queries,
+    float* __restrict__ sims, float* __restrict__ gmax, uint32_t* __restrict__ smax) {
+    const int list[NB] = {};
+    rr_f32w_scan_rows<NB, false>(mat, G, nf, queries, list, sims, gmax, smax);
+}
+
+// The LISTED form: the NB queries are the flagged ones ranked [skip, skip + NB) of a wide filter launch (rr_dense_fltw.hip), read
+// in place from the launch's padded queries.  The chain is the one above, so a flagged query's answer is bit for bit the
+// single-query answer.  An empty slice: every workgroup returns at once.
 template <int NB>
 __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_f32_generic_listed(
     const f32x4* __restrict__ mat, rr_scan_geom G, int nf, const float* __restrict__ queries,
     float* __restrict__ sims, float* __restrict__ gmax, uint32_t* __restrict__ smax,
     const int32_t* __restrict__ flags, int nq_total, int skip, int32_t* __restrict__ list_out) {
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
     int list[NB];
-    const int n = rr_flagged_slice<NB>(flags, nq_total, lane, skip, list);
-    if (blockIdx.x == 0 && tid == 0) {
-        list_out[0] = n;                              // (also when it is 0: the selection behind this launch reads it)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) list_out[1 + b] = list[b];
-    }
+    const int n = rr_flagged_slice<NB>(flags, nq_total, threadIdx.x & 63, skip, list);
+    rr_publish_list<NB>(list_out, n, list);
     if (n == 0) return;
-    const int sub = lane & 15;
-    const int grp = lane >> 4;
-    const int64_t wave = (int64_t)blockIdx.x * (RR_SCAN_THREADS / 64) + (tid >> 6);
-    if (wave >= G.n_waves) return;
-    const int64_t t0 = wave * G.tiles_per_wave;
-    const int64_t t1 = t0 + G.tiles_per_wave < G.n_tiles ? t0 + G.tiles_per_wave : G.n_tiles;
-    const f32x4* q4 = reinterpret_cast<const f32x4*>(queries);
-    float gm[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) gm[b] = -INFINITY;
-    for (int64_t tile = t0; tile < t1; ++tile) {
-        const int64_t row0 = tile * 64;
-        float mine[NB];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) mine[b] = 0.f;
-        for (int it = 0; it < 16; ++it) {
-            int64_t row = row0 + 4 * it + grp;
-            row = row < G.n_rows ? row : G.n_rows - 1;
-            const f32x4* p = mat + row * (int64_t)(nf * 16) + sub;
-            float acc[NB];
-#pragma unroll
-            for (int b = 0; b < NB; ++b) acc[b] = 0.f;
-            for (int i = 0; i < nf; ++i) {
-                const f32x4 x = p[16 * i];
-#pragma unroll
-                for (int b = 0; b < NB; ++b) {
-                    const f32x4 q = q4[(int64_t)list[b] * nf * 16 + 16 * i + sub];
-                    acc[b] = __builtin_fmaf(x.x, q.x, acc[b]);
-                    acc[b] = __builtin_fmaf(x.y, q.y, acc[b]);
-                    acc[b] = __builtin_fmaf(x.z, q.z, acc[b]);
-                    acc[b] = __builtin_fmaf(x.w, q.w, acc[b]);
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                const float sacc = rr_row16_sum(acc[b]);
-                mine[b] = (sub == it) ? sacc : mine[b];
-            }
-        }
-        rr_finish_tile<NB>(G, tile, wave, t0, t1, lane, sub, grp, mine, gm, sims, gmax, smax);
-    }
+    rr_f32w_scan_rows<NB, true>(mat, G, nf, queries, list, sims, gmax, smax);
 }
 
 // ------------------------------------------------------------------ select
@@ -1281,20 +1236,6 @@ int rr_slot_activate(rr_index* ix, int slot) {
     return RR_OK;
 }
 
-// Resident workgroups for a kernel: CUs x blocks per CU the register budget admits.
-template <typename K>
-static int rr_resident_grid(K kernel, int device) {
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, RR_SCAN_THREADS, 0) != hipSuccess ||
-        per_cu < 1)
-        per_cu = 2;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1)
-        cus = 256;
-    int grid = per_cu * cus;
-    if (grid * (RR_SCAN_THREADS / 64) > RR_MAX_SCAN_WAVES) grid = RR_MAX_SCAN_WAVES / (RR_SCAN_THREADS / 64);
-    return grid;
-}
-
 // Splits the tiles into equal contiguous runs, one per wave of (at most) a resident grid.
 rr_scan_geom rr_make_geom(const rr_index* ix, int resident_blocks) {
     rr_scan_geom G;
@@ -1350,34 +1291,35 @@ int rr_resident_waves(const void* kernel, int threads, int device) {
     return waves > RR_MAX_SCAN_WAVES ? RR_MAX_SCAN_WAVES : waves;
 }
 
-template <int NB>
-static rr_scan_geom rr_launch_scan(rr_index* ix, const float* d_q, hipStream_t st) {
+int rr_launch_scan_f32(rr_index* ix, const float* d_q, int nb, hipStream_t st, rr_scan_geom* out) {
     const f32x4* mat = reinterpret_cast<const f32x4*>(ix->d_matrix);
-    const int nf = ix->dim_pad / 64;
-    static int cap6 = 0, capg = 0;   // per template instance
+    const int nf = ix->dim_pad / 64, k = rr_nb_slot(nb);
+    static int waves6[4], wavesg[4];   // per kernel instance
     rr_scan_geom G;
     if (nf == 6) {
-        if (!cap6) cap6 = rr_resident_grid(rr_scan_f32<6, NB>, ix->device);
-        G = rr_make_geom(ix, cap6);
-        const int grid = (G.n_waves + 3) / 4;
-        hipLaunchKernelGGL((rr_scan_f32<6, NB>), dim3(grid), dim3(RR_SCAN_THREADS), 0, st, mat, G, d_q,
+        static constexpr decltype(&rr_scan_f32<6, 1>) kern[4] = {rr_scan_f32<6, 1>, rr_scan_f32<6, 2>, rr_scan_f32<6, 4>, rr_scan_f32<6, 8>};
+        if (!waves6[k]) waves6[k] = rr_resident_waves((const void*)kern[k], RR_SCAN_THREADS, ix->device);
+        G = rr_make_geom(ix, waves6[k] / 4);
+        hipLaunchKernelGGL(kern[k], dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st, mat, G, d_q,
                            ix->d_sims, ix->d_gmax, ix->d_smax, (const int32_t*)nullptr, 0, (int32_t*)nullptr);
     } else {
-        if (!capg) capg = rr_resident_grid(rr_scan_f32_generic<NB>, ix->device);
-        G = rr_make_geom(ix, capg);
-        const int grid = (G.n_waves + 3) / 4;
-        hipLaunchKernelGGL((rr_scan_f32_generic<NB>), dim3(grid), dim3(RR_SCAN_THREADS), 0, st, mat, G, nf,
+        static constexpr decltype(&rr_scan_f32_generic<1>) kern[4] = {rr_scan_f32_generic<1>, rr_scan_f32_generic<2>, rr_scan_f32_generic<4>,
+                                                                      rr_scan_f32_generic<8>};
+        if (!wavesg[k]) wavesg[k] = rr_resident_waves((const void*)kern[k], RR_SCAN_THREADS, ix->device);
+        G = rr_make_geom(ix, wavesg[k] / 4);
+        hipLaunchKernelGGL(kern[k], dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st, mat, G, nf,
                            d_q, ix->d_sims, ix->d_gmax, ix->d_smax);
     }
-    return G;
+    *out = G;
+    return RR_OK;
 }
 
 // one listed launch of the 384-wide fp32 scan into the index's score scratch (rr_dense_listed_fallback): the flagged queries of
 // the call's `nq`, when there are at most eight; the geometry the listed selection reads
 static rr_scan_geom rr_launch_scan_listed(rr_index* ix, const float* d_q, const int32_t* flags, int nq, hipStream_t st) {
-    static int cap = 0;
-    if (!cap) cap = rr_resident_grid(rr_scan_f32<6, 8, true>, ix->device);
-    rr_scan_geom G = rr_make_geom(ix, cap);
+    static int waves = 0;
+    if (!waves) waves = rr_resident_waves((const void*)rr_scan_f32<6, 8, true>, RR_SCAN_THREADS, ix->device);
+    rr_scan_geom G = rr_make_geom(ix, waves / 4);
     hipLaunchKernelGGL((rr_scan_f32<6, 8, true>), dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
                        reinterpret_cast<const f32x4*>(ix->d_matrix), G, d_q, ix->d_sims, ix->d_gmax, ix->d_smax,
                        (const int32_t*)flags, nq, ix->d_flag_list);
@@ -1386,9 +1328,9 @@ static rr_scan_geom rr_launch_scan_listed(rr_index* ix, const float* d_q, const 
 
 // ... of the runtime-width fp32 scan (rr_dense_listed_fallback_wide): the flagged queries ranked [skip, skip + 8)
 static rr_scan_geom rr_launch_scan_generic_listed(rr_index* ix, const float* d_q, const int32_t* flags, int nq, int skip, hipStream_t st) {
-    static int cap = 0;
-    if (!cap) cap = rr_resident_grid(rr_scan_f32_generic_listed<RR_SEL_LISTED>, ix->device);
-    rr_scan_geom G = rr_make_geom(ix, cap);
+    static int waves = 0;
+    if (!waves) waves = rr_resident_waves((const void*)rr_scan_f32_generic_listed<RR_SEL_LISTED>, RR_SCAN_THREADS, ix->device);
+    rr_scan_geom G = rr_make_geom(ix, waves / 4);
     hipLaunchKernelGGL((rr_scan_f32_generic_listed<RR_SEL_LISTED>), dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
                        reinterpret_cast<const f32x4*>(ix->d_matrix), G, ix->dim_pad / 64, d_q, ix->d_sims, ix->d_gmax, ix->d_smax,
                        flags, nq, skip, ix->d_flag_list);
@@ -1414,43 +1356,40 @@ int rr_dense_listed_fallback(rr_index* ix, const float* d_q, int nq, int pool, i
 int rr_dense_listed_fallback_wide(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores,
                                   const int32_t* flags, hipStream_t st) {
     RR_REQUIRE(ix->d_flag_list && ix->d_flag_done, "rr_dense_listed_fallback_wide: the listed scratch is missing");
-    if (ix->dtype == RR_DTYPE_BF16) {                 // bf16 rows: the listed form of rr_scan_bf16_generic (rr_dense_bf16w.hip)
-        for (int p = 0; p < (nq + RR_SEL_LISTED - 1) / RR_SEL_LISTED; ++p) {
-            const rr_scan_geom G = rr_launch_scan_bf16w_listed(ix, d_q, flags, nq, RR_SEL_LISTED * p, st);
-            rr_launch_select_listed(ix, G, pool, d_rows, d_scores, ix->d_flag_done, st);
-        }
-        RR_HIP_TRY(hipGetLastError());
-        return RR_OK;
-    }
+    // bf16 rows: the listed form of rr_scan_bf16_generic (rr_dense_bf16w.hip)
+    const auto scan = ix->dtype == RR_DTYPE_BF16 ? rr_launch_scan_bf16w_listed : rr_launch_scan_generic_listed;
     for (int p = 0; p < (nq + RR_SEL_LISTED - 1) / RR_SEL_LISTED; ++p) {
-        const rr_scan_geom G = rr_launch_scan_generic_listed(ix, d_q, flags, nq, RR_SEL_LISTED * p, st);
+        const rr_scan_geom G = scan(ix, d_q, flags, nq, RR_SEL_LISTED * p, st);
         rr_launch_select_listed(ix, G, pool, d_rows, d_scores, ix->d_flag_done, st);
     }
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }
 
-// Scan + select for up to 8 queries already on the device (padded to dim_pad).
+// Scan + select for up to 8 queries already on the device (padded to dim_pad): THE VALU chunk, either storage dtype, any
+// width.  time_it: the call's scan-time event pair (rr_index_last_scan_ms) brackets this launch.
 static int rr_dense_chunk(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
                           float* d_scores, hipStream_t st, bool time_it) {
+    const bool bf16 = ix->dtype == RR_DTYPE_BF16;
+    const int nb = rr_valu_nb(nq);
     if (time_it) hipEventRecord(ix->ev0, st);
     const int slot = rr_scan_events_begin(ix, st);
-    rr_scan_note(ix, 1, nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8, nq, 0);
     rr_scan_geom G;
-    switch (nq) {
-        case 1: G = rr_launch_scan<1>(ix, d_q, st); break;
-        case 2: G = rr_launch_scan<2>(ix, d_q, st); break;
-        case 3: case 4: G = rr_launch_scan<4>(ix, d_q, st); break;
-        default: G = rr_launch_scan<8>(ix, d_q, st); break;
+    const int rc = !bf16 ? rr_launch_scan_f32(ix, d_q, nb, st, &G)
+                   : ix->dim_pad == 384 ? rr_launch_scan_bf16(ix, d_q, nb, st, &G) : rr_launch_scan_bf16w(ix, d_q, nb, st, &G);
+    if (rc != RR_OK) {
+        // a launcher that refused the index launched nothing: the ring slot was not taken (the next scan records it again),
+        // no scan is noted, and an ev0 without its ev1 must not be read as a scan time
+        if (time_it) ix->timing_valid = false;
+        return rc;
     }
+    rr_scan_note(ix, bf16 ? 2 : 1, nb, nq, 0);
     rr_scan_events_end(ix, slot, st);
     if (time_it) {
         hipEventRecord(ix->ev1, st);
         ix->timing_valid = true;
     }
-    hipLaunchKernelGGL(rr_select, dim3(nq), dim3(RR_SEL_THREADS), 0, st, G, ix->d_sims, ix->d_gmax,
-                       ix->d_smax, pool, ix->row_offset, d_rows, d_scores, ix->d_sel_trace, (const int32_t*)nullptr, nq, (int64_t)0, (int64_t)0, (int64_t)0,
-                       (const int32_t*)nullptr, (int32_t*)nullptr);
+    rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st);
     RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }
@@ -1569,9 +1508,7 @@ static int rr_dense_topk_impl(rr_index* ix, const float* d_q_padded, int nq, int
             // the VALU scan kernels read NB = 1/2/4/8 query slots; slots past n hold zeros
             const int vmax = (mfma_ok && left > valu_max) ? 8 : valu_max;
             n = left < vmax ? left : vmax;
-            rc = !bf16 ? rr_dense_chunk(ix, q, n, pool, rows, scores, st, q0 == 0)
-                 : ix->dim_pad == 384 ? rr_dense_chunk_bf16(ix, q, n, pool, rows, scores, st)
-                                      : rr_dense_chunk_bf16w(ix, q, n, pool, rows, scores, st);
+            rc = rr_dense_chunk(ix, q, n, pool, rows, scores, st, !bf16 && q0 == 0);
         }
         if (rc) return rc;
         q0 += n;
@@ -2065,7 +2002,7 @@ extern "C" int rr_debug_valu_scan(rr_index* ix, const float* d_queries, int32_t 
         RR_REQUIRE(skip >= 0 && skip <= RR_SEL_MAXQ && (wide || skip == 0), "%s: skip %d (0 at width 384, else 0..%d)", who, skip, RR_SEL_MAXQ);
     }
     RR_REQUIRE(sims_cap >= 0 && gmax_cap >= 0 && smax_cap >= 0, "%s: negative cap", who);
-    const int NB = form == 1 ? RR_SEL_LISTED : nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8;
+    const int NB = form == 1 ? RR_SEL_LISTED : rr_valu_nb(nq);
     const void* q_vis = nullptr;
     int rc = rr_device_visible(d_queries, &q_vis, "rr_debug_valu_scan (queries)");
     if (rc != RR_OK) return rc;
@@ -2100,11 +2037,10 @@ extern "C" int rr_debug_valu_scan(rr_index* ix, const float* d_queries, int32_t 
     if (form == 1) {
         G = bf16 ? rr_launch_scan_bf16w_listed(ix, ix->d_q, X.fb, nq, skip, st)
             : wide ? rr_launch_scan_generic_listed(ix, ix->d_q, X.fb, nq, skip, st) : rr_launch_scan_listed(ix, ix->d_q, X.fb, nq, st);
-    } else if (bf16) {
-        G = wide ? rr_debug_launch_scan_bf16w(ix, ix->d_q, NB, st) : rr_debug_launch_scan_bf16(ix, ix->d_q, NB, st);
     } else {
-        G = NB == 1 ? rr_launch_scan<1>(ix, ix->d_q, st) : NB == 2 ? rr_launch_scan<2>(ix, ix->d_q, st)
-          : NB == 4 ? rr_launch_scan<4>(ix, ix->d_q, st) : rr_launch_scan<8>(ix, ix->d_q, st);
+        rc = !bf16 ? rr_launch_scan_f32(ix, ix->d_q, NB, st, &G)
+             : wide ? rr_launch_scan_bf16w(ix, ix->d_q, NB, st, &G) : rr_launch_scan_bf16(ix, ix->d_q, NB, st, &G);
+        if (rc != RR_OK) return rc;
     }
     RR_HIP_TRY(hipGetLastError());
     RR_HIP_TRY(hipStreamSynchronize(st));

@@ -10,16 +10,11 @@
 // rr_scan_bf16<NB>      1..8 queries per matrix read, VALU.  Same shape as rr_scan_f32: a
 //                       16-lane DPP row owns a matrix row, lane j loads 16 B (8 bf16) chunks
 //                       j, j+16, j+32 (a wave instruction = four rows x 256 contiguous bytes),
-//                       one fmaf chain over its 24 elements, rr_row16_sum over the row.
+//                       the per-row chain of rr_dense.h over them.
 // Batches of 5 and more queries over the same storage run on the matrix cores: the filter scan
 // (rr_dense_flt.hip) and the exact split-operand scans (rr_dense_x3.hip, rr_dense_x3w.hip).
 #include "rr_common.h"
 #include "rr_dense.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float rr_bf16_lo(unsigned int w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float rr_bf16_hi(unsigned int w) { return __uint_as_float(w & 0xFFFF0000u); }
 
 // ------------------------------------------------------------------ fp32 -> bf16 rows
 // Round to nearest even on the f32 bits; NaN stays a (quiet) NaN.
@@ -123,28 +118,21 @@ __global__ __launch_bounds__(RR_SCAN_THREADS, (NB <= 1 ? 4 : 2)) void rr_scan_bf
                     for (int i = 0; i < 3; ++i) {
                         const f32x4 q0 = (NB == 1) ? qreg[2 * i] : qs[b][2 * (sub + 16 * i)];
                         const f32x4 q1 = (NB == 1) ? qreg[2 * i + 1] : qs[b][2 * (sub + 16 * i) + 1];
-                        const u32x4 x = cur[i];
-                        acc = __builtin_fmaf(rr_bf16_lo(x.x), q0.x, acc);
-                        acc = __builtin_fmaf(rr_bf16_hi(x.x), q0.y, acc);
-                        acc = __builtin_fmaf(rr_bf16_lo(x.y), q0.z, acc);
-                        acc = __builtin_fmaf(rr_bf16_hi(x.y), q0.w, acc);
-                        acc = __builtin_fmaf(rr_bf16_lo(x.z), q1.x, acc);
-                        acc = __builtin_fmaf(rr_bf16_hi(x.z), q1.y, acc);
-                        acc = __builtin_fmaf(rr_bf16_lo(x.w), q1.z, acc);
-                        acc = __builtin_fmaf(rr_bf16_hi(x.w), q1.w, acc);
+                        acc = rr_bf16_chunk(cur[i], q0, q1, acc);
                     }
                     acc = rr_row16_sum(acc);
                     mine[b] = (sub == it + half) ? acc : mine[b];
                 }
             }
         }
+        // (rr_finish_tile's work, written out: through the shared helper this kernel's registers and schedule change)
         const int64_t my_row = row0 + 4 * sub + grp;
         const bool valid = my_row < G.n_rows;
         const bool group_end = tile == t1 - 1;
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             float v = mine[b];
-            v = (valid && v == v) ? v : -INFINITY;
+            v = rr_rank_last(v, valid);
             sims[(int64_t)b * G.n_pad + my_row] = v;
             const float m = rr_wave_max(v);
             gm[b] = fmaxf(gm[b], m);
@@ -156,37 +144,13 @@ __global__ __launch_bounds__(RR_SCAN_THREADS, (NB <= 1 ? 4 : 2)) void rr_scan_bf
     }
 }
 
-template <int NB>
-static rr_scan_geom rr_launch_scan_bf16(rr_index* ix, const float* d_q, hipStream_t st) {
-    static int waves = 0;
-    if (!waves) waves = rr_resident_waves((const void*)rr_scan_bf16<NB>, RR_SCAN_THREADS, ix->device);
-    rr_scan_geom G = rr_make_geom(ix, waves / 4);
-    hipLaunchKernelGGL((rr_scan_bf16<NB>), dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
+int rr_launch_scan_bf16(rr_index* ix, const float* d_q, int nb, hipStream_t st, rr_scan_geom* out) {
+    static constexpr decltype(&rr_scan_bf16<1>) kern[4] = {rr_scan_bf16<1>, rr_scan_bf16<2>, rr_scan_bf16<4>, rr_scan_bf16<8>};
+    static int waves[4];   // per kernel instance
+    const int k = rr_nb_slot(nb);
+    if (!waves[k]) waves[k] = rr_resident_waves((const void*)kern[k], RR_SCAN_THREADS, ix->device);
+    const rr_scan_geom G = *out = rr_make_geom(ix, waves[k] / 4);
+    hipLaunchKernelGGL(kern[k], dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
                        reinterpret_cast<const u32x4*>(ix->d_matrix), G, d_q, ix->d_sims, ix->d_gmax, ix->d_smax);
-    return G;
-}
-
-#ifdef RR_DEBUG_HARNESS
-// rr_debug_valu_scan (rr_dense.hip): the launch helper above for NB = 1, 2, 4 or 8
-rr_scan_geom rr_debug_launch_scan_bf16(rr_index* ix, const float* d_q, int nb, hipStream_t st) {
-    return nb == 1 ? rr_launch_scan_bf16<1>(ix, d_q, st) : nb == 2 ? rr_launch_scan_bf16<2>(ix, d_q, st)
-         : nb == 4 ? rr_launch_scan_bf16<4>(ix, d_q, st) : rr_launch_scan_bf16<8>(ix, d_q, st);
-}
-#endif
-
-int rr_dense_chunk_bf16(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows,
-                        float* d_scores, hipStream_t st) {
-    const int slot = rr_scan_events_begin(ix, st);
-    rr_scan_note(ix, 2, nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8, nq, 0);
-    rr_scan_geom G;
-    switch (nq) {
-        case 1: G = rr_launch_scan_bf16<1>(ix, d_q, st); break;
-        case 2: G = rr_launch_scan_bf16<2>(ix, d_q, st); break;
-        case 3: case 4: G = rr_launch_scan_bf16<4>(ix, d_q, st); break;
-        default: G = rr_launch_scan_bf16<8>(ix, d_q, st); break;
-    }
-    rr_scan_events_end(ix, slot, st);
-    rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st);
-    RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }

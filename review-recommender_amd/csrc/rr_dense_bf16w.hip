@@ -2,13 +2,9 @@
 // 384-wide rr_scan_bf16 keeps every constant it has).  Semantics of rr_dense_bf16.hip: rows rounded once to bf16, queries
 // and accumulation fp32, every product an exact fp32 product.
 //
-// The chain at width D = dim_pad.  A row is D / 8 chunks of 16 bytes (8 bf16).  Lane j of the 16 lanes of a row takes chunks
-// c = j + 16 i, i = 0 .. ceil(D / 128) - 1; a chunk with 8 c >= D does not exist and adds nothing (D = 64, 192, 320, ..: the
-// last round is half full).  Per chunk eight fmaf in memory order onto the lane's ONE accumulator, which starts at 0; then
-// rr_row16_sum.  NaN -> -inf, rows past the end -> -inf.  At D = 384 this is rr_scan_bf16's chain.  Three places run it and
-// agree bit for bit: rr_scan_bf16_generic (the single-query scan, and 2 .. 8 queries per read where the batched path
-// declines), its listed form (flagged queries of a batched launch) and rr_rescore_chain_wb (rr_dense_fltw.hip), all through
-// rr_bf16w_chunk (rr_dense.h).
+// The per-row chain is the one rr_dense.h defines (rr_bf16_chunk), at D / 8 chunks per row; at D = 384 it is rr_scan_bf16's.
+// Three places run it here: rr_scan_bf16_generic (the single-query scan, and 2 .. 8 queries per read where the batched path
+// declines), its listed form (flagged queries of a batched launch) and rr_rescore_chain_wb (rr_dense_fltw.hip).
 #include "rr_x3.h"
 
 // ------------------------------------------------------------------ the VALU scan
@@ -66,7 +62,7 @@ __device__ __forceinline__ void rr_bf16w_scan_rows(const u32x4* __restrict__ mat
         const int c = sub + 16 * i;
         if (c < units) {
 #pragma unroll
-            for (int b = 0; b < NB; ++b) acc[b] = rr_bf16w_chunk(x, qs[b][2 * c], qs[b][2 * c + 1], acc[b]);
+            for (int b = 0; b < NB; ++b) acc[b] = rr_bf16_chunk(x, qs[b][2 * c], qs[b][2 * c + 1], acc[b]);
         }
         if (++i == nr) {                              // (wave-uniform) the step's rows are complete
             i = 0;
@@ -126,11 +122,7 @@ __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_bf16_generic_listed(
     const int tid = threadIdx.x;
     int list[NB];
     const int n = rr_flagged_slice<NB>(flags, nq_total, tid & 63, skip, list);
-    if (blockIdx.x == 0 && tid == 0) {
-        list_out[0] = n;                              // (also when it is 0: the selection behind this launch reads it)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) list_out[1 + b] = list[b];
-    }
+    rr_publish_list<NB>(list_out, n, list);
     if (n == 0) return;                               // (the whole workgroup: before the barrier)
     const int q4 = 2 * units;
 #pragma unroll
@@ -141,39 +133,18 @@ __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_bf16_generic_listed(
 }
 
 // ------------------------------------------------------------------ host side
-template <int NB>
-static rr_scan_geom rr_launch_scan_bf16w(rr_index* ix, const float* d_q, hipStream_t st) {
-    static int waves = 0;
-    if (!waves) waves = rr_resident_waves((const void*)rr_scan_bf16_generic<NB>, RR_SCAN_THREADS, ix->device);
-    rr_scan_geom G = rr_make_geom(ix, waves / 4);
-    hipLaunchKernelGGL((rr_scan_bf16_generic<NB>), dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
+int rr_launch_scan_bf16w(rr_index* ix, const float* d_q, int nb, hipStream_t st, rr_scan_geom* out) {
+    static constexpr decltype(&rr_scan_bf16_generic<1>) kern[4] = {rr_scan_bf16_generic<1>, rr_scan_bf16_generic<2>, rr_scan_bf16_generic<4>,
+                                                                   rr_scan_bf16_generic<8>};
+    static int waves[4];   // per kernel instance
+    RR_REQUIRE(ix->dtype == RR_DTYPE_BF16 && ix->dim_pad <= RR_FLTW_MAX_DIM && ix->dim_pad % 64 == 0 &&
+                   (nb == 1 || nb == 2 || nb == 4 || nb == 8),
+               "rr_launch_scan_bf16w: 1, 2, 4 or 8 query slots on a bf16 index of width 64 .. %d expected", RR_FLTW_MAX_DIM);
+    const int k = rr_nb_slot(nb);
+    if (!waves[k]) waves[k] = rr_resident_waves((const void*)kern[k], RR_SCAN_THREADS, ix->device);
+    const rr_scan_geom G = *out = rr_make_geom(ix, waves[k] / 4);
+    hipLaunchKernelGGL(kern[k], dim3((G.n_waves + 3) / 4), dim3(RR_SCAN_THREADS), 0, st,
                        reinterpret_cast<const u32x4*>(ix->d_matrix), G, ix->dim_pad / 8, d_q, ix->d_sims, ix->d_gmax, ix->d_smax);
-    return G;
-}
-
-#ifdef RR_DEBUG_HARNESS
-// rr_debug_valu_scan (rr_dense.hip): the launch helper above for NB = 1, 2, 4 or 8
-rr_scan_geom rr_debug_launch_scan_bf16w(rr_index* ix, const float* d_q, int nb, hipStream_t st) {
-    return nb == 1 ? rr_launch_scan_bf16w<1>(ix, d_q, st) : nb == 2 ? rr_launch_scan_bf16w<2>(ix, d_q, st)
-         : nb == 4 ? rr_launch_scan_bf16w<4>(ix, d_q, st) : rr_launch_scan_bf16w<8>(ix, d_q, st);
-}
-#endif
-
-int rr_dense_chunk_bf16w(rr_index* ix, const float* d_q, int nq, int pool, int64_t* d_rows, float* d_scores, hipStream_t st) {
-    RR_REQUIRE(ix->dtype == RR_DTYPE_BF16 && ix->dim_pad <= RR_FLTW_MAX_DIM && ix->dim_pad % 64 == 0 && nq >= 1 && nq <= 8,
-               "rr_dense_chunk_bf16w: 1 .. 8 queries on a bf16 index of width 64 .. %d expected", RR_FLTW_MAX_DIM);
-    const int slot = rr_scan_events_begin(ix, st);
-    rr_scan_note(ix, 2, nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8, nq, 0);
-    rr_scan_geom G;
-    switch (nq) {
-        case 1: G = rr_launch_scan_bf16w<1>(ix, d_q, st); break;
-        case 2: G = rr_launch_scan_bf16w<2>(ix, d_q, st); break;
-        case 3: case 4: G = rr_launch_scan_bf16w<4>(ix, d_q, st); break;
-        default: G = rr_launch_scan_bf16w<8>(ix, d_q, st); break;
-    }
-    rr_scan_events_end(ix, slot, st);
-    rr_launch_select(ix, G, nq, pool, d_rows, d_scores, st);
-    RR_HIP_TRY(hipGetLastError());
     return RR_OK;
 }
 

@@ -1197,9 +1197,8 @@ __global__ __launch_bounds__(256) void rr_fltq_sigma(const uint32_t* __restrict_
 }
 
 // ------------------------------------------------------------------ exact rescoring
-// The listed 8-row M-tiles of a query, rescored with the single-query scans' per-row arithmetic -- lane j of a 16-lane row
-// takes 16-byte units j, j + 16, ... of the row, one fmaf chain over its 24 elements in ascending order, rr_row16_sum over
-// the row (rr_scan_f32<6,1> / rr_scan_bf16<1>).  sc[query][slot][8].
+// The listed 8-row M-tiles of a query, rescored with the single-query scans' per-row chain (rr_dense.h; rr_scan_f32<6,1> /
+// rr_scan_bf16<1>).  sc[query][slot][8].
 //
 // The kernel is a gather of ~500 scattered M-tiles per query (768 B per plane row): what it costs is how many bytes a
 // CU keeps in flight.  A wave therefore takes U M-tiles per pass and issues ALL their row loads before it looks at the
@@ -1213,17 +1212,6 @@ __global__ __launch_bounds__(256) void rr_fltq_sigma(const uint32_t* __restrict_
 // eps): one row in eight of an opened M-tile, typically.  The others get -inf: they are below the cut whatever their
 // exact score is.  The rows that need the exact chain are taken per 16-lane group from a bit mask, one row per group and
 // round, so a round serves up to four rows of four different M-tiles.
-__device__ __forceinline__ float rr_bf16x8_chain(const u32x4 x, const f32x4 q0, const f32x4 q1, float acc) {
-    acc = __builtin_fmaf(__uint_as_float(x.x << 16), q0.x, acc);
-    acc = __builtin_fmaf(__uint_as_float(x.x & 0xFFFF0000u), q0.y, acc);
-    acc = __builtin_fmaf(__uint_as_float(x.y << 16), q0.z, acc);
-    acc = __builtin_fmaf(__uint_as_float(x.y & 0xFFFF0000u), q0.w, acc);
-    acc = __builtin_fmaf(__uint_as_float(x.z << 16), q1.x, acc);
-    acc = __builtin_fmaf(__uint_as_float(x.z & 0xFFFF0000u), q1.y, acc);
-    acc = __builtin_fmaf(__uint_as_float(x.w << 16), q1.z, acc);
-    acc = __builtin_fmaf(__uint_as_float(x.w & 0xFFFF0000u), q1.w, acc);
-    return acc;
-}
 
 #define RR_RESCORE_U 4            // M-tiles per wave and pass (bf16 rows / plane rows); fp32 rows without a plane: half
 template <bool A_BF16>
@@ -1274,12 +1262,12 @@ __global__ __launch_bounds__(256, 3) void rr_rescore_chain(
                     float est = 0.f;
 #pragma unroll
                     for (int i = 0; i < 3; ++i)            // lane `sub`: units sub + 16 i = dims 8 (sub + 16 i) .. + 7
-                        est = rr_bf16x8_chain(x[u][it][i], qs[2 * (sub + 16 * i)], qs[2 * (sub + 16 * i) + 1], est);
+                        est = rr_bf16_chunk(x[u][it][i], qs[2 * (sub + 16 * i)], qs[2 * (sub + 16 * i) + 1], est);
                     est = rr_row16_sum(est);
                     const int64_t row = (int64_t)m8[u] * 8 + 4 * it + grp;
                     const bool live = s0 + u < n;
                     if (A_BF16) {                          // a bf16 index: that WAS the row's chain
-                        if (sub == 0 && live) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = (row < n_rows && est == est) ? est : -INFINITY;
+                        if (sub == 0 && live) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = rr_rank_last(est, row < n_rows);
                     } else {
                         const bool exact = live && row < n_rows && (est >= pre_thr || !(est == est));   // (the 16 lanes of a row agree; NaN: the exact chain decides)
                         need |= exact ? 1u << (2 * u + it) : 0u;
@@ -1302,15 +1290,9 @@ __global__ __launch_bounds__(256, 3) void rr_rescore_chain(
                         for (int i = 0; i < 6; ++i) y[i] = p[16 * i];
                         float acc = 0.f;
 #pragma unroll
-                        for (int i = 0; i < 6; ++i) {
-                            const f32x4 qq = qs[16 * i + sub];
-                            acc = __builtin_fmaf(y[i].x, qq.x, acc);
-                            acc = __builtin_fmaf(y[i].y, qq.y, acc);
-                            acc = __builtin_fmaf(y[i].z, qq.z, acc);
-                            acc = __builtin_fmaf(y[i].w, qq.w, acc);
-                        }
+                        for (int i = 0; i < 6; ++i) acc = rr_f32_chunk(y[i], qs[16 * i + sub], acc);
                         acc = rr_row16_sum(acc);
-                        if (sub == 0) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = acc == acc ? acc : -INFINITY;   // NaN scores rank last
+                        if (sub == 0) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = rr_rank_last(acc, true);
                     }
                 }
             }
@@ -1339,16 +1321,10 @@ __global__ __launch_bounds__(256, 3) void rr_rescore_chain(
                 for (int it = 0; it < 2; ++it) {
                     float acc = 0.f;
 #pragma unroll
-                    for (int i = 0; i < 6; ++i) {
-                        const f32x4 qq = qs[16 * i + sub];
-                        acc = __builtin_fmaf(y[u][it][i].x, qq.x, acc);
-                        acc = __builtin_fmaf(y[u][it][i].y, qq.y, acc);
-                        acc = __builtin_fmaf(y[u][it][i].z, qq.z, acc);
-                        acc = __builtin_fmaf(y[u][it][i].w, qq.w, acc);
-                    }
+                    for (int i = 0; i < 6; ++i) acc = rr_f32_chunk(y[u][it][i], qs[16 * i + sub], acc);
                     acc = rr_row16_sum(acc);
                     const int64_t row = (int64_t)m8[u] * 8 + 4 * it + grp;
-                    if (sub == 0 && s0 + u < n) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = (row < n_rows && acc == acc) ? acc : -INFINITY;
+                    if (sub == 0 && s0 + u < n) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = rr_rank_last(acc, row < n_rows);
                 }
         }
     }

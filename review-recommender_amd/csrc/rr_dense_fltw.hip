@@ -230,10 +230,8 @@ __global__ __launch_bounds__(512, 2) void rr_scan_fltw(
 }
 
 // ------------------------------------------------------------------ exact rescoring at a runtime width
-// rr_rescore_chain's no-plane branch with nf = dim_pad / 64 at run time: per listed 8-row M-tile, lane `sub` of the 16 of a
-// row takes float4s sub + 16 i, i < nf, four fmaf each in x, y, z, w order, then rr_row16_sum -- the chain of
-// rr_scan_f32_generic, so the scores are the single-query scan's bit for bit.  NaN -> -inf, rows past the end -> -inf.
-// A wave takes two M-tiles per pass (four rows' loads in flight per lane and step of i).  sc[query][slot][8].
+// rr_rescore_chain's no-plane branch with nf = dim_pad / 64 at run time: the per-row chain (rr_dense.h) over each listed 8-row
+// M-tile, so the scores are the single-query scan's bit for bit.  A wave takes two M-tiles per pass (four rows' loads in flight per lane and step of i).  sc[query][slot][8].
 __global__ __launch_bounds__(256) void rr_rescore_chain_w(
     const f32x4* __restrict__ mat, int64_t n_rows, int nf, const float* __restrict__ queries,   // [nq][64 nf] fp32, padded
     const uint32_t* __restrict__ mtiles, const int32_t* __restrict__ count, const int32_t* __restrict__ fb, float* __restrict__ sc) {
@@ -271,13 +269,7 @@ __global__ __launch_bounds__(256) void rr_rescore_chain_w(
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int it = 0; it < 2; ++it) {
-                    const f32x4 y = p[u][it][16 * i];
-                    acc[u][it] = __builtin_fmaf(y.x, qq.x, acc[u][it]);
-                    acc[u][it] = __builtin_fmaf(y.y, qq.y, acc[u][it]);
-                    acc[u][it] = __builtin_fmaf(y.z, qq.z, acc[u][it]);
-                    acc[u][it] = __builtin_fmaf(y.w, qq.w, acc[u][it]);
-                }
+                for (int it = 0; it < 2; ++it) acc[u][it] = rr_f32_chunk(p[u][it][16 * i], qq, acc[u][it]);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -285,14 +277,13 @@ __global__ __launch_bounds__(256) void rr_rescore_chain_w(
             for (int it = 0; it < 2; ++it) {
                 const float a = rr_row16_sum(acc[u][it]);
                 const int64_t row = (int64_t)m8[u] * 8 + 4 * it + grp;
-                if (sub == 0 && s0 + u < n) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = (row < n_rows && a == a) ? a : -INFINITY;
+                if (sub == 0 && s0 + u < n) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = rr_rank_last(a, row < n_rows);
             }
     }
 }
 
-// The same launch for the rows of a bf16 index: lane `sub` of a row takes the 16-byte chunks sub + 16 i, i < ceil(units / 16),
-// those with a number below units = dim_pad / 8, eight fmaf each in memory order (rr_bf16w_chunk) onto one accumulator, then
-// rr_row16_sum -- the chain of rr_scan_bf16_generic.  Same lists, same sc layout, same masking of the repeated last tile.
+// The same launch for the rows of a bf16 index (units = dim_pad / 8 chunks per row): the chain of rr_scan_bf16_generic (rr_dense.h).
+// Same lists, same sc layout, same masking of the repeated last tile.
 __global__ __launch_bounds__(256) void rr_rescore_chain_wb(
     const u32x4* __restrict__ mat, int64_t n_rows, int units, const float* __restrict__ queries,   // [nq][8 units] fp32, padded
     const uint32_t* __restrict__ mtiles, const int32_t* __restrict__ count, const int32_t* __restrict__ fb, float* __restrict__ sc) {
@@ -332,7 +323,7 @@ __global__ __launch_bounds__(256) void rr_rescore_chain_wb(
 #pragma unroll
                 for (int u = 0; u < U; ++u)
 #pragma unroll
-                    for (int it = 0; it < 2; ++it) acc[u][it] = rr_bf16w_chunk(p[u][it][c], q0, q1, acc[u][it]);
+                    for (int it = 0; it < 2; ++it) acc[u][it] = rr_bf16_chunk(p[u][it][c], q0, q1, acc[u][it]);
             }
         }
 #pragma unroll
@@ -341,7 +332,7 @@ __global__ __launch_bounds__(256) void rr_rescore_chain_wb(
             for (int it = 0; it < 2; ++it) {
                 const float a = rr_row16_sum(acc[u][it]);
                 const int64_t row = (int64_t)m8[u] * 8 + 4 * it + grp;
-                if (sub == 0 && s0 + u < n) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = (row < n_rows && a == a) ? a : -INFINITY;
+                if (sub == 0 && s0 + u < n) sc[(int64_t)(s0 + u) * 8 + 4 * it + grp] = rr_rank_last(a, row < n_rows);
             }
     }
 }

@@ -51,6 +51,21 @@ Kernel-side mutations, each applied to a copy of the tree, built into the debug 
     (e) rr_bf16w_scan_rows starts pf_i at 1 for waves > 0   test_scan_generic_one_tile_per_wave[bf16], test_runs_..[bf16],
                                                             test_listed_forms[bf16-768]: "bf16 dim 64 n 1000 nq 1 .. 816 scores differ
                                                             from the model, first slot 0 row 68 (tile 1, run 1)" (wave 0's tile is right)
+((a) was run when rr_dot_rows held its own four fmaf.)  The chain step of each storage type is now ONE function (rr_dense.h) that
+every scan and every rescoring kernel calls.  Two adjacent fmaf swapped inside it, run against this file,
+test_gpu_rescore_kernels.py, test_gpu_fltw_kernels.py and test_gpu_bf16_wide_kernels.py (18 tests):
+    (f) rr_f32_chunk: the x and y products swapped          8 fail, every fp32 chain and no other: here test_scan_384_..[f32],
+                                                            test_scan_generic_..[f32], test_runs_..[f32], test_listed_forms[f32-384] and
+                                                            [f32-768]; test_rescoring_of_fp32_rows_with_and_without_the_plane and
+                                                            test_rescoring_of_rows_with_nan_and_inf_elements (rr_rescore_chain, both
+                                                            fp32 branches); test_gpu_fltw_kernels' test_rescored_rows_are_the_chain_bit_
+                                                            for_bit (rr_rescore_chain_w)
+    (g) rr_bf16_chunk: the first two products swapped       6 fail, every bf16 chain and no other: here test_scan_384_..[bf16],
+                                                            test_scan_generic_..[bf16], test_runs_..[bf16], test_listed_forms[bf16-768];
+                                                            test_rescoring_of_bf16_rows (rr_rescore_chain); test_gpu_bf16_wide_kernels'
+                                                            test_rescored_bf16_rows_are_the_chain_bit_for_bit (rr_rescore_chain_wb):
+                                                            "bf16 dim 384 n 1 nq 1 .. 1 scores differ from the model, first slot 0 row 0
+                                                            (tile 0, run 0): kernel 0x3b801170, model 0x3b80116c"
 """
 import pathlib
 import subprocess

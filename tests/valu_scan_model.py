@@ -53,7 +53,7 @@ def from_bits(b):
 
 # ------------------------------------------------------------------ geometry and routing
 def nb_of(nq):
-    """query slots of the plain launch that serves nq queries (rr_dense_chunk, rr_dense_chunk_bf16, rr_dense_chunk_bf16w)"""
+    """query slots of the plain launch that serves nq queries (rr_valu_nb, rr_dense.h)"""
     assert 1 <= nq <= 8
     return 1 if nq <= 1 else 2 if nq <= 2 else 4 if nq <= 4 else 8
 

@@ -378,14 +378,20 @@ int rr_reviews_best_at_dev(rr_reviews* rv, const float* d_queries, int32_t n_que
  *      BertForSequenceClassification: 6 layers, hidden 384, 12 heads, FFN 1536, 512 positions, 1 label)
  *   SentenceTransformer.encode([query], normalize_embeddings=True)        app/app_product_search.py:250-251, app/test.py:232
  *     (BAAI/bge-small-en-v1.5: BertModel of the same block shape, 12 layers, CLS pooling; the l2 normalisation is the caller's)
- * The kernels are built for hidden 384 / 12 heads x 32 / FFN 1536; layer count, vocabulary, positions (<= 512) are free.
+ * Shapes: hidden 384 / 12 heads x 32 / FFN 1536 has kernels of its own, in both precisions.  Every other shape with
+ *   hidden % 128 == 0 in [128, 1024], hidden / n_heads = 32 or 64, ffn % 128 == 0 in [128, 4096]
+ * (TinyBERT-L-2 128 / 2 / 512, BERT-base 768 / 12 / 3072, bge-large 1024 / 16 / 4096, ...) runs the runtime-shape kernels of
+ * csrc/rr_ce_w.hip in RR_CE_PRECISION_F32 only: three bf16 terms per operand, six matrix-core products, any fp32 range.
+ * rr_ce_create answers RR_E_INVALID, with nothing allocated, to RR_CE_PRECISION_BF16 at such a shape (the message names the
+ * precision) and to a shape outside the family (the message names the offending number).  Layer count (<= 48), vocabulary,
+ * positions (<= 512) and labels (<= 64) are free at every shape.
  * Tokenisation (WordPiece): rr_wp_encode_dev below turns documents (ASCII, or UTF-8 on a handle of rr_wp_create_utf8) into
  * the packed ids this call takes, on the device (csrc/rr_wordpiece.hip); what it flags is tokenised on the host
  * (review-recommender_amd/wordpiece.py).  Text PAIRS (the reranker): rr_pairs_measure_dev / rr_pairs_write_dev below assemble
  * them on the device from the token plane of an index and the queries' ids; without a plane they are tokenised on the host. */
 typedef struct rr_ce rr_ce;
 typedef struct rr_ce_config {
-    int32_t hidden, n_layers, n_heads, ffn;       /* 384, L, 12, 1536 */
+    int32_t hidden, n_layers, n_heads, ffn;       /* 384, L, 12, 1536 -- or another shape of the family above */
     int32_t vocab, max_pos, type_vocab;           /* embedding table sizes */
     int32_t n_labels;                             /* classifier outputs (1 for the reranker); 0 = no pooler / classifier */
     float ln_eps;                                 /* 1e-12 for BERT */
@@ -407,7 +413,7 @@ typedef struct rr_ce_config {
  *     intermediate.dense.weight [FFN][H], .bias, output.dense.weight [H][FFN], .bias, output.LayerNorm.weight, .bias
  *   when n_labels > 0, four more: pooler.dense.weight [H][H], pooler.dense.bias, classifier.weight [n_labels][H], classifier.bias
  * Linear weights are rounded once to bf16 (nearest even) on the device (RR_CE_PRECISION_F32 also keeps them as given, and
- * as fp16 pairs);
+ * as fp16 pairs; a shape other than 384 / 12 / 1536 keeps the fp32 matrices only);
  * everything else stays fp32. */
 int rr_ce_create(int32_t device, const rr_ce_config* cfg, const float* const* h_tensors, int32_t n_tensors, rr_ce** out);
 int rr_ce_destroy(rr_ce* ce);
@@ -421,6 +427,13 @@ int rr_ce_destroy(rr_ce* ce);
  * check it (the bf16 attention sizes LDS from it too: an understated max_len is undefined there).
  * RR_CE_PRECISION_F32 takes at most 2^27 tokens per call (RR_E_INVALID beyond: its GEMMs store with 32-bit offsets inside
  * a pair of 16-byte chunks of the activation scratch); its scratch is kept at the handle's largest call.
+ * A shape other than 384 / 12 / 1536 does not use max_len beyond the check against the position table (its attention
+ * reads every length from cu_seqlens), takes at most 8 388 480 tokens per call (RR_E_INVALID beyond: its GEMMs launch one
+ * row of workgroups per 128 tokens), and keeps T x ((4 + ceil(ffn / 2048)) hidden + max(hidden, ffn)) floats of scratch.
+ * No path but the fp16-pair one checks the LENGTHS in cu_seqlens on the device: a sequence of more than 512 tokens is the
+ * caller's to refuse (cross_encoder.py does, before anything is launched).  At these shapes, as on the wide-range
+ * kernels, the attention serves 512 queries per sequence: the context rows of a longer sequence's later tokens are left
+ * unwritten (stale scratch: wrong outputs for that sequence), nothing is read or written out of bounds, no flag is raised.
  * Attention is full inside a sequence (what an all-ones attention mask over the unpadded tokens gives).
  * Asynchronous on `stream`; all pointers are device pointers. */
 int rr_ce_forward_dev(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d_type_ids, const int32_t* d_pos_ids,
@@ -435,7 +448,9 @@ int rr_ce_last_forward_ms(rr_ce* ce, float* out_ms);
  * the pass has finished (this call waits for it).  A pass whose max_len was below a sequence's length (rr_ce_forward_dev)
  * makes this call return RR_E_INVALID instead: running it again on the wide-range kernels would not help.
  * rr_ce_set_wide_range(ce, 1) switches the handle to three bf16 terms per operand and six products (any fp32 range,
- * ~1.6 x the time): run the pass again after it.  cross_encoder.py does both by itself on the host path. */
+ * ~1.6 x the time): run the pass again after it.  cross_encoder.py does both by itself on the host path.
+ * A handle of another shape than 384 / 12 / 1536 has no fp16 anywhere: rr_ce_range_status reports 0, and
+ * rr_ce_set_wide_range succeeds and changes nothing (it runs the three-term arithmetic already). */
 int rr_ce_range_status(rr_ce* ce, int32_t* out_of_range);
 int rr_ce_set_wide_range(rr_ce* ce, int32_t on);
 

@@ -33,8 +33,10 @@ from .wordpiece import WordPieceTokenizer
 
 OUT_LOGITS, OUT_CLS, OUT_HIDDEN = 0, 1, 2       # RR_CE_OUT_*
 PRECISIONS = {"bf16": 0, "fp32": 1}              # RR_CE_PRECISION_*
-HIDDEN, HEADS, FFN = 384, 12, 1536
+HIDDEN, HEADS, FFN = 384, 12, 1536                  # the shape with kernels of its own in both precisions
+MAX_HIDDEN, MAX_FFN = 1024, 4096                    # the family of every other shape (csrc/rr_ce_w.h)
 FP32_MAX_TOKENS = 1 << 27                           # tokens per rr_ce_forward_dev call in fp32 precision (include/rr_hip.h)
+OTHER_SHAPE_MAX_TOKENS = 65535 * 128                # ... at a shape other than 384 / 12 / 1536 (csrc/rr_ce_w.h)
 
 _LAYER_KEYS = ("attention.self.query.weight", "attention.self.query.bias", "attention.self.key.weight",
                "attention.self.key.bias", "attention.self.value.weight", "attention.self.value.bias",
@@ -56,19 +58,56 @@ def _find_prefix(sd: Dict) -> str:
     raise ValueError("state dict holds no '[bert.]embeddings.word_embeddings.weight': not a BERT checkpoint")
 
 
+def model_shape(sd: Dict, n_heads: Optional[int] = None, cfg: Optional[Dict] = None, precision: str = "fp32") -> Tuple[int, int, int]:
+    """(hidden, n_heads, ffn) of a BERT state dict, checked against what rr_ce_create accepts (include/rr_hip.h) and
+    refused in its words.  Needs neither a GPU nor the library.  hidden and ffn are read off the tensors; n_heads is the
+    argument, else `num_attention_heads` of `cfg` (a config.json as a dict), else 12 at hidden 384 and hidden // 64
+    anywhere else (BERT-base, bge-large, TinyBERT; a 32-wide head at another width has to be named).  384 / 12 / 1536
+    runs in both precisions; every other shape needs hidden % 128 == 0 in [128, 1024], a head dim of 32 or 64,
+    ffn % 128 == 0 in [128, 4096] and precision "fp32"."""
+    p = _find_prefix(sd)
+    hidden = int(sd[p + "embeddings.word_embeddings.weight"].shape[1])
+    key = p + "encoder.layer.0.intermediate.dense.weight"
+    if key not in sd:
+        raise ValueError("state dict holds no encoder layers")
+    ffn = int(sd[key].shape[0])
+    if n_heads is None and cfg and cfg.get("num_attention_heads") is not None:
+        n_heads = cfg["num_attention_heads"]
+    if n_heads is None:
+        n_heads = HEADS if hidden == HIDDEN else hidden // 64
+    n_heads = int(n_heads)
+    if (hidden, n_heads, ffn) != (HIDDEN, HEADS, FFN):
+        if hidden < 128 or hidden > MAX_HIDDEN or hidden % 128:
+            raise ValueError(f"rr_ce_create: hidden {hidden} is not a multiple of 128 in [128, {MAX_HIDDEN}]")
+        if n_heads < 1 or hidden % n_heads or hidden // n_heads not in (32, 64):
+            hd = hidden / n_heads if n_heads >= 1 else 0.0
+            raise ValueError(f"rr_ce_create: head dim {hd:g} (hidden {hidden} / {n_heads} heads) is not 32 or 64")
+        if ffn < 128 or ffn > MAX_FFN or ffn % 128:
+            raise ValueError(f"rr_ce_create: ffn {ffn} is not a multiple of 128 in [128, {MAX_FFN}]")
+        if precision == "bf16":
+            raise ValueError(f"rr_ce_create: precision bf16 is built for hidden {HIDDEN} / {HEADS} heads / FFN {FFN} only; hidden "
+                             f"{hidden} / {n_heads} heads / FFN {ffn} runs in precision fp32")
+    return hidden, n_heads, ffn
+
+
 class BertEncoderGPU:
-    """A BERT encoder (+ optional sequence-classification head) resident on one GPU."""
+    """A BERT encoder (+ optional sequence-classification head) resident on one GPU.  `.hidden`, `.n_heads`, `.ffn`: its
+    block shape (`model_shape`)."""
 
     def __init__(self, state_dict: Dict, *, device: int = 0, ln_eps: float = 1e-12, with_head: bool = True,
-                 max_tokens_per_call: int = 131_072, precision: str = "fp32"):
-        """``precision``: "fp32" = the reference's arithmetic (fp32 weights and activations, products on the fp16 matrix
+                 max_tokens_per_call: int = 131_072, precision: str = "fp32", n_heads: Optional[int] = None):
+        """``n_heads``: attention heads (default: 12 at hidden 384, hidden // 64 elsewhere; `model_shape`).
+        ``precision``: "fp32" = the reference's arithmetic (fp32 weights and activations, products on the fp16 matrix
         cores as exact as an fp32 multiply-add chain: logits / embeddings within 1e-5 of `transformers`; a value beyond
         fp16's range switches the handle to the wide-range kernels, see `out_of_range`), "bf16" = the fast path (bf16
-        operands, fp32 accumulation: 2.5e-2 on O(1) logits, ~2.7x the throughput).  include/rr_hip.h: RR_CE_PRECISION_*."""
+        operands, fp32 accumulation: 2.5e-2 on O(1) logits, ~2.7x the throughput).  include/rr_hip.h: RR_CE_PRECISION_*.
+        A shape other than 384 / 12 / 1536 runs in "fp32" only, on the three-term kernels (any fp32 range: `out_of_range`
+        stays False)."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
         self.precision = precision
         sd = state_dict
+        self.hidden, self.n_heads, self.ffn = model_shape(sd, n_heads, precision=precision)      # (before any device call)
         p = _find_prefix(sd)
         word = _np(sd[p + "embeddings.word_embeddings.weight"])
         pos = _np(sd[p + "embeddings.position_embeddings.weight"])
@@ -89,14 +128,11 @@ class BertEncoderGPU:
             n_labels = cw.shape[0]
             tensors += [_np(sd[p + "pooler.dense.weight"]), _np(sd[p + "pooler.dense.bias"]), cw,
                         _np(sd["classifier.bias"])]
-        if word.shape[1] != HIDDEN or tensors[5 + 10].shape != (FFN, HIDDEN):
-            raise ValueError(f"the kernels are built for hidden {HIDDEN} / FFN {FFN} (MiniLM-L6, bge-small); got hidden "
-                             f"{word.shape[1]}, FFN {tensors[5 + 10].shape[0]}")
         self.n_layers, self.n_labels, self.vocab, self.max_pos = n_layers, n_labels, word.shape[0], pos.shape[0]
         self.type_vocab, self.device = typ.shape[0], device
         self.max_tokens_per_call = int(max_tokens_per_call)
         self.wide_range = False                         # set_wide_range: which fp32-mode kernels the NEXT launch runs
-        cfg = _lib.CEConfig(HIDDEN, n_layers, HEADS, FFN, self.vocab, self.max_pos, self.type_vocab, n_labels, ln_eps,
+        cfg = _lib.CEConfig(self.hidden, n_layers, self.n_heads, self.ffn, self.vocab, self.max_pos, self.type_vocab, n_labels, ln_eps,
                             PRECISIONS[precision])
         ptrs = (C.c_void_p * len(tensors))(*[t.ctypes.data for t in tensors])
         h = C.c_void_p()
@@ -121,20 +157,22 @@ class BertEncoderGPU:
                 raise ValueError("token ids and token type ids differ in length")
 
     def forward_ids(self, seqs: Sequence[Tuple[Sequence[int], Sequence[int]]], mode: int = OUT_LOGITS) -> np.ndarray:
-        """seqs: (token_ids, type_ids) per sequence (unpadded).  Returns logits (n, n_labels), CLS states (n, 384)
-        or the hidden states of all tokens (sum of lengths, 384) by `mode`.  Sequences are packed back to back and
+        """seqs: (token_ids, type_ids) per sequence (unpadded).  Returns logits (n, n_labels), CLS states (n, hidden)
+        or the hidden states of all tokens (sum of lengths, hidden) by `mode`.  Sequences are packed back to back and
         processed in chunks of at most `max_tokens_per_call` tokens; inside a chunk they are sorted by length only for
         the launch bound (the result is independent of batch composition: there is no padding to attend to)."""
         torch = self._torch
         self._check(seqs)
         n = len(seqs)
-        width = {OUT_LOGITS: self.n_labels, OUT_CLS: HIDDEN, OUT_HIDDEN: HIDDEN}[mode]
+        width = {OUT_LOGITS: self.n_labels, OUT_CLS: self.hidden, OUT_HIDDEN: self.hidden}[mode]
         lens = np.array([len(s[0]) for s in seqs], dtype=np.int64)
         if mode == OUT_LOGITS and self.n_labels == 0:
             raise ValueError("this encoder was loaded without a classification head")
         out = np.empty((int(lens.sum()) if mode == OUT_HIDDEN else n, width), dtype=np.float32)
         lib = _lib.load()
         cap = min(self.max_tokens_per_call, FP32_MAX_TOKENS) if self.precision == "fp32" else self.max_tokens_per_call
+        if (self.hidden, self.n_heads, self.ffn) != (HIDDEN, HEADS, FFN):
+            cap = min(cap, OTHER_SHAPE_MAX_TOKENS)
         start = 0
         tok_done = 0
         while start < n:
@@ -186,7 +224,7 @@ class BertEncoderGPU:
         be at least every sequence's length (`out_of_range` reports a shorter one as a ValueError)."""
         torch = self._torch
         n_tokens = int(tok.numel())
-        width = {OUT_LOGITS: self.n_labels, OUT_CLS: HIDDEN, OUT_HIDDEN: HIDDEN}[mode]
+        width = {OUT_LOGITS: self.n_labels, OUT_CLS: self.hidden, OUT_HIDDEN: self.hidden}[mode]
         out = torch.empty((n_tokens if mode == OUT_HIDDEN else n_seqs, width), dtype=torch.float32, device=self._dev)
         p = lambda t: C.c_void_p(t.data_ptr())
         _lib.check(_lib.load().rr_ce_forward_dev(
@@ -258,10 +296,11 @@ class CrossEncoder:
     show_progress_bar=False)` -> float32 (len(pairs),) for a single-label model."""
 
     def __init__(self, state_dict: Dict, tokenizer: Optional[WordPieceTokenizer] = None, *, device: int = 0,
-                 max_length: int = 512, activation: Optional[str] = None, ln_eps: float = 1e-12, precision: str = "fp32"):
+                 max_length: int = 512, activation: Optional[str] = None, ln_eps: float = 1e-12, precision: str = "fp32",
+                 n_heads: Optional[int] = None):
         """``precision`` "fp32" (default: the reference reranks in fp32, app/app_product_search.py:277-278) or "bf16"
-        (fast path, logits within 2.5e-2): see BertEncoderGPU."""
-        self.model = BertEncoderGPU(state_dict, device=device, ln_eps=ln_eps, with_head=True, precision=precision)
+        (fast path, logits within 2.5e-2; hidden 384 / 12 heads / FFN 1536 only): see BertEncoderGPU, also for ``n_heads``."""
+        self.model = BertEncoderGPU(state_dict, device=device, ln_eps=ln_eps, with_head=True, precision=precision, n_heads=n_heads)
         if self.model.n_labels < 1:
             raise ValueError("the state dict has no pooler / classifier: not a sequence-classification checkpoint")
         self.tokenizer = tokenizer
@@ -275,6 +314,8 @@ class CrossEncoder:
         sd, vocab, cfg = load_state_dict_dir(path)
         tok = WordPieceTokenizer.from_vocab_file(vocab) if vocab else None
         kw.setdefault("ln_eps", float(cfg.get("layer_norm_eps", 1e-12)))
+        if cfg.get("num_attention_heads") is not None:
+            kw.setdefault("n_heads", int(cfg["num_attention_heads"]))
         return cls(sd, tok, **kw)
 
     def _post(self, logits: np.ndarray) -> np.ndarray:
@@ -306,13 +347,14 @@ class CrossEncoder:
 
 class QueryEncoder:
     """`SentenceTransformer` on the call the reference makes: `encode([query], normalize_embeddings=True)` ->
-    (n, 384) float32; CLS pooling (bge-small-en-v1.5's pooling config)."""
+    (n, hidden) float32 (384 for bge-small-en-v1.5; `.hidden`); CLS pooling (bge-small-en-v1.5's pooling config)."""
 
     def __init__(self, state_dict: Dict, tokenizer: Optional[WordPieceTokenizer] = None, *, device: int = 0,
-                 max_length: int = 512, ln_eps: float = 1e-12, precision: str = "fp32"):
+                 max_length: int = 512, ln_eps: float = 1e-12, precision: str = "fp32", n_heads: Optional[int] = None):
         """``precision`` "fp32" by default: the query vector feeds K1, whose answers are held to a 4e-7 tie band -- a bf16
         encoder would move dense scores by ~2e-3 (one short sequence per query: the fp32 forward costs microseconds)."""
-        self.model = BertEncoderGPU(state_dict, device=device, ln_eps=ln_eps, with_head=False, precision=precision)
+        self.model = BertEncoderGPU(state_dict, device=device, ln_eps=ln_eps, with_head=False, precision=precision, n_heads=n_heads)
+        self.hidden = self.model.hidden                 # the width of the vectors: an index's `dim`
         self.tokenizer = tokenizer
         self.max_length = min(int(max_length), self.model.max_pos)
 
@@ -321,6 +363,8 @@ class QueryEncoder:
         sd, vocab, cfg = load_state_dict_dir(path)
         tok = WordPieceTokenizer.from_vocab_file(vocab) if vocab else None
         kw.setdefault("ln_eps", float(cfg.get("layer_norm_eps", 1e-12)))
+        if cfg.get("num_attention_heads") is not None:
+            kw.setdefault("n_heads", int(cfg["num_attention_heads"]))
         return cls(sd, tok, **kw)
 
     def encode_ids(self, seqs, normalize_embeddings: bool = False) -> np.ndarray:
@@ -330,7 +374,7 @@ class QueryEncoder:
         return e
 
     def encode_dev(self, tok, typ, pos, cu, n_seqs: int, max_len: int):
-        """CLS rows (n_seqs, 384), a DEVICE tensor, of sequences already packed on the device (embed.DeviceWordPiece makes
+        """CLS rows (n_seqs, hidden), a DEVICE tensor, of sequences already packed on the device (embed.DeviceWordPiece makes
         them from text): `forward_packed_dev` with OUT_CLS, asynchronous on torch's current stream, not normalised."""
         return self.model.forward_packed_dev(tok, typ, pos, cu, n_seqs, max_len, OUT_CLS)
 

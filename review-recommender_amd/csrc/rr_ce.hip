@@ -24,12 +24,15 @@
 //                    in the same token-stationary form
 //   ce_head          pooler (tanh) + classifier on the [CLS] rows, fp32
 // The fp32 precision (RR_CE_PRECISION_F32) has kernels of its own: rr_ce_h2.hip, and the wide-range ones further down.
+// Every block shape other than 384 / 12 / 1536 (rr_ce_w.h lists the family) runs ce_forward_w below: ce_gemm_x3 at the
+// configuration's N, K and the runtime-shape kernels of rr_ce_w.hip, fp32 precision only.
 #include <cmath>
 #include <type_traits>
 #include <vector>
 
 #include "rr_common.h"
 #include "rr_ce_h2.h"
+#include "rr_ce_w.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -1211,6 +1214,11 @@ struct rr_ce {
     void *hx = nullptr, *ctxh = nullptr;      // h2 images of the residual stream / the attention context (inter32 doubles as the FFN's)
     unsigned* d_flag = nullptr;                // OR-ed with 1 by a producer that met a value outside fp16's range
     bool wide_range = false;                   // rr_ce_set_wide_range: the bf16 three-term kernels (any fp32 range)
+    // a shape other than 384 / 12 / 1536 (ce_forward_w, rr_ce_w.hip): fp32 weights only, scratch sized by the configuration --
+    // h32 [capw][hidden], qkv32 [capw][3 hidden], y32 [capw][hidden], inter32 [capw][max(hidden, ffn)]
+    bool other_shape = false;
+    int64_t capw = 0;
+    float* zero_bias = nullptr;                // [hidden] zeros: the bias of FFN-2's K chunks behind the first
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     std::mutex mu;
@@ -1268,7 +1276,7 @@ extern "C" int rr_ce_destroy(rr_ce* ce) {
     hipFree(ce->h32); hipFree(ce->hb); hipFree(ce->qkv); hipFree(ce->ctx);
     hipFree(ce->h32c); hipFree(ce->hbc); hipFree(ce->ctxc);
     hipFree(ce->qkv32); hipFree(ce->y32); hipFree(ce->inter32);
-    hipFree(ce->hx); hipFree(ce->ctxh); hipFree(ce->d_flag);
+    hipFree(ce->hx); hipFree(ce->ctxh); hipFree(ce->d_flag); hipFree(ce->zero_bias);
     hipFree(ce->h32c32); hipFree(ce->y32c); hipFree(ce->hxc); hipFree(ce->ctxhc); hipFree(ce->interhc);
     if (ce->ev0) hipEventDestroy(ce->ev0);
     if (ce->ev1) hipEventDestroy(ce->ev1);
@@ -1282,9 +1290,14 @@ extern "C" int rr_ce_create(int32_t device, const rr_ce_config* cfg, const float
     *out = nullptr;
     RR_REQUIRE(cfg && t, "rr_ce_create: NULL argument");
     static_assert(CE_H % 128 == 0 && CE_FFN % 128 == 0, "ce_gemm_x3 and ce_gemm_h2 take 128 output features per workgroup");
-    RR_REQUIRE(cfg->hidden == CE_H && cfg->n_heads == CE_HEADS && cfg->ffn == CE_FFN,
-               "rr_ce_create: the kernels are built for hidden 384 / 12 heads x 32 / FFN 1536 (MiniLM-L6, bge-small); "
-               "got hidden %d heads %d ffn %d", cfg->hidden, cfg->n_heads, cfg->ffn);
+    // 384 / 12 / 1536 has the kernels of this file and of rr_ce_h2.hip; every other shape of the family runs ce_forward_w
+    const bool other_shape = !(cfg->hidden == CE_H && cfg->n_heads == CE_HEADS && cfg->ffn == CE_FFN);
+    if (other_shape) {
+        if (int rc = ce_w_check_shape("rr_ce_create", cfg->hidden, cfg->n_heads, cfg->ffn, true)) return rc;
+        RR_REQUIRE(cfg->precision != RR_CE_PRECISION_BF16,
+                   "rr_ce_create: precision bf16 is built for hidden 384 / 12 heads / FFN 1536 only; hidden %d / %d heads / FFN %d "
+                   "runs in precision fp32", cfg->hidden, cfg->n_heads, cfg->ffn);
+    }
     RR_REQUIRE(cfg->n_layers >= 1 && cfg->n_layers <= 48 && cfg->vocab >= 1 && cfg->max_pos >= 1 && cfg->max_pos <= 512 &&
                    cfg->type_vocab >= 1 && cfg->n_labels >= 0 && cfg->n_labels <= 64 && cfg->ln_eps > 0.f,
                "rr_ce_create: bad configuration (layers %d vocab %d max_pos %d types %d labels %d)", cfg->n_layers,
@@ -1300,7 +1313,8 @@ extern "C" int rr_ce_create(int32_t device, const rr_ce_config* cfg, const float
     ce->device = device;
     ce->cfg = *cfg;
     ce->layers = new rr_ce_layer[cfg->n_layers];
-    const size_t H = CE_H, F = CE_FFN;
+    ce->other_shape = other_shape;
+    const size_t H = (size_t)cfg->hidden, F = (size_t)cfg->ffn;
     int rc = RR_OK;
     auto f32 = [&](float** d, const float* s, size_t n) { if (!rc) rc = ce_upload_f32(d, s, n); };
     auto b16 = [&](unsigned short* d, const float* s, size_t n) { if (!rc) rc = ce_upload_bf16(d, s, n); };
@@ -1315,20 +1329,24 @@ extern "C" int rr_ce_create(int32_t device, const rr_ce_config* cfg, const float
     for (int l = 0; l < cfg->n_layers && !rc; ++l) {
         const float* const* p = t + 5 + 16 * l;      // q_w q_b k_w k_b v_w v_b o_w o_b ln1_g ln1_b f1_w f1_b f2_w f2_b ln2_g ln2_b
         rr_ce_layer& L = ce->layers[l];
-        alloc16(&L.wqkv, 3 * H * H);
-        if (!rc) { b16(L.wqkv, p[0], H * H); b16(L.wqkv + H * H, p[2], H * H); b16(L.wqkv + 2 * H * H, p[4], H * H); }
+        if (!other_shape) alloc16(&L.wqkv, 3 * H * H);
+        if (!rc && !other_shape) { b16(L.wqkv, p[0], H * H); b16(L.wqkv + H * H, p[2], H * H); b16(L.wqkv + 2 * H * H, p[4], H * H); }
         if (!rc && hipMalloc((void**)&L.bqkv, sizeof(float) * 3 * H) != hipSuccess) rc = RR_E_NOMEM;
         if (!rc) {
             hipMemcpy(L.bqkv, p[1], sizeof(float) * H, hipMemcpyHostToDevice);
             hipMemcpy(L.bqkv + H, p[3], sizeof(float) * H, hipMemcpyHostToDevice);
             hipMemcpy(L.bqkv + 2 * H, p[5], sizeof(float) * H, hipMemcpyHostToDevice);
         }
-        alloc16(&L.wo, H * H);   b16(L.wo, p[6], H * H);   f32(&L.bo, p[7], H);
+        f32(&L.bo, p[7], H);
         f32(&L.ln1_g, p[8], H);  f32(&L.ln1_b, p[9], H);
-        alloc16(&L.w1, F * H);   b16(L.w1, p[10], F * H);  f32(&L.b1, p[11], F);
+        f32(&L.b1, p[11], F);
         f32(&L.b2, p[13], H);
-        alloc16(&L.w2p, H * F);
-        if (!rc) {
+        if (!other_shape) {
+            alloc16(&L.wo, H * H);   b16(L.wo, p[6], H * H);
+            alloc16(&L.w1, F * H);   b16(L.w1, p[10], F * H);
+            alloc16(&L.w2p, H * F);
+        }
+        if (!rc && !other_shape) {
             // position 8 h + jj of a 16-group holds column 8 (jj >> 2) + 4 h + (jj & 3): quads (0, 2, 1, 3)
             std::vector<float> perm(H * F);
             for (size_t n = 0; n < H; ++n)
@@ -1348,10 +1366,20 @@ extern "C" int rr_ce_create(int32_t device, const rr_ce_config* cfg, const float
             }
             f32(&L.wo32, p[6], H * H);
             f32(&L.w1_32, p[10], F * H);
-            f32(&L.w2_32, p[12], H * F);
+            if (!other_shape) f32(&L.w2_32, p[12], H * F);
+            else if (!rc) {
+                // FFN-2 runs one K chunk of CE_W_KCHUNK columns at a time: chunk c = columns [k0, k1) as a matrix [H][k1 - k0]
+                // of its own, the chunks back to back (chunk c starts at H * k0)
+                std::vector<float> ch(H * F);
+                for (size_t k0 = 0; k0 < F; k0 += CE_W_KCHUNK) {
+                    const size_t w = F - k0 < CE_W_KCHUNK ? F - k0 : CE_W_KCHUNK;
+                    for (size_t n = 0; n < H; ++n) memcpy(&ch[H * k0 + n * w], p[12] + n * F + k0, sizeof(float) * w);
+                }
+                f32(&L.w2_32, ch.data(), H * F);
+            }
             // the same four matrices as h2 images (two fp16 planes, as large as the fp32 matrix): ce_gemm_h2's A operand
             auto h2 = [&](void** d, const float* src32, size_t n, size_t k) {
-                if (rc) return;
+                if (rc || other_shape) return;
                 if (hipMalloc(d, n * k * 4) != hipSuccess) { rc = RR_E_NOMEM; return; }
                 ce_h2_pack(src32, (int)n, (int)k, *d, (int64_t)n, nullptr);
             };
@@ -1366,7 +1394,11 @@ extern "C" int rr_ce_create(int32_t device, const rr_ce_config* cfg, const float
         f32(&ce->wp, p[0], H * H); f32(&ce->bp, p[1], H);
         f32(&ce->wc, p[2], (size_t)cfg->n_labels * H); f32(&ce->bc, p[3], (size_t)cfg->n_labels);
     }
-    if (!rc) {
+    if (!rc && other_shape) {
+        std::vector<float> zeros(H, 0.f);
+        f32(&ce->zero_bias, zeros.data(), H);
+    }
+    if (!rc && !other_shape) {
         std::vector<float> tab(2 * CE_GELU_N);
         ce_gelu_table(tab.data());
         f32(&ce->gelu_tab, tab.data(), tab.size());
@@ -1644,6 +1676,70 @@ static int ce_forward_x3(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d
     return RR_OK;
 }
 
+// A shape other than 384 / 12 / 1536: the scratch of ce_forward_w, sized by the configuration
+static int ce_reserve_w(rr_ce* ce, int64_t tokens) {
+    if (tokens <= ce->capw) return RR_OK;
+    RR_HIP_TRY(hipDeviceSynchronize());
+    hipFree(ce->h32); hipFree(ce->qkv32); hipFree(ce->y32); hipFree(ce->inter32);
+    ce->h32 = ce->qkv32 = ce->y32 = ce->inter32 = nullptr;
+    ce->capw = 0;
+    const size_t n = (size_t)rr_round_up(tokens, 1024), H = (size_t)ce->cfg.hidden, F = (size_t)ce->cfg.ffn;
+    hipError_t e = hipMalloc((void**)&ce->h32, n * H * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&ce->qkv32, n * 3 * H * 4);
+    const size_t parts = (F + CE_W_KCHUNK - 1) / CE_W_KCHUNK;                               // FFN-2's partial products, T x hidden each
+    if (e == hipSuccess) e = hipMalloc((void**)&ce->y32, n * H * 4 * parts);
+    if (e == hipSuccess) e = hipMalloc((void**)&ce->inter32, n * (F > H ? F : H) * 4);      // (also the output projection's T x hidden)
+    if (e != hipSuccess) { rr_set_error("rr_ce_forward: fp32 activation scratch for %lld tokens: %s", (long long)tokens, hipGetErrorString(e)); return RR_E_NOMEM; }
+    ce->capw = (int64_t)n;
+    return RR_OK;
+}
+
+// Any other shape of the family (rr_ce_w.h): the structure of ce_forward_x3 with N, K from the configuration, the runtime-shape
+// small kernels of rr_ce_w.hip and its attention at head dim 32 / 64 -- and FFN-2 one K chunk of CE_W_KCHUNK per launch (a sum
+// over 4096 k in ce_gemm_x3's one accumulator is twice numpy float32's error).  Three bf16 terms per operand: any fp32 range.
+static int ce_forward_w(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d_type_ids, const int32_t* d_pos_ids,
+                        const int32_t* d_cu_seqlens, int n_seqs, int T, int mode, float* d_out, hipStream_t st) {
+    const int H = ce->cfg.hidden, F = ce->cfg.ffn, heads = ce->cfg.n_heads;
+    ce_w_embed_ln(d_token_ids, d_type_ids, d_pos_ids, T, H, ce->cfg.vocab, ce->cfg.max_pos, ce->cfg.type_vocab, ce->word, ce->pos, ce->type,
+                  ce->eln_g, ce->eln_b, ce->cfg.ln_eps, ce->h32, st);
+    const unsigned mt = (unsigned)((T + 127) / 128);
+    for (int l = 0; l < ce->cfg.n_layers; ++l) {
+        const rr_ce_layer& L = ce->layers[l];
+        hipLaunchKernelGGL((ce_gemm_x3<false>), dim3(3 * H / 128, mt), dim3(256), 0, st, ce->h32, L.wqkv32, L.bqkv, T, 3 * H, H, ce->qkv32);
+        ce_w_attention(ce->qkv32, d_cu_seqlens, n_seqs, H, heads, ce->y32, st);
+        // (y32 holds the context; the projection's output goes to the first T x hidden floats of inter32)
+        hipLaunchKernelGGL((ce_gemm_x3<false>), dim3(H / 128, mt), dim3(256), 0, st, ce->y32, L.wo32, L.bo, T, H, H, ce->inter32);
+        ce_w_add_ln(ce->inter32, 1, 0, ce->h32, T, H, L.ln1_g, L.ln1_b, ce->cfg.ln_eps, st);
+        // The FFN one K chunk of FFN-2 at a time: columns [k0, k0 + w) of the intermediate are a matrix [T][w] of their own
+        // (FFN-1 on rows k0 .. of W1: every element what the whole product gives), and y32 part c = their product with chunk
+        // c of W2.  The LayerNorm adds the parts: at ffn 4096 two sums over 2048 k instead of one accumulator over 4096.
+        int parts = 0;
+        for (int k0 = 0; k0 < F; k0 += CE_W_KCHUNK, ++parts) {
+            const int w = F - k0 < CE_W_KCHUNK ? F - k0 : CE_W_KCHUNK;
+            float* xc = ce->inter32 + (size_t)T * k0;
+            hipLaunchKernelGGL((ce_gemm_x3<true>), dim3(w / 128, mt), dim3(256), 0, st, ce->h32, L.w1_32 + (size_t)k0 * H, L.b1 + k0, T, w, H, xc);
+            hipLaunchKernelGGL((ce_gemm_x3<false>), dim3(H / 128, mt), dim3(256), 0, st, xc, L.w2_32 + (size_t)H * k0,
+                               parts == 0 ? L.b2 : ce->zero_bias, T, H, w, ce->y32 + (size_t)parts * T * H);
+        }
+        ce_w_add_ln(ce->y32, parts, (int64_t)T * H, ce->h32, T, H, L.ln2_g, L.ln2_b, ce->cfg.ln_eps, st);
+    }
+    if (mode == RR_CE_OUT_HIDDEN)
+        RR_HIP_TRY(hipMemcpyAsync(d_out, ce->h32, sizeof(float) * (size_t)T * H, hipMemcpyDeviceToDevice, st));
+    else
+        ce_w_head(ce->h32, d_cu_seqlens, n_seqs, H, ce->wp, ce->bp, ce->wc, ce->bc, ce->cfg.n_labels, mode, d_out, st);
+    return RR_OK;
+}
+
+static int ce_w_attributes_once(int device) {
+    static std::mutex mu;
+    static bool done[64] = {false};
+    std::lock_guard<std::mutex> lk(mu);
+    if (device < 0 || device >= 64 || done[device]) return RR_OK;
+    if (int rc = ce_w_set_attributes()) return rc;
+    done[device] = true;
+    return RR_OK;
+}
+
 extern "C" int rr_ce_forward_dev(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d_type_ids,
                                  const int32_t* d_pos_ids, const int32_t* d_cu_seqlens, int32_t n_seqs,
                                  int64_t n_tokens, int32_t max_len, int32_t mode, float* d_out, void* stream) {
@@ -1656,6 +1752,22 @@ extern "C" int rr_ce_forward_dev(rr_ce* ce, const int32_t* d_token_ids, const in
     RR_REQUIRE(mode != RR_CE_OUT_LOGITS || ce->cfg.n_labels > 0, "rr_ce_forward_dev: the model was created without a classifier head");
     std::lock_guard<std::mutex> lk(ce->mu);
     RR_HIP_TRY(hipSetDevice(ce->device));
+    if (ce->other_shape) {                                  // routed by shape: rr_ce_set_wide_range changes nothing here
+        RR_REQUIRE(n_tokens <= CE_W_MAX_TOKENS, "rr_ce_forward_dev: %lld tokens in one call at hidden %d; at most %lld",
+                   (long long)n_tokens, ce->cfg.hidden, (long long)CE_W_MAX_TOKENS);
+        int rc = ce_reserve_w(ce, n_tokens);
+        if (!rc) rc = ce_w_attributes_once(ce->device);
+        if (rc) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        hipEventRecord(ce->ev0, st);
+        RR_HIP_TRY(hipMemsetAsync(ce->d_flag, 0, 4, st));   // (rr_ce_range_status reads it: no fp16 anywhere, never raised)
+        rc = ce_forward_w(ce, d_token_ids, d_type_ids, d_pos_ids, d_cu_seqlens, n_seqs, (int)n_tokens, mode, d_out, st);
+        if (rc) return rc;
+        hipEventRecord(ce->ev1, st);
+        ce->timed = true;
+        RR_HIP_TRY(hipGetLastError());
+        return RR_OK;
+    }
     const bool f32 = ce->cfg.precision == RR_CE_PRECISION_F32;
     const bool h2 = f32 && !ce->wide_range;
     // scratch: per token for every path, and one compact row per sequence for the [CLS]-only tail of the last layer
@@ -1783,6 +1895,21 @@ extern "C" int rr_debug_ce_embed_ln(rr_ce* ce, const int32_t* d_tok, const int32
     RR_REQUIRE(T >= 1, "rr_debug_ce_embed_ln: %d tokens", T);
     CE_DBG_HANDLE("rr_debug_ce_embed_ln");
     ce_launch_embed_ln(ce, d_tok, d_typ, d_pos, T, d_h32, d_hb, nullptr);
+    RR_HIP_TRY(hipGetLastError());
+    RR_HIP_TRY(hipDeviceSynchronize());
+    return RR_OK;
+}
+
+// tests/test_gpu_k5_wide_kernels.py: h32 [T][hidden] = LayerNorm(word[tok] + type[typ] + pos[pos]) through ce_embed_ln_w (rr_ce_w.hip) with
+// the tables of a handle of either precision and any shape (at 384 the bits of rr_debug_ce_embed_ln's h32)
+extern "C" int rr_debug_ce_w_embed_ln(rr_ce* ce, const int32_t* d_tok, const int32_t* d_typ, const int32_t* d_pos, int32_t T, float* d_h32) {
+    RR_REQUIRE(d_tok && d_typ && d_pos && d_h32, "rr_debug_ce_w_embed_ln: NULL argument");
+    RR_REQUIRE(T >= 1, "rr_debug_ce_w_embed_ln: %d tokens", T);
+    RR_REQUIRE(ce, "rr_debug_ce_w_embed_ln: NULL handle");
+    std::lock_guard<std::mutex> lk(ce->mu);
+    RR_HIP_TRY(hipSetDevice(ce->device));
+    ce_w_embed_ln(d_tok, d_typ, d_pos, T, ce->cfg.hidden, ce->cfg.vocab, ce->cfg.max_pos, ce->cfg.type_vocab, ce->word, ce->pos, ce->type,
+                  ce->eln_g, ce->eln_b, ce->cfg.ln_eps, d_h32, nullptr);
     RR_HIP_TRY(hipGetLastError());
     RR_HIP_TRY(hipDeviceSynchronize());
     return RR_OK;

@@ -143,5 +143,13 @@ int rr_debug_ce_bf16_proj(rr_ce* ce, int32_t layer, const unsigned short* d_hb, 
 int rr_debug_ce_bf16_attention(const unsigned short* d_qkv, int32_t T, const int32_t* d_cu, int32_t n_seqs, int32_t max_len,
                                unsigned short* d_ctx, unsigned short* d_ctx_cls);
 int rr_debug_ce_bf16_ffn(rr_ce* ce, int32_t layer, const unsigned short* d_ctx, float* d_h32, unsigned short* d_hb, int32_t M);
+// tests/test_gpu_k5_wide_kernels.py: the runtime-shape kernels of rr_ce_w.hip (ce_attention_x3w, ce_add_ln_w, ce_embed_ln_w) one
+// launch at a time on caller data, through the launchers ce_forward_w calls.  The attention takes qkv [T][3 hidden] with Q
+// unscaled and writes ctx [T][hidden] (hidden % 128 == 0 in [128, 1024], hidden / n_heads 32 or 64); the add-LayerNorm updates
+// d_h in place; the embedding LayerNorm takes the tables of a handle of either precision and any shape and writes
+// h32 [T][hidden].  See the definitions.
+int rr_debug_ce_w_attention(const float* d_qkv, int32_t T, const int32_t* d_cu, int32_t n_seqs, int32_t hidden, int32_t n_heads, float* d_ctx);
+int rr_debug_ce_w_add_ln(const float* d_y, float* d_h, int32_t T, int32_t hidden, const float* d_g, const float* d_b, float eps);
+int rr_debug_ce_w_embed_ln(rr_ce* ce, const int32_t* d_tok, const int32_t* d_typ, const int32_t* d_pos, int32_t T, float* d_h32);
 }
 #endif

@@ -40,7 +40,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .cross_encoder import HIDDEN, OUT_CLS
+from .cross_encoder import OUT_CLS
 from .index import ProductIndex
 from .wordpiece import WordPieceTokenizer
 
@@ -271,15 +271,16 @@ def _embed_into(index: ProductIndex, lens: Sequence[int], queue_docs, host_text,
     if encoder.tokenizer is None:
         raise ValueError("no vocabulary was loaded: the builder tokenises text")
     n = len(lens)
-    if first_row < 0 or first_row + n > index.n_rows or index.dim != HIDDEN:
-        raise ValueError(f"{n} rows of dim {HIDDEN} from row {first_row} do not fit an index of {index.n_rows} x {index.dim}")
+    hidden = encoder.model.hidden                     # the encoder's width = the rows' width
+    if first_row < 0 or first_row + n > index.n_rows or index.dim != hidden:
+        raise ValueError(f"{n} rows of dim {hidden} from row {first_row} do not fit an index of {index.n_rows} x {index.dim}")
     model, L = encoder.model, encoder.max_length
     dev = torch.device("cuda", model.device)
     wp = getattr(encoder, "_device_wp", None)
     if wp is None:
         wp = encoder._device_wp = DeviceWordPiece(encoder.tokenizer, model.device)
     lib = _lib.load()
-    kept = np.empty((n, HIDDEN), dtype=np.float32) if keep_rows else None
+    kept = np.empty((n, hidden), dtype=np.float32) if keep_rows else None
     fp32 = model.precision == "fp32"
     host_docs: List[int] = []
     with torch.cuda.device(dev):
@@ -295,7 +296,7 @@ def _embed_into(index: ProductIndex, lens: Sequence[int], queue_docs, host_text,
         def keep(out, where):
             # the normalised fp32 rows of this chunk through a small fp32 index: the same kernel, so the same bits
             if scratch[0] is None or scratch[0].n_rows < out.shape[0]:
-                scratch[0] = ProductIndex(None, n_rows=max(out.shape[0], 256), dim=HIDDEN, device=model.device)
+                scratch[0] = ProductIndex(None, n_rows=max(out.shape[0], 256), dim=hidden, device=model.device)
             _lib.check(lib.rr_index_store_rows_dev(scratch[0].handle, C.c_void_p(out.data_ptr()), out.shape[0], 0, None,
                                                    NORMALIZE_EPS, C.c_void_p(main.cuda_stream)), "rr_index_store_rows_dev")
             kept[where] = scratch[0].download_rows(0, out.shape[0])
@@ -413,7 +414,7 @@ def build_product_embeddings(products, encoder, *, text_col: str = "agg_text", r
     if not (0 <= lo < hi <= len(texts)):
         raise ValueError(f"rows=({lo}, {hi}) outside the {len(texts)} products left after filtering")
     meta, texts = meta.iloc[lo:hi].reset_index(drop=True), texts[lo:hi]
-    index = ProductIndex(None, n_rows=hi - lo, dim=HIDDEN, device=encoder.model.device, row_offset=lo, dtype=dtype)
+    index = ProductIndex(None, n_rows=hi - lo, dim=encoder.model.hidden, device=encoder.model.device, row_offset=lo, dtype=dtype)
     emb = embed_texts_into(index, texts, encoder, chunk_tokens=chunk_tokens,
                            keep_rows=data_dir is not None and dtype != "f32", stats=stats)
     if data_dir is not None:
@@ -509,7 +510,7 @@ def build_product_embeddings_device(products, text, encoder, *, rows: Optional[T
             lens_k = lens[kept]
             lap("host_clean")
 
-            index = ProductIndex(None, n_rows=m, dim=HIDDEN, device=model.device, row_offset=lo, dtype=dtype)
+            index = ProductIndex(None, n_rows=m, dim=model.hidden, device=model.device, row_offset=lo, dtype=dtype)
             keep_rows = data_dir is not None and dtype != "f32"
             emb_parts: List[np.ndarray] = []
             host_docs: List[int] = []
@@ -652,7 +653,7 @@ def build_review_embeddings(reviews, encoder, *, no_spam: bool = False, no_dedup
                             stage_bytes: int = STAGE_BYTES, log=None):
     """nlp/11_build_product_embeddings.py:99-165 on the GPU -> (table, emb, ReviewIndex or None).
 
-    table = the surviving rows of id, sku, ts, stars, text (the RAW text) in file order, emb = their float32 (m, 384) rows,
+    table = the surviving rows of id, sku, ts, stars, text (the RAW text) in file order, emb = their float32 (m, hidden) rows (hidden = the encoder's width),
     l2-normalised with eps 1e-12.  The raw text goes to the device in row blocks through two pinned buffers of `stage_bytes`;
     rr_textprep_clean_dev normalises it in place and answers a length and a status word per row; the rows it flags
     (textprep.model_clean says which) are cleaned by `normalize_text` / `looks_spammy` here and written into their slots
@@ -770,7 +771,7 @@ def build_review_embeddings(reviews, encoder, *, no_spam: bool = False, no_dedup
             def queue_docs(wp, a, b, L, cap):
                 return wp.queue_dev(d_ctext.data_ptr() + int(coff[a]), int(coff[b] - coff[a]), d_coff[a:b + 1] - int(coff[a]), L, cap)
 
-            index = ProductIndex(None, n_rows=m, dim=HIDDEN, device=model.device)
+            index = ProductIndex(None, n_rows=m, dim=model.hidden, device=model.device)
             tok_stats: dict = {}
             _embed_into(index, lens_k.tolist(), queue_docs, lambda i: normalize_text(texts[int(keep[i])]), encoder, first_row=0,
                         chunk_tokens=chunk_tokens, keep_rows=False, stats=tok_stats)
@@ -782,7 +783,7 @@ def build_review_embeddings(reviews, encoder, *, no_spam: bool = False, no_dedup
             review_index = None
             if product_skus is not None:
                 from .reviews import ReviewIndex
-                d_rows = torch.empty((m, HIDDEN), dtype=torch.float32, device=dev)
+                d_rows = torch.empty((m, model.hidden), dtype=torch.float32, device=dev)
                 _lib.check(_lib.load().rr_index_copy_rows_dev(index.handle, 0, m, C.c_void_p(d_rows.data_ptr()), C.c_void_p(st_ptr)),
                            "rr_index_copy_rows_dev")
                 review_index = ReviewIndex.from_device_rows(table, d_rows, product_skus, device=model.device)

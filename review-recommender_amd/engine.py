@@ -673,6 +673,10 @@ class SearchEngine:
                              f"{n_emb} rows")
         if "sku" not in meta.columns or "agg_text" not in meta.columns:
             raise ValueError("metadata must have 'sku' and 'agg_text' columns")  # app/test.py:138-139
+        from .cross_encoder import QueryEncoder as _QueryEncoder
+        idx_dim = embeddings.shape[1] if index is None else index.dim
+        if isinstance(encoder, _QueryEncoder) and encoder.hidden != idx_dim:
+            raise ValueError(f"the query encoder makes vectors of width {encoder.hidden} but the index has dim {idx_dim}")
         self.flavour = flavour
         self.meta = meta.reset_index(drop=True)
         self.encoder, self.cross_encoder = encoder, cross_encoder

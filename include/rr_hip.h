@@ -420,6 +420,10 @@ int rr_ce_destroy(rr_ce* ce);
 #define RR_CE_OUT_LOGITS 0   /* d_out [n_seqs][n_labels]: classifier(tanh(pooler([CLS]))), raw logits (no activation) */
 #define RR_CE_OUT_CLS    1   /* d_out [n_seqs][hidden]: last_hidden_state[:, 0] (CLS pooling of the query encoder) */
 #define RR_CE_OUT_HIDDEN 2   /* d_out [n_tokens][hidden]: last_hidden_state of every token (diagnostic / parity tests) */
+#define RR_CE_OUT_MEAN   3   /* d_out [n_seqs][hidden]: the mean of last_hidden_state over a sequence's tokens, float32, in ONE
+                              * fixed order that depends on the sequence's length only (csrc/rr_ce_pool.hip): the pooling of
+                              * sentence-transformers' `pooling_mode_mean_tokens` (all-MiniLM, e5, gte).  Not normalised.  Every
+                              * layer runs over all tokens: the last layer's [CLS]-only tail serves LOGITS and CLS alone. */
 /* Forward over PACKED sequences (no padding is computed): sequence s owns tokens [cu_seqlens[s], cu_seqlens[s+1]);
  * token / type / position ids are per token (position = index inside its sequence); max_len = longest sequence: it must be
  * at least every sequence's length (attention sizes its LDS from it).  In RR_CE_PRECISION_F32 a longer sequence gets NaN
@@ -443,7 +447,7 @@ int rr_ce_forward_dev(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d_ty
 int rr_ce_last_forward_ms(rr_ce* ce, float* out_ms);
 /* RR_CE_PRECISION_F32 multiplies on the fp16 matrix cores: every fp32 operand as hi + lo / 2048 in two fp16 numbers, three
  * products per fp32 product (csrc/rr_ce_h2.hip; as exact as an fp32 multiply-add chain).  fp16 ends at 65504: a forward pass
- * that meets a larger activation raises a flag on the device, writes NaN logits / CLS rows for the whole call (never a wrong
+ * that meets a larger activation raises a flag on the device, writes NaN logits / CLS rows / mean-pooled rows for the whole call (never a wrong
  * finite number; RR_CE_OUT_HIDDEN rows are left as computed: ask here) and reports it here -- *out_of_range = 1 -- once
  * the pass has finished (this call waits for it).  A pass whose max_len was below a sequence's length (rr_ce_forward_dev)
  * makes this call return RR_E_INVALID instead: running it again on the wide-range kernels would not help.
@@ -859,8 +863,8 @@ int rr_query_strip_dev(rr_query* h, const int32_t* d_wp_tok, const int32_t* d_wp
  * beyond a capacity (*out_bad = how many). */
 int rr_query_status(rr_query* h, int32_t* out_bad);
 
-/* The query VECTORS of a batch: the encoder's CLS rows (rr_ce_forward_dev with RR_CE_OUT_CLS over the WordPiece ids of the
- * same staged bytes) to the unit vectors K1 reads.  Row q of d_out = d_rows[q] / max(||d_rows[q]||, eps) in float32, every
+/* The query VECTORS of a batch: the encoder's pooled rows (rr_ce_forward_dev with RR_CE_OUT_CLS, or RR_CE_OUT_MEAN for
+ * an encoder that pools the mean over the tokens, over the WordPiece ids of the same staged bytes) to the unit vectors K1 reads.  Row q of d_out = d_rows[q] / max(||d_rows[q]||, eps) in float32, every
  * rounding the one numpy makes in `e / np.maximum(np.linalg.norm(e, axis=1, keepdims=True), eps)` on a C-contiguous float32
  * array (cross_encoder.QueryEncoder.encode_ids), so the result equals the host's bit for bit (querytext.model_query_vectors
  * states the same in plain Python; tests/test_query_vectors_model.py proves it against numpy):

@@ -205,7 +205,9 @@ DEBUG_PROTOTYPES = {
     "rr_debug_ce_w_attention": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "rr_debug_ce_w_add_ln": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_f32]),
     "rr_debug_ce_w_embed_ln": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
-    "rr_debug_ce_embed_ln": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "rr_debug_ce_pool_mean": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp]),
+    "rr_debug_ce_pool_time": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "rr_debug_ce_embed_ln":(C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "rr_debug_ce_bf16_proj": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp]),
     "rr_debug_ce_bf16_attention": (C.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "rr_debug_ce_bf16_ffn": (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32]),

@@ -54,6 +54,10 @@ def parse_args(argv=None):
     ap.add_argument("--ce-precision", choices=["fp32", "bf16"], default="fp32",
                     help="arithmetic of the two GPU encoders: fp32 = the reference's (logits / embeddings within 1e-5 of "
                          "transformers; ~6x the time of bf16), bf16 = the fast path (2.5e-2 on logits)")
+    ap.add_argument("--pooling", choices=["auto", "cls", "mean"], default="auto",
+                    help="the query encoder's sentence vector: auto = what --emb-model-dir's 1_Pooling/config.json says (cls "
+                         "without one; any pooling but cls / mean is refused), cls = last_hidden_state[:, 0], mean = the mean "
+                         "over the tokens; it must be the pooling the product vectors were built with")
     ap.add_argument("--gate", choices=["host", "device"], default="host",
                     help="where the attribute gate's terms are matched: host = str.lower() and substring searches in Python "
                          "(the reference's way), device = a gate plane of agg_text[:6000] on the GPU (csrc/rr_gate.hip; up to "
@@ -76,7 +80,8 @@ def _load_encoders(args=None):
     if args is not None and (args.emb_model_dir or args.rerank_model_dir):
         from .cross_encoder import CrossEncoder, QueryEncoder
         if args.emb_model_dir:
-            enc = QueryEncoder.from_pretrained_dir(args.emb_model_dir, device=args.device, precision=args.ce_precision)
+            enc = QueryEncoder.from_pretrained_dir(args.emb_model_dir, device=args.device, precision=args.ce_precision,
+                                                   pooling=getattr(args, "pooling", "auto"))
         if args.rerank_model_dir:
             try:
                 ce = CrossEncoder.from_pretrained_dir(args.rerank_model_dir, device=args.device, precision=args.ce_precision)

@@ -31,7 +31,8 @@ import numpy as np
 from . import _lib
 from .wordpiece import WordPieceTokenizer
 
-OUT_LOGITS, OUT_CLS, OUT_HIDDEN = 0, 1, 2       # RR_CE_OUT_*
+OUT_LOGITS, OUT_CLS, OUT_HIDDEN, OUT_MEAN = 0, 1, 2, 3       # RR_CE_OUT_*
+POOLINGS = {"cls": OUT_CLS, "mean": OUT_MEAN}    # QueryEncoder(pooling=...): the sentence vector's output mode
 PRECISIONS = {"bf16": 0, "fp32": 1}              # RR_CE_PRECISION_*
 HIDDEN, HEADS, FFN = 384, 12, 1536                  # the shape with kernels of its own in both precisions
 MAX_HIDDEN, MAX_FFN = 1024, 4096                    # the family of every other shape (csrc/rr_ce_w.h)
@@ -156,15 +157,21 @@ class BertEncoderGPU:
             if len(typ) != len(ids):
                 raise ValueError("token ids and token type ids differ in length")
 
+    def _width(self, mode: int) -> int:
+        widths = {OUT_LOGITS: self.n_labels, OUT_CLS: self.hidden, OUT_HIDDEN: self.hidden, OUT_MEAN: self.hidden}
+        if mode not in widths:
+            raise ValueError(f"rr_ce_forward_dev: unknown mode {mode}")
+        return widths[mode]
+
     def forward_ids(self, seqs: Sequence[Tuple[Sequence[int], Sequence[int]]], mode: int = OUT_LOGITS) -> np.ndarray:
-        """seqs: (token_ids, type_ids) per sequence (unpadded).  Returns logits (n, n_labels), CLS states (n, hidden)
-        or the hidden states of all tokens (sum of lengths, hidden) by `mode`.  Sequences are packed back to back and
+        """seqs: (token_ids, type_ids) per sequence (unpadded).  Returns logits (n, n_labels), CLS states (n, hidden), the mean over
+        each sequence's tokens (n, hidden; OUT_MEAN, in `model_pool_mean`'s order) or the hidden states of all tokens (sum of lengths, hidden) by `mode`.  Sequences are packed back to back and
         processed in chunks of at most `max_tokens_per_call` tokens; inside a chunk they are sorted by length only for
         the launch bound (the result is independent of batch composition: there is no padding to attend to)."""
         torch = self._torch
         self._check(seqs)
         n = len(seqs)
-        width = {OUT_LOGITS: self.n_labels, OUT_CLS: self.hidden, OUT_HIDDEN: self.hidden}[mode]
+        width = self._width(mode)
         lens = np.array([len(s[0]) for s in seqs], dtype=np.int64)
         if mode == OUT_LOGITS and self.n_labels == 0:
             raise ValueError("this encoder was loaded without a classification head")
@@ -224,7 +231,7 @@ class BertEncoderGPU:
         be at least every sequence's length (`out_of_range` reports a shorter one as a ValueError)."""
         torch = self._torch
         n_tokens = int(tok.numel())
-        width = {OUT_LOGITS: self.n_labels, OUT_CLS: self.hidden, OUT_HIDDEN: self.hidden}[mode]
+        width = self._width(mode)
         out = torch.empty((n_tokens if mode == OUT_HIDDEN else n_seqs, width), dtype=torch.float32, device=self._dev)
         p = lambda t: C.c_void_p(t.data_ptr())
         _lib.check(_lib.load().rr_ce_forward_dev(
@@ -291,6 +298,51 @@ def load_state_dict_dir(path) -> Tuple[Dict, Optional[pathlib.Path], Dict]:
     return sd, (vocab if vocab.exists() else None), cfg
 
 
+_POOLING_FLAGS = {"pooling_mode_cls_token": "cls", "pooling_mode_mean_tokens": "mean"}
+
+
+def pooling_of_dir(path) -> str:
+    """"cls" or "mean": what a sentence-transformers model directory says about its pooling, `1_Pooling/config.json` beside
+    the transformer (the directory root, or the parent of a `0_Transformer/` that was passed itself).  Host only.  No such
+    file: "cls" (a bare Hugging Face directory; bge's pooling).  Exactly `pooling_mode_cls_token` set: "cls"; exactly
+    `pooling_mode_mean_tokens`: "mean".  Anything else -- max, mean_sqrt_len, weightedmean, lasttoken, several modes
+    concatenated, none at all -- is a ValueError that names the modes: the encoder has no kernel for them, and CLS rows
+    returned in silence would be wrong vectors."""
+    d = pathlib.Path(path)
+    dirs = [d] + ([d.parent] if d.name == "0_Transformer" else [])
+    f = next((x / "1_Pooling" / "config.json" for x in dirs if (x / "1_Pooling" / "config.json").exists()), None)
+    if f is None:
+        return "cls"
+    cfg = json.loads(f.read_text())
+    on = sorted(k for k, v in cfg.items() if k.startswith("pooling_mode_") and v)
+    if len(on) == 1 and on[0] in _POOLING_FLAGS:
+        return _POOLING_FLAGS[on[0]]
+    raise ValueError(f"{f}: pooling {' + '.join(on) if on else '(no pooling_mode_* set)'} is not supported: the encoder pools "
+                     "with pooling_mode_cls_token or pooling_mode_mean_tokens alone")
+
+
+def model_pool_mean(hidden_rows, cu) -> np.ndarray:
+    """The CPU statement of csrc/rr_ce_pool.hip's `ce_pool_mean`, bit for bit: (n_seqs, H) float32 means of the packed rows
+    `hidden_rows` (sum of lengths, H) of the sequences `cu` (n_seqs + 1 offsets, every length >= 1), every operation one
+    float32 rounding, in the kernel's order -- which depends on a sequence's own length only:
+        p_j = 0, then p_j += row[t] for t = j, j + 8, j + 16, ... < len, in increasing t          (j = 0 .. 7)
+        out = (((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7))) / float32(len)"""
+    h = np.ascontiguousarray(hidden_rows, dtype=np.float32)
+    cu = np.asarray(cu, dtype=np.int64)
+    if h.ndim != 2 or cu.ndim != 1 or len(cu) < 2 or cu[0] != 0 or cu[-1] != len(h) or (np.diff(cu) < 1).any():
+        raise ValueError("model_pool_mean: rows (T, H) and cu_seqlens from 0 to T with every length >= 1")
+    out = np.empty((len(cu) - 1, h.shape[1]), dtype=np.float32)
+    for s in range(len(cu) - 1):
+        rows = h[cu[s]:cu[s + 1]]
+        p = np.zeros((8, h.shape[1]), dtype=np.float32)
+        for t in range(0, len(rows), 8):                 # rows t .. t + 7 go to p_0 .. p_7: every p_j sees its rows in increasing t
+            blk = rows[t:t + 8]
+            p[:len(blk)] += blk
+        tot = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]))
+        out[s] = tot / np.float32(len(rows))
+    return out
+
+
 class CrossEncoder:
     """`sentence_transformers.CrossEncoder` on the calls the reference makes: `predict(pairs, batch_size=64,
     show_progress_bar=False)` -> float32 (len(pairs),) for a single-label model."""
@@ -347,12 +399,21 @@ class CrossEncoder:
 
 class QueryEncoder:
     """`SentenceTransformer` on the call the reference makes: `encode([query], normalize_embeddings=True)` ->
-    (n, hidden) float32 (384 for bge-small-en-v1.5; `.hidden`); CLS pooling (bge-small-en-v1.5's pooling config)."""
+    (n, hidden) float32 (384 for bge-small-en-v1.5; `.hidden`).  `.pooling`: "cls" (last_hidden_state[:, 0]: bge's pooling
+    config, the default) or "mean" (the mean over a sequence's tokens: all-MiniLM, multi-qa-MiniLM, e5, gte), `.out_mode` the
+    forward's output mode for it (OUT_CLS / OUT_MEAN); both pool on the device.  `from_pretrained_dir` reads the directory's
+    `1_Pooling/config.json` (`pooling_of_dir`) and refuses every other pooling.  Not applied here: prompts / prefixes
+    ("query: " of e5) -- the caller's -- and a `2_Normalize` module (`normalize_embeddings` is the caller's, and the
+    reference always passes True)."""
 
     def __init__(self, state_dict: Dict, tokenizer: Optional[WordPieceTokenizer] = None, *, device: int = 0,
-                 max_length: int = 512, ln_eps: float = 1e-12, precision: str = "fp32", n_heads: Optional[int] = None):
-        """``precision`` "fp32" by default: the query vector feeds K1, whose answers are held to a 4e-7 tie band -- a bf16
+                 max_length: int = 512, ln_eps: float = 1e-12, precision: str = "fp32", n_heads: Optional[int] = None,
+                 pooling: str = "cls"):
+        """``pooling`` "cls" | "mean" (the class docstring).  ``precision`` "fp32" by default: the query vector feeds K1, whose answers are held to a 4e-7 tie band -- a bf16
         encoder would move dense scores by ~2e-3 (one short sequence per query: the fp32 forward costs microseconds)."""
+        if pooling not in POOLINGS:
+            raise ValueError(f"pooling must be one of {sorted(POOLINGS)}, not {pooling!r}")
+        self.pooling, self.out_mode = pooling, POOLINGS[pooling]
         self.model = BertEncoderGPU(state_dict, device=device, ln_eps=ln_eps, with_head=False, precision=precision, n_heads=n_heads)
         self.hidden = self.model.hidden                 # the width of the vectors: an index's `dim`
         self.tokenizer = tokenizer
@@ -365,18 +426,21 @@ class QueryEncoder:
         kw.setdefault("ln_eps", float(cfg.get("layer_norm_eps", 1e-12)))
         if cfg.get("num_attention_heads") is not None:
             kw.setdefault("n_heads", int(cfg["num_attention_heads"]))
+        if kw.get("pooling") in (None, "auto"):         # (not passed: the directory's; an unsupported one is refused there)
+            kw["pooling"] = pooling_of_dir(path)
         return cls(sd, tok, **kw)
 
     def encode_ids(self, seqs, normalize_embeddings: bool = False) -> np.ndarray:
-        e = self.model.forward_ids(seqs, OUT_CLS)
+        e = self.model.forward_ids(seqs, self.out_mode)
         if normalize_embeddings:       # torch.nn.functional.normalize(p=2, dim=1, eps=1e-12)
             e = (e / np.maximum(np.linalg.norm(e, axis=1, keepdims=True), 1e-12)).astype(np.float32)
         return e
 
     def encode_dev(self, tok, typ, pos, cu, n_seqs: int, max_len: int):
-        """CLS rows (n_seqs, hidden), a DEVICE tensor, of sequences already packed on the device (embed.DeviceWordPiece makes
-        them from text): `forward_packed_dev` with OUT_CLS, asynchronous on torch's current stream, not normalised."""
-        return self.model.forward_packed_dev(tok, typ, pos, cu, n_seqs, max_len, OUT_CLS)
+        """Pooled rows (n_seqs, hidden), a DEVICE tensor, of sequences already packed on the device (embed.DeviceWordPiece makes
+        them from text): `forward_packed_dev` with `.out_mode` (CLS rows or token means), asynchronous on torch's current
+        stream, not normalised."""
+        return self.model.forward_packed_dev(tok, typ, pos, cu, n_seqs, max_len, self.out_mode)
 
     def encode(self, sentences, normalize_embeddings: bool = False, **_ignored) -> np.ndarray:
         if self.tokenizer is None:

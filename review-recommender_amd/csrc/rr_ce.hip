@@ -33,6 +33,7 @@
 #include "rr_common.h"
 #include "rr_ce_h2.h"
 #include "rr_ce_w.h"
+#include "rr_ce_pool.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -1498,6 +1499,10 @@ static int ce_reserve_f32(rr_ce* ce, int64_t tokens) {
     return RR_OK;
 }
 
+// The outputs made of the [CLS] row alone (logits, the CLS embedding): their last layer runs its tail on one compact row per
+// sequence.  RR_CE_OUT_HIDDEN and RR_CE_OUT_MEAN need every token's row of the last layer.
+static inline bool ce_mode_cls_only(int mode) { return mode == RR_CE_OUT_LOGITS || mode == RR_CE_OUT_CLS; }
+
 static int ce_reserve_seqs_f32(rr_ce* ce, int64_t seqs) {
     if (seqs <= ce->cap32_seqs) return RR_OK;
     RR_HIP_TRY(hipDeviceSynchronize());
@@ -1594,7 +1599,7 @@ static int ce_forward_bf16(rr_ce* ce, const int32_t* d_token_ids, const int32_t*
         // The last layer of a [CLS]-pooled output (logits, CLS embedding) needs keys and values of every token but
         // only the [CLS] query row: attention runs for that row alone and everything behind it -- output projection,
         // both LayerNorms, the FFN -- on one compact row per sequence instead of one per token.
-        const bool cls_tail = (l == ce->cfg.n_layers - 1) && mode != RR_CE_OUT_HIDDEN;
+        const bool cls_tail = (l == ce->cfg.n_layers - 1) && ce_mode_cls_only(mode);
         const int Mr = cls_tail ? n_seqs : T;                              // rows behind the attention
         float* r32 = cls_tail ? ce->h32c : ce->h32;
         unsigned short* rb = cls_tail ? ce->hbc : ce->hb;
@@ -1607,6 +1612,8 @@ static int ce_forward_bf16(rr_ce* ce, const int32_t* d_token_ids, const int32_t*
     }
     if (mode == RR_CE_OUT_HIDDEN)
         RR_HIP_TRY(hipMemcpyAsync(d_out, ce->h32, sizeof(float) * (size_t)T * CE_H, hipMemcpyDeviceToDevice, st));
+    else if (mode == RR_CE_OUT_MEAN)
+        ce_pool_mean(ce->h32, d_cu_seqlens, n_seqs, CE_H, d_out, nullptr, st);
     else
         hipLaunchKernelGGL(ce_head, dim3((unsigned)n_seqs), dim3(256), 0, st, ce->h32c, (const int32_t*)nullptr, ce->wp, ce->bp, ce->wc, ce->bc,
                            ce->cfg.n_labels, mode, d_out, (const unsigned*)nullptr);
@@ -1621,7 +1628,7 @@ static int ce_forward_h2(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d
                    ce->eln_g, ce->eln_b, ce->cfg.ln_eps, ce->h32, ce->hx, xs, ce->d_flag, st);
     for (int l = 0; l < ce->cfg.n_layers; ++l) {
         const rr_ce_layer& L = ce->layers[l];
-        const bool cls_tail = l == ce->cfg.n_layers - 1 && mode != RR_CE_OUT_HIDDEN;
+        const bool cls_tail = l == ce->cfg.n_layers - 1 && ce_mode_cls_only(mode);
         // QKV as ONE h2 image of [T][1152] inside the qkv32 allocation (Q scaled by log2 e / sqrt 32)
         ce_h2_gemm(CE_H2_EPI_H2, L.wqkv_h2, 3 * CE_H, ce->hx, xs, T, CE_H, L.bqkv, nullptr, ce->qkv32, xs, ce->d_flag, st,
                    0.17677669529663687f * 1.4426950408889634f, CE_H);
@@ -1646,8 +1653,11 @@ static int ce_forward_h2(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d
         ce_h2_gemm(CE_H2_EPI_F32, L.w2_h2, CE_H, ce->inter32, xs, T, CE_FFN, L.b2, ce->y32, nullptr, 0, ce->d_flag, st);
         ce_h2_add_ln(ce->y32, ce->h32, T, L.ln2_g, L.ln2_b, ce->cfg.ln_eps, ce->hx, xs, ce->d_flag, st);
     }
-    // (mode != RR_CE_OUT_HIDDEN left through the last layer's [CLS] tail above)
-    RR_HIP_TRY(hipMemcpyAsync(d_out, ce->h32, sizeof(float) * (size_t)T * CE_H, hipMemcpyDeviceToDevice, st));
+    // (the [CLS]-only modes left through the last layer's tail above)
+    if (mode == RR_CE_OUT_MEAN)      // a raised range flag: NaN rows for the whole call, as ce_head writes them
+        ce_pool_mean(ce->h32, d_cu_seqlens, n_seqs, CE_H, d_out, (const unsigned*)ce->d_flag, st);
+    else
+        RR_HIP_TRY(hipMemcpyAsync(d_out, ce->h32, sizeof(float) * (size_t)T * CE_H, hipMemcpyDeviceToDevice, st));
     return RR_OK;
 }
 
@@ -1670,6 +1680,8 @@ static int ce_forward_x3(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d
     }
     if (mode == RR_CE_OUT_HIDDEN)
         RR_HIP_TRY(hipMemcpyAsync(d_out, ce->h32, sizeof(float) * (size_t)T * CE_H, hipMemcpyDeviceToDevice, st));
+    else if (mode == RR_CE_OUT_MEAN)
+        ce_pool_mean(ce->h32, d_cu_seqlens, n_seqs, CE_H, d_out, nullptr, st);
     else
         hipLaunchKernelGGL(ce_head, dim3((unsigned)n_seqs), dim3(256), 0, st, ce->h32, d_cu_seqlens, ce->wp, ce->bp, ce->wc, ce->bc,
                            ce->cfg.n_labels, mode, d_out, (const unsigned*)nullptr);
@@ -1725,6 +1737,8 @@ static int ce_forward_w(rr_ce* ce, const int32_t* d_token_ids, const int32_t* d_
     }
     if (mode == RR_CE_OUT_HIDDEN)
         RR_HIP_TRY(hipMemcpyAsync(d_out, ce->h32, sizeof(float) * (size_t)T * H, hipMemcpyDeviceToDevice, st));
+    else if (mode == RR_CE_OUT_MEAN)
+        ce_pool_mean(ce->h32, d_cu_seqlens, n_seqs, H, d_out, nullptr, st);
     else
         ce_w_head(ce->h32, d_cu_seqlens, n_seqs, H, ce->wp, ce->bp, ce->wc, ce->bc, ce->cfg.n_labels, mode, d_out, st);
     return RR_OK;
@@ -1748,7 +1762,8 @@ extern "C" int rr_ce_forward_dev(rr_ce* ce, const int32_t* d_token_ids, const in
                n_seqs, (long long)n_tokens);
     RR_REQUIRE(max_len >= 1 && max_len <= ce->cfg.max_pos, "rr_ce_forward_dev: max_len %d outside [1, %d]", max_len,
                ce->cfg.max_pos);
-    RR_REQUIRE(mode == RR_CE_OUT_LOGITS || mode == RR_CE_OUT_CLS || mode == RR_CE_OUT_HIDDEN, "rr_ce_forward_dev: unknown mode %d", mode);
+    RR_REQUIRE(mode == RR_CE_OUT_LOGITS || mode == RR_CE_OUT_CLS || mode == RR_CE_OUT_HIDDEN || mode == RR_CE_OUT_MEAN,
+               "rr_ce_forward_dev: unknown mode %d", mode);
     RR_REQUIRE(mode != RR_CE_OUT_LOGITS || ce->cfg.n_labels > 0, "rr_ce_forward_dev: the model was created without a classifier head");
     std::lock_guard<std::mutex> lk(ce->mu);
     RR_HIP_TRY(hipSetDevice(ce->device));
@@ -1773,7 +1788,7 @@ extern "C" int rr_ce_forward_dev(rr_ce* ce, const int32_t* d_token_ids, const in
     // scratch: per token for every path, and one compact row per sequence for the [CLS]-only tail of the last layer
     int rc = ce_reserve(ce, n_tokens);
     if (!rc) rc = f32 ? ce_reserve_f32(ce, n_tokens) : ce_reserve_seqs(ce, n_seqs);
-    if (!rc && h2 && mode != RR_CE_OUT_HIDDEN) rc = ce_reserve_seqs_f32(ce, n_seqs);
+    if (!rc && h2 && ce_mode_cls_only(mode)) rc = ce_reserve_seqs_f32(ce, n_seqs);
     if (!rc) rc = ce_set_attributes(ce->device);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;

@@ -30,5 +30,6 @@ void ce_w_add_ln(const float* y, int parts, int64_t pstride, float* h32, int T, 
 // every sequence of cu_seqlens has 1 .. 512 tokens
 void ce_w_attention(const float* qkv, const int32_t* cu, int n_seqs, int hidden, int n_heads, float* ctx, hipStream_t st);
 // mode RR_CE_OUT_CLS: out [n_seqs][hidden] = h32[cu[seq]]; RR_CE_OUT_LOGITS: out [n_seqs][n_labels] = wc tanh(wp x + bp) + bc
+// (the two [CLS]-row modes only: RR_CE_OUT_HIDDEN is a copy and RR_CE_OUT_MEAN is rr_ce_pool.h's ce_pool_mean, both in ce_forward_w)
 void ce_w_head(const float* h32, const int32_t* cu, int n_seqs, int hidden, const float* wp, const float* bp, const float* wc,
                const float* bc, int n_labels, int mode, float* out, hipStream_t st);

@@ -151,5 +151,13 @@ int rr_debug_ce_bf16_ffn(rr_ce* ce, int32_t layer, const unsigned short* d_ctx, 
 int rr_debug_ce_w_attention(const float* d_qkv, int32_t T, const int32_t* d_cu, int32_t n_seqs, int32_t hidden, int32_t n_heads, float* d_ctx);
 int rr_debug_ce_w_add_ln(const float* d_y, float* d_h, int32_t T, int32_t hidden, const float* d_g, const float* d_b, float eps);
 int rr_debug_ce_w_embed_ln(rr_ce* ce, const int32_t* d_tok, const int32_t* d_typ, const int32_t* d_pos, int32_t T, float* d_h32);
+// tests/test_gpu_k5_pool_kernel.py: ONE ce_pool_mean launch (rr_ce_pool.hip: RR_CE_OUT_MEAN's kernel) on caller rows h32 [T][hidden]
+// and cu_seqlens [n_seqs + 1] (device pointers), through the launcher the forward passes call: out [n_seqs][hidden].  A host
+// copy of cu is checked before anything is launched -- it runs from 0 to T, every length is in [1, 512] -- and hidden is a
+// multiple of 128 in [128, 1024]: RR_E_INVALID otherwise.  tools/pooling_time.py: rr_debug_ce_pool_time, the same launch and a
+// device-to-device copy of the same rows under HIP events (ms_pool / ms_copy [reps]).  See the definitions.
+int rr_debug_ce_pool_mean(const float* d_h32, int32_t T, const int32_t* d_cu, int32_t n_seqs, int32_t hidden, float* d_out);
+int rr_debug_ce_pool_time(const float* d_h32, int32_t T, const int32_t* d_cu, int32_t n_seqs, int32_t hidden, float* d_out, float* d_copy,
+                          int32_t warmup, int32_t reps, float* ms_pool, float* ms_copy);
 }
 #endif

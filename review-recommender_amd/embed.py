@@ -40,7 +40,6 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .cross_encoder import OUT_CLS
 from .index import ProductIndex
 from .wordpiece import WordPieceTokenizer
 
@@ -275,6 +274,7 @@ def _embed_into(index: ProductIndex, lens: Sequence[int], queue_docs, host_text,
     if first_row < 0 or first_row + n > index.n_rows or index.dim != hidden:
         raise ValueError(f"{n} rows of dim {hidden} from row {first_row} do not fit an index of {index.n_rows} x {index.dim}")
     model, L = encoder.model, encoder.max_length
+    out_mode = encoder.out_mode                       # OUT_CLS or OUT_MEAN: the encoder's pooling, one row per document either way
     dev = torch.device("cuda", model.device)
     wp = getattr(encoder, "_device_wp", None)
     if wp is None:
@@ -319,10 +319,10 @@ def _embed_into(index: ProductIndex, lens: Sequence[int], queue_docs, host_text,
             h = info.numpy()
             tok, typ, pos, cu = wp.views(packed, nd, cap, int(h[0]))
             narrow = fp32 and not model.wide_range      # which kernels THIS launch runs: decides its redo, whatever comes later
-            out = model.forward_packed_dev(tok, typ, pos, cu, nd, int(h[nd + 1]), OUT_CLS)
+            out = model.forward_packed_dev(tok, typ, pos, cu, nd, int(h[nd + 1]), out_mode)
             store(out, first_row + a)
             flag = None
-            if narrow:                      # an out-of-range pass leaves NaN in every CLS row of its call (include/rr_hip.h)
+            if narrow:                      # an out-of-range pass leaves NaN in every pooled row of its call (include/rr_hip.h)
                 flag = torch.empty(1, dtype=torch.bool, pin_memory=True)
                 flag.copy_(torch.isnan(out[:, 0]).any().reshape(1), non_blocking=True)
             done = torch.cuda.Event()
@@ -383,7 +383,7 @@ def _embed_into(index: ProductIndex, lens: Sequence[int], queue_docs, host_text,
             pos = (np.arange(T, dtype=np.int32) - np.repeat(cu[:-1], sl)).astype(np.int32)
             d = torch.from_numpy(np.concatenate([ids, np.zeros(T, np.int32), pos, cu])).to(dev)
             rows = torch.from_numpy(np.asarray(part, dtype=np.int64) + first_row).to(dev)
-            args = (d[:T], d[T:2 * T], d[2 * T:3 * T], d[3 * T:], len(part), int(sl.max()), OUT_CLS)
+            args = (d[:T], d[T:2 * T], d[2 * T:3 * T], d[3 * T:], len(part), int(sl.max()), out_mode)
             out = model.forward_packed_dev(*args)
             if fp32 and not model.wide_range and model.out_of_range():
                 model.set_wide_range(True)
@@ -817,6 +817,9 @@ def parse_args(argv=None):
                          "tokens (--batch), not by rows")
     ap.add_argument("--out-dir", type=str, default="data/processed")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32", help="encoder arithmetic")
+    ap.add_argument("--pooling", choices=["auto", "cls", "mean"], default="auto",
+                    help="the sentence vector: auto = what the model directory's 1_Pooling/config.json says (cls without one; "
+                         "any pooling but cls / mean is refused), cls = last_hidden_state[:, 0], mean = the mean over the tokens")
     # review-only options
     ap.add_argument("--no-spam", action="store_true", help="disable spam filter")
     ap.add_argument("--no-dedup", action="store_true", help="disable (sku,text) dedup")
@@ -837,7 +840,7 @@ def _main_product_from_reviews(args) -> int:
     device = int(str(args.device).split(":")[-1])
     reviews = P.load_reviews(args.reviews)
     products, _, text = P.build_products(reviews, device=device, keep_device=True)
-    encoder = QueryEncoder.from_pretrained_dir(args.model, device=device, precision=args.precision)
+    encoder = QueryEncoder.from_pretrained_dir(args.model, device=device, precision=args.precision, pooling=args.pooling)
     index, meta, emb, _ = build_product_embeddings_device(products, text, encoder, chunk_tokens=max(1, args.batch) * 512,
                                                           data_dir=args.out_dir)
     print(f"[product] rows={len(meta):,}  batch={args.batch}", flush=True)
@@ -859,7 +862,7 @@ def main(argv=None) -> int:
     if not text_col:
         raise ValueError("Provide --text-col for product text (e.g., agg_text).")
     device = int(str(args.device).split(":")[-1])
-    encoder = QueryEncoder.from_pretrained_dir(args.model, device=device, precision=args.precision)
+    encoder = QueryEncoder.from_pretrained_dir(args.model, device=device, precision=args.precision, pooling=args.pooling)
     index, meta, emb = build_product_embeddings(df, encoder, text_col=text_col, chunk_tokens=max(1, args.batch) * 512,
                                                 data_dir=args.out_dir)
     print(f"[product] rows={len(meta):,}  batch={args.batch}", flush=True)
@@ -884,7 +887,7 @@ def _main_review(args) -> int:
               "id, sku, ts, stars and text", file=sys.stderr)
         return 2
     device = int(str(args.device).split(":")[-1])
-    encoder = QueryEncoder.from_pretrained_dir(args.model, device=device, precision=args.precision)
+    encoder = QueryEncoder.from_pretrained_dir(args.model, device=device, precision=args.precision, pooling=args.pooling)
     table, emb, _ = build_review_embeddings(df, encoder, no_spam=args.no_spam, no_dedup=args.no_dedup,
                                             chunk_tokens=max(1, args.batch) * 512, data_dir=args.out_dir,
                                             log=lambda line: print(line, flush=True))

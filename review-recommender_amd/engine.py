@@ -622,7 +622,7 @@ class SearchEngine:
     (querytext.QueryText, csrc/rr_query.hip) for the consumers that are on the device (K2; the gate with gate="device"; the
     pairs with rerank="device").  The queries the kernels hand back are searched again through the host functions.  The two
     give bitwise the same frames, snips and dbg.
-    query_vectors: "host" (the default) encodes the queries with ``encoder.encode`` (Python WordPiece per query, ids up, CLS
+    query_vectors: "host" (the default) encodes the queries with ``encoder.encode`` (Python WordPiece per query, ids up, pooled
     rows down, numpy's l2 normalisation, vectors up again); "device" makes them in the query front from the staged bytes
     (device WordPiece of the encoder's vocabulary, the forward, rr_query_vectors_dev) and K1 reads them where they are.  It
     needs query_text="device" and an ``encoder`` that is this package's `QueryEncoder` with a tokenizer.  The queries the

@@ -28,9 +28,10 @@ _lock = threading.Lock()
 
 def configure(data_dir=None, *, engine: Optional[SearchEngine] = None, emb_model_dir: str = "",
               rerank_model_dir: str = "", encoder=None, cross_encoder=None, device: int = 0,
-              flavour: str = "app") -> SearchEngine:
+              flavour: str = "app", pooling: str = "auto") -> SearchEngine:
     """Builds (or adopts) the engine behind `run_search`.  Models: local Hugging Face directories run on the GPU
-    (cross_encoder.QueryEncoder / CrossEncoder); alternatively any object with the sentence-transformers call shape
+    (cross_encoder.QueryEncoder / CrossEncoder; `pooling` "auto" = the sentence vector `emb_model_dir`'s
+    1_Pooling/config.json names -- "cls" without one, any pooling but cls / mean refused -- or "cls" / "mean"); alternatively any object with the sentence-transformers call shape
     (`encode([q], normalize_embeddings=True)`, `predict(pairs, batch_size=64, show_progress_bar=False)`)."""
     global _engine
     with _lock:
@@ -39,7 +40,7 @@ def configure(data_dir=None, *, engine: Optional[SearchEngine] = None, emb_model
                 raise ValueError("configure() needs data_dir (the reference's data/processed layout) or an engine")
             if emb_model_dir and encoder is None:
                 from .cross_encoder import QueryEncoder
-                encoder = QueryEncoder.from_pretrained_dir(emb_model_dir, device=device)
+                encoder = QueryEncoder.from_pretrained_dir(emb_model_dir, device=device, pooling=pooling)
             if rerank_model_dir and cross_encoder is None:
                 from .cross_encoder import CrossEncoder
                 cross_encoder = CrossEncoder.from_pretrained_dir(rerank_model_dir, device=device)

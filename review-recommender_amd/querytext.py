@@ -13,7 +13,7 @@ functions.  `model_front` states in plain Python, without ``re``, what the kerne
 doctok.model_tokenize does for the document tokenizer.
 
 With a `QueryEncoder` the front also makes the query VECTORS K1 reads (`QueryFront.qvecs`): the device WordPiece tokenizer
-of the encoder's vocabulary over the same staged bytes, the forward with CLS output and `rr_query_vectors_dev`, which
+of the encoder's vocabulary over the same staged bytes, the forward with the encoder's pooled output (CLS rows or token means) and `rr_query_vectors_dev`, which
 normalises the rows with numpy's float32 roundings, bit for bit.  `model_query_vectors` states that kernel in plain Python,
 the pairwise order of the additions written out.
 
@@ -285,7 +285,7 @@ class QueryText:
     with the cross-encoder's ``max_length``.  ``encoder``: a cross_encoder.QueryEncoder with a (lower-casing) tokenizer, on
     this device, when the query VECTORS are wanted too: every front then also tokenises the staged bytes with the encoder's
     vocabulary (truncated to ``encoder.max_length`` as ``encode_pair(s, None, max_length)`` truncates), runs the forward and
-    normalises the CLS rows as numpy does (rr_query_vectors_dev) into ``QueryFront.qvecs`` -- bit for bit the rows of
+    normalises the pooled rows (CLS or mean, the encoder's `out_mode`) as numpy does (rr_query_vectors_dev) into ``QueryFront.qvecs`` -- bit for bit the rows of
     ``encoder.encode(queries, normalize_embeddings=True)``.  A query the encoder's tokenizer kernel hands back carries
     FLAG_ENCODER; its sequence is the placeholder [CLS] [SEP].  The row of every flagged query is zeros."""
 
@@ -454,7 +454,7 @@ class QueryText:
 
     def redo_vectors(self, front: QueryFront) -> bool:
         """After the batch of ``front`` has been waited for: when its forward ran on the fp16-pair kernels and met an
-        activation beyond fp16's range (``encoder.model.out_of_range()``; its CLS rows, and so ``front.qvecs``, are NaN), the
+        activation beyond fp16's range (``encoder.model.out_of_range()``; its pooled rows, and so ``front.qvecs``, are NaN), the
         handle is switched to the wide-range kernels as `BertEncoderGPU.forward_ids` switches it (``set_wide_range``), the
         forward and the normalisation are queued again INTO ``front.qvecs`` and True is returned: the caller searches the
         batch again.  False (and nothing queued) otherwise."""
